@@ -1,12 +1,17 @@
 """bench.py -- 512x512 hyperspectral tiles/s of the HyperSTARCOP train step (fwd + loss + bwd + Adam).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
 Workload (BASELINE.json configs[1]): the 4-channel (mag1c + RGB) MobileNetV2 U-Net, batch 16 per GPU, fp32,
 synthetic seeded tiles resident in HBM, random-init weights.  A step is exactly ModelModule.training_step +
 backward + Adam.step (reference model_module.py:69-88,172-185), executed by the HIP kernels with no autograd
 graph.  One JSON line on rank 0; see DESIGN.md "Measurement" for the roofline / cpu_baseline definitions.
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else, after the timed
+region: the live roofline pass, the per-rank exchange diagnostics (N > 1), the fp32-x3 loop, `extra` and `cpu_baseline`
+(--no-extras / --no-cpu-baseline leave out the last ones).  --dump-outputs DIR writes what the last timed step computed
+(see dump_outputs) so that two builds can be compared output for output: the inputs and the initial weights are seeded.
 """
 import argparse
 import json
@@ -298,6 +303,28 @@ def bench_extras(model, dev, precision):
     return out
 
 
+DUMP_CAP = 7 << 20      # elements per dumped array (28 MiB as float32): the parameters (6.63 M) fit whole, the whole dump stays below 64 MB
+
+
+def dump_outputs(out_dir, net, plan):
+    """What a caller of the timed step receives from its last call, as float32 / float64 .npy files: the returned loss
+    accumulator, the train-mode logits, the parameters after the Adam update and the BatchNorm running statistics.  An
+    array above DUMP_CAP elements is stored as a fixed, seeded sample of its flattened elements (the same at every run)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    stats = [b.detach().reshape(-1) for b in net.buffers() if b.is_floating_point()]
+    arrays = {"loss_sum": plan.loss_acc.detach().double(),                                 # sum of the weighted per-pixel losses
+              "logits": plan.buf["logits"].detach().float(),
+              "parameters": net.flat_parameters().detach().float(),
+              "running_stats": torch.cat(stats).float() if stats else torch.zeros(0)}
+    for i, (name, t) in enumerate(arrays.items()):
+        a = t.cpu().numpy()
+        if a.size > DUMP_CAP:
+            idx = np.unique(np.random.default_rng(1000 + i).integers(0, a.size, DUMP_CAP))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def self_launch(n, backend):
     """Re-executes this command line under torch.distributed.run with n ranks on this node (rendezvous on 127.0.0.1:free port)
     and returns its exit code.  The driver may call `python bench.py --gpus N` directly; every rank then runs main() with
@@ -325,8 +352,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--batch", type=int, default=16, help="tiles per GPU (weak scaling)")
     ap.add_argument("--tile", type=int, default=512)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip the mag1c / inference measurements reported under `extra`")
+    ap.add_argument("--full", action="store_true", help="after the timed steps also run the live roofline pass, the per-rank exchange "
+                    "diagnostics (N > 1), the fp32-x3 loop, `extra` and `cpu_baseline`; a plain run reports the timed steps only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the last timed step computed as DIR/<name>.npy "
+                    "(loss, logits, updated parameters, BatchNorm running statistics; rank 0)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip `cpu_baseline`")
+    ap.add_argument("--no-extras", action="store_true", help="with --full: skip the fp32-x3 loop and the mag1c / inference measurements reported under `extra`")
     ap.add_argument("--overlap", type=int, default=1, help="1: weight gradients on a second HIP stream (default); 0: serial "
                     "launches (use for rocprofv3 per-kernel durations that match the roofline pass)")
     ap.add_argument("--precision", default="fp32", choices=["fp32", "fp32-x3", "fp32-bwd2", "fp32-2", "bf16"],
@@ -338,6 +369,8 @@ def main():
                          "on the same memory (SURVEY.md section 5; also STARCOP_GRADSYNC)")
     ap.add_argument("--graph", type=int, default=0, help="1: replay the step from a captured hipGraph (default: eager two-stream launches, measured faster)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     backend = os.environ.get("STARCOP_BENCH_BACKEND", "nccl")       # "gloo": functional check of the N>1 path on a 1-GPU box
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -408,6 +441,9 @@ def main():
     if world > 1:
         dist.barrier()
     elapsed = time.perf_counter() - t0
+    loss = float(net._plans[(B, T, T)].loss_acc.item()) / (B * T * T)
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, net, net._plans[(B, T, T)])
     per_rank = None
     if world > 1:
         cdev = dev if backend == "nccl" else "cpu"
@@ -415,6 +451,7 @@ def main():
         t = torch.tensor([elapsed], device=cdev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if world > 1 and args.full:
         # ---- diagnostics of the exchange, OUTSIDE the timed region (every rank takes part): each rank's own step time and, from
         # device events around the two buckets of a few more steps, how much of the gradient exchange was NOT hidden behind the
         # encoder's backward -- what a first multi-GPU run needs to tell a slow rank from an exposed collective
@@ -432,11 +469,10 @@ def main():
         per_rank = [{"rank": r, "ms_per_step": round(float(v[0]), 3), "overlap_window_ms": round(float(v[1]), 3),
                      "exposed_ms_bucket_encoder": round(float(v[2]), 3), "exposed_ms_bucket_decoder_wait": round(float(v[3]), 3)}
                     for r, v in enumerate(allr)]
-    loss = float(net._plans[(B, T, T)].loss_acc.item()) / (B * T * T)
 
     # ---- roofline of the dominant kernel family, measured live with events on the launch stream (eager, instrumented)
     roof = roof_streaming = roof_lowest = None
-    if rank == 0:
+    if rank == 0 and args.full:
         net.profile = {}
         overlap, net.overlap_wgrad = net.overlap_wgrad, False     # serial launches: a kernel's events bracket only itself
         prof_steps = 3
@@ -553,8 +589,9 @@ def main():
                           "parallelism": f"dp{world}", "hipgraph": graph is not None, "final_loss": round(loss, 6),
                           "precision": args.precision},
                "roofline": roof}
-        if per_rank is not None:
+        if sync is not None:
             out["config"]["gradsync"] = sync.mode
+        if per_rank is not None:
             out["per_rank"] = per_rank          # own (not max-over-ranks) step time; exposed = stream time the step waited for a bucket
         if roof_streaming is not None:
             out["roofline_streaming"] = roof_streaming
@@ -574,7 +611,7 @@ def main():
                                             f"convolutions 2500 / {int(nprod)} = {BF16_MFMA_PEAK_TFLOPS / nprod:.1f} TFLOP/s fp32-equivalent on the 16-bit MFMA, all other "
                                             f"layers {FP32_MFMA_PEAK_TFLOPS} TFLOP/s; the whole step (incl. loss, BatchNorm, Adam, which this floor prices at zero) "
                                             f"achieves {80.39 * tiles / elapsed / world / 1e3:.1f} TFLOP/s algorithmic"}
-        if world == 1 and not args.no_extras:
+        if world == 1 and args.full and not args.no_extras:
             # the bit-faithful split (three bf16 terms, six products, fp32's exponent range) timed by the same loop
             if args.precision == "fp32" and T == 512:
                 net.precision = "fp32-x3"
@@ -588,7 +625,7 @@ def main():
                 out["config"]["precision_exact_tiles_s"] = round(B * 10 / (time.perf_counter() - t1), 2)
                 net.precision = "fp32"
             out["extra"] = bench_extras(model, dev, args.precision)
-        if not args.no_cpu_baseline and world == 1:       # reported at N=1 only (other ranks would idle at the exit barrier)
+        if args.full and not args.no_cpu_baseline and world == 1:       # reported at N=1 only (other ranks would idle at the exit barrier)
             out["cpu_baseline"] = cpu_baseline()
         print(json.dumps(out))
     if world > 1:

@@ -14,7 +14,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def test_bench_two_ranks_one_gpu(hip):
     env = dict(os.environ, STARCOP_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1", MASTER_PORT="29541", WORLD_SIZE="2")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--tile", "256"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--tile", "256", "--full"]
     procs = [subprocess.Popen(cmd, env=dict(env, RANK=str(r), LOCAL_RANK=str(r)), stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, cwd=ROOT)
              for r in (1, 0)]
     outs = []
@@ -103,7 +103,7 @@ def test_bench_self_launches_n_ranks(hip):
     itself (torch.distributed.run on 127.0.0.1) and report n_gpus from the live process group.  gloo on the one GPU of this box;
     with the default backend the same command demands N visible GPUs and refuses loudly otherwise."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--tile", "128"]
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "2", "--tile", "128", "--full"]
     p = subprocess.run(cmd, env=dict(env, STARCOP_BENCH_BACKEND="gloo"), capture_output=True, text=True, cwd=ROOT, timeout=400)
     assert p.returncode == 0, (p.stdout[-500:], p.stderr[-1500:])
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]

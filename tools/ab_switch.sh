@@ -7,7 +7,7 @@ for f in True False True False; do
 import sys, runpy
 import starcop_amd.network as n
 setattr(n.HyperStarcopUNet, '$ATTR', $f)
-sys.argv = ['bench.py', '--steps', '40', '--warmup', '8', '--no-cpu-baseline', '--no-extras'] + '$*'.split()
+sys.argv = ['bench.py', '--steps', '40', '--warmup', '8', '--full', '--no-cpu-baseline', '--no-extras'] + '$*'.split()
 runpy.run_path('bench.py', run_name='__main__')" 2>/dev/null | tail -1 | python -c "
 import sys, json
 d = json.loads(sys.stdin.read()); f = d['roofline']['families_ms_per_step']

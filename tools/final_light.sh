@@ -16,5 +16,5 @@ python tools/prof_summary.py $S > $OUT/kernel_trace_stats_bench_b16_serial.txt
 python tools/gap_analysis.py $E 0.3 0.7 > $OUT/gap_analysis_eager.txt
 python tools/phase_gaps.py $E > $OUT/phase_gaps_eager.txt
 python tools/trace_tail.py $E 16 > $OUT/trace_tail_eager.txt
-python bench.py > $OUT/bench_full.log 2>&1; grep "^{" $OUT/bench_full.log > $OUT/bench_line.json
+python bench.py --full > $OUT/bench_full.log 2>&1; grep "^{" $OUT/bench_full.log > $OUT/bench_line.json
 ls $OUT

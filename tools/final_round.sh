@@ -13,6 +13,6 @@ rocprofv3 --kernel-trace -d /tmp/p_m -o run -- python $ROOT/tools/bench_mag1c.py
 cd $ROOT; python tools/prof_summary.py $(find /tmp/p_m -name "*.db" | head -1) > $OUT/mag1c_kernel_trace.txt
 python tools/bench_mag1c.py > $OUT/mag1c_bench.log 2>&1
 for a in "--precision bf16 --batch 64" "--precision fp32 --batch 64" "--precision fp32-x3"; do
-  python bench.py $a --steps 12 --warmup 3 --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > "$OUT/bench_line_$(echo $a | tr -d ' -').json"
+  python bench.py $a --steps 12 --warmup 3 --full --no-cpu-baseline --no-extras 2>/dev/null | tail -1 > "$OUT/bench_line_$(echo $a | tr -d ' -').json"
 done
 ls $OUT
