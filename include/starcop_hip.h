@@ -624,6 +624,43 @@ int sc_band_ratio(const float* background, const float* signal, float* out, int 
 int sc_clip_scale(const float* x, float* out, size_t n, float div, float lo, float hi, float mult,
                   int nan_to_num, sc_stream stream);
 
+/* Sanchez-Garcia multiple-linear-regression ratio (starcop/data/feature_extration.py:58-125, ratio_MLR_local and its
+ * _5IN / _9IN / _5IN_simplediv wrappers).  For B tiles of n pixels: the least-squares fit with intercept of the target band t
+ * on k <= 9 regressor bands x_1..x_k over ALL pixels (sklearn LinearRegression), r = intercept + sum_j coef_j x_j, then
+ *   SC_MLR_C_MATCHED   : R = (c*r - t)/(t + 1e-6), c = trimmed sum(t) / trimmed sum(r) (sc_trimmed_sums, p = 5, float32
+ *                        division as sc_band_ratio); -0.5 where (r < 1e-6 and t < 1e-6) or t == 0
+ *   SC_MLR_SIMPLE_PLUS : R0 = -t/(r + 1e-6), R = (R0 - mean(R0))/std(R0) (ddof 0, fp64 over the tile); min(R) where t == 0
+ *   SC_MLR_RESIDUAL    : R = (t - r)/(r + 1e-6); 0 where t == 0
+ * and with autoclip != 0, R = clip(R, -0.2, 0.2).
+ * Regressor j of tile b is the plane base + b*tile_stride + band_off[j] and the target of tile b is target + b*target_tile_stride
+ * (offsets and strides in floats), so a stacked (B, bands, H, W) tensor is used in place.
+ *   sc_mlr_moments : fp64 sums of z and z z^T (z = [x, t] minus a per-band shift) into per-work-group partials of `work`
+ *   sc_mlr_solve   : fixed-order reduction of those partials, equilibrated fp64 Jacobi eigen-solve, minimum-norm solution;
+ *                    coef[b][0..k-1] = coefficients (0 for a zero-variance band), coef[b][k] = intercept (fp64, device)
+ *   sc_mlr_fit     : sc_mlr_moments + sc_mlr_solve
+ *   sc_mlr_predict : r[b][i] (dense [B][n] fp32) from coef
+ *   sc_mlr_ratio   : out[b][i] (dense [B][n] fp32) from coef and t; SC_MLR_C_MATCHED also reads r (sc_mlr_predict), the other
+ *                    divisions evaluate r in fp64 themselves and take r = NULL
+ * No atomics: repeated calls give bit-identical results.  work: sc_mlr_workspace_bytes(B, n, k) bytes.              */
+enum sc_mlr_division { SC_MLR_C_MATCHED = 0, SC_MLR_SIMPLE_PLUS = 1, SC_MLR_RESIDUAL = 2 };
+typedef struct sc_mlr_args {
+  const float* base;             /* regressor planes                                    */
+  long long band_off[16];        /* offset of regressor j from base, floats (j < k)     */
+  int32_t k;                     /* regressors, 1..9                                    */
+  long long tile_stride;         /* floats between tiles of the regressors              */
+  const float* target;           /* target plane of tile 0                              */
+  long long target_tile_stride;  /* floats between tiles of the target                  */
+  int32_t B;                     /* tiles                                               */
+  size_t n;                      /* pixels per tile (H*W, any value >= 2)               */
+} sc_mlr_args;
+size_t sc_mlr_workspace_bytes(int B, size_t n, int k);
+int sc_mlr_moments(const sc_mlr_args* a, void* work, size_t work_bytes, sc_stream stream);
+int sc_mlr_solve(const sc_mlr_args* a, double* coef, void* work, size_t work_bytes, sc_stream stream);
+int sc_mlr_fit(const sc_mlr_args* a, double* coef, void* work, size_t work_bytes, sc_stream stream);
+int sc_mlr_predict(const sc_mlr_args* a, const double* coef, float* r, sc_stream stream);
+int sc_mlr_ratio(const sc_mlr_args* a, const double* coef, const float* r, int division, int autoclip, float* out, void* work, size_t work_bytes,
+                 sc_stream stream);
+
 /* ------------------------------------------------------------------------- */
 /* evaluation masks of the baselines and of run_validation.
  * Thresholded prediction with an optional binary opening by a 3x3 structuring element:

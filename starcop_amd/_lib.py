@@ -90,6 +90,14 @@ class sc_mag1c_args(C.Structure):
                 ("scatter_mf", C.c_void_p), ("scatter_alb", C.c_void_p), ("scatter_is_f64", C.c_int32)]
 
 
+class sc_mlr_args(C.Structure):
+    """multiple-linear-regression ratio operands (include/starcop_hip.h: sc_mlr_args)"""
+    _fields_ = [("base", C.c_void_p), ("band_off", C.c_longlong * 16), ("k", C.c_int32), ("tile_stride", C.c_longlong),
+                ("target", C.c_void_p), ("target_tile_stride", C.c_longlong), ("B", C.c_int32), ("n", C.c_size_t)]
+
+
+MLR_C_MATCHED, MLR_SIMPLE_PLUS, MLR_RESIDUAL = 0, 1, 2
+
 _vp, _i, _f, _d, _sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/starcop_hip.h declares
@@ -156,6 +164,12 @@ SIGNATURES = {
     "sc_trimmed_sums": (_i, [_vp, _i, _sz, _d, _vp, _vp, _sz, _vp]),
     "sc_band_ratio": (_i, [_vp, _vp, _vp, _i, _sz, _vp, _vp, _f, _f, _vp]),
     "sc_clip_scale": (_i, [_vp, _vp, _sz, _f, _f, _f, _f, _i, _vp]),
+    "sc_mlr_workspace_bytes": (_sz, [_i, _sz, _i]),
+    "sc_mlr_moments": (_i, [C.POINTER(sc_mlr_args), _vp, _sz, _vp]),
+    "sc_mlr_solve": (_i, [C.POINTER(sc_mlr_args), _vp, _vp, _sz, _vp]),
+    "sc_mlr_fit": (_i, [C.POINTER(sc_mlr_args), _vp, _vp, _sz, _vp]),
+    "sc_mlr_predict": (_i, [C.POINTER(sc_mlr_args), _vp, _vp, _vp]),
+    "sc_mlr_ratio": (_i, [C.POINTER(sc_mlr_args), _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "sc_packed_weight_floats_thin16": (_sz, [_i, _i, _i]),
     "sc_pack_weights_thin16": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "sc_conv3x3_thin16": (_i, [C.POINTER(sc_conv_args), _vp]),
