@@ -661,6 +661,28 @@ int sc_mlr_predict(const sc_mlr_args* a, const double* coef, float* r, sc_stream
 int sc_mlr_ratio(const sc_mlr_args* a, const double* coef, const float* r, int division, int autoclip, float* out, void* work, size_t work_bytes,
                  sc_stream stream);
 
+/* Connected-component labelling and the plume label masks (starcop/data/mask_creation.py:6-27 proposed_mask, called by
+ * WindowDataset at sampling_dataset.py:298-303 and cached as labelbinary.tif by _cache_data_permian_2019 :453-460).
+ *   sc_proposed_mask        : for each of N images, T = mag1c >= threshold (NaN unset), D = dilation(opening(T)) with the 3x3
+ *                             element se_bits (SC_SE_CROSS = skimage disk(1); erosion: outside the image set, dilations: outside
+ *                             unset -- skimage's binary_erosion / binary_dilation borders; se_bits = 0: D = T), components of D
+ *                             with 8-connectivity (skimage.measure.label's default), out[n][h][w] (uint8) = T & D & (the
+ *                             component of the pixel holds a pixel with alpha != 0).  mag1c plane n = mag1c + n*mag1c_plane_stride
+ *                             and alpha plane n = alpha + n*alpha_plane_stride (elements; dense H x W planes), so channel 3 of a
+ *                             (N, 4, H, W) label_rgba tensor is read in place.
+ *   sc_connected_components : labels[n][h][w] (int32) of mask != 0, connectivity 1 (4-neighbours) or 2 (8-neighbours); background
+ *                             0, components numbered 1.. by their first pixel in raster order (scipy.ndimage.label /
+ *                             skimage.measure.label); counts[n] = number of components (device int32).
+ * Union-find: a per-tile pass in LDS, a border merge with device atomics, a flatten; the root of a component is its minimum
+ * raster index, so repeated calls give identical bits.  4 (proposed_mask) / 5 (connected_components) launches per call.
+ * N <= 65535, H*W < 2^31.  work: sc_label_workspace_bytes(N, H, W) bytes (enough for either).                    */
+size_t sc_label_workspace_bytes(int N, int H, int W);
+int sc_connected_components(const uint8_t* mask, int connectivity, int32_t* labels, int32_t* counts,
+                            void* work, size_t work_bytes, int N, int H, int W, sc_stream stream);
+int sc_proposed_mask(const float* mag1c, int64_t mag1c_plane_stride, const uint8_t* alpha, int64_t alpha_plane_stride,
+                     float threshold, int se_bits, uint8_t* out, void* work, size_t work_bytes,
+                     int N, int H, int W, sc_stream stream);
+
 /* ------------------------------------------------------------------------- */
 /* evaluation masks of the baselines and of run_validation.
  * Thresholded prediction with an optional binary opening by a 3x3 structuring element:

@@ -11,6 +11,7 @@ Public surface (mirrors the reference):
   starcop_amd.validation.run_validation ; starcop_amd.baselines.Mag1cBaseline / SanchezBaseline / VaronBaseline / binary_opening
   starcop_amd.features.FEATURES / extract_features / ratio_MLR_local (+ _5IN / _9IN / _5IN_simplediv) / mlr_fit /
     ratio_2c_match_c_from_sums_outlier / weight_mag1c
+  starcop_amd.mask_creation.proposed_mask / connected_components / write_label_masks (the labelbinary target)
 All compute runs in starcop_amd/libstarcop_hip.so (include/starcop_hip.h); there is no CPU fallback.
 """
 __version__ = "0.1.0"

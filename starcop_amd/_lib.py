@@ -170,6 +170,9 @@ SIGNATURES = {
     "sc_mlr_fit": (_i, [C.POINTER(sc_mlr_args), _vp, _vp, _sz, _vp]),
     "sc_mlr_predict": (_i, [C.POINTER(sc_mlr_args), _vp, _vp, _vp]),
     "sc_mlr_ratio": (_i, [C.POINTER(sc_mlr_args), _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
+    "sc_label_workspace_bytes": (_sz, [_i, _i, _i]),
+    "sc_connected_components": (_i, [_vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
+    "sc_proposed_mask": (_i, [_vp, C.c_int64, _vp, C.c_int64, _f, _i, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "sc_packed_weight_floats_thin16": (_sz, [_i, _i, _i]),
     "sc_pack_weights_thin16": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "sc_conv3x3_thin16": (_i, [C.POINTER(sc_conv_args), _vp]),
