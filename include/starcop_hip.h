@@ -683,6 +683,40 @@ int sc_proposed_mask(const float* mag1c, int64_t mag1c_plane_stride, const uint8
                      float threshold, int se_bits, uint8_t* out, void* work, size_t work_bytes,
                      int N, int H, int W, sc_stream stream);
 
+/* Simulated multispectral bands from an AVIRIS-NG radiance cube: the spectral-response-function resampling of
+ * starcop/data/aviris.py:262-331 (transform_to_srf; the weights of :288-312, the sum and fill mask of :318-327), which
+ * starcop/process_aviris.py:26-90 (aviris_as_sensor) runs once per WorldView-3 / Sentinel-2 band and per 50-column window.
+ *   sc_srf_bands : out[j][l][s] = sum over k in support(j) of w[k] * x[l][s][band[k]] for every output band j < n_out in one launch;
+ *                  each product in fp64 (float32 value promoted exactly), added in ascending band order onto a +0.0 seed,
+ *                  rounded once to float32 -- bit-equal to numpy's np.sum(w[:, None, None] * x_stack, axis=0).  With
+ *                  has_fill, out[j][l][s] = fill where any support value equals fill (float32 comparison).
+ * Cube element (l, s, b) = x[l*line_stride + s*sample_stride + b*band_stride] (elements, >= 0): ENVI BIP / BIL / BSQ memmap chunks
+ * and permuted tensor views are read in place; only the band window [min band, max band] of the CSR is read.  Output plane j,
+ * line l starts at out + j*out_plane_stride + l*out_line_stride (samples dense), so a chunk can land at a line offset of a whole
+ * flight-line buffer.  The weights are CSR rows (ptr[n_out + 1], band[nnz] strictly ascending within a row, w[nnz] fp64) given
+ * twice: on the device for the kernel, and ptr_host / band_host for the argument checks and the band window (no device read
+ * back).  SC_ERR_ARG for bad dims, n_out outside [1, 64], an empty row, a band outside [0, B) or a row that is not ascending.
+ * No atomics: repeated calls give identical bits.                                                                        */
+typedef struct sc_srf_args {
+  const float* x;              /* cube element (0, 0, 0)                                  */
+  int64_t line_stride;         /* elements                                                */
+  int64_t sample_stride;
+  int64_t band_stride;
+  int32_t L, S, B;             /* lines, samples, bands                                   */
+  int32_t n_out;               /* output bands, 1..64                                     */
+  const int32_t* ptr;          /* [n_out + 1] device                                      */
+  const int32_t* band;         /* [nnz] device                                            */
+  const double* w;             /* [nnz] device                                            */
+  const int32_t* ptr_host;     /* the same ptr / band on the host                         */
+  const int32_t* band_host;
+  float* out;                  /* float32                                                 */
+  int64_t out_plane_stride;    /* elements between output bands                          */
+  int64_t out_line_stride;     /* elements between output lines                           */
+  int32_t has_fill;
+  float fill;
+} sc_srf_args;
+int sc_srf_bands(const sc_srf_args* a, sc_stream stream);
+
 /* ------------------------------------------------------------------------- */
 /* evaluation masks of the baselines and of run_validation.
  * Thresholded prediction with an optional binary opening by a 3x3 structuring element:

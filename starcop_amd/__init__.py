@@ -12,6 +12,8 @@ Public surface (mirrors the reference):
   starcop_amd.features.FEATURES / extract_features / ratio_MLR_local (+ _5IN / _9IN / _5IN_simplediv) / mlr_fit /
     ratio_2c_match_c_from_sums_outlier / weight_mag1c
   starcop_amd.mask_creation.proposed_mask / connected_components / write_label_masks (the labelbinary target)
+  starcop_amd.aviris.load_srf_wv3 / load_srf_s2 / transform_to_srf / transform_to_worldview_3 / transform_to_sentinel_2;
+    starcop_amd.pipeline.aviris_as_sensor (the simulated WV3 / S2 bands of an AVIRIS-NG flight line)
 All compute runs in starcop_amd/libstarcop_hip.so (include/starcop_hip.h); there is no CPU fallback.
 """
 __version__ = "0.1.0"

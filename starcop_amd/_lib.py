@@ -98,6 +98,15 @@ class sc_mlr_args(C.Structure):
 
 MLR_C_MATCHED, MLR_SIMPLE_PLUS, MLR_RESIDUAL = 0, 1, 2
 
+
+class sc_srf_args(C.Structure):
+    """spectral-response-function band simulation operands (include/starcop_hip.h: sc_srf_args)"""
+    _fields_ = [("x", C.c_void_p), ("line_stride", C.c_int64), ("sample_stride", C.c_int64), ("band_stride", C.c_int64),
+                ("L", C.c_int32), ("S", C.c_int32), ("B", C.c_int32), ("n_out", C.c_int32),
+                ("ptr", C.c_void_p), ("band", C.c_void_p), ("w", C.c_void_p), ("ptr_host", C.c_void_p), ("band_host", C.c_void_p),
+                ("out", C.c_void_p), ("out_plane_stride", C.c_int64), ("out_line_stride", C.c_int64),
+                ("has_fill", C.c_int32), ("fill", C.c_float)]
+
 _vp, _i, _f, _d, _sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/starcop_hip.h declares
@@ -171,6 +180,7 @@ SIGNATURES = {
     "sc_mlr_predict": (_i, [C.POINTER(sc_mlr_args), _vp, _vp, _vp]),
     "sc_mlr_ratio": (_i, [C.POINTER(sc_mlr_args), _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "sc_label_workspace_bytes": (_sz, [_i, _i, _i]),
+    "sc_srf_bands": (_i, [C.POINTER(sc_srf_args), _vp]),
     "sc_connected_components": (_i, [_vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "sc_proposed_mask": (_i, [_vp, C.c_int64, _vp, C.c_int64, _f, _i, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "sc_packed_weight_floats_thin16": (_sz, [_i, _i, _i]),

@@ -1,0 +1,191 @@
+"""WorldView-3 and Sentinel-2 bands simulated from AVIRIS-NG radiance on the GPU.
+
+Mirrors the reference's starcop/data/aviris.py:155-331 (load_srf_s2, load_srf_wv3, transform_to_worldview_3,
+transform_to_sentinel_2, transform_to_srf): each simulated band is the spectral response function (SRF) of the sensor band
+resampled to the nearest AVIRIS band, normalised to sum one, applied as a float64 weighted sum over those AVIRIS bands.
+The weights are built on the host (:func:`srf_weights`, the reference's pandas arithmetic); the sums run in libstarcop_hip.so
+(include/starcop_hip.h: sc_srf_bands), all output bands in one pass over the cube.  The file-to-file driver is
+``pipeline.aviris_as_sensor``.
+"""
+import numpy as np
+import pandas as pd
+import torch
+
+from . import _lib
+from ._lib import check, ptr, stream
+
+SRF_S2 = None
+SRF_WV3 = None
+
+BANDS_S2_RESOLUTION = {"B1": 60, "B2": 10, "B3": 10, "B4": 10, "B5": 20, "B6": 20, "B7": 20, "B8": 10, "B8A": 20, "B9": 60,
+                       "B10": 60, "B11": 20, "B12": 20}
+
+SRF_WV3_FILE = "gs://starcop/WV3/WV3-SRF.csv"
+SRF_S2_FILE = "gs://starcop/S2/S2-SRF_joint.csv"
+
+NOUT_MAX = 64                      # output bands per sc_srf_bands call
+
+
+def _read_srf(path):
+    """CSV indexed by SR_WL without the rows where no band is above 1e-6 (aviris.py:178-185, 206-213)"""
+    if str(path).startswith("gs://"):
+        raise NotImplementedError(f"{path}: reading from Google Cloud Storage is not supported; pass a local copy with "
+                                  "path_override (with cache=True it is then used by the transform_to_* functions)")
+    srf = pd.read_csv(path).set_index("SR_WL")
+    return srf.loc[np.any((srf > 1e-6).values, axis=1)]
+
+
+def load_srf_s2(cache=True, path_override=None, drop_by_minimum=False):
+    """Sentinel-2 SRF table (columns S2A_SR_AV_B1.. / S2B_SR_AV_B1..).  ``drop_by_minimum``: also drop the rows
+    411 .. drop_by_minimum - 1 nm, as the reference does."""
+    global SRF_S2
+    if cache and SRF_S2 is not None:
+        return SRF_S2
+    srf = _read_srf(SRF_S2_FILE if path_override is None else path_override)
+    if drop_by_minimum:
+        srf = srf.drop(list(range(411, drop_by_minimum)))
+    if cache:
+        SRF_S2 = srf
+    return srf
+
+
+def load_srf_wv3(cache=True, path_override=None):
+    """WorldView-3 SWIR SRF table (columns SWIR1..SWIR8)"""
+    global SRF_WV3
+    if cache and SRF_WV3 is not None:
+        return SRF_WV3
+    srf = _read_srf(SRF_WV3_FILE if path_override is None else path_override)
+    if cache:
+        SRF_WV3 = srf
+    return srf
+
+
+def nearest_band(bands_nanometers, wavelengths):
+    """index of the nearest AVIRIS band of every wavelength: scipy's interp1d(centres, arange, kind="nearest") -- midpoints
+    computed as c[i] / 2 + c[i + 1] / 2, a wavelength exactly on one goes to the lower band, one outside [min, max] of the
+    centres raises ValueError"""
+    c = np.asarray(bands_nanometers, dtype=np.float64)
+    order = np.argsort(c, kind="mergesort")
+    cs = c[order]
+    q = np.asarray(wavelengths, dtype=np.float64)
+    if np.any(q < cs[0]) or np.any(q > cs[-1]):
+        raise ValueError(f"SRF wavelengths outside the AVIRIS band range [{cs[0]}, {cs[-1]}] nm")
+    half = cs / 2.0
+    idx = np.searchsorted(half[1:] + half[:-1], q, side="left").clip(0, len(cs) - 1)
+    return order[idx]
+
+
+def srf_weights(bands, srf, bands_nanometers):
+    """Host CSR of the AVIRIS weights of each output band (aviris.py:288-312): rows of ``srf[band]`` above 1e-4, normalised by
+    their sum, summed per nearest AVIRIS band (pandas' group sum) in ascending band order.
+    -> (ptr int32 [len(bands) + 1], band int32 [nnz], w float64 [nnz])"""
+    nearest = nearest_band(bands_nanometers, srf.index)
+    ptrs, idx, wts = [0], [], []
+    for name in bands:
+        col = srf[name]
+        keep = ~(col <= 1e-4).values
+        kept = col[keep]
+        per_band = (kept / kept.sum()).groupby(nearest[keep]).sum()
+        idx.append(per_band.index.values.astype(np.int32))
+        wts.append(per_band.values.astype(np.float64))
+        ptrs.append(ptrs[-1] + len(per_band))
+    return (np.asarray(ptrs, dtype=np.int32), np.concatenate(idx).astype(np.int32) if idx else np.zeros(0, np.int32),
+            np.concatenate(wts) if wts else np.zeros(0, np.float64))
+
+
+class SrfPlan:
+    """Host CSR uploaded once, split into calls of at most 64 output bands; ``run`` computes them for one cube."""
+
+    def __init__(self, ptrs, band, w, device="cuda"):
+        ptrs = np.asarray(ptrs, dtype=np.int64)
+        self.n_out = len(ptrs) - 1
+        self.parts = []
+        for j0 in range(0, self.n_out, NOUT_MAX):
+            j1 = min(j0 + NOUT_MAX, self.n_out)
+            k0, k1 = int(ptrs[j0]), int(ptrs[j1])
+            p = np.ascontiguousarray(ptrs[j0:j1 + 1] - k0, dtype=np.int32)
+            b = np.ascontiguousarray(band[k0:k1], dtype=np.int32)
+            if b.size == 0:
+                b = np.zeros(1, np.int32)        # every row empty: the call raises on the empty row, not on a null pointer
+            wk = np.ascontiguousarray(w[k0:k1], dtype=np.float64)
+            dev = [torch.from_numpy(a.copy() if a.size else np.zeros(1, a.dtype)).to(device) for a in (p, b, wk)]
+            self.parts.append((j0, j1, p, b, dev))
+
+    def run(self, x, out, fill=None):
+        """x: device float32 (L, S, B) view with any non-negative strides; out: device float32 (n_out, L, S) view with dense
+        samples (its plane and line strides are passed on)"""
+        lib = _lib.load()
+        _lib.require_device(x)
+        _lib.require_device(out)
+        if x.dtype != torch.float32 or out.dtype != torch.float32:
+            raise ValueError("sc_srf_bands: float32 cube and output expected")
+        if x.dim() != 3 or out.dim() != 3 or tuple(out.shape) != (self.n_out,) + tuple(x.shape[:2]):
+            raise ValueError(f"sc_srf_bands: cube {tuple(x.shape)} and output {tuple(out.shape)} do not match {self.n_out} bands")
+        if out.shape[2] > 1 and out.stride(2) != 1:
+            raise ValueError("sc_srf_bands: output samples must be dense")
+        L, S, B = x.shape
+        for j0, j1, p, b, (pd_, bd, wd) in self.parts:
+            a = _lib.sc_srf_args()
+            a.x = x.data_ptr()
+            a.line_stride, a.sample_stride, a.band_stride = x.stride()
+            a.L, a.S, a.B, a.n_out = L, S, B, j1 - j0
+            a.ptr, a.band, a.w = pd_.data_ptr(), bd.data_ptr(), wd.data_ptr()
+            a.ptr_host, a.band_host = p.ctypes.data, b.ctypes.data
+            a.out = out[j0].data_ptr()
+            a.out_plane_stride, a.out_line_stride = out.stride(0), out.stride(1)
+            a.has_fill = int(fill is not None)
+            a.fill = float(fill) if fill is not None else 0.0
+            check(lib.sc_srf_bands(a, stream()))
+        return out
+
+
+def transform_to_srf(aviris, bands, srf, resolution_dst=10, bands_nanometers_aviris=None, fill_value_default=0., sigma_bands=None,
+                     verbose=False):
+    """aviris.py:262-331 on the GPU: ``aviris`` is a (C, H, W) float32 device tensor with any strides (``bip.permute(2, 0, 1)`` is
+    read in place) or numpy array; returns the (len(bands), H, W) float32 simulated bands as a device tensor (numpy for numpy).
+    Pixels holding ``fill_value_default`` in any band of a support become ``fill_value_default`` (None: nothing is masked).
+    ``bands_nanometers_aviris`` (the C band centres) is required; resampling to ``resolution_dst`` is not implemented, pass None."""
+    if resolution_dst is not None:
+        raise NotImplementedError("transform_to_srf: resampling to resolution_dst is not implemented; pass resolution_dst=None")
+    if bands_nanometers_aviris is None:
+        raise ValueError("transform_to_srf: bands_nanometers_aviris is required (a tensor carries no band descriptions)")
+    host = isinstance(aviris, np.ndarray)
+    x = aviris
+    if host:
+        a = aviris if all(s >= 0 for s in aviris.strides) else np.ascontiguousarray(aviris)
+        _lib.require_device()
+        x = torch.from_numpy(a).cuda()
+    if x.dim() != 3 or x.shape[0] != len(bands_nanometers_aviris):
+        raise ValueError(f"transform_to_srf: expected a (C, H, W) cube with C = {len(bands_nanometers_aviris)} bands, "
+                         f"got {tuple(x.shape)}")
+    if x.dtype != torch.float32:
+        raise ValueError(f"transform_to_srf: float32 radiance expected, got {x.dtype}")
+    _lib.require_device(x)
+    ptrs, band, w = srf_weights(list(bands), srf, bands_nanometers_aviris)
+    if verbose:
+        print(f"transform_to_srf: {len(bands)} bands from {len(band)} AVIRIS band weights")
+    out = torch.empty((len(bands),) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
+    SrfPlan(ptrs, band, w, x.device).run(x.permute(1, 2, 0), out, fill_value_default)
+    return out.cpu().numpy() if host else out
+
+
+def transform_to_worldview_3(aviris, bands_wv3, resolution_dst=10, bands_nanometers_aviris=None, fill_value_default=0., verbose=False):
+    """aviris.py:224-234: the WV3 SWIR bands ``bands_wv3`` (e.g. ["SWIR1", ...]) with the cached SRF (load_srf_wv3)"""
+    return transform_to_srf(aviris, bands_wv3, load_srf_wv3(), resolution_dst=resolution_dst,
+                            bands_nanometers_aviris=bands_nanometers_aviris, fill_value_default=fill_value_default, verbose=verbose)
+
+
+def sentinel_2_srf(sensor="S2A"):
+    """the columns of the joint S2 table that belong to ``sensor``, renamed from f"{sensor}_SR_AV_B1" to "B1" (aviris.py:244-245)"""
+    srf_s2 = load_srf_s2()
+    srf = srf_s2[[c for c in srf_s2.columns if sensor in c]].copy()
+    srf.columns = [c.replace(f"{sensor}_SR_AV_", "") for c in srf.columns]
+    return srf
+
+
+def transform_to_sentinel_2(aviris, bands_s2, resolution_dst=10, sensor="S2A", bands_nanometers_aviris=None, fill_value_default=0.,
+                            verbose=False):
+    """aviris.py:237-259: the S2A or S2B bands ``bands_s2`` (e.g. ["B8A", "B11"]) with the cached joint SRF (load_srf_s2); the
+    anti-aliasing sigmas of the reference only matter for the resampling, which is not implemented"""
+    return transform_to_srf(aviris, bands_s2, sentinel_2_srf(sensor), resolution_dst=resolution_dst,
+                            bands_nanometers_aviris=bands_nanometers_aviris, fill_value_default=fill_value_default, verbose=verbose)

@@ -261,3 +261,120 @@ def aviris_scene_mag1c(aviris_img_folder, mf_filename, albedo_filename=None, use
     if albedo_filename is not None:
         io.write_tiff(albedo_filename, alb.cpu().numpy(), blocksize=128, extra_tags={**tags, **io.gdal_metadata_tag(md, ["Albedo"])})
     return mf, alb
+
+
+BANDS_S2 = ["B1", "B2", "B3", "B4", "B5", "B6", "B7", "B8", "B8A", "B9", "B10", "B11", "B12"]
+BANDS_WV3 = ["SWIR1", "SWIR2", "SWIR3", "SWIR4", "SWIR5", "SWIR6", "SWIR7", "SWIR8"]
+BANDS_SENSOR = {"S2A": BANDS_S2, "S2B": BANDS_S2, "WV3": BANDS_WV3}
+
+_NANOMETERS = ("nanometers", "nanometer", "nm")
+
+
+def _nodata_text(v):
+    return f"{float(v):.9g}"
+
+
+@torch.no_grad()
+def aviris_as_sensor(aviris_img_folder_or_path, folder_dest, sensors=list(BANDS_SENSOR), bands=BANDS_SENSOR, columns_read=50,
+                     path_tiffs_temp=".", disable_pbar=True, device="cuda", lines_per_chunk=None):
+    """``aviris_as_sensor`` of the reference (starcop/process_aviris.py:26-90) on the MI355X: writes
+    ``{folder_dest}/{sensor}_{band}.tif`` for every band of ``bands[sensor]`` (WV3 SWIR1..8, S2A / S2B B1..B12) simulated from the
+    ENVI radiance ``<name>_img`` of an AVIRIS-NG flight-line folder, skipping files that already exist.  The SRF tables come from the
+    module caches of :mod:`starcop_amd.aviris` (``load_srf_wv3`` / ``load_srf_s2`` with ``path_override``).
+
+    The cube is streamed in chunks of ``lines_per_chunk`` lines (default: about 256 MB) memmap -> pinned staging -> device with two
+    buffers, so the upload of one chunk overlaps the kernel on the previous one; one ``sc_srf_bands`` call per chunk computes every
+    missing band of every sensor.  Band centres come from the header (nanometers), the fill value from its ``data ignore value``
+    (none: nothing is masked and no nodata tag is written).  Outputs: float32 (lines, samples), tiled 128 x 128, the radiance file's
+    georeferencing, GDAL_NODATA = the fill value, the band name as description.  ``columns_read``, ``path_tiffs_temp`` and
+    ``disable_pbar`` are accepted for the reference's signature and ignored.  Returns the list of files written."""
+    import os
+    from concurrent.futures import ThreadPoolExecutor
+    from . import aviris, io_formats as io
+    for sensor in sensors:
+        if sensor != "WV3" and not str(sensor).startswith("S2"):
+            raise NotImplementedError(f"Sensor {sensor} not known. Expected sensors [WV3, S2A, S2B]")
+    src = str(aviris_img_folder_or_path)
+    if src.endswith(".tif"):
+        raise NotImplementedError(f"{src}: only ENVI flight-line folders are supported, not GeoTIFF radiance")
+    if str(folder_dest).startswith("gs://"):
+        raise NotImplementedError(f"{folder_dest}: writing to Google Cloud Storage is not supported")
+    folder = src.rstrip("/")
+    name = os.path.basename(folder)
+    envi_path = os.path.join(folder, f"{name}_img")
+    if not os.path.exists(envi_path):
+        raise NotImplementedError(f"{folder}: no ENVI radiance {name}_img; the one-file-per-band layout is not supported")
+    todo = [(sensor, band, os.path.join(folder_dest, f"{sensor}_{band}.tif")) for sensor in sensors for band in bands[sensor]]
+    todo = [t for t in todo if not os.path.exists(t[2])]
+    if not todo:
+        return []
+    os.makedirs(folder_dest, exist_ok=True)
+
+    cube, meta = io.open_envi(envi_path)
+    header = meta["header"]
+    units = str(header.get("wavelength units", "nanometers")).strip().lower()
+    if units not in _NANOMETERS:
+        raise ValueError(f"{envi_path}: wavelength units '{units}', expected nanometers")
+    if meta["wavelengths"] is None:
+        raise ValueError(f"{envi_path}: the header has no wavelength list")
+    if cube.dtype.kind not in "fiu" or (cube.dtype.kind == "f" and cube.dtype.itemsize != 4) or \
+            (cube.dtype.kind in "iu" and cube.dtype.itemsize > 2):
+        raise NotImplementedError(f"{envi_path}: radiance of type {cube.dtype} (float32 or 8/16-bit integers expected)")
+    fill = header.get("data ignore value")
+    fill = float(fill) if fill is not None else None
+
+    ptr_parts, band_parts, w_parts = [np.zeros(1, np.int32)], [], []
+    for sensor in dict.fromkeys(s for s, _, _ in todo):
+        names = [b for s, b, _ in todo if s == sensor]
+        srf = aviris.load_srf_wv3() if sensor == "WV3" else aviris.sentinel_2_srf(sensor)
+        p, b, w = aviris.srf_weights(names, srf, meta["wavelengths"])
+        ptr_parts.append(p[1:] + ptr_parts[-1][-1])
+        band_parts.append(b)
+        w_parts.append(w)
+    plan = aviris.SrfPlan(np.concatenate(ptr_parts), np.concatenate(band_parts), np.concatenate(w_parts), device)
+
+    L, S, B = cube.shape
+    perm = tuple(int(v) for v in np.argsort([-s for s in cube.strides], kind="stable"))    # memory order of (line, sample, band)
+    inv = tuple(int(v) for v in np.argsort(perm))
+    if lines_per_chunk is None:
+        lines_per_chunk = max(1, (256 << 20) // (S * B * 4))
+    lpc = max(1, min(int(lines_per_chunk), L))
+    nmax = lpc * S * B
+    out = torch.empty((plan.n_out, L, S), dtype=torch.float32, device=device)
+    pinned = [torch.empty(nmax, dtype=torch.float32).pin_memory() for _ in range(2)]
+    staged = [torch.empty(nmax, dtype=torch.float32, device=device) for _ in range(2)]
+    uploaded = [torch.cuda.Event() for _ in range(2)]
+    consumed = [torch.cuda.Event() for _ in range(2)]
+    used = [False, False]
+    compute = torch.cuda.current_stream(device)
+    upload = torch.cuda.Stream(device)
+    for c, l0 in enumerate(range(0, L, lpc)):
+        i = c % 2
+        n = min(lpc, L - l0)
+        raw = cube[l0:l0 + n].transpose(perm)
+        if used[i]:
+            uploaded[i].synchronize()                         # the previous upload from this pinned buffer has finished
+        host = pinned[i][:raw.size].view(raw.shape)
+        np.copyto(host.numpy(), raw, casting="unsafe")
+        dev = staged[i][:raw.size].view(raw.shape)
+        with torch.cuda.stream(upload):
+            if used[i]:
+                upload.wait_event(consumed[i])                # the kernel that read this device buffer has finished
+            dev.copy_(host, non_blocking=True)
+            uploaded[i].record(upload)
+        compute.wait_event(uploaded[i])
+        plan.run(dev.permute(inv), out[:, l0:l0 + n], fill)
+        consumed[i].record(compute)
+        used[i] = True
+    result = out.cpu().numpy()
+
+    geo = io.envi_geo_tags(header)
+    if fill is not None:
+        geo[42113] = (2, (_nodata_text(fill),))
+
+    def write(j):
+        _, band, path = todo[j]
+        io.write_tiff(path, result[j], blocksize=128, extra_tags={**geo, **io.gdal_metadata_tag({}, [band])})
+        return path
+    with ThreadPoolExecutor(max_workers=min(8, len(todo))) as pool:
+        return list(pool.map(write, range(len(todo))))
