@@ -717,6 +717,42 @@ typedef struct sc_srf_args {
 } sc_srf_args;
 int sc_srf_bands(const sc_srf_args* a, sc_stream stream);
 
+/* Window statistics of a mag1c flight line: the table scripts/preprocessing/stats_mag1c.py:24-70 writes (512 x 512 windows at
+ * overlap 256) and starcop/data/sampling_dataset.py:112-179, 408-439 samples the no-plume windows from.
+ *   sc_window_stats : for each of n_win windows (row_off, col_off, height, width; any sizes, any overlap, duplicates allowed) of one
+ *                     float32 scene, over V = { min(v, clip_max) : v in window, v != fill (if has_fill), v >= 0 } (stats_mag1c.py:
+ *                     45-48: NaN fails v >= 0, -0.0 passes, +inf becomes clip_max, a NaN fill masks nothing):
+ *                       count[i]                 number of members (int64)
+ *                       sum_mean[i][0..1]        sum and mean, accumulated in fp64
+ *                       stats[i][0..6]           max, min, percentiles 1, 5, 50 (median), 95, 99 (float32)
+ *                     Percentiles are numpy.percentile(method="linear") / numpy.median of the float32 values as numpy >= 2.0
+ *                     evaluates them: virtual index float32(count - 1) * (float32(q) / float32(100)), the two neighbouring EXACT
+ *                     order statistics a <= b, weight t = frac(index), a + (b - a) * t, or b - (b - a) * (1 - t) where t >= 0.5,
+ *                     every operation rounded to float32; median = (a + b) / 2 of the two middle order statistics.  The sign of a
+ *                     zero result is unspecified (-0.0 and +0.0 are equal keys).  count == 0: count 0, NaN everywhere else.
+ * Scene element (r, c) = x[r*row_stride + c] (row_stride >= W elements): a column slice of a wider tensor is read in place, no
+ * per-window copies.  The windows are given twice: on the device for the kernels, on the host for the argument check (every window
+ * inside the scene, height and width >= 1) that runs before anything is launched.  H*W < 2^31, 1 <= n_win <= 2^20, clip_max >= 0.
+ * All ten order statistics of a window are resolved together by an exact 3-pass radix select (11 + 10 + 10 bits of the non-
+ * negative float bit patterns); integer histogram atomics only, the fp64 sums are added in a fixed order: repeated calls give
+ * identical bits.  7 launches per call.  work: sc_window_stats_workspace_bytes(n_win) bytes (about 48 KiB per window).      */
+typedef struct sc_winstats_args {
+  const float* x;                /* scene element (0, 0), device                            */
+  int64_t row_stride;            /* elements                                                */
+  int32_t H, W;
+  int32_t has_fill;
+  float fill;
+  float clip_max;
+  int32_t n_win;
+  const int32_t* windows;        /* [n_win][4] device                                       */
+  const int32_t* windows_host;   /* the same on the host                                    */
+  int64_t* count;                /* [n_win] device                                          */
+  double* sum_mean;              /* [n_win][2] device                                       */
+  float* stats;                  /* [n_win][7] device                                       */
+} sc_winstats_args;
+size_t sc_window_stats_workspace_bytes(int n_win);
+int sc_window_stats(const sc_winstats_args* a, void* work, size_t work_bytes, sc_stream stream);
+
 /* ------------------------------------------------------------------------- */
 /* evaluation masks of the baselines and of run_validation.
  * Thresholded prediction with an optional binary opening by a 3x3 structuring element:

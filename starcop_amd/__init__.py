@@ -14,6 +14,8 @@ Public surface (mirrors the reference):
   starcop_amd.mask_creation.proposed_mask / connected_components / write_label_masks (the labelbinary target)
   starcop_amd.aviris.load_srf_wv3 / load_srf_s2 / transform_to_srf / transform_to_worldview_3 / transform_to_sentinel_2;
     starcop_amd.pipeline.aviris_as_sensor (the simulated WV3 / S2 bands of an AVIRIS-NG flight line)
+  starcop_amd.sampling.window_stats / stats_mag1c (mag1c statistics of every 512 x 512 window of a flight line) /
+    mag1c_stats_dataframe / windows_intersect / select_non_overlapping / sampling_no_plumes (which windows become samples)
 All compute runs in starcop_amd/libstarcop_hip.so (include/starcop_hip.h); there is no CPU fallback.
 """
 __version__ = "0.1.0"

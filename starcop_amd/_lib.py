@@ -107,6 +107,15 @@ class sc_srf_args(C.Structure):
                 ("out", C.c_void_p), ("out_plane_stride", C.c_int64), ("out_line_stride", C.c_int64),
                 ("has_fill", C.c_int32), ("fill", C.c_float)]
 
+
+class sc_winstats_args(C.Structure):
+    """window-statistics operands (include/starcop_hip.h: sc_winstats_args)"""
+    _fields_ = [("x", C.c_void_p), ("row_stride", C.c_int64), ("H", C.c_int32), ("W", C.c_int32),
+                ("has_fill", C.c_int32), ("fill", C.c_float), ("clip_max", C.c_float), ("n_win", C.c_int32),
+                ("windows", C.c_void_p), ("windows_host", C.c_void_p),
+                ("count", C.c_void_p), ("sum_mean", C.c_void_p), ("stats", C.c_void_p)]
+
+
 _vp, _i, _f, _d, _sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/starcop_hip.h declares
@@ -181,6 +190,8 @@ SIGNATURES = {
     "sc_mlr_ratio": (_i, [C.POINTER(sc_mlr_args), _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "sc_label_workspace_bytes": (_sz, [_i, _i, _i]),
     "sc_srf_bands": (_i, [C.POINTER(sc_srf_args), _vp]),
+    "sc_window_stats_workspace_bytes": (_sz, [_i]),
+    "sc_window_stats": (_i, [C.POINTER(sc_winstats_args), _vp, _sz, _vp]),
     "sc_connected_components": (_i, [_vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "sc_proposed_mask": (_i, [_vp, C.c_int64, _vp, C.c_int64, _f, _i, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "sc_packed_weight_floats_thin16": (_sz, [_i, _i, _i]),
