@@ -753,6 +753,47 @@ typedef struct sc_winstats_args {
 size_t sc_window_stats_workspace_bytes(int n_win);
 int sc_window_stats(const sc_winstats_args* a, void* work, size_t work_bytes, sc_stream stream);
 
+/* Orthorectification of EMIT products through the granule's geometry look-up table: what starcop/models/mag1c_emit.py:86-88
+ * (ei.georreference(mag1c_output, fill_value_default=...) and the same on the albedo, the georreferenced=True default of
+ * mag1c_emit) leaves in its outputs; the gather is restated in the note at mag1c_emit.py:206-221 (single_image_ortho).
+ *   sc_glt_ortho : for P planes in one launch
+ *                    out[p][i][j] = src_p[gy - 1][gx - 1]   if glt_x[i][j] != 0 and glt_y[i][j] != 0
+ *                                   fill[p]                 otherwise
+ *                  with (gx, gy) = (glt_x[i][j], glt_y[i][j]) (1-based column / row of the swath), or their absolute values when
+ *                  `absolute` is set (AVIRIS-NG GLTs mark interpolated pixels with a negative index).
+ * Pure data movement: elements are copied as words of elem_bytes (1, 2, 4 or 8; one width per call) and fill values are bit patterns
+ * (the low elem_bytes of fill_bits[p]), so the result is bit-equal to the numpy gather for float32, float64, uint8, int16, int32,
+ * .. including NaN payloads and -0.0.  Source plane p is read in place: element (r, c) = src[p] + (r*row_stride[p] +
+ * c*col_stride[p]) elements, strides >= 0 -- a stacked (P, rows, cols) tensor is src[p] = base + p*plane_stride, a pixel-interleaved
+ * (rows, cols, C) cube is src[p] = base + p with col_stride = C, lists of separate tensors and permuted views likewise.  A plane may
+ * cover only the top-left plane_rows[p] x plane_cols[p] of the swath (0 = the whole swath): GLT entries beyond it give fill[p].
+ * glt_x / glt_y: dense int32 [out_h][out_w]; out: dense [P][out_h][out_w].
+ * A GLT entry that is not no-data and points outside the swath (gx > cols, gy > rows, or negative without `absolute`) is never
+ * dereferenced: the pixel gets fill[p] in every plane and *oob_count (device, may be NULL; the caller zeroes it) is incremented once
+ * per such pixel.  The two GLT words are read once per pixel; 16-byte stores when out_w * elem_bytes is a multiple of 16 and out /
+ * glt_x / glt_y are 16-byte aligned.  SC_ERR_ARG for bad dims, P outside [1, 64], an unsupported elem_bytes, null or misaligned
+ * pointers, negative strides, a plane extent outside the swath.  No other atomics: repeated calls give identical bits.          */
+#define SC_ORTHO_MAX_PLANES 64
+typedef struct sc_ortho_args {
+  const int32_t* glt_x;                          /* [out_h][out_w] device: 1-based swath column, 0 = no data */
+  const int32_t* glt_y;                          /* [out_h][out_w] device: 1-based swath row, 0 = no data    */
+  int32_t out_h, out_w;
+  int32_t rows, cols;                            /* the swath the GLT indexes                                 */
+  int32_t P;                                     /* planes, 1..64                                             */
+  int32_t elem_bytes;                            /* 1, 2, 4 or 8                                              */
+  int32_t absolute;                              /* use |gx|, |gy|                                            */
+  int32_t reserved;
+  const void* src[SC_ORTHO_MAX_PLANES];          /* element (0, 0) of every plane, device                     */
+  int64_t row_stride[SC_ORTHO_MAX_PLANES];       /* elements                                                  */
+  int64_t col_stride[SC_ORTHO_MAX_PLANES];
+  int32_t plane_rows[SC_ORTHO_MAX_PLANES];       /* extent of the plane inside the swath; 0 = rows / cols     */
+  int32_t plane_cols[SC_ORTHO_MAX_PLANES];
+  uint64_t fill_bits[SC_ORTHO_MAX_PLANES];       /* raw bit pattern of every plane's fill value               */
+  void* out;                                     /* [P][out_h][out_w] device                                  */
+  uint64_t* oob_count;                           /* device, or NULL                                           */
+} sc_ortho_args;
+int sc_glt_ortho(const sc_ortho_args* a, sc_stream stream);
+
 /* ------------------------------------------------------------------------- */
 /* evaluation masks of the baselines and of run_validation.
  * Thresholded prediction with an optional binary opening by a 3x3 structuring element:

@@ -16,6 +16,8 @@ Public surface (mirrors the reference):
     starcop_amd.pipeline.aviris_as_sensor (the simulated WV3 / S2 bands of an AVIRIS-NG flight line)
   starcop_amd.sampling.window_stats / stats_mag1c (mag1c statistics of every 512 x 512 window of a flight line) /
     mag1c_stats_dataframe / windows_intersect / select_non_overlapping / sampling_no_plumes (which windows become samples)
+  starcop_amd.ortho.georeference / emit_geo_tags (orthorectification through a geometry look-up table); starcop_amd.mag1c.mag1c_emit
+    (the EMIT driver with its georreferenced=True default); pipeline.emit_granule_predict(georeferenced=True, out_folder=...)
 All compute runs in starcop_amd/libstarcop_hip.so (include/starcop_hip.h); there is no CPU fallback.
 """
 __version__ = "0.1.0"

@@ -116,6 +116,20 @@ class sc_winstats_args(C.Structure):
                 ("count", C.c_void_p), ("sum_mean", C.c_void_p), ("stats", C.c_void_p)]
 
 
+ORTHO_MAX_PLANES = 64
+
+
+class sc_ortho_args(C.Structure):
+    """GLT orthorectification operands (include/starcop_hip.h: sc_ortho_args)"""
+    _fields_ = [("glt_x", C.c_void_p), ("glt_y", C.c_void_p), ("out_h", C.c_int32), ("out_w", C.c_int32),
+                ("rows", C.c_int32), ("cols", C.c_int32), ("P", C.c_int32), ("elem_bytes", C.c_int32),
+                ("absolute", C.c_int32), ("reserved", C.c_int32),
+                ("src", C.c_void_p * ORTHO_MAX_PLANES), ("row_stride", C.c_int64 * ORTHO_MAX_PLANES),
+                ("col_stride", C.c_int64 * ORTHO_MAX_PLANES), ("plane_rows", C.c_int32 * ORTHO_MAX_PLANES),
+                ("plane_cols", C.c_int32 * ORTHO_MAX_PLANES), ("fill_bits", C.c_uint64 * ORTHO_MAX_PLANES),
+                ("out", C.c_void_p), ("oob_count", C.c_void_p)]
+
+
 _vp, _i, _f, _d, _sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/starcop_hip.h declares
@@ -192,6 +206,7 @@ SIGNATURES = {
     "sc_srf_bands": (_i, [C.POINTER(sc_srf_args), _vp]),
     "sc_window_stats_workspace_bytes": (_sz, [_i]),
     "sc_window_stats": (_i, [C.POINTER(sc_winstats_args), _vp, _sz, _vp]),
+    "sc_glt_ortho": (_i, [C.POINTER(sc_ortho_args), _vp]),
     "sc_connected_components": (_i, [_vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "sc_proposed_mask": (_i, [_vp, C.c_int64, _vp, C.c_int64, _f, _i, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "sc_packed_weight_floats_thin16": (_sz, [_i, _i, _i]),

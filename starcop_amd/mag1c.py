@@ -2,7 +2,7 @@
 (/root/reference/starcop/models/mag1c.py: rmf :284, acrwl1mf :177, func_by_groups :117,
 get_mask_bad_bands :98, generate_template_from_bands :60) plus the two drivers' group semantics
 (starcop/process_aviris.py:189-219 -> :func:`acrwl1mf_by_groups`, starcop/models/mag1c_emit.py:40-90 ->
-:func:`mag1c_columns`).
+:func:`mag1c_columns`, and :func:`mag1c_emit` with the reference function's name and its georreferenced=True default).
 
 All groups of a scene are filtered by ONE launch of ``sc_mag1c_groups`` (a work-group per group, all 31
 covariance/Cholesky rounds inside the kernel); the host only sorts pixel indices by group (torch plumbing) and
@@ -403,6 +403,42 @@ def mag1c_columns(raw, template, fill_value=-9999.0, column_step=None, num_iter=
     # Pixel order inside a block follows the reference's boolean indexing raw[:, c0:c1][valid] (row-major).
     return _run_column_groups(raw, 0, S, valid, gcol, 0, template, num_iter, covariance_lerp_alpha, 1.0,
                               (False, False, False, True), float(fill_value), torch.float32)
+
+
+@torch.no_grad()
+def mag1c_emit(raw, wavelengths, fwhm, fill_value=-9999.0, glt_x=None, glt_y=None, georreferenced=True, column_step=None,
+               num_iter=30, covariance_lerp_alpha=1e-4, use_wavelength_range=DEFAULT_WAVELENGTH_RANGE):
+    """``mag1c_emit`` of the reference (starcop/models/mag1c_emit.py:16-90) without the ``EMITImage`` object: ``raw`` is its
+    ``load_raw(transpose=False)`` (rows, cols, bands) radiance, ``wavelengths`` / ``fwhm`` its band centres and widths (nm),
+    ``fill_value`` its ``fill_value_default``, ``glt_x`` / ``glt_y`` its geometry look-up table (``location/glt_x|glt_y`` of the
+    granule).  Keeps the bands inside ``use_wavelength_range`` (:40-43), builds the CH4 target from them (:45-48), filters blocks
+    of ``column_step`` columns (None: the whole image at once, :56) with :func:`mag1c_columns` and, with ``georreferenced=True``
+    (the reference's default, :86-88), orthorectifies both results through the GLT (:func:`starcop_amd.ortho.georeference`,
+    no-data = ``fill_value``).  Returns (mf, albedo) float32 device tensors: (H_o, W_o) of the GLT, or (rows, cols) in sensor
+    geometry with ``georreferenced=False``."""
+    if georreferenced and (glt_x is None or glt_y is None):
+        raise ValueError("mag1c_emit: georreferenced=True needs the granule's glt_x and glt_y (pass georreferenced=False for "
+                         "sensor geometry)")
+    w = np.asarray(wavelengths, dtype=np.float64)
+    fw = np.asarray(fwhm, dtype=np.float64)
+    raw = torch.as_tensor(raw)
+    if raw.dim() != 3 or raw.shape[2] != w.size or fw.size != w.size:
+        raise ValueError(f"mag1c_emit: radiance {tuple(raw.shape)} does not end in the {w.size} bands of wavelengths / fwhm")
+    sel = (w >= use_wavelength_range[0]) & (w <= use_wavelength_range[1])
+    assert sel.any(), "There are no bands in the selected wavelength range"
+    idx = np.flatnonzero(sel)
+    if idx[-1] - idx[0] + 1 == idx.size:
+        sub = raw[..., int(idx[0]):int(idx[-1]) + 1]
+    else:
+        sub = raw[..., torch.from_numpy(idx).to(raw.device)]
+    target = generate_template_from_bands(centers=w[sel], fwhm=fw[sel])
+    mf, alb = mag1c_columns(sub, target[:, 1], fill_value, column_step=column_step, num_iter=num_iter,
+                            covariance_lerp_alpha=covariance_lerp_alpha)
+    if not georreferenced:
+        return mf, alb
+    from .ortho import georeference
+    out = georeference([mf, alb], glt_x, glt_y, fill_value_default=fill_value)
+    return out[0], out[1]
 
 
 # ------------------------------------------------------------------------------------------------

@@ -4,6 +4,7 @@ The reference spreads this over its drivers and notebooks; the steps and their o
   * EMIT (BASELINE configs[4]): ``mag1c_emit`` (starcop/models/mag1c_emit.py:16-90: bands in [2122, 2488] nm, float64
     filter on blocks of ``column_step`` columns) -> RGB = nearest bands to 640/550/460 nm -> range rescale of
     starcop/emit_tools/emit_dataset.py:62-106 -> ``model(x)`` -> sigmoid > 0.5;
+    optionally orthorectified through the granule's GLT and written as GeoTIFFs (``georeferenced=True``, ``out_folder``);
   * AVIRIS-NG (configs[2]): ``run_mag1c`` (starcop/process_aviris.py:189-219: per detector column, alpha = 0) and the
     pre-computed RGB products -> ``padded_predict``.
 Everything stays on the device between the stages; with ``torch.distributed`` initialised the column blocks of the
@@ -107,7 +108,7 @@ def _merge_column_shards(t, c0, c1, group=None):
 @torch.no_grad()
 def emit_scene_predict(model, raw, wavelengths, template, fill_value=-9999.0, column_step=2, num_iter=30,
                        covariance_lerp_alpha=1e-4, column_range=None, tile=None, halo=RECEPTIVE_HALO, ratio_bands=None,
-                       distributed=None, group=None, strips=True):
+                       distributed=None, group=None, strips=True, georeferenced=False, glt_x=None, glt_y=None):
     """``raw``: (rows, cols, S) float32 EMIT L1B radiance (device or host), ``wavelengths``: (S,) nm, ``template``: unit CH4
     absorption for the bands inside [2122, 2488] nm (``mag1c.generate_template_from_bands``; (K,) or (K, 2)).
     Returns a dict of device tensors: ``mf`` (rows, cols) ppm*m, ``albedo``, ``input`` (4, H', W') in the AVIRIS value range,
@@ -123,7 +124,11 @@ def emit_scene_predict(model, raw, wavelengths, template, fill_value=-9999.0, co
     inference tiles are partitioned over the ranks; the per-rank mf / albedo columns are merged (one all_reduce) before the
     network input is built, so every rank returns the full-scene result.  ``column_range=(c0, c1)`` (explicit manual shard,
     c0 / c1 on column_step boundaries) returns ONLY ``mf`` and ``albedo`` of that shard: a network input built from a partial
-    mf would be wrong for the whole scene."""
+    mf would be wrong for the whole scene.
+    ``georeferenced=True`` (with the granule's ``glt_x`` / ``glt_y``) orthorectifies the products: see
+    :func:`georeference_products`."""
+    if georeferenced and (glt_x is None or glt_y is None):
+        raise ValueError("emit_scene_predict: georeferenced=True needs glt_x and glt_y")
     raw = torch.as_tensor(raw)
     dev = raw.device if raw.is_cuda else model.device
     raw = raw.to(dev).float()
@@ -136,8 +141,44 @@ def emit_scene_predict(model, raw, wavelengths, template, fill_value=-9999.0, co
     if ratio_bands is not None:
         ia, ir = nearest_bands(w, ratio_bands)
         ratio = (raw[..., ia].contiguous(), raw[..., ir].contiguous())
-    return _emit_predict_parts(model, sub, rgb, ratio, template, fill_value, column_step, num_iter, covariance_lerp_alpha, column_range,
-                               tile, halo, distributed, group, strips)
+    out = _emit_predict_parts(model, sub, rgb, ratio, template, fill_value, column_step, num_iter, covariance_lerp_alpha, column_range,
+                              tile, halo, distributed, group, strips)
+    return georeference_products(out, glt_x, glt_y, fill_value) if georeferenced else out
+
+
+ORTHO_PRODUCTS = ("mf", "albedo", "prediction", "ratio", "pred_binary")
+
+
+def georeference_products(out, glt_x, glt_y, fill_value=-9999.0):
+    """Orthorectifies the 2-D products of an EMIT prediction dict through the granule's GLT (what ``georreferenced=True`` does to
+    the outputs of the reference's ``mag1c_emit``, mag1c_emit.py:86-88, extended to everything the notebook plots): ``mf``,
+    ``albedo``, ``prediction``, ``ratio`` and the three RGB planes of the network input (read in place from ``input[1:4]``, new key
+    ``rgb``) go through ONE ``sc_glt_ortho`` call (float32, no-data = ``fill_value``), ``pred_binary`` (int64, no-data = 0: not a
+    plume) through a second one -- one call per dtype, the GLT uploaded once.  The network output covers the swath cropped to
+    multiples of 32; GLT entries beyond it are no-data.  The sensor-geometry tensors stay in the dict under ``<key>_raw``;
+    ``input`` stays in sensor geometry."""
+    from .ortho import georeference
+    swath = tuple(out["mf"].shape)
+    dev = out["mf"].device
+    gx = torch.from_numpy(np.ascontiguousarray(glt_x, dtype=np.int32)).to(dev) if not isinstance(glt_x, torch.Tensor) else glt_x
+    gy = torch.from_numpy(np.ascontiguousarray(glt_y, dtype=np.int32)).to(dev) if not isinstance(glt_y, torch.Tensor) else glt_y
+    by_dtype = {}
+    for k in ORTHO_PRODUCTS:
+        if out.get(k) is not None:
+            by_dtype.setdefault(out[k].dtype, []).append(k)
+    res = dict(out)
+    for dt, keys in by_dtype.items():
+        planes = [out[k] for k in keys]
+        rgb = dt == torch.float32 and out.get("input") is not None
+        if rgb:
+            planes += list(out["input"][1:4].unbind(0))
+        fill = 0 if dt == torch.int64 else fill_value
+        geo = georeference(planes, gx, gy, fill_value_default=fill, shape=swath)
+        for i, k in enumerate(keys):
+            res[k + "_raw"], res[k] = out[k], geo[i]
+        if rgb:
+            res["rgb"] = geo[len(keys):]
+    return res
 
 
 def _emit_predict_parts(model, sub, rgb, ratio, template, fill_value, column_step, num_iter, covariance_lerp_alpha, column_range, tile, halo,
@@ -186,15 +227,32 @@ def _emit_predict_parts(model, sub, rgb, ratio, template, fill_value, column_ste
 
 @torch.no_grad()
 def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_lerp_alpha=1e-4, tile=None, halo=RECEPTIVE_HALO,
-                         ratio_bands=None, distributed=None, group=None, rows=None, threads=8, strips=True):
+                         ratio_bands=None, distributed=None, group=None, rows=None, threads=8, strips=True, georeferenced=False,
+                         out_folder=None, geotransform=None, overwrite=False):
     """The notebook path of the reference end to end FROM THE FILE (notebooks/inference_on_raw_EMIT_nc_file.ipynb cells 8-19:
     ``EMITImage(path)`` -> ``mag1c_emit`` -> RGB bands -> rescale -> ``model`` -> threshold): opens the EMIT L1B radiance granule
     (NetCDF-4) with :mod:`starcop_amd.hdf5_reader`, reads ONLY what the pipeline touches -- the contiguous band slice inside
     [2122, 2488] nm chunk-wise, the three RGB band planes, the two ratio bands if asked for: ~0.35 GB of the 1.8 GB cube -- builds the
     CH4 target from the file's band centres / widths (shipped look-up table) and runs :func:`emit_scene_predict`'s device pipeline.
     ``rows``: optional slice of downtrack lines.  Returns its dict plus ``wavelengths``, ``fwhm`` (the mag1c bands) and ``glt_x`` /
-    ``glt_y`` (host arrays, or None) for orthorectification by the caller."""
+    ``glt_y`` (host arrays, or None).
+
+    ``georeferenced=True`` orthorectifies the products through that GLT on the device (:func:`georeference_products`: the
+    sensor-geometry tensors move to ``<key>_raw``, ``rgb`` is added); the file must carry a GLT and ``rows`` must be None (the
+    GLT indexes the whole granule).  With ``out_folder`` (only with ``georeferenced=True``) the orthorectified products are
+    written as tiled GeoTIFFs (BLOCKSIZE 128): ``mag1c.tif``, ``albedo.tif``, ``pred.tif`` (float32, GDAL_NODATA = the fill
+    value), ``predbinary.tif`` (uint8) and ``rgb.tif`` (3 bands, the RGB planes of the network input), with band descriptions
+    and the georeferencing of :func:`starcop_amd.ortho.emit_geo_tags` from the file's root attributes ``geotransform`` /
+    ``spatial_ref`` -- ``geotransform=`` overrides the attribute; with neither, the files carry no georeferencing and one warning
+    is issued.  Existing files are skipped unless ``overwrite=True``; the paths written are returned under ``files``."""
     from .hdf5_reader import H5File
+    if out_folder is not None:
+        if str(out_folder).startswith("gs://"):
+            raise NotImplementedError(f"{out_folder}: writing to Google Cloud Storage is not supported")
+        if not georeferenced:
+            raise ValueError("emit_granule_predict: out_folder writes the orthorectified products; pass georeferenced=True")
+    if georeferenced and rows is not None:
+        raise ValueError("emit_granule_predict: georeferenced=True needs the whole granule (rows=None): the GLT indexes all of its lines")
     dev = model.device
     rs = rows or slice(None)
     with H5File(nc_path) as f:
@@ -213,6 +271,9 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
         rgb_h = np.stack([plane(i) for i in nearest_bands(wl)])
         ratio_h = [plane(i) for i in nearest_bands(wl, ratio_bands)] if ratio_bands is not None else None
         glt = (f["location/glt_x"].read(), f["location/glt_y"].read()) if ("location/glt_x" in f and "location/glt_y" in f) else (None, None)
+        root = f.attrs("/") if out_folder is not None else {}
+    if georeferenced and glt[0] is None:
+        raise ValueError(f"{nc_path}: no location/glt_x, location/glt_y to orthorectify with")
 
     def up(a):
         h = torch.from_numpy(a)
@@ -220,8 +281,50 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
     template = mag1c.generate_template_from_bands(wl[b0:b1], fwhm[b0:b1])
     out = _emit_predict_parts(model, up(sub_h), up(rgb_h), tuple(up(a) for a in ratio_h) if ratio_h else None, template, fill, column_step,
                               num_iter, covariance_lerp_alpha, None, tile, halo, distributed, group, strips)
+    if georeferenced:
+        out = georeference_products(out, glt[0], glt[1], fill)
     out.update(wavelengths=wl[b0:b1], fwhm=fwhm[b0:b1], glt_x=glt[0], glt_y=glt[1], fill_value=fill)
+    if out_folder is not None:
+        gt = geotransform if geotransform is not None else root.get("geotransform")
+        out["files"] = _write_emit_products(out, str(out_folder), fill, gt, root.get("spatial_ref"), overwrite)
     return out
+
+
+EMIT_PRODUCT_FILES = {"mag1c.tif": ("mf", ["CH4 Absorption (ppm x m)"]), "albedo.tif": ("albedo", ["Albedo"]),
+                      "pred.tif": ("prediction", ["Plume probability"]), "predbinary.tif": ("pred_binary", ["Plume mask"]),
+                      "rgb.tif": ("rgb", ["Red (640 nm)", "Green (550 nm)", "Blue (460 nm)"])}
+
+
+def _write_emit_products(out, folder, fill, geotransform, spatial_ref, overwrite):
+    """the orthorectified products of :func:`emit_granule_predict` -> GeoTIFFs in ``folder``; returns the paths written"""
+    import os
+    import warnings
+    from . import io_formats as io
+    from .ortho import emit_geo_tags
+    todo = [(os.path.join(folder, name), key, desc) for name, (key, desc) in EMIT_PRODUCT_FILES.items()]
+    todo = [t for t in todo if overwrite or not os.path.exists(t[0])]
+    if not todo:
+        return []
+    os.makedirs(folder, exist_ok=True)
+    if geotransform is None:
+        warnings.warn("emit_granule_predict: the granule has no geotransform attribute and none was passed: the GeoTIFFs are "
+                      "written without georeferencing")
+        geo = {}
+    else:
+        geo = emit_geo_tags(geotransform, spatial_ref)
+    nodata = {42113: (2, (_nodata_text(fill),))}
+    md = {"wavelengths": out["wavelengths"], "mag1c": "acrwl1mf"}
+    written = []
+    for path, key, desc in todo:
+        a = out[key].cpu().numpy()
+        if key == "pred_binary":
+            tags = {**geo, **io.gdal_metadata_tag({}, desc)}
+            a = a.astype(np.uint8)
+        else:
+            tags = {**geo, **nodata, **io.gdal_metadata_tag(md if key in ("mf", "albedo") else {}, desc)}
+        io.write_tiff(path, a, blocksize=128, extra_tags=tags)
+        written.append(path)
+    return written
 
 
 @torch.no_grad()
