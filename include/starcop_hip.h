@@ -794,6 +794,65 @@ typedef struct sc_ortho_args {
 } sc_ortho_args;
 int sc_glt_ortho(const sc_ortho_args* a, sc_stream stream);
 
+/* Cutting the sampled windows of a flight line into dense sample tensors: the reads of WindowDataset.__getitem__,
+ * starcop/data/sampling_dataset.py:259-303 -- RasterioReader.read_from_window(window, boundless=True).load(boundless=True) at :266,
+ * nodata -> 0 at :269-271, the acquisition-date multiply at :285 / :289 and np.clip at :287 / :293 -- for every window of a chunk
+ * and every product in one launch.
+ *   sc_window_cut : out[w][p][i][j], dense [n_win][P][out_h][out_w]; with (r, c) = (row_off[w] + i, col_off[w] + j)
+ *                     v = plane p holds (r, c) ? src_p[(r - row0_p) * row_stride_p + (c - col0_p) * col_stride_p] : 0
+ *                     if ops_p & SC_WCUT_FILL  and v == fill_p : v = 0            (a NaN fill masks nothing)
+ *                     if ops_p & SC_WCUT_SCALE : v = v * scale_p                  (one float32 multiply, one rounding)
+ *                     if ops_p & SC_WCUT_CLIP  : v = min(max(v, lo_p), hi_p) as numpy.clip evaluates it: NaN stays NaN
+ * Reads are boundless: a window may hang over any edge of the scene, lie wholly outside it or be larger than it; offsets may be
+ * negative.  Plane p is read in place through its pointer and non-negative element strides and covers rows [row0_p, row0_p + rows_p)
+ * and columns [col0_p, col0_p + cols_p) of the scene (the extent must lie inside the scene_rows x scene_cols scene): a decoded
+ * (H, W) plane, one band of a chunky (H, W, 4) label image (col_stride = 4), one band of a pixel-interleaved radiance cube
+ * (col_stride = bands), or only the row band of a flight line that the windows touch (row0 > 0).  Nothing outside a plane's extent
+ * is dereferenced.
+ * One element width per call: elem_bytes 1, 2 or 4.  SC_WCUT_SCALE / SC_WCUT_CLIP need elem_bytes = 4; when any plane of the call
+ * has one, every plane of the call is read as float32 and fill_p is compared as a float32 (fill_bits holds its bit pattern: -0.0
+ * matches +0.0, a NaN fill matches nothing).  Without them the call is pure data movement: fill_bits is compared as a bit pattern of
+ * elem_bytes and a hit is replaced by zero bits, so the result is bit-equal to the numpy restatement for every dtype of that width.
+ * The float32 multiply is x * float32(s), s evaluated in float64 by the caller in the reference's order (factor / 100 /
+ * solar_irradiance): what `values *= s` computes on a float32 array under numpy 1.x, the numpy of the published dataset.
+ * The windows are given twice, as [n_win][2] int32 (row_off, col_off) tables on the device (for the kernel) and on the host (for the
+ * checks): row_off + out_h and col_off + out_w must stay inside int32.  Every check runs on the host before the launch; the device
+ * table is read back (n_win * 8 bytes) and must equal the host one, so -- the one exception to the convention above -- this call waits
+ * for `stream` and cannot be captured into a graph.  1 <= P <= 64, 1 <= n_win <= 2^20, out_h * out_w < 2^31.
+ * 16-byte stores when out_w * elem_bytes is a multiple of 16 and `out` is 16-byte aligned, element stores otherwise; source loads
+ * assume element alignment only (col_off mod 4 takes every value).  SC_ERR_ARG for bad dims, P or n_win out of range, an
+ * unsupported elem_bytes, scale / clip at 1 or 2 bytes, unordered clip bounds, null or misaligned pointers, negative strides, a
+ * plane extent outside the scene, window tables that differ.  No atomics, nothing written outside `out`: repeated calls give
+ * identical bits.                                                                                                              */
+#define SC_WCUT_MAX_PLANES 64
+#define SC_WCUT_FILL 1
+#define SC_WCUT_SCALE 2
+#define SC_WCUT_CLIP 4
+typedef struct sc_wcut_args {
+  int32_t scene_rows, scene_cols;                /* the grid the window offsets refer to                      */
+  int32_t out_h, out_w;                          /* size of every window of the call                          */
+  int32_t P;                                     /* planes, 1..64                                             */
+  int32_t elem_bytes;                            /* 1, 2 or 4                                                 */
+  int32_t n_win;
+  int32_t reserved;
+  const int32_t* win_off;                        /* [n_win][2] (row_off, col_off), device                     */
+  const int32_t* win_off_host;                   /* the same on the host                                      */
+  const void* src[SC_WCUT_MAX_PLANES];           /* element (row0, col0) of every plane, device               */
+  int64_t row_stride[SC_WCUT_MAX_PLANES];        /* elements                                                  */
+  int64_t col_stride[SC_WCUT_MAX_PLANES];
+  int32_t row0[SC_WCUT_MAX_PLANES];              /* origin of the plane inside the scene                      */
+  int32_t col0[SC_WCUT_MAX_PLANES];
+  int32_t rows[SC_WCUT_MAX_PLANES];              /* its extent                                                */
+  int32_t cols[SC_WCUT_MAX_PLANES];
+  uint32_t ops[SC_WCUT_MAX_PLANES];              /* SC_WCUT_FILL | SC_WCUT_SCALE | SC_WCUT_CLIP               */
+  uint32_t fill_bits[SC_WCUT_MAX_PLANES];        /* bit pattern of the fill value (low elem_bytes bytes)      */
+  float scale[SC_WCUT_MAX_PLANES];
+  float clip_lo[SC_WCUT_MAX_PLANES];
+  float clip_hi[SC_WCUT_MAX_PLANES];
+  void* out;                                     /* [n_win][P][out_h][out_w] device                           */
+} sc_wcut_args;
+int sc_window_cut(const sc_wcut_args* a, sc_stream stream);
+
 /* ------------------------------------------------------------------------- */
 /* evaluation masks of the baselines and of run_validation.
  * Thresholded prediction with an optional binary opening by a 3x3 structuring element:

@@ -130,6 +130,23 @@ class sc_ortho_args(C.Structure):
                 ("out", C.c_void_p), ("oob_count", C.c_void_p)]
 
 
+WCUT_MAX_PLANES = 64
+WCUT_FILL, WCUT_SCALE, WCUT_CLIP = 1, 2, 4
+
+
+class sc_wcut_args(C.Structure):
+    """window-cut operands (include/starcop_hip.h: sc_wcut_args)"""
+    _fields_ = [("scene_rows", C.c_int32), ("scene_cols", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32),
+                ("P", C.c_int32), ("elem_bytes", C.c_int32), ("n_win", C.c_int32), ("reserved", C.c_int32),
+                ("win_off", C.c_void_p), ("win_off_host", C.c_void_p),
+                ("src", C.c_void_p * WCUT_MAX_PLANES), ("row_stride", C.c_int64 * WCUT_MAX_PLANES),
+                ("col_stride", C.c_int64 * WCUT_MAX_PLANES), ("row0", C.c_int32 * WCUT_MAX_PLANES),
+                ("col0", C.c_int32 * WCUT_MAX_PLANES), ("rows", C.c_int32 * WCUT_MAX_PLANES), ("cols", C.c_int32 * WCUT_MAX_PLANES),
+                ("ops", C.c_uint32 * WCUT_MAX_PLANES), ("fill_bits", C.c_uint32 * WCUT_MAX_PLANES),
+                ("scale", C.c_float * WCUT_MAX_PLANES), ("clip_lo", C.c_float * WCUT_MAX_PLANES),
+                ("clip_hi", C.c_float * WCUT_MAX_PLANES), ("out", C.c_void_p)]
+
+
 _vp, _i, _f, _d, _sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/starcop_hip.h declares
@@ -207,6 +224,7 @@ SIGNATURES = {
     "sc_window_stats_workspace_bytes": (_sz, [_i]),
     "sc_window_stats": (_i, [C.POINTER(sc_winstats_args), _vp, _sz, _vp]),
     "sc_glt_ortho": (_i, [C.POINTER(sc_ortho_args), _vp]),
+    "sc_window_cut": (_i, [C.POINTER(sc_wcut_args), _vp]),
     "sc_connected_components": (_i, [_vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "sc_proposed_mask": (_i, [_vp, C.c_int64, _vp, C.c_int64, _f, _i, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "sc_packed_weight_floats_thin16": (_sz, [_i, _i, _i]),

@@ -25,6 +25,33 @@ SRF_S2_FILE = "gs://starcop/S2/S2-SRF_joint.csv"
 
 NOUT_MAX = 64                      # output bands per sc_srf_bands call
 
+# aviris.py:31-49: band-averaged solar irradiance in W / m^2 / nm (Sentinel-2: the SOLAR_IRRADIANCE metadata of the L1C products
+# divided by 1000; WorldView-3: the published SWIR band values, kept as the quotients the reference evaluates)
+SOLAR_IRRADIANCE_S2B = {"B01": 1.8743, "B02": 1.95977, "B03": 1.82493, "B04": 1.51279, "B05": 1.42578, "B06": 1.29113, "B07": 1.17557,
+                        "B08": 1.04128, "B8A": 0.95393, "B09": 0.81758, "B10": 0.36541, "B11": 0.24708, "B12": 0.08775}
+SOLAR_IRRADIANCE_S2A = {"B01": 1.88469, "B02": 1.95972, "B03": 1.82324, "B04": 1.51206, "B05": 1.42464, "B06": 1.28761, "B07": 1.16208,
+                        "B08": 1.04163, "B8A": 0.95532, "B09": 0.81292, "B10": 0.36715, "B11": 0.24559, "B12": 0.08525}
+SOLAR_IRRADIANCE_WV3 = {f"SWIR{i + 1}": v / 1000 for i, v in enumerate((477.8728, 263.2926, 224.9720, 197.3366, 90.3976, 85.0757,
+                                                                         76.9260, 68.0897))}
+SOLAR_IRRADIANCE = {"S2A": SOLAR_IRRADIANCE_S2A, "S2B": SOLAR_IRRADIANCE_S2B, "WV3": SOLAR_IRRADIANCE_WV3}
+
+
+def earth_sun_distance_correction_factor(date_of_acquisition):
+    """aviris.py:53-72: ``1 - 0.01673 cos(0.0172 (t - 4))`` with t the day of the year (1 on January 1st); 0.01673 is the
+    eccentricity of the Earth's orbit, 0.0172 = 2 pi / 365.256363."""
+    tm_yday = date_of_acquisition.timetuple().tm_yday
+    return 1 - 0.01673 * np.cos(0.0172 * (tm_yday - 4))
+
+
+def observation_date_correction_factor(date_of_acquisition, solar_altitude):
+    """aviris.py:75-107 with the solar altitude (degrees above the horizon at the centre of the flight line, what
+    ``pysolar.solar.get_altitude`` returns there) as an INPUT: ``pi d^2 / cos(sza pi / 180)``, ``sza = 90 - solar_altitude``,
+    ``d`` = :func:`earth_sun_distance_correction_factor`, evaluated in float64 in the reference's order.  pysolar is not a
+    dependency of this package and no ephemeris of its own is offered in its place."""
+    sza = 90 - float(solar_altitude)
+    d = earth_sun_distance_correction_factor(date_of_acquisition)
+    return np.pi * (d ** 2) / np.cos(sza / 180. * np.pi)
+
 
 def _read_srf(path):
     """CSV indexed by SR_WL without the rows where no band is above 1e-6 (aviris.py:178-185, 206-213)"""

@@ -336,6 +336,34 @@ def envi_geo_tags(header: Dict[str, object]) -> Dict[int, tuple]:
     return tags
 
 
+def window_geo_tags(info, row_off: int, col_off: int) -> Dict[int, tuple]:
+    """Georeferencing tags of a window of a raster: the source's, moved to the window's upper-left corner (what the transform
+    of ``RasterioReader.read_from_window(window, boundless=True)`` is, sampling_dataset.py:266).  ``info``: a ``TiffInfo`` or a
+    {tag: (type, values)} dict.  A ModelTiepoint (33922) with its ModelPixelScale (33550) is re-anchored at pixel (0, 0) of the
+    window; a ModelTransformation (34264) gets its translation column shifted by the rotated offset.  Offsets may be negative
+    (a window that starts outside the raster).  The geo keys (34735-34737) are carried over; nodata and metadata tags are not.
+    A source without georeferencing gives {}."""
+    tags = info.tags if isinstance(info, TiffInfo) else dict(info)
+    row_off, col_off = int(row_off), int(col_off)
+    out: Dict[int, tuple] = {}
+    if 33922 in tags and 33550 in tags:
+        sx, sy = (float(v) for v in tags[33550][1][:2])
+        i, j, k, x, y, z = (float(v) for v in tags[33922][1][:6])
+        out[33550] = tags[33550]
+        out[33922] = (12, (0.0, 0.0, 0.0, x + (col_off - i) * sx, y - (row_off - j) * sy, z))
+    elif 34264 in tags:
+        m = [float(v) for v in tags[34264][1]]
+        m[3] = m[3] + m[0] * col_off + m[1] * row_off
+        m[7] = m[7] + m[4] * col_off + m[5] * row_off
+        out[34264] = (12, tuple(m))
+    else:
+        return {}
+    for t in (34735, 34736, 34737):
+        if t in tags:
+            out[t] = tags[t]
+    return out
+
+
 def gdal_metadata_tag(tags: Dict[str, object], descriptions: Sequence[str] = ()) -> Dict[int, tuple]:
     """GDAL_METADATA (42112): the XML in which GDAL / rasterio keep dataset tags and band descriptions -- what
     ``save_cog(..., descriptions=[...], tags={...})`` leaves in the reference's products (process_aviris.py:222-232)."""

@@ -39,6 +39,14 @@ PERMIAN_UNLABELED_PLUMES = [
     "ang20191007t195115_r768_c0_w512_h512", "ang20191012t162223_r3072_c0_w512_h512", "ang20191005t215301_r4864_c0_w512_h512"]
 
 
+def __getattr__(name):
+    # sampling_dataset.py:182-386 lives in window_dataset.py (which imports this module): resolved on first use
+    if name == "WindowDataset":
+        from .window_dataset import WindowDataset
+        return WindowDataset
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 def _rchw(w) -> Tuple[int, int, int, int]:
     if hasattr(w, "row_off"):
         return int(w.row_off), int(w.col_off), int(w.height), int(w.width)
