@@ -887,6 +887,18 @@ int sc_gather_augment(const float* tiles, int M, int C, int Hs, int Ws, const in
                       const int32_t* col_off, const float* cos_t, const float* sin_t, const int32_t* flags, int B,
                       int h, int w, int mode, float* out, sc_stream stream);
 
+/* Label sums of the training windows of the resident tiles (starcop/data/datamodule.py:17-64, tiled_dataframe: frac_positives =
+ * torch.sum(label window) / window size):  out[m][k] = sum of labels[m][r][c] over window k = (row_off, col_off, height, width),
+ * accumulated in fp64.  labels: [M][H][W] f32 dense, device; the K windows are shared by all tiles and given twice, on the device
+ * for the kernel and on the host for the argument check that runs before the launch; out: [M][K] f64 device.  Any H, W >= 1 with
+ * H*W < 2^31 and any window inside the tile (width 1, odd offsets, overlapping, repeated, the whole tile).  One launch, no
+ * workspace, no allocation, no synchronisation.  The additions have a fixed order (per-lane fp64 partials, wavefront shuffle, LDS)
+ * and there are no atomics: repeated calls give identical bits, and windows whose partial sums are integers below 2^53 ({0, 1}
+ * labels) are exact.  16-byte loads where a row segment is 16-byte aligned, element loads at its ragged ends.  SC_ERR_ARG for
+ * M < 1, K < 1, bad dims, a null or misaligned pointer, an empty window or one that leaves the tile; nothing is launched then.  */
+int sc_tile_window_sums(const float* labels, int M, int H, int W, const int32_t* windows, const int32_t* windows_host, int K,
+                        double* out, sc_stream stream);
+
 /* ------------------------------------------------------------------------- */
 /* HOST functions (no device involved): decoders of the on-disk sample format -- one tiled GeoTIFF per product per sample,
  * read by rasterio in the reference (starcop/data/dataset.py:66-76, written by save_cog at sampling_dataset.py:332-355).

@@ -387,10 +387,12 @@ def load_sample(folder: str, products: Sequence[str], window=None) -> np.ndarray
 
 
 def load_tileset(folders: Sequence[str], input_products: Sequence[str], output_products: Sequence[str] = ("labelbinary",),
-                 weight_loss: Optional[str] = "weight_mag1c", ids: Optional[Sequence[str]] = None, device="cuda", workers: int = 8):
+                 weight_loss: Optional[str] = "weight_mag1c", ids: Optional[Sequence[str]] = None, device="cuda", workers: int = 8,
+                 extra_products: Sequence[str] = ()):
     """Reads the sample folders of a split (the ``folder`` column of the reference's train.csv / test.csv, datamodule.py:98-106)
     into PINNED host buffers with a pool of decoder threads (zlib releases the GIL) and uploads each tensor with one
-    asynchronous copy -> ``datamodule.ResidentTileSet`` (tiles resident in HBM for the whole training run)."""
+    asynchronous copy -> ``datamodule.ResidentTileSet`` (tiles resident in HBM for the whole training run).  ``extra_products``
+    (e.g. what only the plot loaders show) are kept one (M,1,H,W) plane each in ``ResidentTileSet.extras``."""
     import torch
     from concurrent.futures import ThreadPoolExecutor
     from .datamodule import ResidentTileSet
@@ -400,6 +402,7 @@ def load_tileset(folders: Sequence[str], input_products: Sequence[str], output_p
     M = len(folders)
     pin = torch.cuda.is_available()
     groups = [("inputs", list(input_products)), ("outputs", list(output_products))] + ([("weight_loss", [weight_loss])] if weight_loss else [])
+    groups += [("extra:" + p, [p]) for p in extra_products]
     host = {name: torch.empty((M, len(p), H, W), dtype=torch.float32, pin_memory=pin) for name, p in groups}
 
     def work(i):
@@ -411,4 +414,4 @@ def load_tileset(folders: Sequence[str], input_products: Sequence[str], output_p
     if pin:
         torch.cuda.current_stream().synchronize()        # the pinned staging buffers may be released after this
     return ResidentTileSet(dev["inputs"], dev["outputs"], dev.get("weight_loss"), ids=ids or [os.path.basename(f.rstrip("/")) for f in folders],
-                           device=device)
+                           device=device, extras={p: dev["extra:" + p] for p in extra_products})
