@@ -394,11 +394,16 @@ int sc_cast_f64_f32(const double* in, float* out, size_t n, sc_stream stream);
 typedef struct sc_cast_desc { const double* in; float* out; uint64_t n; } sc_cast_desc;
 int sc_cast_f64_f32_batch(const sc_cast_desc* descs_dev, int n_descs, sc_stream stream);
 
-/* stem: conv 3x3 stride 2 pad 1, Cin<=8 -> 32, input read through its prologue
- * (SC_SRC_NORM fuses DataNormalizer.normalize_x, starcop/data/normalizer_module.py:134-135) */
+/* stem: conv 3x3 stride 2 pad 1, Cin<=16 -> 32, input read through its prologue
+ * (SC_SRC_NORM fuses DataNormalizer.normalize_x, starcop/data/normalizer_module.py:134-135).  Cin <= 8: the HyperSTARCOP inputs
+ * (models/model_module.py:244-251), with or without statistics rows; 9 <= Cin <= 16: the 13 Sentinel-2 bands of the cloud detector
+ * (starcop/sentinel2/models.py:63-78), inference only -- stats must be NULL.  sc_stem_conv_wgrad keeps Cin <= 8. */
 int sc_stem_conv_fwd(const sc_src* in, const float* w /*[32][Cin][3][3]*/, float* out,
                      int N, int Cin, int Hin, int Win, float* stats /* rows: SC_STAT_STEM on (Hout,Wout) */,
                      sc_stream stream);
+/* the kernel sc_stem_conv_fwd launches for (Cin, input width, 16-byte alignment of out); SC_ERR_ARG for Cin outside [1,16] */
+enum sc_stem_kernel { SC_STEM_K_MFMA4 = 0, SC_STEM_K_VALU4 = 1, SC_STEM_K_VALU8 = 2, SC_STEM_K_VALU16 = 3 };
+int sc_stem_fwd_kernel(int Cin, int Win, int out_aligned16);
 size_t sc_stem_wgrad_workspace_floats(int N, int Cin, int Hin, int Win);
 int sc_stem_conv_wgrad(const sc_src* dy, const sc_src* in, float* part, size_t part_floats,
                        float* dw, int N, int Cin, int Hin, int Win, sc_stream stream);
@@ -406,6 +411,14 @@ int sc_stem_conv_wgrad(const sc_src* dy, const sc_src* in, float* part, size_t p
 /* segmentation head: conv 3x3 pad 1, Cin -> 1, bias (fwd/dgrad: Cin <= 32; wgrad: Cin in {8, 16}) */
 int sc_head_conv_fwd(const sc_src* in, const float* w /*[1][Cin][3][3]*/, const float* bias,
                      float* out, int N, int Cin, int H, int W, sc_stream stream);
+/* K-class head, 1 <= K <= 8, Cin <= 32, same source modes (RAW / AFFINE, no upsample): smp.Unet(classes=K) followed by
+ * torch.argmax(dim=1).type(uint8) (starcop/sentinel2/models.py:63-78; classes = settings.model.num_classes,
+ * models/model_module.py:244-251).  At least one of logits / classes is non-NULL; with logits == NULL no logit is stored.  classes
+ * follows torch.argmax: the first maximal index wins, a NaN counts as maximal and the first NaN wins.  K == 1 forwards to
+ * sc_head_conv_fwd (classes, if asked for, are zeros). */
+int sc_head_conv_fwd_k(const sc_src* in, const float* w /*[K][Cin][3][3]*/, const float* bias /*[K]*/,
+                       float* logits /*[N][K][H][W] or NULL*/, uint8_t* classes /*[N][H][W] or NULL*/,
+                       int N, int Cin, int K, int H, int W, sc_stream stream);
 int sc_head_conv_dgrad(const float* dlogits, const float* w, float* gin,
                        int N, int Cin, int H, int W, sc_stream stream);
 size_t sc_head_wgrad_workspace_floats(int N, int Cin, int H, int W);

@@ -174,9 +174,11 @@ SIGNATURES = {
     "sc_cast_f64_f32": (_i, [_vp, _vp, _sz, _vp]),
     "sc_cast_f64_f32_batch": (_i, [_vp, _i, _vp]),
     "sc_stem_conv_fwd": (_i, [C.POINTER(sc_src), _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
+    "sc_stem_fwd_kernel": (_i, [_i, _i, _i]),
     "sc_stem_wgrad_workspace_floats": (_sz, [_i, _i, _i, _i]),
     "sc_stem_conv_wgrad": (_i, [C.POINTER(sc_src), C.POINTER(sc_src), _vp, _sz, _vp, _i, _i, _i, _i, _vp]),
     "sc_head_conv_fwd": (_i, [C.POINTER(sc_src), _vp, _vp, _vp, _i, _i, _i, _i, _vp]),
+    "sc_head_conv_fwd_k": (_i, [C.POINTER(sc_src), _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "sc_head_conv_dgrad": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "sc_head_wgrad_workspace_floats": (_sz, [_i, _i, _i, _i]),
     "sc_head_conv_wgrad": (_i, [_vp, C.POINTER(sc_src), _vp, _sz, _vp, _vp, _i, _i, _i, _i, _vp]),

@@ -4,6 +4,8 @@
 //   head 3x3, Cin(16) -> 1, bias       -- segmentation_head.0
 // forward / backward-data / backward-weight, all with the "normalise on load" prologues of
 // sc_common.h.  Reference call site of the whole network: starcop/models/model_module.py:244-251.
+// Forward only: the stem up to 16 channels and the head with K <= 8 classes and a fused argmax
+// (the 13-band, 4-class cloud detector of starcop/sentinel2/models.py:63-78).
 #include <type_traits>
 #include "sc_common.h"
 #ifndef SC_HEAD_RB
@@ -922,9 +924,10 @@ __global__ __launch_bounds__(256) void k_dw_fwd_plane(const SrcD in, const float
   }
 }
 
-// ---------------------------------------------------------------- stem (3x3 s2, Cin<=8 -> 32)
+// ---------------------------------------------------------------- stem (3x3 s2, Cin<=8 -> 32; forward without statistics: Cin<=16)
 constexpr int STEM_CO = 32;
 constexpr int STEM_MAXCI = 8;
+constexpr int STEM_MAXCI_FWD = 16;      // k_stem_fwd16
 
 // CINT: compile-time bound of the channel loops (4 for the 4-channel HyperSTARCOP input, STEM_MAXCI otherwise)
 template <int CINT>
@@ -1113,6 +1116,82 @@ __global__ __launch_bounds__(256) void k_stem_fwd4m(const SrcD in, const float* 
       const int co = threadIdx.x >> 1, k = threadIdx.x & 1;
       stats[(stat_row() * STEM_CO + co) * 2 + k] = (s_red[0][co][k] + s_red[1][co][k]) + (s_red[2][co][k] + s_red[3][co][k]);
     }
+  }
+}
+
+// The wide stem, 9 <= Cin <= 16 (the 13 Sentinel-2 bands of starcop/sentinel2/models.py:65-70): k_stem_fwd's tile, grid, staging and
+// FMA order (ci ascending, then the nine taps), with the input patch staged in TWO chunks of 8 channels through the same 36 KB of LDS
+// -- all 16 channels at once would be 72 KB = two work-groups per CU by LDS alone, while the 144 operand registers of a thread
+// already set two waves per SIMD, so the second half of the LDS would buy nothing.  No statistics rows (inference only).
+__global__ __launch_bounds__(256) void k_stem_fwd16(const SrcD in, const float* __restrict__ w, float* __restrict__ out,
+                                                    int Cin, int Hin, int Win, int Hout, int Wout) {
+  constexpr int CH = 8, NCH = STEM_MAXCI_FWD / CH;
+  constexpr int PS = 65, PSP = 66, NE = 17 * PS, NIT = (NE + 255) / 256;
+  __shared__ float s_in[CH][17 * PSP];
+  const int n = blockIdx.z;
+  const int tiles_x = (Wout + 31) >> 5;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int oy = ty * 8 + (threadIdx.x >> 5), ox = tx * 32 + (threadIdx.x & 31);
+  const bool ok = (oy < Hout) && (ox < Wout);
+  const int iy0 = ty * 16 - 1, ix0 = tx * 64 - 1;
+  float v[NCH * CH * 9];
+#pragma unroll
+  for (int ch = 0; ch < NCH; ++ch) {
+    float raw[CH][NIT];
+#pragma unroll
+    for (int cl = 0; cl < CH; ++cl) {
+      const int ci = ch * CH + cl;
+      if (ci < Cin) {
+        const float* xb = in.x + ((size_t)n * Cin + ci) * Hin * Win;
+#pragma unroll
+        for (int i = 0; i < NIT; ++i) {
+          const int e = threadIdx.x + i * 256;
+          const int r = e / PS, cc = e - r * PS;
+          const int iy = iy0 + r, ix = ix0 + cc;
+          const bool inb = (e < NE) && iy >= 0 && iy < Hin && ix >= 0 && ix < Win;
+          raw[cl][i] = xb[inb ? (size_t)iy * Win + ix : 0];
+        }
+      }
+    }
+    if (ch) __syncthreads();          // the previous chunk's operands have been read
+#pragma unroll
+    for (int cl = 0; cl < CH; ++cl) {
+      const int ci = ch * CH + cl;
+      if (ci < Cin) {
+        float4 c0 = make_float4(1.f, 0.f, 0.f, 0.f); float c4 = 0.f;
+        if (in.mode != SC_SRC_RAW) { c0 = *reinterpret_cast<const float4*>(in.cst + (size_t)ci * SC_CST); c4 = in.cst[(size_t)ci * SC_CST + 4]; }
+#pragma unroll
+        for (int i = 0; i < NIT; ++i) {
+          const int e = threadIdx.x + i * 256;
+          const int r = e / PS, cc = e - r * PS;
+          const int iy = iy0 + r, ix = ix0 + cc;
+          const bool inb = iy >= 0 && iy < Hin && ix >= 0 && ix < Win;
+          const float t = (in.mode == SC_SRC_RAW) ? raw[cl][i] : sc_prologue(in.mode, in.act, raw[cl][i], 0.f, c0, c4);
+          if (e < NE) s_in[cl][r * PSP + cc] = inb ? t : 0.f;
+        }
+      }
+    }
+    __syncthreads();
+#pragma unroll
+    for (int cl = 0; cl < CH; ++cl)
+#pragma unroll
+      for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+        for (int kw = 0; kw < 3; ++kw)
+          v[(ch * CH + cl) * 9 + kh * 3 + kw] =
+              (ch * CH + cl < Cin) ? s_in[cl][(2 * (threadIdx.x >> 5) + kh) * PSP + 2 * (threadIdx.x & 31) + kw] : 0.f;
+  }
+  const size_t HWo = (size_t)Hout * Wout;
+  for (int co = 0; co < STEM_CO; ++co) {
+    float acc = 0.f;
+#pragma unroll
+    for (int ci = 0; ci < NCH * CH; ++ci) {
+      if (ci < Cin) {
+#pragma unroll
+        for (int t = 0; t < 9; ++t) acc = fmaf(w[(co * Cin + ci) * 9 + t], v[ci * 9 + t], acc);      // (uniform index: scalar loads, SGPR operands)
+      }
+    }
+    if (ok) out[((size_t)n * STEM_CO + co) * HWo + (size_t)oy * Wout + ox] = acc;
   }
 }
 
@@ -1509,6 +1588,242 @@ __global__ __launch_bounds__(256) void k_head_fwd(const SrcD in, const float* __
   out[(size_t)n * H * W + (size_t)y * W + x] = acc;
 }
 
+// ---------------------------------------------------------------- K-class head (3x3, Cin<=32 -> K<=8, bias) with fused argmax
+constexpr int HEADK_MAXK = 8;
+
+// torch.argmax(dim=1) of one pixel's K logits a[k * S]: the first maximal index; a NaN counts as maximal and the first NaN wins
+// (once the running best is a NaN neither test below can pass again)
+template <int KT, int S>
+__device__ __forceinline__ uint32_t head_argmax(const float* a, int K) {
+  float best = a[0];
+  uint32_t idx = 0;
+#pragma unroll
+  for (int k = 1; k < KT; ++k) {
+    const float t = a[k * S];
+    if (k < K && (t > best || (t != t && best == best))) { best = t; idx = k; }
+  }
+  return idx;
+}
+
+// Cin = 16 (the decoder's last block), K <= KT classes: k_head_fwd16's tile (16 rows x 64 columns, a thread owns 4 adjacent pixels,
+// channels in two passes of 8) with KT x 4 accumulators per thread; the patch values of one (ci, kh) -- a 16-byte and two 4-byte LDS
+// reads -- now feed 12 KT FMAs.  Patch rows as in k_head_fwd16v: left halo at [3], columns at [4, 68), right halo at [68].  VEC: the
+// 16-byte staging of k_head_fwd16v (W % 4 == 0, 16-byte aligned planes), next pass requested before this pass's stencil; otherwise
+// the 4-byte staging of k_head_fwd16.  logits == NULL: nothing but the class index (1 byte per pixel) leaves the launch.
+// lvec / cvec: 16-byte logit stores / 4-byte class stores (W % 4 == 0 and the output's base aligned accordingly).
+template <int KT, bool VEC>
+__global__ __launch_bounds__(256, 2) void k_head_fwdk16(const SrcD in, const float* __restrict__ w, const float* __restrict__ bias,
+                                                       float* __restrict__ logits, uint8_t* __restrict__ classes, int K, int H, int W,
+                                                       int lvec, int cvec) {
+  constexpr int CIN = 16, CP = 8, TR = 16, TC = 64, PR = TR + 2, PC = 68, NROW = CP * PR, QW = NROW / 16, NHALO = NROW * 2;
+  static_assert(NROW % 16 == 0 && NHALO <= 512, "four waves x QW requests of four rows; two halo elements per thread");
+  __shared__ __attribute__((aligned(16))) float s_in[NROW * PC + 4];
+  __shared__ __attribute__((aligned(16))) float s_w[KT * CIN * 12];      // 9 taps per (class, channel), padded to 12; classes >= K: zeros
+  __shared__ float s_sc[CIN * 2];
+  const int n = blockIdx.z;
+  const int tiles_x = (W + TC - 1) / TC;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int y0 = ty * TR, x0 = tx * TC;
+  const float lo = sc_act_lo(in.act), hi = sc_act_hi(in.act);
+  const bool raw = in.mode == SC_SRC_RAW;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const float* plane0 = in.x + (size_t)n * CIN * H * W;
+  // ---- 16-byte staging (VEC)
+  const int lr = lane >> 4, xg = x0 + 4 * (lane & 15);
+  const bool okx = xg < W;                                               // (W % 4 == 0: a 16-byte group is inside or outside as a whole)
+  float4 v[VEC ? QW : 1];
+  float hv[2];
+  auto issue = [&](int pass) {
+#pragma unroll
+    for (int u = 0; u < QW; ++u) {
+      const int rr = 4 * (wave + 4 * u) + lr, ci = rr / PR, y = y0 - 1 + rr - ci * PR;
+      const bool oky = (y >= 0) && (y < H);
+      v[VEC ? u : 0] = *reinterpret_cast<const float4*>(plane0 + ((size_t)(pass * CP + ci) * H + (oky ? y : 0)) * W + (okx ? xg : 0));
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int e = threadIdx.x + 256 * h, ec = e < NHALO ? e : 0, rr = ec >> 1, ci = rr / PR, y = y0 - 1 + rr - ci * PR;
+      const int x = (ec & 1) ? x0 + TC : x0 - 1;
+      const bool ok = (y >= 0) && (y < H) && (x >= 0) && (x < W);
+      hv[h] = plane0[((size_t)(pass * CP + ci) * H + (ok ? y : 0)) * W + (ok ? x : 0)];
+    }
+  };
+  auto commit = [&](int pass) {
+#pragma unroll
+    for (int u = 0; u < QW; ++u) {
+      const int rr = 4 * (wave + 4 * u) + lr, ci = rr / PR, y = y0 - 1 + rr - ci * PR;
+      const bool ok = (y >= 0) && (y < H) && okx;
+      const float sc = s_sc[(pass * CP + ci) * 2], sh = s_sc[(pass * CP + ci) * 2 + 1];
+      const float4 q = v[VEC ? u : 0];
+      float4 t;
+      t.x = ok ? sc_pro_affine(q.x, sc, sh, lo, hi) : 0.f; t.y = ok ? sc_pro_affine(q.y, sc, sh, lo, hi) : 0.f;
+      t.z = ok ? sc_pro_affine(q.z, sc, sh, lo, hi) : 0.f; t.w = ok ? sc_pro_affine(q.w, sc, sh, lo, hi) : 0.f;
+      *reinterpret_cast<float4*>(&s_in[rr * PC + 4 + 4 * (lane & 15)]) = t;
+    }
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const int e = threadIdx.x + 256 * h;
+      if (e < NHALO) {
+        const int rr = e >> 1, ci = rr / PR, y = y0 - 1 + rr - ci * PR;
+        const int x = (e & 1) ? x0 + TC : x0 - 1;
+        const bool ok = (y >= 0) && (y < H) && (x >= 0) && (x < W);
+        const float sc = s_sc[(pass * CP + ci) * 2], sh = s_sc[(pass * CP + ci) * 2 + 1];
+        s_in[rr * PC + ((e & 1) ? PC : 3)] = ok ? sc_pro_affine(hv[h], sc, sh, lo, hi) : 0.f;
+      }
+    }
+  };
+  // ---- 4-byte staging: a wave takes whole patch rows, lane = column x0 - 1 + lane (slots 3..66); lanes 0, 1 also fetch the
+  // columns x0 + 63, x0 + 64 (slots 67, 68); SC_HEAD_RB rows in flight
+  auto stage4 = [&](int pass) {
+    constexpr int RB = SC_HEAD_RB;
+    const int xa = x0 - 1 + lane, xb = x0 + 63 + lane;                   // xb only for lane < 2
+    const bool oka = (xa >= 0) && (xa < W), okb = (lane < 2) && (xb < W);
+#pragma unroll 1
+    for (int rr0 = wave; rr0 < NROW; rr0 += 4 * RB) {
+      float va[RB], vb[RB];
+#pragma unroll
+      for (int u = 0; u < RB; ++u) {
+        const int rr = rr0 + 4 * u;
+        const int rc = rr < NROW ? rr : 0;
+        const int ci = rc / PR, y = y0 - 1 + rc - ci * PR;
+        const bool oky = (y >= 0) && (y < H);
+        const float* row = plane0 + ((size_t)(pass * CP + ci) * H + (oky ? y : 0)) * W;
+        va[u] = row[oka ? xa : 0];
+        vb[u] = row[okb ? xb : 0];
+      }
+#pragma unroll
+      for (int u = 0; u < RB; ++u) {
+        const int rr = rr0 + 4 * u;
+        if (rr < NROW) {
+          const int ci = rr / PR, y = y0 - 1 + rr - ci * PR;
+          const bool oky = (y >= 0) && (y < H);
+          const float sc = s_sc[(pass * CP + ci) * 2], sh = s_sc[(pass * CP + ci) * 2 + 1];
+          s_in[rr * PC + 3 + lane] = (oky && oka) ? sc_pro_affine(va[u], sc, sh, lo, hi) : 0.f;
+          if (lane < 2) s_in[rr * PC + 67 + lane] = (oky && okb) ? sc_pro_affine(vb[u], sc, sh, lo, hi) : 0.f;
+        }
+      }
+    }
+  };
+  if (VEC) issue(0);
+  for (int i = threadIdx.x; i < KT * CIN * 12; i += 256) {
+    const int kc = i / 12, t = i - 12 * kc;
+    s_w[i] = (t < 9 && kc < K * CIN) ? w[kc * 9 + t] : 0.f;
+  }
+  if (threadIdx.x >= 224 && threadIdx.x < 224 + CIN * 2) {
+    const int i = threadIdx.x - 224, c = i >> 1, h = i & 1;
+    s_sc[i] = raw ? (h ? 0.f : 1.f) : in.cst[(size_t)c * SC_CST + h];
+  }
+  __syncthreads();
+  const int py = threadIdx.x >> 4, pxg = threadIdx.x & 15;
+  float acc[KT][4];
+#pragma unroll
+  for (int k = 0; k < KT; ++k) {
+    const float b0 = (bias && k < K) ? bias[k] : 0.f;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) acc[k][o] = b0;
+  }
+#pragma unroll
+  for (int pass = 0; pass < CIN / CP; ++pass) {
+    if (VEC) {
+      commit(pass);
+    } else {
+      if (pass) __syncthreads();
+      stage4(pass);
+    }
+    __syncthreads();
+    if (VEC && pass + 1 < CIN / CP) issue(pass + 1);
+#pragma unroll 1
+    for (int ci = 0; ci < CP; ++ci) {
+      float vv[3][6];
+#pragma unroll
+      for (int kh = 0; kh < 3; ++kh) {
+        const float* rp = &s_in[(ci * PR + py + kh) * PC + 4 * pxg + 3];
+        const float4 a = *reinterpret_cast<const float4*>(rp + 1);
+        vv[kh][0] = rp[0]; vv[kh][1] = a.x; vv[kh][2] = a.y; vv[kh][3] = a.z; vv[kh][4] = a.w; vv[kh][5] = rp[5];
+      }
+#pragma unroll
+      for (int k = 0; k < KT; ++k) {
+        const float4* wp = reinterpret_cast<const float4*>(&s_w[(k * CIN + pass * CP + ci) * 12]);     // broadcast reads
+        const float4 w0 = wp[0], w1 = wp[1], w2 = wp[2];
+        const float wk[9] = {w0.x, w0.y, w0.z, w0.w, w1.x, w1.y, w1.z, w1.w, w2.x};
+#pragma unroll
+        for (int kh = 0; kh < 3; ++kh)
+#pragma unroll
+          for (int kw = 0; kw < 3; ++kw)
+#pragma unroll
+            for (int o = 0; o < 4; ++o) acc[k][o] = fmaf(wk[kh * 3 + kw], vv[kh][o + kw], acc[k][o]);
+      }
+    }
+    if (VEC && pass + 1 < CIN / CP) __syncthreads();
+  }
+  const int y = y0 + py, x = x0 + 4 * pxg;
+  if (y >= H || x >= W) return;
+  const size_t HW = (size_t)H * W, pix = (size_t)y * W + x;
+  if (logits) {
+#pragma unroll
+    for (int k = 0; k < KT; ++k) {
+      if (k < K) {
+        float* op = logits + ((size_t)n * K + k) * HW + pix;
+        if (lvec) {
+          *reinterpret_cast<float4*>(op) = make_float4(acc[k][0], acc[k][1], acc[k][2], acc[k][3]);
+        } else {
+#pragma unroll
+          for (int o = 0; o < 4; ++o) if (x + o < W) op[o] = acc[k][o];
+        }
+      }
+    }
+  }
+  if (classes) {
+    uint32_t c[4];
+#pragma unroll
+    for (int o = 0; o < 4; ++o) c[o] = head_argmax<KT, 4>(&acc[0][o], K);
+    uint8_t* cp = classes + (size_t)n * HW + pix;
+    if (cvec) {
+      *reinterpret_cast<uint32_t*>(cp) = c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24);
+    } else {
+#pragma unroll
+      for (int o = 0; o < 4; ++o) if (x + o < W) cp[o] = (uint8_t)c[o];
+    }
+  }
+}
+
+// any Cin <= 32: k_head_fwd<0>'s tile (8 x 32, one pixel per thread, taps in LDS) with HEADK_MAXK accumulators
+__global__ __launch_bounds__(256) void k_head_fwdk(const SrcD in, const float* __restrict__ w, const float* __restrict__ bias,
+                                                   float* __restrict__ logits, uint8_t* __restrict__ classes, int Cin, int K, int H, int W) {
+  constexpr int KT = HEADK_MAXK, PR = HT_R + 2, PC = HT_C + 2;
+  __shared__ float s_in[HEAD_MAXCI * PR * PC];
+  __shared__ float s_w[KT * HEAD_MAXCI * 9];                            // [k][ci][tap]; classes >= K: zeros
+  const int n = blockIdx.z;
+  const int tiles_x = (W + HT_C - 1) / HT_C;
+  const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
+  const int y0 = ty * HT_R, x0 = tx * HT_C;
+  for (int i = threadIdx.x; i < KT * Cin * 9; i += 256) s_w[i] = i < K * Cin * 9 ? w[i] : 0.f;
+  head_stage_patch<PC, 0>(in, s_in, n, Cin, H, W, y0, x0);
+  __syncthreads();
+  const int py = threadIdx.x >> 5, px = threadIdx.x & 31;
+  const int y = y0 + py, x = x0 + px;
+  if (y >= H || x >= W) return;
+  float acc[KT];
+#pragma unroll
+  for (int k = 0; k < KT; ++k) acc[k] = (bias && k < K) ? bias[k] : 0.f;
+  for (int ci = 0; ci < Cin; ++ci) {
+    float vv[9];
+#pragma unroll
+    for (int t = 0; t < 9; ++t) vv[t] = s_in[(ci * PR + py + t / 3) * PC + px + (t % 3)];
+#pragma unroll
+    for (int k = 0; k < KT; ++k)
+#pragma unroll
+      for (int t = 0; t < 9; ++t) acc[k] = fmaf(s_w[(k * Cin + ci) * 9 + t], vv[t], acc[k]);
+  }
+  const size_t HW = (size_t)H * W, pix = (size_t)y * W + x;
+  if (logits) {
+#pragma unroll
+    for (int k = 0; k < KT; ++k)
+      if (k < K) logits[((size_t)n * K + k) * HW + pix] = acc[k];
+  }
+  if (classes) classes[(size_t)n * HW + pix] = (uint8_t)head_argmax<KT, 1>(acc, K);
+}
+
 __global__ __launch_bounds__(256) void k_head_dgrad(const float* __restrict__ dl, const float* __restrict__ w,
                                                     float* __restrict__ gin, int Cin, int H, int W) {
   constexpr int PR = HT_R + 2, PC = HT_C + 2;
@@ -1897,17 +2212,28 @@ extern "C" int sc_cast_f64_f32(const double* in, float* out, size_t n, sc_stream
 extern "C" int sc_stem_conv_fwd(const sc_src* in, const float* w, float* out, int N, int Cin, int Hin, int Win,
                                 float* stats, sc_stream stream) {
   SC_REQUIRE(in && in->C == Cin, "sc_stem_conv_fwd: source channels != Cin");
-  SC_REQUIRE(Cin >= 1 && Cin <= STEM_MAXCI, "sc_stem_conv_fwd: Cin must be in [1,%d] (got %d)", STEM_MAXCI, Cin);
+  SC_REQUIRE(Cin >= 1 && Cin <= STEM_MAXCI_FWD, "sc_stem_conv_fwd: Cin must be in [1,%d] (got %d)", STEM_MAXCI_FWD, Cin);
+  SC_REQUIRE(!stats || Cin <= STEM_MAXCI, "sc_stem_conv_fwd: statistics rows need Cin <= %d (got %d): the wide stem is inference only", STEM_MAXCI, Cin);
   SC_REQUIRE(in->mode != SC_SRC_BNBWD && in->up == 0, "sc_stem_conv_fwd: unsupported source mode");
   const int Hout = (Hin - 1) / 2 + 1, Wout = (Win - 1) / 2 + 1;
   dim3 grid(((Wout + 31) / 32) * ((Hout + 7) / 8), 1, N);
-  static const bool mfma_off = [] { const char* e = getenv("STARCOP_STEM_MFMA"); return e && atoi(e) == 0; }();      // (same-box A/B)
-  if (Cin <= 4 && !mfma_off && Wout % 4 == 0 && ((uintptr_t)out & 15) == 0)
-    hipLaunchKernelGGL(k_stem_fwd4m, grid, dim3(256), 0, (hipStream_t)stream, to_srcd(*in), w, out, Cin, Hin, Win, Hout, Wout, stats);
-  else if (Cin <= 4) hipLaunchKernelGGL(k_stem_fwd<4>, grid, dim3(256), 0, (hipStream_t)stream, to_srcd(*in), w, out, Cin, Hin, Win, Hout, Wout, stats);
-  else hipLaunchKernelGGL(k_stem_fwd<STEM_MAXCI>, grid, dim3(256), 0, (hipStream_t)stream, to_srcd(*in), w, out, Cin, Hin, Win, Hout, Wout, stats);
+  switch (sc_stem_fwd_kernel(Cin, Win, ((uintptr_t)out & 15) == 0)) {
+    case SC_STEM_K_MFMA4: hipLaunchKernelGGL(k_stem_fwd4m, grid, dim3(256), 0, (hipStream_t)stream, to_srcd(*in), w, out, Cin, Hin, Win, Hout, Wout, stats); break;
+    case SC_STEM_K_VALU4: hipLaunchKernelGGL(k_stem_fwd<4>, grid, dim3(256), 0, (hipStream_t)stream, to_srcd(*in), w, out, Cin, Hin, Win, Hout, Wout, stats); break;
+    case SC_STEM_K_VALU8: hipLaunchKernelGGL(k_stem_fwd<STEM_MAXCI>, grid, dim3(256), 0, (hipStream_t)stream, to_srcd(*in), w, out, Cin, Hin, Win, Hout, Wout, stats); break;
+    default: hipLaunchKernelGGL(k_stem_fwd16, grid, dim3(256), 0, (hipStream_t)stream, to_srcd(*in), w, out, Cin, Hin, Win, Hout, Wout); break;
+  }
   SC_LAUNCH_OK("sc_stem_conv_fwd");
   return SC_OK;
+}
+
+// which kernel sc_stem_conv_fwd launches (its own dispatch rule, exported so that a caller can tell the paths apart)
+extern "C" int sc_stem_fwd_kernel(int Cin, int Win, int out_aligned16) {
+  if (Cin < 1 || Cin > STEM_MAXCI_FWD) return SC_ERR_ARG;
+  const int Wout = (Win - 1) / 2 + 1;
+  static const bool mfma_off = [] { const char* e = getenv("STARCOP_STEM_MFMA"); return e && atoi(e) == 0; }();      // (same-box A/B)
+  if (Cin <= 4) return (!mfma_off && Wout % 4 == 0 && out_aligned16) ? SC_STEM_K_MFMA4 : SC_STEM_K_VALU4;
+  return Cin <= STEM_MAXCI ? SC_STEM_K_VALU8 : SC_STEM_K_VALU16;
 }
 
 extern "C" size_t sc_stem_wgrad_workspace_floats(int N, int Cin, int Hin, int Win) {
@@ -1948,6 +2274,42 @@ extern "C" int sc_head_conv_fwd(const sc_src* in, const float* w, const float* b
     hipLaunchKernelGGL((k_head_fwd<0>), grid, dim3(256), 0, (hipStream_t)stream, to_srcd(*in), w, bias, out, Cin, H, W);
   }
   SC_LAUNCH_OK("sc_head_conv_fwd");
+  return SC_OK;
+}
+
+template <int KT>
+static void launch_head_fwdk16(bool vec, dim3 grid, hipStream_t st, const SrcD& s, const float* w, const float* bias, float* logits,
+                               uint8_t* classes, int K, int H, int W, int lvec, int cvec) {
+  if (vec) hipLaunchKernelGGL((k_head_fwdk16<KT, true>), grid, dim3(256), 0, st, s, w, bias, logits, classes, K, H, W, lvec, cvec);
+  else hipLaunchKernelGGL((k_head_fwdk16<KT, false>), grid, dim3(256), 0, st, s, w, bias, logits, classes, K, H, W, lvec, cvec);
+}
+
+extern "C" int sc_head_conv_fwd_k(const sc_src* in, const float* w, const float* bias, float* logits, uint8_t* classes, int N,
+                                  int Cin, int K, int H, int W, sc_stream stream) {
+  SC_REQUIRE(in && in->C == Cin, "sc_head_conv_fwd_k: source channels != Cin");
+  SC_REQUIRE(Cin >= 1 && Cin <= HEAD_MAXCI, "sc_head_conv_fwd_k: Cin must be in [1,%d]", HEAD_MAXCI);
+  SC_REQUIRE(K >= 1 && K <= HEADK_MAXK, "sc_head_conv_fwd_k: K must be in [1,%d] (got %d)", HEADK_MAXK, K);
+  SC_REQUIRE((in->mode == SC_SRC_RAW || in->mode == SC_SRC_AFFINE) && in->up == 0, "sc_head_conv_fwd_k: unsupported source mode");
+  SC_REQUIRE(logits || classes, "sc_head_conv_fwd_k: at least one of logits / classes must be given");
+  SC_REQUIRE(w && N > 0 && H > 0 && W > 0, "sc_head_conv_fwd_k: bad argument");
+  hipStream_t st = (hipStream_t)stream;
+  if (K == 1) {      // one class: the binary head's kernels; argmax over one logit is 0 whatever its value
+    if (classes && hipMemsetAsync(classes, 0, (size_t)N * H * W, st) != hipSuccess) { sc_set_error("sc_head_conv_fwd_k: memset failed"); return SC_ERR_LAUNCH; }
+    return logits ? sc_head_conv_fwd(in, w, bias, logits, N, Cin, H, W, stream) : SC_OK;
+  }
+  if (Cin == 16) {
+    dim3 g16(((W + 63) / 64) * ((H + 15) / 16), 1, N);
+    const bool w4 = W % 4 == 0;
+    const bool vec = w4 && ((uintptr_t)in->x & 15) == 0;
+    const int lvec = w4 && ((uintptr_t)logits & 15) == 0, cvec = w4 && ((uintptr_t)classes & 3) == 0;
+    if (K <= 2) launch_head_fwdk16<2>(vec, g16, st, to_srcd(*in), w, bias, logits, classes, K, H, W, lvec, cvec);
+    else if (K <= 4) launch_head_fwdk16<4>(vec, g16, st, to_srcd(*in), w, bias, logits, classes, K, H, W, lvec, cvec);
+    else launch_head_fwdk16<8>(vec, g16, st, to_srcd(*in), w, bias, logits, classes, K, H, W, lvec, cvec);
+  } else {
+    dim3 grid(((W + HT_C - 1) / HT_C) * ((H + HT_R - 1) / HT_R), 1, N);
+    hipLaunchKernelGGL(k_head_fwdk, grid, dim3(256), 0, st, to_srcd(*in), w, bias, logits, classes, Cin, K, H, W);
+  }
+  SC_LAUNCH_OK("sc_head_conv_fwd_k");
   return SC_OK;
 }
 

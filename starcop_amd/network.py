@@ -311,12 +311,13 @@ class HyperStarcopUNet(nn.Module):
 
     def __init__(self, in_channels=4, classes=1):
         super().__init__()
-        if classes != 1:
-            raise ValueError("HyperStarcopUNet: the HIP segmentation head implements classes=1 "
-                             "(starcop/config.yaml:40 num_classes: 1)")
-        if not (1 <= in_channels <= 8):
-            raise ValueError("HyperStarcopUNet: in_channels must be in [1, 8]")
-        self.in_channels = in_channels
+        # inference runs for every pair below; training needs classes == 1 (starcop/config.yaml:40 num_classes: 1) and
+        # in_channels <= 8 -- refused at the first training forward (_forward_impl), so that such a model still loads and predicts
+        if not (1 <= classes <= self.MAX_CLASSES):
+            raise ValueError(f"HyperStarcopUNet: classes must be in [1, {self.MAX_CLASSES}] (sc_head_conv_fwd_k)")
+        if not (1 <= in_channels <= self.MAX_IN_CHANNELS):
+            raise ValueError(f"HyperStarcopUNet: in_channels must be in [1, {self.MAX_IN_CHANNELS}] (sc_stem_conv_fwd)")
+        self.in_channels, self.classes = in_channels, classes
         self.encoder = _Encoder(in_channels)
         self.decoder = _Decoder()
         self.segmentation_head = nn.Sequential(nn.Conv2d(DECODER_CHANNELS[-1], classes, 3, padding=1))
@@ -326,6 +327,9 @@ class HyperStarcopUNet(nn.Module):
         self._pflat = self._gflat = None
         self._pack_version = None
         self.register_load_state_dict_post_hook(HyperStarcopUNet._after_load)
+
+    MAX_IN_CHANNELS, MAX_CLASSES = 16, 8                 # forward kernels: the stem's channels, the head's classes
+    MAX_TRAIN_IN_CHANNELS, MAX_TRAIN_CLASSES = 8, 1      # ... of which sc_stem_conv_wgrad / sc_head_conv_bwd cover these
 
     @staticmethod
     def _after_load(module, incompatible_keys):
@@ -506,7 +510,7 @@ class HyperStarcopUNet(nn.Module):
             o2 = T(f"d{b}b", blk.conv2[0].out_channels, sh, "raw", blk.conv2[1], ACT_RELU)
             ops.append(dict(type="conv3", conv=blk.conv2[0], ins=[o1], up=False, out=o2))
             cur = o2
-        logits = T("logits", 1, 0, "fin")
+        logits = T("logits", self.classes, 0, "fin")
         ops.append(dict(type="head", conv=self.segmentation_head[0], ins=[cur], out=logits))
         return ops, tensors
 
@@ -593,7 +597,8 @@ class HyperStarcopUNet(nn.Module):
     class _Plan:
         pass
 
-    def _get_plan(self, N, H, W, need_grad):
+    def _get_plan(self, N, H, W, need_grad, want_logits=True):
+        """want_logits=False (predict_classes): a plan created by this call gets no logits buffer; the first call that wants one adds it"""
         key = (N, H, W)
         plan = self._plans.get(key)
         dev = self._pflat.device
@@ -618,7 +623,7 @@ class HyperStarcopUNet(nn.Module):
             irt_e = {self._ops[i]["out"].name for i in plan.irt}
             for op in self._ops:
                 t = op["out"]
-                if t.kind != "input" and t.name not in plan.buf and t.name not in irt_e:      # (a fused block's expanded tensor exists
+                if t.kind != "input" and t.name not in plan.buf and t.name not in irt_e and t.name != "logits":      # (a fused block's expanded tensor exists
                     plan.buf[t.name] = torch.empty((N, t.C, H >> t.shift, W >> t.shift), **f32)     #  only in inference: _forward_impl)
                 if t.bn is not None:
                     Ho, Wo = H >> t.shift, W >> t.shift
@@ -673,6 +678,10 @@ class HyperStarcopUNet(nn.Module):
             plan.n_eval = 0
             plan.has_grad = False
             self._plans[key] = plan
+        if want_logits and "logits" not in plan.buf:
+            plan.buf["logits"] = torch.empty((N, self.classes, H, W), dtype=torch.float32, device=dev)
+        if not want_logits and getattr(plan, "classes", None) is None:
+            plan.classes = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
         if need_grad and not plan.has_grad:
             lib = _lib.load()
             f32 = dict(dtype=torch.float32, device=dev)
@@ -949,8 +958,14 @@ class HyperStarcopUNet(nn.Module):
     def _dy_src(self, plan, t):
         return make_src(plan.grad[t.name], t.C, SRC_BNBWD, act=t.act, cst=plan.cstb[t.name], aux=plan.buf[t.name])
 
-    def _forward_impl(self, x, x_cst, training, need_grad, _recheck=0):
-        """x: (N,C,H,W) fp32 device tensor (raw physical units if x_cst is given, else already normalised)."""
+    def _forward_impl(self, x, x_cst, training, need_grad, _recheck=0, head="logits"):
+        """x: (N,C,H,W) fp32 device tensor (raw physical units if x_cst is given, else already normalised).
+        head: "logits" -> plan.buf["logits"] (N,K,H,W); "classes" -> plan.classes (N,H,W) uint8 = argmax over K, no logits stored."""
+        if training and (self.classes > self.MAX_TRAIN_CLASSES or self.in_channels > self.MAX_TRAIN_IN_CHANNELS):
+            raise NotImplementedError(
+                f"HyperStarcopUNet(in_channels={self.in_channels}, classes={self.classes}) runs in eval mode only: training needs two "
+                f"kernels that do not exist -- the stem weight gradient above {self.MAX_TRAIN_IN_CHANNELS} input channels "
+                f"(sc_stem_conv_wgrad) and the backward of the K-class head (sc_head_conv_bwd is the 1-class head's)")
         _lib.require_device(x)
         lib = _lib.load()
         if x.dim() != 4 or x.shape[1] != self.in_channels:
@@ -961,7 +976,7 @@ class HyperStarcopUNet(nn.Module):
                                "divisible by 32.")
         self._ensure_flat()
         x = x.contiguous().float()
-        plan = self._get_plan(N, H, W, need_grad)
+        plan = self._get_plan(N, H, W, need_grad, want_logits=head == "logits")
         plan.buf["x"] = x
         plan.x_cst = x_cst
         plan.generation = getattr(plan, "generation", 0) + 1     # activations of an earlier forward of this shape are gone
@@ -1137,8 +1152,14 @@ class HyperStarcopUNet(nn.Module):
                                              plan.fin_amax.data_ptr() + 4 * plan.fin_slot[o.name], st))
             elif ty == "head":
                 s = self._src_of(plan, op["ins"][0])
-                check(lib.sc_head_conv_fwd(C.byref(s), ptr(conv.weight), ptr(conv.bias), ptr(plan.buf[o.name]),
-                                           N, conv.in_channels, Ho, Wo, st))
+                if self.classes == 1 and head == "logits":
+                    check(lib.sc_head_conv_fwd(C.byref(s), ptr(conv.weight), ptr(conv.bias), ptr(plan.buf[o.name]),
+                                               N, conv.in_channels, Ho, Wo, st))
+                else:       # K classes and / or the fused argmax: exactly one of the two outputs
+                    check(lib.sc_head_conv_fwd_k(C.byref(s), ptr(conv.weight), ptr(conv.bias),
+                                                 ptr(plan.buf[o.name]) if head == "logits" else None,
+                                                 ptr(plan.classes) if head == "classes" else None,
+                                                 N, conv.in_channels, self.classes, Ho, Wo, st))
             self._pe(tok)
             if o.bn is not None and training and not bn_done and not ("f" in _EXP_NO_BNFIN and plan.generation > 3):
                 bn = o.bn
@@ -1179,7 +1200,7 @@ class HyperStarcopUNet(nn.Module):
                                           f"({self.FP16_MAX_ACT:g}) and was clamped; the forward is redone with the adapted scale.  "
                                           f"Forwards between two checks (range_check_every={self.range_check_every}) are not re-examined: "
                                           f"set range_check_every=1 for data of unknown range")
-                        return self._forward_impl(x, x_cst, training, need_grad, _recheck=_recheck + 1)
+                        return self._forward_impl(x, x_cst, training, need_grad, _recheck=_recheck + 1, head=head)
                     self._inference_unrepaired += 1
                     warnings.warn(f"HyperStarcopUNet (inference, precision='fp32'): activations still outside the fp16 range after 6 "
                                   f"re-runs with adapted scales ({worst:.4g}); the returned logits carry operands clamped to "
@@ -1830,13 +1851,23 @@ class HyperStarcopUNet(nn.Module):
 
     # ------------------------------------------------------------------------------------------
     def forward(self, x, normalizer_consts=None):
-        """(B,C,H,W) -> (B,1,H,W) logits.  ``normalizer_consts`` (C,8) fuses DataNormalizer.normalize_x into the stem."""
+        """(B,C,H,W) -> (B,classes,H,W) logits.  ``normalizer_consts`` (C,8) fuses DataNormalizer.normalize_x into the stem."""
         need_grad = torch.is_grad_enabled() and self.training and any(p.requires_grad for p in self.parameters())
         if need_grad:
             self._ensure_flat()
             return _UNetFunction.apply(self, x, normalizer_consts, *list(self.parameters()))
         plan = self._forward_impl(x, normalizer_consts, self.training, False)
         return plan.buf["logits"].clone()
+
+    @torch.no_grad()
+    def predict_classes(self, x, normalizer_consts=None):
+        """(B,C,H,W) -> (B,H,W) uint8 = ``torch.argmax(logits, dim=1).type(torch.uint8)`` (starcop/sentinel2/models.py:75-78), eval mode
+        only.  Same plan and launches as the eval forward up to the head, which writes the class index instead of the logits
+        (sc_head_conv_fwd_k with logits = NULL): the logits are never stored, and a plan that only serves this call has no buffer for them."""
+        if self.training:
+            raise RuntimeError("HyperStarcopUNet.predict_classes: eval mode only (call .eval() first)")
+        plan = self._forward_impl(x, normalizer_consts, False, False, head="classes")
+        return plan.classes.clone()
 
 
 class _UNetFunction(torch.autograd.Function):
