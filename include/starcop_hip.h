@@ -913,6 +913,45 @@ int sc_tile_window_sums(const float* labels, int M, int H, int W, const int32_t*
                         double* out, sc_stream stream);
 
 /* ------------------------------------------------------------------------- */
+/* Regression path (starcop/models/model_module_regression.py): the pointwise networks SimpleCNN_v2 (one 1x1 convolution) and
+ * SimpleCNN_v3 (two, no activation between them; models/architectures/baselines.py:43-70) and the losses of
+ * models/utils/losses.py (F.l1_loss / F.mse_loss, default reduction).
+ *
+ * Network: Cin -> C1 [-> Cout], every count in 1..SC_PWREG_MAXC, `layers` 1 or 2 (one layer: C1 == Cout), bias always present.
+ * `params` is one flat fp32 device buffer in state_dict order: W1[C1][Cin], b1[C1], then for two layers W2[Cout][C1], b2[Cout]
+ * (sc_pwreg_param_floats of them; 0 for an unsupported shape).  Tensors are dense NCHW fp32, any H*W >= 1.
+ *
+ *   sc_pwreg_fwd          pred[N][Cout][H][W] from x[N][Cin][H][W], layer by layer in fp32 (an fmaf chain over ascending input
+ *                         channel, starting from the bias).  16-byte loads and stores when H*W is a multiple of 4 and both
+ *                         tensors start on 16-byte boundaries (then every plane does), element accesses otherwise.
+ *   sc_reg_loss           *loss_sum = sum |pred - y| (SC_REG_L1) or sum (pred - y)^2 (SC_REG_MSE) over n elements, in fp64 (the
+ *                         caller divides by n); dpred (optional) = d mean / d pred = sign(pred - y) / n with sign(0) = 0, or
+ *                         2 (pred - y) / n.  work: SC_REG_LOSS_PARTS doubles.  Fixed summation order, no atomics.
+ *   sc_pwreg_train_sweep  one pass over x and y: prediction and g = sign(pred - y) | (pred - y) in registers, nothing of that
+ *                         size is stored; mode SC_PWREG_G_FROM_MEMORY reads g[N][Cout][H][W] from y_or_g instead (params may be
+ *                         NULL).  Writes sc_pwreg_sweep_blocks(N, H, W) partial rows of SC_PWREG_PART_DOUBLES doubles:
+ *                         M[16][16] = sum_pixels g x^T, s[16] = sum_pixels g, and the loss sum.
+ *   sc_pwreg_finalize     one work-group: sums the rows in a fixed order, multiplies the moments by `scale` (1/n for L1, 2/n for
+ *                         MSE, 1 for g from memory), forms in fp64   one layer: dW = M, db = s;   two layers: dW2 = M W1^T + s b1^T,
+ *                         db2 = s, dW1 = W2^T M, db1 = W2^T s   and writes grad (fp32, flat, parameter order) and, if not NULL,
+ *                         *loss_sum (unscaled).
+ * No floating-point atomics anywhere; the sweep's grid depends on N*H*W only; equal inputs give equal bits.                  */
+#define SC_PWREG_MAXC 16
+#define SC_PWREG_PART_DOUBLES 273
+#define SC_REG_LOSS_PARTS 256
+enum sc_reg_loss_kind { SC_REG_L1 = 0, SC_REG_MSE = 1, SC_PWREG_G_FROM_MEMORY = 2 };
+size_t sc_pwreg_param_floats(int Cin, int C1, int Cout, int layers);
+int sc_pwreg_fwd(const float* x, const float* params, int N, int Cin, int C1, int Cout, int layers, int H, int W, float* pred,
+                 sc_stream stream);
+int sc_reg_loss(const float* pred, const float* y, size_t n, int kind, double* loss_sum, float* dpred, double* work,
+                sc_stream stream);
+int sc_pwreg_sweep_blocks(int N, int H, int W);
+int sc_pwreg_train_sweep(const float* x, const float* y_or_g, const float* params, int N, int Cin, int C1, int Cout, int layers,
+                         int H, int W, int mode, double* part, sc_stream stream);
+int sc_pwreg_finalize(const double* part, int nblocks, const float* params, int Cin, int C1, int Cout, int layers, double scale,
+                      float* grad, double* loss_sum, sc_stream stream);
+
+/* ------------------------------------------------------------------------- */
 /* HOST functions (no device involved): decoders of the on-disk sample format -- one tiled GeoTIFF per product per sample,
  * read by rasterio in the reference (starcop/data/dataset.py:66-76, written by save_cog at sampling_dataset.py:332-355).
  *   sc_tiff_lzw_decode : TIFF 6.0 LZW (GDAL's default COG compression); *written = bytes produced (<= n_out)

@@ -18,6 +18,8 @@ Public surface (mirrors the reference):
     mag1c_stats_dataframe / windows_intersect / select_non_overlapping / sampling_no_plumes (which windows become samples)
   starcop_amd.ortho.georeference / emit_geo_tags (orthorectification through a geometry look-up table); starcop_amd.mag1c.mag1c_emit
     (the EMIT driver with its georreferenced=True default); pipeline.emit_granule_predict(georeferenced=True, out_folder=...)
+  starcop_amd.model_module_regression.ModelModuleRegression / l1 / mse (the regression twin; get_model serves both modes);
+    starcop_amd.pointwise_net.SimpleCNN_v2 / SimpleCNN_v3; features.set_learned_model (the learned band-ratio product)
 All compute runs in starcop_amd/libstarcop_hip.so (include/starcop_hip.h); there is no CPU fallback.
 """
 __version__ = "0.1.0"

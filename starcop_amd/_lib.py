@@ -272,10 +272,18 @@ SIGNATURES = {
     "sc_upsample_bilinear2x": (_i, [C.POINTER(sc_src), _vp, _i, _i, _i, _i, _vp]),
     "sc_maxpool2x2_bwd": (_i, [C.POINTER(sc_src), _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "sc_upsample_bilinear2x_bwd": (_i, [_vp, _vp, _i, _i, _i, _i, _vp]),
+    "sc_pwreg_param_floats": (_sz, [_i, _i, _i, _i]),
+    "sc_pwreg_fwd": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sc_reg_loss": (_i, [_vp, _vp, _sz, _i, _vp, _vp, _vp, _vp]),
+    "sc_pwreg_sweep_blocks": (_i, [_i, _i, _i]),
+    "sc_pwreg_train_sweep": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
+    "sc_pwreg_finalize": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _d, _vp, _vp, _vp]),
     "sc_tiff_lzw_decode": (_i, [_vp, _sz, _vp, _sz, C.POINTER(C.c_size_t)]),
     "sc_tiff_unpredict": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp]),
 }
-PACK_SPD = 8           # ... and of its data gradient sc_conv3x3_sp_dgrad
+REG_L1, REG_MSE, PWREG_G_FROM_MEMORY = 0, 1, 2       # enum sc_reg_loss_kind
+PWREG_MAXC, PWREG_PART_DOUBLES, REG_LOSS_PARTS = 16, 273, 256
+PACK_SPD = 8          # ... and of its data gradient sc_conv3x3_sp_dgrad
 PACK_SP = 7            # sc_pack_desc.bx3 code of the phase-filter layout of sc_conv3x3_sp
 PACK_PW3 = 6           # sc_pack_desc.bx3 code of the pointwise layout of sc_conv1x1_pw3
 PACK_THIN16 = 5        # sc_pack_desc.bx3 code of the register layout of sc_conv3x3_thin16

@@ -202,9 +202,60 @@ def ratio_MLR_local_5IN_simplediv(IN1, IN2, IN3, IN4, IN5, target_B, division="s
     return ratio_MLR_local([IN1, IN2, IN3, IN4, IN5], target_B, division=division, autoclip=autoclip)
 
 
+# ------------------------------------------------------------------------------------------------ learned band ratio
+# feature_extration.py:127-175: a cnn_v2 regression model predicts WV3 band 8 from bands 1-6; the product is the matched ratio of
+# the real band 8 against that prediction.  The reference pulls its checkpoint from a bucket on first use; here the model is
+# handed over explicitly with set_learned_model() -- the project ships no weights.
+_learned_model = None
+
+
+def set_learned_model(module_or_checkpoint_path, settings=None):
+    """The model behind ``ratio_lrn_bands2band8only_60ep_512_l1``: a module mapping (B, 6, H, W) to (B, 1, H, W) (a
+    ``ModelModuleRegression`` or a bare ``SimpleCNN_v2(6, 1)``), or the path of a local ``ModelModuleRegression`` checkpoint to
+    load with ``settings``.  ``None`` unsets it.  Returns the module."""
+    global _learned_model
+    m = module_or_checkpoint_path
+    if isinstance(m, (str, bytes)) or hasattr(m, "__fspath__"):
+        path = m.decode() if isinstance(m, bytes) else str(m)
+        if path.startswith("gs://"):
+            raise NotImplementedError(f"{path}: remote checkpoints are not fetched; copy the file and pass its local path")
+        if settings is None:
+            raise ValueError("set_learned_model(path) needs the settings the checkpoint was trained with")
+        from .model_module_regression import ModelModuleRegression
+        m = ModelModuleRegression.load_from_checkpoint(path, settings=settings)
+        m = m.to("cuda")
+    if m is not None:
+        m.eval()
+    _learned_model = m
+    return m
+
+
 def use_pretrained_model_b1to6_b8(*inputs, **kwargs):
-    raise NotImplementedError("ratio_lrn_bands2band8only_60ep_512_l1 needs the reference's remote regression checkpoint "
-                              "(ModelModuleRegression), which this project does not ship")
+    """feature_extration.py:152-175 for every (H, W) tile: stack bands 1-6, run the learned model, then
+    ``ratio_2c_match_c_from_sums_outlier(target, output, zero_value_out=-0.5)`` with -0.5 where the target band is 0."""
+    if _learned_model is None:
+        raise NotImplementedError("ratio_lrn_bands2band8only_60ep_512_l1 needs the reference's regression checkpoint "
+                                  "(wv3_cnn_v2_bands2band8only_60ep_512_l1), which this project does not ship: load one with "
+                                  "features.set_learned_model(module_or_checkpoint_path, settings)")
+    if kwargs or len(inputs) != 7:
+        raise TypeError("use_pretrained_model_b1to6_b8(inB1, inB2, inB3, inB4, inB5, inB6, outB8)")
+    bands = [torch.as_tensor(b) for b in inputs]
+    for b in bands:
+        _lib.require_device(b)
+    target = bands[6].contiguous().float()
+    shape = tuple(target.shape)
+    if len(shape) < 2 or any(tuple(b.shape) != shape for b in bands):
+        raise ValueError("the six input bands and the target band must all have one (..., H, W) shape")
+    H, W = shape[-2:]
+    x = torch.stack([b.float().reshape(-1, H, W) for b in bands[:6]], 1).contiguous()          # (B, 6, H, W)
+    with torch.no_grad():
+        output = _learned_model(x)
+    if tuple(output.shape) != (x.shape[0], 1, H, W):
+        raise ValueError(f"the learned model must map (B, 6, H, W) to (B, 1, H, W), got {tuple(output.shape)}")
+    tgt = target.reshape(-1, H, W)
+    R = ratio_2c_match_c_from_sums_outlier(tgt, output[:, 0], zero_value_out=-0.5)
+    R[tgt == 0] = -0.5
+    return R.reshape(shape)
 
 
 # ------------------------------------------------------------------------------------------------ the feature registry
