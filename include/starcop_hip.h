@@ -147,6 +147,11 @@ typedef struct sc_conv_args {
   const sc_bnr_args* bnr;/* data-gradient launches (SC_SRC_BNBWD source): also leave the BatchNorm-backward sums of out0's tensor, or NULL */
 } sc_conv_args;
 int sc_conv2d_mfma(const sc_conv_args* a, sc_stream stream);
+/* HOST: whether sc_conv2d_mfma hands these arguments (ks = 1) to its register-streaming pointwise kernel, and which variant of it:
+ * -1 = no (the LDS-staged kernels take the launch), else 100 * (src[0] is SC_SRC_BNBWD) + 10 * NCB (16-channel output blocks per
+ * wave: 1, 2, 5, 6 forward; 2, 3, 5, 6 for a BNBWD source) + NKS (K steps of 4 input channels in registers: 4, 6 or 8).  The pointers
+ * are only tested for NULL and 16-byte alignment.  The entry point dispatches on this value. */
+int sc_pw_stream_variant(const sc_conv_args* a);
 /* 1x1 convolution for few-pixel / long-K layers (the <= 64^2 inverted-residual projections and the data gradients of the
  * expansions): 32-pixel tiles, the four waves of a work-group split K, operands go global -> registers -> MFMA (no LDS
  * staging).  Same arguments as sc_conv2d_mfma with ks = 1, nsrc = 1 and sc_pack_weights(ks=1) filters; co_t in {32, 64};
@@ -279,18 +284,25 @@ int sc_conv3x3_wgrad_thin16(const sc_wgrad_args* a, sc_stream stream);
  * ignored; statistics rows = sc_stat_rows(SC_STAT_PW3, N, H, W) = one row per 32 flat pixels of the batch. */
 size_t sc_packed_weight_floats_pw3(int Cout, int Cin, int transpose_flip);
 int sc_conv1x1_pw3(const sc_conv_args* a, sc_stream stream);
+/* HOST: the kernel variant sc_conv1x1_pw3 launches for this shape (Cout = the launch's output channels: the layer's Cin for a data
+ * gradient) -- the 32-channel output blocks a wave owns: 4, 2 or 1; -1 for a bad shape.  The entry point dispatches on this value. */
+int sc_conv1x1_pw3_variant(int N, int H, int W, int Cout);
 /* its weight gradient (K = pixels; H*W must be a multiple of 8): same sc_wgrad_args as sc_conv2d_wgrad_mfma with ks = 1, nsrc = 1;
  * workspace from sc_wgrad_pw3_workspace_floats; pending != NULL defers the sum over the K-slice partials to
  * sc_wgrad_reduce_batch (as sc_conv2d_wgrad_mfma_deferred), NULL finishes it here. */
 size_t sc_wgrad_pw3_workspace_floats(int N, int H, int W, int Cout, int Cin);
 int sc_conv1x1_wgrad_pw3(const sc_wgrad_args* a, sc_wgrad_pending* pending_host, sc_stream stream);
+/* HOST: the kernel variant sc_conv1x1_wgrad_pw3 launches: 10 * tm + tn, the 32-channel blocks of dy (tm) and of the input (tn) a
+ * wave owns -- 11, 12, 21 or 22; -1 for a bad shape.  The entry point dispatches on this value. */
+int sc_wgrad_pw3_variant(int N, int H, int W, int Cout, int Cin);
 
 /* One launch per MobileNetV2 inverted-residual block in INFERENCE (conv_irb.hip; torchvision InvertedResidual.conv inside
  * smp.Unet('mobilenet_v2').encoder, eval-mode BatchNorm: starcop/models/model_module.py:90-98 forward, :244-251 the network; the
  * notebook / padded_predict path starcop/models/utils/padding.py:13-50):
  *     x -> conv1x1 (Cin -> hidden) -> BN_e + ReLU6 -> depthwise 3x3 (stride 1 | 2, pad 1) -> BN_d + ReLU6 -> conv1x1 (hidden -> Cout)
  *       -> raw p (residual = 0: BN_p is the consumers' business, as for every other convolution here)
- *       -> z = x + BN_p(p)  (residual = 1: Cin == Cout; z_absmax, if not NULL, is raised to max |z| like sc_add_srcs_absmax does)
+ *       -> z = x + BN_p(p)  (residual = 1: Cin == Cout; x as the source forms it, an AFFINE source's scale, shift and activation
+ *          applied; z_absmax, if not NULL, is raised to max |z| like sc_add_srcs_absmax does)
  * The expanded tensors never leave the CU.  Both 1x1 filters come in the sc_conv1x1_pw3 layout (sc_pack_weights_batch with
  * SC_PACK_PW3, transpose_flip 0); fp32 accuracy (three exact bf16 terms per operand, six MFMA products, fp32 stencil).
  * Stride 1: 8 <= Cin <= 160, hidden % 32 == 0, Cout <= 384 subject to the accumulator budget; stride 2 (no residual; H, W are the INPUT
@@ -308,6 +320,12 @@ typedef struct sc_irb_args {
   int32_t N, Cin, hidden, Cout, H, W, stride, residual;
 } sc_irb_args;
 int sc_irb_supported(int Cin, int hidden, int Cout, int H, int W, int stride);
+/* HOST: the kernel variant sc_irb_eval launches for a block shape: -1 = unsupported, else
+ *   10000 * tiling (0 = A: 4 x 8 output pixels, 64-channel chunks; 1 = B: 8 x 8, 32-channel chunks; 2 = C: 8 x 8, 64-channel chunks,
+ *   8 waves -- development knob only; 3 = the stride-2 form of A) + 1000 * projection pairs per wave (1..3)
+ *   + 10 * expansion K steps held in registers (2, 4, 6 or 10) + work-groups per CU (1 | 2).
+ * The entry point dispatches on this value. */
+int sc_irb_variant(int Cin, int hidden, int Cout, int stride);
 int sc_irb_eval(const sc_irb_args* a, sc_stream stream);
 
 /* Fused TRAINING execution of the expansion + depthwise pair of a STRIDE-2 MobileNetV2 inverted-residual block (torchvision

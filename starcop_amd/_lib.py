@@ -159,6 +159,7 @@ SIGNATURES = {
     "sc_pack_work_items": (_sz, [_i, _i, _i, _i, _i, _i]),
     "sc_pack_weights_batch": (_i, [_vp, _vp, _i, C.c_uint32, _vp]),
     "sc_conv2d_mfma": (_i, [C.POINTER(sc_conv_args), _vp]),
+    "sc_pw_stream_variant": (_i, [C.POINTER(sc_conv_args)]),
     "sc_conv1x1_ksplit": (_i, [C.POINTER(sc_conv_args), _vp]),
     "sc_wgrad_bx3_workspace_floats": (_sz, [_i, _i, _i, _i, _i]),
     "sc_conv3x3_wgrad_bx3": (_i, [C.POINTER(sc_wgrad_args), _vp]),
@@ -254,9 +255,12 @@ SIGNATURES = {
     "sc_wgrad_reduce_batch": (_i, [_vp, _vp, _i, C.c_uint32, _vp]),
     "sc_packed_weight_floats_pw3": (_sz, [_i, _i, _i]),
     "sc_conv1x1_pw3": (_i, [C.POINTER(sc_conv_args), _vp]),
+    "sc_conv1x1_pw3_variant": (_i, [_i, _i, _i, _i]),
     "sc_wgrad_pw3_workspace_floats": (_sz, [_i, _i, _i, _i, _i]),
+    "sc_wgrad_pw3_variant": (_i, [_i, _i, _i, _i, _i]),
     "sc_conv1x1_wgrad_pw3": (_i, [C.POINTER(sc_wgrad_args), C.POINTER(sc_wgrad_pending), _vp]),
     "sc_irb_supported": (_i, [_i, _i, _i, _i, _i, _i]),
+    "sc_irb_variant": (_i, [_i, _i, _i, _i]),
     "sc_irb_eval": (_i, [C.POINTER(sc_irb_args), _vp]),
     "sc_irt_supported": (_i, [_i, _i, _i, _i, _i]),
     "sc_irt_rows": (_i, [_i, _i, _i, _i, _i]),

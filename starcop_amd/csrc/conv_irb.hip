@@ -347,6 +347,8 @@ __global__ __launch_bounds__(TH * TW * (HC / 8), OCC) void k_irb(const IrbP p) {
   // ---- epilogue: accp[q][i] = P[output pixel pmb*32 + 8*(i/4) + 4*lhi + (i%4)][cout pcb*32 + l31]
   const bool vec4 = (Wo & 3) == 0;
   const bool xraw = p.x.mode == SC_SRC_RAW;
+  // the residual term is the block input as the staging prologue formed it: affine, then the source's activation
+  const float xlo = xraw ? -__builtin_inff() : sc_act_lo(p.x.act), xhi = xraw ? __builtin_inff() : sc_act_hi(p.x.act);
   float zmx = 0.f;
 #pragma unroll
   for (int q = 0; q < MAXPP; ++q) {
@@ -371,8 +373,8 @@ __global__ __launch_bounds__(TH * TW * (HC / 8), OCC) void k_irb(const IrbP p) {
       if (vec4) {          // W % 4 == 0 and x % 4 == 0: the four pixels are inside the row
         if (p.residual) {
           const float4 xv = *reinterpret_cast<const float4*>(xb + idx);
-          v[0] = fmaf(v[0], scp, shp) + fmaf(xv.x, xsc, xsh); v[1] = fmaf(v[1], scp, shp) + fmaf(xv.y, xsc, xsh);
-          v[2] = fmaf(v[2], scp, shp) + fmaf(xv.z, xsc, xsh); v[3] = fmaf(v[3], scp, shp) + fmaf(xv.w, xsc, xsh);
+          v[0] = fmaf(v[0], scp, shp) + sc_pro_affine(xv.x, xsc, xsh, xlo, xhi); v[1] = fmaf(v[1], scp, shp) + sc_pro_affine(xv.y, xsc, xsh, xlo, xhi);
+          v[2] = fmaf(v[2], scp, shp) + sc_pro_affine(xv.z, xsc, xsh, xlo, xhi); v[3] = fmaf(v[3], scp, shp) + sc_pro_affine(xv.w, xsc, xsh, xlo, xhi);
           zmx = fmaxf(fmaxf(zmx, fmaxf(fabsf(v[0]), fabsf(v[1]))), fmaxf(fabsf(v[2]), fabsf(v[3])));
         }
         *reinterpret_cast<float4*>(ob + idx) = make_float4(v[0], v[1], v[2], v[3]);
@@ -381,7 +383,7 @@ __global__ __launch_bounds__(TH * TW * (HC / 8), OCC) void k_irb(const IrbP p) {
         for (int u = 0; u < 4; ++u) {
           if (x + u >= Wo) continue;
           float o = v[u];
-          if (p.residual) { o = fmaf(o, scp, shp) + fmaf(xb[idx + u], xsc, xsh); zmx = fmaxf(zmx, fabsf(o)); }
+          if (p.residual) { o = fmaf(o, scp, shp) + sc_pro_affine(xb[idx + u], xsc, xsh, xlo, xhi); zmx = fmaxf(zmx, fabsf(o)); }
           ob[idx + u] = o;
         }
       }
@@ -403,12 +405,14 @@ static int irb_launch3(const IrbP& p, hipStream_t st) {
   SC_LAUNCH_OK("sc_irb_eval");
   return SC_OK;
 }
+// the expansion K steps a launch keeps in registers: the smallest of 2, 4, 6, 10 that holds ceil(Cin / 16)
+static inline int irb_nke(int nks_e) { return nks_e <= 2 ? 2 : (nks_e <= 4 ? 4 : (nks_e <= 6 ? 6 : 10)); }
 template <int TH, int TW, int HC, int MAXPP, int OCC, int NKEMAX, int S = 1>
-static int irb_launch(const IrbP& p, hipStream_t st) {
-  if (p.nks_e <= 2) return irb_launch3<TH, TW, HC, 2, MAXPP, OCC, S>(p, st);
-  if (p.nks_e <= 4) return irb_launch3<TH, TW, HC, 4, MAXPP, OCC, S>(p, st);
-  if (p.nks_e <= 6) return irb_launch3<TH, TW, HC, 6, MAXPP, OCC, S>(p, st);
-  if constexpr (NKEMAX >= 10) return irb_launch3<TH, TW, HC, 10, MAXPP, OCC, S>(p, st);
+static int irb_launch(const IrbP& p, int nke, hipStream_t st) {
+  if (nke == 2) return irb_launch3<TH, TW, HC, 2, MAXPP, OCC, S>(p, st);
+  if (nke == 4) return irb_launch3<TH, TW, HC, 4, MAXPP, OCC, S>(p, st);
+  if (nke == 6) return irb_launch3<TH, TW, HC, 6, MAXPP, OCC, S>(p, st);
+  if constexpr (NKEMAX >= 10) { if (nke == 10) return irb_launch3<TH, TW, HC, 10, MAXPP, OCC, S>(p, st); }
   sc_set_error("sc_irb_eval: internal dispatch error"); return SC_ERR_ARG;
 }
 
@@ -419,7 +423,7 @@ static int irb_launch(const IrbP& p, hipStream_t st) {
 //      work-group is half the L2 -> L1 filter traffic of A -- measured LEVEL with A on the 32 x 32 blocks (35.3 / 56.5 vs 33.7 / 55.1 us on
 //      features.8 / .12 at batch 16) and slower at 64 x 64 (65 vs 51 us): the filter traffic is not what a chunk waits for either; kept
 //      behind STARCOP_IRB_CFG=2 as the measured alternative
-enum { IRB_A = 0, IRB_B = 1, IRB_C = 2 };
+enum { IRB_A = 0, IRB_B = 1, IRB_C = 2, IRB_A2 = 3 };      // (IRB_A2: the stride-2 form of A, below)
 static inline int irb_pairs_per_wave(int cfg, int Cout) {
   const int CB = (Cout + 31) / 32;
   return cfg == IRB_A ? (CB + 3) / 4 : (cfg == IRB_B ? (2 * CB + 3) / 4 : (2 * CB + 7) / 8);
@@ -460,6 +464,19 @@ extern "C" int sc_irb_supported(int Cin, int hidden, int Cout, int H, int W, int
   return irb_pick_cfg(Cin, hidden, Cout) >= 0 ? 1 : 0;
 }
 
+// Which k_irb instantiation sc_irb_eval launches for a block shape, without touching the GPU: -1 = unsupported, else
+//   10000 * tiling (0 = A: 4 x 8 pixels, 64-channel chunks; 1 = B: 8 x 8, 32-channel chunks; 2 = C: 8 x 8, 64-channel chunks, 8 waves;
+//                   3 = the stride-2 form of A) + 1000 * projection pairs per wave (1..3) + 10 * NKE (expansion K steps in registers:
+//   2, 4, 6, 10) + work-groups per CU (1 | 2).  sc_irb_eval dispatches on this value.
+extern "C" int sc_irb_variant(int Cin, int hidden, int Cout, int stride) {
+  if (!sc_irb_supported(Cin, hidden, Cout, 1, 1, stride)) return -1;
+  const int nke = irb_nke((Cin + 15) / 16);
+  if (stride == 2) return 30000 + 1000 * irb_pairs_per_wave(IRB_A, Cout) + 10 * nke + 1;
+  const int cfg = irb_pick_cfg(Cin, hidden, Cout);
+  const int occ = cfg == IRB_A && irb_occ2(Cin, Cout) ? 2 : 1;
+  return 10000 * cfg + 1000 * irb_pairs_per_wave(cfg, Cout) + 10 * nke + occ;
+}
+
 extern "C" int sc_irb_eval(const sc_irb_args* a, sc_stream stream) {
   SC_REQUIRE(a != nullptr, "sc_irb_eval: null args");
   SC_REQUIRE(a->stride == 1 || a->stride == 2, "sc_irb_eval: stride 1 or 2 (got %d)", a->stride);
@@ -481,21 +498,18 @@ extern "C" int sc_irb_eval(const sc_irb_args* a, sc_stream stream) {
   p.Ho = (a->H - 1) / a->stride + 1; p.Wo = (a->W - 1) / a->stride + 1;
   p.nks_e = (a->Cin + 15) / 16; p.nks_p = (a->hidden + 15) / 16; p.residual = a->residual ? 1 : 0;
   hipStream_t st = (hipStream_t)stream;
-  if (a->stride == 2) {
-    p.tiles_x = (p.Wo + 7) / 8; p.tiles_y = (p.Ho + 3) / 4;
-    return irb_pairs_per_wave(IRB_A, a->Cout) <= 1 ? irb_launch<4, 8, 64, 1, 1, 6, 2>(p, st) : irb_launch<4, 8, 64, 2, 1, 6, 2>(p, st);
-  }
-  const int cfg = irb_pick_cfg(a->Cin, a->hidden, a->Cout);
-  const int mpp = irb_pairs_per_wave(cfg, a->Cout);
-  p.tiles_x = (a->W + 7) / 8; p.tiles_y = cfg == IRB_A ? (a->H + 3) / 4 : (a->H + 7) / 8;
+  const int variant = sc_irb_variant(a->Cin, a->hidden, a->Cout, a->stride);
+  const int cfg = variant / 10000, mpp = (variant / 1000) % 10, nke = (variant / 10) % 100, occ = variant % 10;
+  p.tiles_x = (p.Wo + 7) / 8; p.tiles_y = (cfg == IRB_A || cfg == IRB_A2) ? (p.Ho + 3) / 4 : (p.Ho + 7) / 8;
+  if (cfg == IRB_A2) return mpp <= 1 ? irb_launch<4, 8, 64, 1, 1, 6, 2>(p, nke, st) : irb_launch<4, 8, 64, 2, 1, 6, 2>(p, nke, st);
   if (cfg == IRB_A) {
-    if (irb_occ2(a->Cin, a->Cout)) return irb_launch<4, 8, 64, 1, 2, 6>(p, st);
-    if (mpp <= 1) return irb_launch<4, 8, 64, 1, 1, 10>(p, st);
-    if (mpp == 2) return irb_launch<4, 8, 64, 2, 1, 10>(p, st);
-    return irb_launch<4, 8, 64, 3, 1, 10>(p, st);
+    if (occ == 2) return irb_launch<4, 8, 64, 1, 2, 6>(p, nke, st);
+    if (mpp <= 1) return irb_launch<4, 8, 64, 1, 1, 10>(p, nke, st);
+    if (mpp == 2) return irb_launch<4, 8, 64, 2, 1, 10>(p, nke, st);
+    return irb_launch<4, 8, 64, 3, 1, 10>(p, nke, st);
   }
-  if (cfg == IRB_C) return mpp <= 1 ? irb_launch<8, 8, 64, 1, 1, 6>(p, st) : irb_launch<8, 8, 64, 2, 1, 6>(p, st);
-  if (mpp <= 1) return irb_launch<8, 8, 32, 1, 1, 10>(p, st);
-  if (mpp == 2) return irb_launch<8, 8, 32, 2, 1, 10>(p, st);
-  return irb_launch<8, 8, 32, 3, 1, 10>(p, st);
+  if (cfg == IRB_C) return mpp <= 1 ? irb_launch<8, 8, 64, 1, 1, 6>(p, nke, st) : irb_launch<8, 8, 64, 2, 1, 6>(p, nke, st);
+  if (mpp <= 1) return irb_launch<8, 8, 32, 1, 1, 10>(p, nke, st);
+  if (mpp == 2) return irb_launch<8, 8, 32, 2, 1, 10>(p, nke, st);
+  return irb_launch<8, 8, 32, 3, 1, 10>(p, nke, st);
 }

@@ -1390,6 +1390,31 @@ static const float* sc_identity_cst(int C) {
 
 const float* sc_identity_cst_table(int C) { return sc_identity_cst(C); }
 
+// Which k_pw_stream instantiation sc_conv2d_mfma launches for these arguments, without touching the GPU: -1 = not the streaming
+// kernel (the LDS-staged kernels take the launch), else 100 * (source is SC_SRC_BNBWD) + 10 * NCB (cout blocks of 16 per wave)
+// + NKS (K steps of 4 input channels held in registers).  sc_conv2d_mfma dispatches on this value.
+extern "C" int sc_pw_stream_variant(const sc_conv_args* a) {
+  if (a == nullptr || a->ks != 1 || a->nsrc != 1 || a->N <= 0 || a->H <= 0 || a->W <= 0 || a->Cout <= 0) return -1;
+  if (a->co_t != 32 && a->co_t != 64) return -1;
+  static const bool pws_off = [] { const char* e = getenv("STARCOP_PWS"); return e && atoi(e) == 0; }();      // (same-box A/B)
+  const long HWl = (long)a->H * a->W;
+  const int K = a->src[0].C, M = a->Cout;
+  if (K <= 0 || K % 8 != 0) return -1;
+  const bool bnb = a->src[0].mode == SC_SRC_BNBWD;      // data gradients of the projections: few dy channels, many outputs; no bnr epilogue here
+  if (a->src[0].mode != SC_SRC_RAW && a->src[0].cst == nullptr) return -1;
+  if (bnb && a->src[0].aux == nullptr) return -1;
+  const bool plain = (a->src[0].mode == SC_SRC_RAW || a->src[0].mode == SC_SRC_AFFINE || (bnb && a->bnr == nullptr && a->stats == nullptr)) &&
+                     a->src[0].up == 0 && a->csplit == a->Cout && !a->accum0 && a->add0 == nullptr && a->add1 == nullptr && a->out0 != nullptr;
+  const bool aligned = (((uintptr_t)a->src[0].x | (uintptr_t)a->out0 | (bnb ? (uintptr_t)a->src[0].aux : 0)) & 15) == 0;
+  const int nks = K / 4;
+  // short contractions only: the long-K projections (96 / 144 -> 24 at 128^2) measured a tie without and 3-8 us slower with the
+  // statistics epilogue (a lane keeps NKS filter registers per cout block: two waves per SIMD)
+  const bool ks_ok = bnb ? (nks == 4 || nks == 6 || nks == 8) : (nks == 6 || nks == 8);
+  if (pws_off || !plain || !aligned || !ks_ok || M > 192 || HWl < 4096 || HWl % 256 != 0 || HWl >= (1L << 30)) return -1;
+  const int ncb = bnb ? (M <= 32 ? 2 : (M <= 96 ? 3 : (M <= 160 ? 5 : 6))) : (M <= 16 ? 1 : (M <= 32 ? 2 : (M <= 160 ? 5 : 6)));
+  return (bnb ? 100 : 0) + 10 * ncb + nks;
+}
+
 extern "C" int sc_conv2d_mfma(const sc_conv_args* a, sc_stream stream) {
   SC_REQUIRE(a != nullptr, "sc_conv2d_mfma: null args");
   SC_REQUIRE(a->ks == 1 || a->ks == 3, "sc_conv2d_mfma: ks must be 1 or 3 (got %d)", a->ks);
@@ -1409,20 +1434,13 @@ extern "C" int sc_conv2d_mfma(const sc_conv_args* a, sc_stream stream) {
     SC_REQUIRE(a->src[s].mode != SC_SRC_BNBWD || a->src[s].aux != nullptr, "sc_conv2d_mfma: BNBWD source needs aux");
     SC_REQUIRE(a->src[s].mode != SC_SRC_BNBWD || a->nsrc == 1, "sc_conv2d_mfma: a BNBWD source cannot be part of a concat");
   }
+  const int pws = a->ks == 1 ? sc_pw_stream_variant(a) : -1;      // large planes: the streaming kernel (k_pw_stream) where its shape conditions hold
   if (a->ks == 1) {
-    // large planes, forward: the streaming kernel (k_pw_stream) where its shape conditions hold
-    static const bool pws_off = [] { const char* e = getenv("STARCOP_PWS"); return e && atoi(e) == 0; }();      // (same-box A/B)
     const long HWl = (long)a->H * a->W;
     const int K = a->src[0].C, M = a->Cout;
-    const bool bnb = a->src[0].mode == SC_SRC_BNBWD;      // data gradients of the projections: few dy channels, many outputs; no bnr epilogue here
-    const bool plain = a->nsrc == 1 && (a->src[0].mode == SC_SRC_RAW || a->src[0].mode == SC_SRC_AFFINE || (bnb && a->bnr == nullptr && a->stats == nullptr)) &&
-                       a->src[0].up == 0 && a->csplit == a->Cout && !a->accum0 && a->add0 == nullptr && a->add1 == nullptr && a->out0 != nullptr;
-    const bool aligned = (((uintptr_t)a->src[0].x | (uintptr_t)a->out0 | (bnb ? (uintptr_t)a->src[0].aux : 0)) & 15) == 0;
-    const int nks = K / 4;
-    // short contractions only: the long-K projections (96 / 144 -> 24 at 128^2) measured a tie without and 3-8 us slower with the
-    // statistics epilogue (a lane keeps NKS filter registers per cout block: two waves per SIMD)
-    const bool ks_ok = bnb ? (nks == 4 || nks == 6 || nks == 8) : (nks == 6 || nks == 8);
-    if (!pws_off && plain && aligned && ks_ok && (M <= 32 || (M <= 192 && nks <= 8)) && HWl >= 4096 && HWl % 256 == 0 && HWl < (1L << 30) && a->co_t != 16) {
+    if (pws >= 0) {
+      const bool bnb = pws >= 100;
+      const int ncb = (pws / 10) % 10, nks = pws % 10;
       PwsP q;
       q.x = a->src[0].x; q.aux = a->src[0].aux; q.cst = a->src[0].mode == SC_SRC_RAW ? nullptr : a->src[0].cst;
       q.act = a->src[0].mode == SC_SRC_RAW ? (int)SC_ACT_NONE : a->src[0].act;
@@ -1436,15 +1454,15 @@ extern "C" int sc_conv2d_mfma(const sc_conv_args* a, sc_stream stream) {
 #define SC_PWSB(NCB_, CP_) do { if (nks == 4) hipLaunchKernelGGL((k_pw_stream<NCB_, 4, CP_, true>), dim3((unsigned)(groups / (4 / CP_))), dim3(256), 0, st, q); \
                                 else if (nks == 6) hipLaunchKernelGGL((k_pw_stream<NCB_, 6, CP_, true>), dim3((unsigned)(groups / (4 / CP_))), dim3(256), 0, st, q); \
                                 else hipLaunchKernelGGL((k_pw_stream<NCB_, 8, CP_, true>), dim3((unsigned)(groups / (4 / CP_))), dim3(256), 0, st, q); } while (0)
-        if (M <= 32) SC_PWSB(2, 1);
-        else if (M <= 96) SC_PWSB(3, 2);
-        else if (M <= 160) SC_PWSB(5, 2);
+        if (ncb == 2) SC_PWSB(2, 1);
+        else if (ncb == 3) SC_PWSB(3, 2);
+        else if (ncb == 5) SC_PWSB(5, 2);
         else SC_PWSB(6, 2);
 #undef SC_PWSB
       }
-      else if (M <= 16) SC_PWS_K(1, 1);
-      else if (M <= 32) SC_PWS_K(2, 1);
-      else if (M <= 160) SC_PWS_K(5, 2);                   // (the expansions: few input channels, up to 160 / 192 couts in two parts)
+      else if (ncb == 1) SC_PWS_K(1, 1);
+      else if (ncb == 2) SC_PWS_K(2, 1);
+      else if (ncb == 5) SC_PWS_K(5, 2);                   // (the expansions: few input channels, up to 160 / 192 couts in two parts)
       else SC_PWS_K(6, 2);
 #undef SC_PWS_K
 #undef SC_PWS

@@ -438,6 +438,18 @@ extern "C" size_t sc_packed_weight_floats_pw3(int Cout, int Cin, int transpose_f
   return MBE * nks * 3 * 64 * 4;
 }
 
+// Which k_pw3 instantiation sc_conv1x1_pw3 launches for an N x H x W plane with Cout output channels (M; a data gradient's M is
+// the layer's Cin), without touching the GPU: the cout blocks of 32 a wave owns -- 4, 2 or 1 (-1: bad shape).  More blocks per wave
+// re-use the source registers, as long as the grid still fills the device.  sc_conv1x1_pw3 dispatches on this value.
+extern "C" int sc_conv1x1_pw3_variant(int N, int H, int W, int Cout) {
+  if (N <= 0 || H <= 0 || W <= 0 || Cout <= 0) return -1;
+  const long npb = ((long)N * H * W + 31) / 32;
+  const int MB = (Cout + 31) / 32;
+  for (int c = 4; c >= 2; c >>= 1)
+    if (MB >= c - (c == 4 ? 1 : 0) && npb * ((MB + c - 1) / c) >= 1536) return c;
+  return 1;
+}
+
 extern "C" int sc_conv1x1_pw3(const sc_conv_args* a, sc_stream stream) {
   SC_REQUIRE(a != nullptr, "sc_conv1x1_pw3: null args");
   SC_REQUIRE(a->ks == 1 && a->nsrc == 1, "sc_conv1x1_pw3: ks must be 1 with a single source");
@@ -470,9 +482,7 @@ extern "C" int sc_conv1x1_pw3(const sc_conv_args* a, sc_stream stream) {
     p.bnr_y = a->bnr->y; p.bnr_cst = a->bnr->cst; p.bnr_rows = a->bnr->rows; p.bnr_act = a->bnr->act;
   }
   const int MB = (p.M + 31) / 32;
-  int ncb = 1;
-  for (int c = 4; c >= 2; c >>= 1)
-    if (MB >= c - (c == 4 ? 1 : 0) && (long)p.npb * ((MB + c - 1) / c) >= 1536) { ncb = c; break; }
+  const int ncb = sc_conv1x1_pw3_variant(a->N, a->H, a->W, a->Cout);
   const bool bnb = p.s.mode == SC_SRC_BNBWD;
   dim3 grid((p.npb + 3) / 4, (MB + ncb - 1) / ncb);
   const size_t lds = (size_t)p.nks * 16 * (bnb ? 8 : 2) * sizeof(float);
@@ -490,6 +500,14 @@ extern "C" size_t sc_wgrad_pw3_workspace_floats(int N, int H, int W, int Cout, i
   const PwWPlan pl = plan_pw3_wgrad(N, H, W, Cout, Cin);
   const size_t E = (size_t)pl.CoP * pl.CiP;
   return (size_t)pl.nparts * E + sc_reduce_scratch_floats(pl.nparts, E);
+}
+
+// Which k_pw3_wgrad instantiation sc_conv1x1_wgrad_pw3 launches, without touching the GPU: 10 * tm + tn, the 32-channel blocks of
+// dy (tm) and of the input (tn) a wave owns -- 11, 12, 21 or 22 (-1: bad shape).  sc_conv1x1_wgrad_pw3 dispatches on this value.
+extern "C" int sc_wgrad_pw3_variant(int N, int H, int W, int Cout, int Cin) {
+  if (N <= 0 || H <= 0 || W <= 0 || Cout <= 0 || Cin <= 0) return -1;
+  const PwWPlan pl = plan_pw3_wgrad(N, H, W, Cout, Cin);
+  return 10 * pl.tm + pl.tn;
 }
 
 extern "C" int sc_conv1x1_wgrad_pw3(const sc_wgrad_args* a, sc_wgrad_pending* pending, sc_stream stream) {
@@ -512,10 +530,12 @@ extern "C" int sc_conv1x1_wgrad_pw3(const sc_wgrad_args* a, sc_wgrad_pending* pe
   dim3 grid(pl.nparts, pl.CoP / (32 * pl.tm), pl.CiP / (32 * pl.tn));
   const size_t lds = (size_t)3 * pl.tm * pl.tn * 16 * 64 * sizeof(float);
   hipStream_t st = (hipStream_t)stream;
-  if (pl.tm == 2 && pl.tn == 2) hipLaunchKernelGGL((k_pw3_wgrad<2, 2, 2>), grid, dim3(256), lds, st, p);
-  else if (pl.tm == 2) hipLaunchKernelGGL((k_pw3_wgrad<2, 1, 3>), grid, dim3(256), lds, st, p);
-  else if (pl.tn == 2) hipLaunchKernelGGL((k_pw3_wgrad<1, 2, 3>), grid, dim3(256), lds, st, p);
-  else hipLaunchKernelGGL((k_pw3_wgrad<1, 1, 4>), grid, dim3(256), lds, st, p);
+  const int variant = sc_wgrad_pw3_variant(a->N, a->H, a->W, a->Cout, a->Cin);
+  if (variant == 22) hipLaunchKernelGGL((k_pw3_wgrad<2, 2, 2>), grid, dim3(256), lds, st, p);
+  else if (variant == 21) hipLaunchKernelGGL((k_pw3_wgrad<2, 1, 3>), grid, dim3(256), lds, st, p);
+  else if (variant == 12) hipLaunchKernelGGL((k_pw3_wgrad<1, 2, 3>), grid, dim3(256), lds, st, p);
+  else if (variant == 11) hipLaunchKernelGGL((k_pw3_wgrad<1, 1, 4>), grid, dim3(256), lds, st, p);
+  else { sc_set_error("sc_conv1x1_wgrad_pw3: bad shape"); return SC_ERR_ARG; }
   SC_LAUNCH_OK("sc_conv1x1_wgrad_pw3");
   if (pending) {
     pending->part = a->part; pending->dw = a->dw; pending->nparts = pl.nparts; pending->taps = 1;

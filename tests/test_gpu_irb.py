@@ -13,7 +13,7 @@ pytestmark = pytest.mark.gpu
 
 from hip_ops import DEV, cst_affine, dev, pack_pw3, relerr  # noqa: E402
 from starcop_amd import _lib  # noqa: E402
-from starcop_amd._lib import ACT_NONE, SRC_AFFINE, SRC_RAW, check, make_src, ptr, sc_irb_args, stream  # noqa: E402
+from starcop_amd._lib import ACT_NONE, ACT_RELU, SRC_AFFINE, SRC_RAW, check, make_src, ptr, sc_irb_args, stream  # noqa: E402
 
 # (N, Cin, hidden, Cout, H, W, residual, input source[, stride]): features.8-13 (32 x 32 planes: 8 x 8 tiles, 32-channel chunks, one / two
 # projection pairs per wave), features.15-17 (16 x 16: 4 x 8 tiles, 64-channel chunks, two / three pairs), ragged planes (the
@@ -38,14 +38,16 @@ CASES = [
 ]
 
 
-def _run(case, seed):
+def _run(case, seed, act=ACT_NONE, xscale=1.5):
+    """act / xscale: the activation of an AFFINE input source (the block input is then act(scale x + shift), in the expansion and in the
+    residual sum alike) and the spread of the raw input"""
     N, Cin, hid, Cout, H, W, res, mode = case[:8]
     stride = case[8] if len(case) > 8 else 1
     Ho, Wo = (H - 1) // stride + 1, (W - 1) // stride + 1
     lib = _lib.load()
     assert lib.sc_irb_supported(Cin, hid, Cout, H, W, stride)
     g = torch.Generator().manual_seed(seed)
-    x = torch.randn(N, Cin, H, W, generator=g) * 1.5
+    x = torch.randn(N, Cin, H, W, generator=g) * xscale
     xs, xh = torch.rand(Cin, generator=g) + 0.5, torch.randn(Cin, generator=g) * 0.3
     We = torch.randn(hid, Cin, generator=g) * (2.0 / Cin) ** 0.5
     Wd = torch.randn(hid, 3, 3, generator=g) * 0.4
@@ -56,6 +58,8 @@ def _run(case, seed):
     affine = mode == "affine"
     # float64 reference
     xa = x.double() * xs.double()[None, :, None, None] + xh.double()[None, :, None, None] if affine else x.double()
+    if affine and act != ACT_NONE:
+        xa = F.relu(xa) if act == ACT_RELU else F.relu6(xa)
     e = F.relu6(F.conv2d(xa, We.double()[:, :, None, None]) * se.double()[None, :, None, None] + he.double()[None, :, None, None])
     d = F.relu6(F.conv2d(e, Wd.double()[:, None], stride=stride, padding=1, groups=hid) * sd.double()[None, :, None, None] + hd.double()[None, :, None, None])
     p = F.conv2d(d, Wp.double()[:, :, None, None])
@@ -63,7 +67,7 @@ def _run(case, seed):
     # HIP
     xd = dev(x)
     a = sc_irb_args()
-    a.x = make_src(xd, Cin, SRC_AFFINE, act=ACT_NONE, cst=cst_affine(xs, xh)) if affine else make_src(xd, Cin, SRC_RAW)
+    a.x = make_src(xd, Cin, SRC_AFFINE, act=act, cst=cst_affine(xs, xh)) if affine else make_src(xd, Cin, SRC_RAW)
     wpe, wpp = pack_pw3(dev(We[:, :, None, None]), 0), pack_pw3(dev(Wp[:, :, None, None]), 0)
     ce, cd, cp = cst_affine(se, he), cst_affine(sd, hd), cst_affine(sp, hp)
     wd = dev(Wd)
