@@ -306,7 +306,8 @@ int sc_wgrad_pw3_variant(int N, int H, int W, int Cout, int Cin);
  * The expanded tensors never leave the CU.  Both 1x1 filters come in the sc_conv1x1_pw3 layout (sc_pack_weights_batch with
  * SC_PACK_PW3, transpose_flip 0); fp32 accuracy (three exact bf16 terms per operand, six MFMA products, fp32 stencil).
  * Stride 1: 8 <= Cin <= 160, hidden % 32 == 0, Cout <= 384 subject to the accumulator budget; stride 2 (no residual; H, W are the INPUT
- * plane, the output is ((H - 1) / 2 + 1) x ((W - 1) / 2 + 1)): Cin <= 96, hidden % 64 == 0 (sc_irb_supported). */
+ * plane, the output is ((H - 1) / 2 + 1) x ((W - 1) / 2 + 1)): Cin <= 96, hidden % 64 == 0 (sc_irb_supported).  gfx950 only: the kernel
+ * needs its 160 KB of LDS per work-group (the stride-2 tiling and every block with Cin > 96 use more than 64 KB). */
 typedef struct sc_irb_args {
   sc_src x;                  /* block input [N,Cin,H,W]: SC_SRC_RAW or SC_SRC_AFFINE                                  */
   const float* wpk_expand;   /* PW3 pack of the expansion filter [hidden][Cin]                                         */

@@ -21,50 +21,13 @@
 //             sc_add_srcs_absmax), 16-byte stores of four neighbouring pixels.
 // Two barriers per chunk; one work-group per CU (up to 512 registers per lane: the filter operands of the next MFMA phase are in
 // flight in registers while the current phase runs).
-#include "sc_common.h"
+#include "sc_split.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float floatx2;
-typedef __attribute__((ext_vector_type(4))) unsigned int uintx4;
-
-// exact three-term bf16 split of two floats (a = t0 + t1 + t2 up to 2^-24 |a|); packed pairs, low half = first value
-__device__ __forceinline__ void irb_split3x2(float a, float b, unsigned& t0, unsigned& t1, unsigned& t2) {
-  floatx2 v = {a, b};
-  const bf16x2 h0 = __builtin_convertvector(v, bf16x2);
-  v -= __builtin_convertvector(h0, floatx2);
-  const bf16x2 h1 = __builtin_convertvector(v, bf16x2);
-  v -= __builtin_convertvector(h1, floatx2);
-  const bf16x2 h2 = __builtin_convertvector(v, bf16x2);
-  t0 = __builtin_bit_cast(unsigned, h0);
-  t1 = __builtin_bit_cast(unsigned, h1);
-  t2 = __builtin_bit_cast(unsigned, h2);
-}
-__device__ __forceinline__ void irb_split8(const float (&v)[8], uintx4 (&t)[3]) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    unsigned t0, t1, t2;
-    irb_split3x2(v[2 * q], v[2 * q + 1], t0, t1, t2);
-    t[0][q] = t0; t[1][q] = t1; t[2][q] = t2;
-  }
-}
-__device__ __forceinline__ floatx16 irb_mfma(const uintx4& a, const uintx4& b, const floatx16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// the six products of weight >= 2^-24, smallest first.  (Two alternating accumulators per chain -- independent back-to-back MFMAs --
-// measured 5-10 % SLOWER: the chains are not what a chunk waits for, tools/bench_irb.py.)
-__device__ __forceinline__ floatx16 irb_mfma6(const uintx4 (&a)[3], const uintx4 (&b)[3], floatx16 c) {
-  c = irb_mfma(a[1], b[1], c);
-  c = irb_mfma(a[2], b[0], c);
-  c = irb_mfma(a[0], b[2], c);
-  c = irb_mfma(a[1], b[0], c);
-  c = irb_mfma(a[0], b[1], c);
-  c = irb_mfma(a[0], b[0], c);
-  return c;
-}
+// (mfma6 with two alternating accumulators per chain -- independent back-to-back MFMAs -- measured 5-10 % SLOWER here: the chains are
+// not what a chunk waits for, tools/bench_irb.py.)
 
 struct IrbP {
   SrcD x;                  // block input [N][Cin][H][W]: RAW or AFFINE
@@ -227,7 +190,7 @@ __global__ __launch_bounds__(TH * TW * (HC / 8), OCC) void k_irb(const IrbP p) {
         v[j] = (ok && c < Cin) ? sc_pro_affine(xv[j], sc, sh, lo, hi) : 0.f;
       }
       uintx4 t[3];
-      irb_split8(v, t);
+      split8(v, t);
 #pragma unroll
       for (int c3 = 0; c3 < 3; ++c3) s_x[((size_t)c3 * KGIN + kg) * NPXP + px] = t[c3];
     }
@@ -277,7 +240,7 @@ __global__ __launch_bounds__(TH * TW * (HC / 8), OCC) void k_irb(const IrbP p) {
             uintx4 a[3];
 #pragma unroll
             for (int t = 0; t < 3; ++t) a[t] = s_x[((size_t)t * KGIN + 2 * ks + lhi) * NPXP + emb[q] * 32 + l31];
-            acc = irb_mfma6(a, be[ks], acc);
+            acc = mfma6(a, be[ks], acc);
           }
         }
         // acc[i] = E[pixel emb*32 + 8*(i/4) + 4*lhi + (i%4)][hidden channel enb*32 + l31]
@@ -318,7 +281,7 @@ __global__ __launch_bounds__(TH * TW * (HC / 8), OCC) void k_irb(const IrbP p) {
 #pragma unroll
       for (int j = 0; j < 8; ++j) d8[j] = __builtin_amdgcn_fmed3f(fmaf(d8[j], scd[j], shd[j]), 0.f, 6.f);
       uintx4 t[3];
-      irb_split8(d8, t);
+      split8(d8, t);
 #pragma unroll
       for (int c3 = 0; c3 < 3; ++c3) s_d[((size_t)c3 * KGC + okg) * NOUT + opx] = t[c3];
     }
@@ -339,7 +302,7 @@ __global__ __launch_bounds__(TH * TW * (HC / 8), OCC) void k_irb(const IrbP p) {
 #pragma unroll
         for (int j = 0; j < 6; ++j)
 #pragma unroll
-          for (int q = 0; q < MAXPP; ++q) accp[q] = irb_mfma(a[q][PA[j]], bp[q][ks][PB[j]], accp[q]);
+          for (int q = 0; q < MAXPP; ++q) accp[q] = mfma_bf16(a[q][PA[j]], bp[q][ks][PB[j]], accp[q]);
       }
     }
   }
@@ -399,8 +362,7 @@ __global__ __launch_bounds__(TH * TW * (HC / 8), OCC) void k_irb(const IrbP p) {
 template <int TH, int TW, int HC, int NKE, int MAXPP, int OCC, int S = 1>
 static int irb_launch3(const IrbP& p, hipStream_t st) {
   const size_t lds = irb_smem_bytes<TH, TW, HC, S>(p.nks_e);
-  static bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_irb<TH, TW, HC, NKE, MAXPP, OCC, S>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024) == hipSuccess;
-  if (!attr_ok) { sc_set_error("sc_irb_eval: cannot raise the dynamic LDS limit"); return SC_ERR_LAUNCH; }
+  if (int rc = sc_lds_limit(&k_irb<TH, TW, HC, NKE, MAXPP, OCC, S>, lds, "sc_irb_eval")) return rc;
   hipLaunchKernelGGL((k_irb<TH, TW, HC, NKE, MAXPP, OCC, S>), dim3((unsigned)(p.N * p.tiles_x * p.tiles_y)), dim3(IrbCfg<TH, TW, HC, S>::NTHR), lds, st, p);
   SC_LAUNCH_OK("sc_irb_eval");
   return SC_OK;

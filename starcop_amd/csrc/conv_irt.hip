@@ -23,48 +23,11 @@
 //       contraction over PIXELS (G);
 //   (2) rows = hidden channels, columns = pixels: a lane owns ONE pixel and 16 channels -> the registers are the B operand of a
 //       contraction over HIDDEN channels (dx) with the filter rows permuted to the accumulator's channel order.
-#include "sc_common.h"
+#include "sc_split.h"
 #include <stdlib.h>
 
 namespace {
 
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float floatx2;
-typedef __attribute__((ext_vector_type(4))) unsigned int uintx4;
-
-__device__ __forceinline__ void split3x2(float a, float b, unsigned& t0, unsigned& t1, unsigned& t2) {
-  floatx2 v = {a, b};
-  const bf16x2 h0 = __builtin_convertvector(v, bf16x2);
-  v -= __builtin_convertvector(h0, floatx2);
-  const bf16x2 h1 = __builtin_convertvector(v, bf16x2);
-  v -= __builtin_convertvector(h1, floatx2);
-  const bf16x2 h2 = __builtin_convertvector(v, bf16x2);
-  t0 = __builtin_bit_cast(unsigned, h0);
-  t1 = __builtin_bit_cast(unsigned, h1);
-  t2 = __builtin_bit_cast(unsigned, h2);
-}
-__device__ __forceinline__ void split8(const float (&v)[8], uintx4 (&t)[3]) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    unsigned t0, t1, t2;
-    split3x2(v[2 * q], v[2 * q + 1], t0, t1, t2);
-    t[0][q] = t0; t[1][q] = t1; t[2][q] = t2;
-  }
-}
-__device__ __forceinline__ floatx16 mfma_bf16(const uintx4& a, const uintx4& b, const floatx16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// the six products of weight >= 2^-24, smallest first
-__device__ __forceinline__ floatx16 mfma6(const uintx4 (&a)[3], const uintx4 (&b)[3], floatx16 c) {
-  c = mfma_bf16(a[1], b[1], c);
-  c = mfma_bf16(a[2], b[0], c);
-  c = mfma_bf16(a[0], b[2], c);
-  c = mfma_bf16(a[1], b[0], c);
-  c = mfma_bf16(a[0], b[1], c);
-  c = mfma_bf16(a[0], b[0], c);
-  return c;
-}
 // two independent six-product blocks issued alternately: a chain of dependent MFMAs on ONE accumulator runs at the instruction's
 // latency (16 passes), two interleaved chains at its issue rate
 __device__ __forceinline__ void mfma6x2(const uintx4 (&a)[3], const uintx4 (&b)[3], floatx16& c, const uintx4 (&d)[3], const uintx4 (&e)[3],
@@ -981,18 +944,6 @@ int irt_fill(IrtP& p, const sc_irt_args* a, const char* who) {
   p.npb = (int)((NP + 31) / 32);
   return SC_OK;
 }
-template <typename K>
-void irt_lds_attr(K kern, size_t lds) {
-  // once per kernel (the pointer identifies the instantiation); not a stream operation, so it is safe under graph capture too
-  static const void* done[16];
-  static int ndone = 0;
-  if (lds <= 64 * 1024) return;
-  const void* f = reinterpret_cast<const void*>(kern);
-  for (int i = 0; i < ndone; ++i) if (done[i] == f) return;
-  (void)hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (ndone < 16) done[ndone++] = f;
-}
-
 }  // namespace
 
 // =================================================================================================================================
@@ -1019,8 +970,8 @@ extern "C" int sc_irt_expand_stats(const sc_irt_args* a, float* stats, sc_stream
   const int wgs = irt_stat_wgs(p.npb);
   const size_t lds = (size_t)p.nch * nks * 3 * 64 * 16 + 64 * 4 + (size_t)4 * p.nch * 32 * 2 * 4;
   hipStream_t st = (hipStream_t)stream;
-  if (nks == 1) { irt_lds_attr(&k_irt_stats<1>, lds); hipLaunchKernelGGL((k_irt_stats<1>), dim3(wgs), dim3(256), lds, st, p); }
-  else { irt_lds_attr(&k_irt_stats<2>, lds); hipLaunchKernelGGL((k_irt_stats<2>), dim3(wgs), dim3(256), lds, st, p); }
+  if (nks == 1) { if (int rc = sc_lds_limit(&k_irt_stats<1>, lds, "sc_irt_expand_stats")) return rc; hipLaunchKernelGGL((k_irt_stats<1>), dim3(wgs), dim3(256), lds, st, p); }
+  else { if (int rc = sc_lds_limit(&k_irt_stats<2>, lds, "sc_irt_expand_stats")) return rc; hipLaunchKernelGGL((k_irt_stats<2>), dim3(wgs), dim3(256), lds, st, p); }
   SC_LAUNCH_OK("sc_irt_expand_stats");
   return SC_OK;
 }
@@ -1039,8 +990,8 @@ extern "C" int sc_irt_fwd(const sc_irt_args* a, float* d_out, float* stats_d, sc
   if (per_cu < 1) per_cu = 1;
   if (per_cu > 4) per_cu = 4;
   const int wgs = p.ntiles < 256 * per_cu ? p.ntiles : 256 * per_cu;
-  if (nks == 1) { irt_lds_attr(&k_irt_fwd<1, 2>, lds); hipLaunchKernelGGL((k_irt_fwd<1, 2>), dim3(wgs), dim3(256), lds, st, p); }
-  else { irt_lds_attr(&k_irt_fwd<2, 2>, lds); hipLaunchKernelGGL((k_irt_fwd<2, 2>), dim3(wgs), dim3(256), lds, st, p); }
+  if (nks == 1) { if (int rc = sc_lds_limit(&k_irt_fwd<1, 2>, lds, "sc_irt_fwd")) return rc; hipLaunchKernelGGL((k_irt_fwd<1, 2>), dim3(wgs), dim3(256), lds, st, p); }
+  else { if (int rc = sc_lds_limit(&k_irt_fwd<2, 2>, lds, "sc_irt_fwd")) return rc; hipLaunchKernelGGL((k_irt_fwd<2, 2>), dim3(wgs), dim3(256), lds, st, p); }
   SC_LAUNCH_OK("sc_irt_fwd");
   return SC_OK;
 }
@@ -1065,10 +1016,10 @@ extern "C" int sc_irt_bwd(const sc_irt_args* a, const sc_src* dy_d, double* e_su
   p.wpk = wpk;
   if (nks == 1) {
     hipLaunchKernelGGL((k_irt_pack<1>), dim3(p.nch), dim3(256), 0, st, p, wpk);
-    irt_lds_attr(&k_irt_bwd<1>, lds); hipLaunchKernelGGL((k_irt_bwd<1>), grid, dim3(256), lds, st, p);
+    if (int rc = sc_lds_limit(&k_irt_bwd<1>, lds, "sc_irt_bwd")) return rc; hipLaunchKernelGGL((k_irt_bwd<1>), grid, dim3(256), lds, st, p);
   } else {
     hipLaunchKernelGGL((k_irt_pack<2>), dim3(p.nch), dim3(256), 0, st, p, wpk);
-    irt_lds_attr(&k_irt_bwd<2>, lds); hipLaunchKernelGGL((k_irt_bwd<2>), grid, dim3(256), lds, st, p);
+    if (int rc = sc_lds_limit(&k_irt_bwd<2>, lds, "sc_irt_bwd")) return rc; hipLaunchKernelGGL((k_irt_bwd<2>), grid, dim3(256), lds, st, p);
   }
   SC_LAUNCH_OK("sc_irt_bwd");
   return SC_OK;

@@ -21,48 +21,9 @@
 //   * the weight gradient  dW[cout][cin] = sum_pixels dy[cout][px] x[cin][px]  with K = pixels: both operands are 32-byte
 //     contiguous reads per lane (8 pixels of the lane's channel), split in registers; the four waves of a work-group take
 //     interleaved K steps and sum their accumulators through LDS in a fixed order before the partial is written.
-#include "sc_common.h"
+#include "sc_split.h"
 
 namespace {
-
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-typedef __attribute__((ext_vector_type(2))) float floatx2;
-typedef __attribute__((ext_vector_type(4))) unsigned int uintx4;
-
-// exact three-term bf16 split of two floats; packed pairs (low half = first value)
-__device__ __forceinline__ void split3x2(float a, float b, unsigned& t0, unsigned& t1, unsigned& t2) {
-  floatx2 v = {a, b};
-  const bf16x2 h0 = __builtin_convertvector(v, bf16x2);
-  v -= __builtin_convertvector(h0, floatx2);
-  const bf16x2 h1 = __builtin_convertvector(v, bf16x2);
-  v -= __builtin_convertvector(h1, floatx2);
-  const bf16x2 h2 = __builtin_convertvector(v, bf16x2);
-  t0 = __builtin_bit_cast(unsigned, h0);
-  t1 = __builtin_bit_cast(unsigned, h1);
-  t2 = __builtin_bit_cast(unsigned, h2);
-}
-__device__ __forceinline__ void split8(const float (&v)[8], uintx4 (&t)[3]) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    unsigned t0, t1, t2;
-    split3x2(v[2 * q], v[2 * q + 1], t0, t1, t2);
-    t[0][q] = t0; t[1][q] = t1; t[2][q] = t2;
-  }
-}
-__device__ __forceinline__ floatx16 mfma_bf16(const uintx4& a, const uintx4& b, const floatx16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
-}
-// the six products of weight >= 2^-24, smallest first
-__device__ __forceinline__ floatx16 mfma6(const uintx4 (&a)[3], const uintx4 (&b)[3], floatx16 c) {
-  c = mfma_bf16(a[1], b[1], c);
-  c = mfma_bf16(a[2], b[0], c);
-  c = mfma_bf16(a[0], b[2], c);
-  c = mfma_bf16(a[1], b[0], c);
-  c = mfma_bf16(a[0], b[1], c);
-  c = mfma_bf16(a[0], b[0], c);
-  return c;
-}
 
 struct PwP {
   SrcD s;                 // the single source: AFFINE / RAW (forward) or BNBWD (backward-data)

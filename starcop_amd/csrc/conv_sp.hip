@@ -27,46 +27,16 @@
 // Pipeline: patch and filters double-buffered, ONE barrier per 16-channel chunk; chunk k+1 is converted / stored at the top of
 // chunk k (its global loads were issued a whole chunk earlier) and the loads of chunk k+2 are re-issued into the same registers
 // right behind ("refill": DESIGN.md section 11 rule 2); all loads unconditional (clamped chunk index), so the waits stay exact.
-#include "sc_common.h"
+#include "sc_split.h"
 #include "conv_sp_pack.h"
 #include <cstdlib>
 #include <type_traits>
 
 namespace {
 
-typedef __attribute__((ext_vector_type(2))) float floatx2;
-typedef __attribute__((ext_vector_type(4))) unsigned int uintx4;
-typedef __attribute__((ext_vector_type(8))) _Float16 halfx8;
-typedef __attribute__((ext_vector_type(2))) _Float16 halfx2;
-typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
-typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2;
-
-constexpr float SP_SX = 2.f, SP_HMAX = 65504.f;
 #ifndef SP_INTERLEAVE
 #define SP_INTERLEAVE 4
 #endif
-
-__device__ __forceinline__ void sp_split2h(float a, float b, unsigned& t0, unsigned& t1) {
-  const floatx2 v = {a, b};
-  const halfx2 h0 = __builtin_convertvector(v, halfx2);
-  t0 = __builtin_bit_cast(unsigned, h0);
-  float ra, rb;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(ra) : "v"(t0), "v"(v[0]));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(rb) : "v"(t0), "v"(v[1]));
-  const halfx2 h1 = __builtin_convertvector(floatx2{ra, rb}, halfx2);
-  t1 = __builtin_bit_cast(unsigned, h1);
-}
-
-// activation operand scale from the sources' bounds (h_act_scale of conv_bx3.hip: the default 2 unless a bound says 2 M > 32752)
-__device__ __forceinline__ float sp_act_scale(const float* xb0, const float* xb1) {
-  float M = fmaxf(xb0 ? *xb0 : 0.f, xb1 ? *xb1 : 0.f);
-  if (!(M * SP_SX > 32752.f)) return SP_SX;
-  M = fminf(M, 3.0e38f);
-  int e;
-  (void)frexpf(32752.f / M, &e);
-  e = e - 1 < -120 ? -120 : e - 1;
-  return ldexpf(1.f, e);
-}
 
 struct ConvSPP {
   SrcD s0, s1;             // s0: low-resolution source [N][C0][Hl][Wl]; s1: skip source [N][C1][2 Hl][2 Wl] (C1 = 0: none); AFFINE or RAW
@@ -137,7 +107,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_sp(const ConvSPP p) {
   const int nku = (C0 + 15) >> 4, nkt = nku + 4 * ((C1 + 15) >> 4);
   const uintx4* wbase = p.wpk + (size_t)cot * nkt * WST;
 
-  const float hsx = BF ? 1.f : sp_act_scale(p.xb0, p.xb1);
+  const float hsx = BF ? 1.f : h_act_scale(p.xb0, p.xb1);
   const float hinv = BF ? 1.f : 1.f / (hsx * SP_SW);
 
   floatx16 acc[NPP][2];    // [group pp][px]
@@ -189,7 +159,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_sp(const ConvSPP p) {
       for (int j = 0; j < 4; ++j) xv[r][j] = xb[(size_t)(j < jmax ? j : jmax) * plane + o];
     }
     if constexpr (BF) { slo = sc_act_lo(s.act); shi = sc_act_hi(s.act); }
-    else { slo = fmaxf(sc_act_lo(s.act) * hsx, -SP_HMAX); shi = fminf(sc_act_hi(s.act) * hsx, SP_HMAX); }
+    else { slo = fmaxf(sc_act_lo(s.act) * hsx, -SC_H_MAX); shi = fminf(sc_act_hi(s.act) * hsx, SC_H_MAX); }
     const float* cb = s.cst + (size_t)cb0 * SC_CST;      // (RAW sources read the host's identity table: no load under a branch)
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
@@ -212,7 +182,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_sp(const ConvSPP p) {
       }
       unsigned a0, a1 = 0u;
       if constexpr (BF) a0 = __builtin_bit_cast(unsigned, __builtin_convertvector((floatx2){v[0], v[1]}, bf16x2));
-      else sp_split2h(v[0], v[1], a0, a1);
+      else split2h<false>(v[0], v[1], a0, a1);
       if (jp == 0) { t0.x = a0; t1.x = a1; } else { t0.y = a0; t1.y = a1; }
     }
     const int e = sidx + 128 * r;
@@ -393,7 +363,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_sp(const ConvSPP p) {
 // the K chunks, every one with 2 x 2 taps (conv_sp_pack.h); the work-group skeleton, LDS layout and pipeline are the forward
 // kernel's with   phase row py -> wave half h = cin block pair,  px -> cin block mx,  and the source offset of tap (a, b) taken from
 // the chunk's parity: (1 - a - qy, 1 - b - qx).  Tile = 8 groups of 32 low-resolution pixels x 128 input channels; the source is the
-// BatchNorm / activation-backward operand (g, y -> A g' + B y + D) with the gradient range scale of conv_bx3.hip (absmax).
+// BatchNorm / activation-backward operand (g, y -> A g' + B y + D) with the gradient range scale h_grad_scale (absmax).
 struct ConvSPD {
   SrcD dy;                 // SC_SRC_BNBWD source [N][Co][2 Hl][2 Wl]
   const uintx4* wpk;       // spd pack
@@ -405,16 +375,6 @@ struct ConvSPD {
   int Cskip, accum_skip;   // wave half 1 of the one channel tile; skip_mode 2 (skip tiles): from the channel tiles cot >= ntu (conv_sp_pack.h)
   int skip_mode, ntu, nts; // ntu: tiles of 128 up-sampled channels; nts: skip tiles (mode 2) of 32 skip channels x 4 output parities
 };
-
-__device__ __forceinline__ float spd_grad_scale(const float* absmax) {      // (h_grad_scale of conv_bx3.hip)
-  const float M = absmax ? *absmax : 0.f;
-  if (!(M > 0.f) || !(M < 3.0e38f)) return 1.f;
-  int e;
-  (void)frexpf(M, &e);
-  e = 5 - e;
-  e = e < -100 ? -100 : (e > 100 ? 100 : e);
-  return ldexpf(1.f, e);
-}
 
 template <int TW, bool BF, int NPP = 2>
 __global__ __launch_bounds__(512, 2) void k_conv3_spd(const ConvSPD p) {
@@ -458,7 +418,7 @@ __global__ __launch_bounds__(512, 2) void k_conv3_spd(const ConvSPD p) {
   const int nkt = 4 * ((Co + 15) >> 4);
   const uintx4* wbase = p.wpk + (size_t)cot * nkt * WST;
 
-  const float hsx = BF ? 1.f : spd_grad_scale(p.absmax);
+  const float hsx = BF ? 1.f : h_grad_scale(p.absmax);
   const float hinv = BF ? 1.f : 1.f / (hsx * SP_SW);
 
   floatx16 acc[NPP][2];    // [group pp][cin block mx]
@@ -528,11 +488,11 @@ __global__ __launch_bounds__(512, 2) void k_conv3_spd(const ConvSPD p) {
       for (int h = 0; h < 2; ++h) {
         const int j = 2 * jp + h;
         const float t = sc_pro_bnbwd(xv[r][j], av[r][j], cs0[j], cs1[j], cs2[j], cs3[j], cs4[j], slo, shi) * hsx;
-        v[h] = (pyx[r] != 0xFFFFFFFFu && j < nch) ? (BF ? t : __builtin_amdgcn_fmed3f(t, -SP_HMAX, SP_HMAX)) : 0.f;
+        v[h] = (pyx[r] != 0xFFFFFFFFu && j < nch) ? (BF ? t : __builtin_amdgcn_fmed3f(t, -SC_H_MAX, SC_H_MAX)) : 0.f;
       }
       unsigned a0, a1 = 0u;
       if constexpr (BF) a0 = __builtin_bit_cast(unsigned, __builtin_convertvector((floatx2){v[0], v[1]}, bf16x2));
-      else sp_split2h(v[0], v[1], a0, a1);
+      else split2h<false>(v[0], v[1], a0, a1);
       if (jp == 0) { t0.x = a0; t1.x = a1; } else { t0.y = a0; t1.y = a1; }
     }
     const int e = sidx + 128 * r;
@@ -793,31 +753,12 @@ extern "C" int sc_conv3x3_sp(const sc_conv_args* a, sc_stream stream) {
   const long ncot = (a->Cout + 31) / 32;
   const long grid = (tiles + 7) / 8 * 8 * ncot;
   SC_REQUIRE(grid < (1L << 31), "sc_conv3x3_sp: grid too large");
-  static const bool attr_ok = [] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3_sp<32, false>), hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes<32>()) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3_sp<16, false>), hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes<16>()) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3_sp<32, true>), hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes<32>()) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3_sp<16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes<16>()) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3_sp<16, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes<16>()) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3_sp<16, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes<16>()) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3_sp<32, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes<32>()) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3_sp<32, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes<32>()) == hipSuccess;
-  }();
-  SC_REQUIRE(attr_ok, "sc_conv3x3_sp: cannot reserve %d bytes of LDS", sp_smem_bytes<32>());
   const bool bf = a->terms == 1;
-  if (TW == 32 && npp == 1) {
-    if (bf) hipLaunchKernelGGL((k_conv3_sp<32, true, 1>), dim3((unsigned)grid), dim3(512), sp_smem_bytes<32>(), (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((k_conv3_sp<32, false, 1>), dim3((unsigned)grid), dim3(512), sp_smem_bytes<32>(), (hipStream_t)stream, p);
-  } else if (TW == 32) {
-    if (bf) hipLaunchKernelGGL((k_conv3_sp<32, true>), dim3((unsigned)grid), dim3(512), sp_smem_bytes<32>(), (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((k_conv3_sp<32, false>), dim3((unsigned)grid), dim3(512), sp_smem_bytes<32>(), (hipStream_t)stream, p);
-  } else if (npp == 1) {
-    if (bf) hipLaunchKernelGGL((k_conv3_sp<16, true, 1>), dim3((unsigned)grid), dim3(512), sp_smem_bytes<16>(), (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((k_conv3_sp<16, false, 1>), dim3((unsigned)grid), dim3(512), sp_smem_bytes<16>(), (hipStream_t)stream, p);
-  } else {
-    if (bf) hipLaunchKernelGGL((k_conv3_sp<16, true>), dim3((unsigned)grid), dim3(512), sp_smem_bytes<16>(), (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((k_conv3_sp<16, false>), dim3((unsigned)grid), dim3(512), sp_smem_bytes<16>(), (hipStream_t)stream, p);
-  }
+  void (*const kern)(ConvSPP) = npp == 2 ? (!bf ? (TW == 32 ? k_conv3_sp<32, false> : k_conv3_sp<16, false>) : (TW == 32 ? k_conv3_sp<32, true> : k_conv3_sp<16, true>))
+                                       : (TW == 16 ? (!bf ? k_conv3_sp<16, false, 1> : k_conv3_sp<16, true, 1>) : (!bf ? k_conv3_sp<32, false, 1> : k_conv3_sp<32, true, 1>));
+  const int lds = TW == 32 ? sp_smem_bytes<32>() : sp_smem_bytes<16>();
+  if (int rc = sc_lds_limit(kern, lds, "sc_conv3x3_sp")) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, (hipStream_t)stream, p);
   SC_LAUNCH_OK("sc_conv3x3_sp");
   return SC_OK;
 }
@@ -871,31 +812,12 @@ extern "C" int sc_conv3x3_sp_dgrad(const sc_conv_args* a, sc_stream stream) {
   const long ncot = p.ntu + p.nts;
   const long grid = (tiles + 7) / 8 * 8 * ncot;
   SC_REQUIRE(grid < (1L << 31), "sc_conv3x3_sp_dgrad: grid too large");
-  static const bool attr_ok = [] {
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3_spd<32, false>), hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes<32>()) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3_spd<16, false>), hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes<16>()) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3_spd<32, true>), hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes<32>()) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3_spd<16, true>), hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes<16>()) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3_spd<16, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes<16>()) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3_spd<16, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes<16>()) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3_spd<32, false, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes<32>()) == hipSuccess &&
-           hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv3_spd<32, true, 1>), hipFuncAttributeMaxDynamicSharedMemorySize, sp_smem_bytes<32>()) == hipSuccess;
-  }();
-  SC_REQUIRE(attr_ok, "sc_conv3x3_sp_dgrad: cannot reserve %d bytes of LDS", sp_smem_bytes<32>());
   const bool bf = a->terms == 1;
-  if (TW == 32 && npp == 1) {
-    if (bf) hipLaunchKernelGGL((k_conv3_spd<32, true, 1>), dim3((unsigned)grid), dim3(512), sp_smem_bytes<32>(), (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((k_conv3_spd<32, false, 1>), dim3((unsigned)grid), dim3(512), sp_smem_bytes<32>(), (hipStream_t)stream, p);
-  } else if (TW == 32) {
-    if (bf) hipLaunchKernelGGL((k_conv3_spd<32, true>), dim3((unsigned)grid), dim3(512), sp_smem_bytes<32>(), (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((k_conv3_spd<32, false>), dim3((unsigned)grid), dim3(512), sp_smem_bytes<32>(), (hipStream_t)stream, p);
-  } else if (npp == 1) {
-    if (bf) hipLaunchKernelGGL((k_conv3_spd<16, true, 1>), dim3((unsigned)grid), dim3(512), sp_smem_bytes<16>(), (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((k_conv3_spd<16, false, 1>), dim3((unsigned)grid), dim3(512), sp_smem_bytes<16>(), (hipStream_t)stream, p);
-  } else {
-    if (bf) hipLaunchKernelGGL((k_conv3_spd<16, true>), dim3((unsigned)grid), dim3(512), sp_smem_bytes<16>(), (hipStream_t)stream, p);
-    else hipLaunchKernelGGL((k_conv3_spd<16, false>), dim3((unsigned)grid), dim3(512), sp_smem_bytes<16>(), (hipStream_t)stream, p);
-  }
+  void (*const kern)(ConvSPD) = npp == 2 ? (!bf ? (TW == 32 ? k_conv3_spd<32, false> : k_conv3_spd<16, false>) : (TW == 32 ? k_conv3_spd<32, true> : k_conv3_spd<16, true>))
+                                       : (TW == 16 ? (!bf ? k_conv3_spd<16, false, 1> : k_conv3_spd<16, true, 1>) : (!bf ? k_conv3_spd<32, false, 1> : k_conv3_spd<32, true, 1>));
+  const int lds = TW == 32 ? sp_smem_bytes<32>() : sp_smem_bytes<16>();
+  if (int rc = sc_lds_limit(kern, lds, "sc_conv3x3_sp_dgrad")) return rc;
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, (hipStream_t)stream, p);
   SC_LAUNCH_OK("sc_conv3x3_sp_dgrad");
   return SC_OK;
 }

@@ -16,24 +16,10 @@
 //                    prologue, no split in the loop), 256 x 128 tiles, K slices -> partials [slice][9 * Cout][Cup]
 //   4. k_spw_reduce: fixed-order sum of the slices (bit-reproducible) -> dw[co][ci][tap] inside the layer's [Cout][Cin][3][3] gradient
 // The skip channels' columns of dw come from the 3x3 kernel on the skip source alone (sc_wgrad_scatter_cols puts them in place).
-#include "sc_common.h"
+#include "sc_split.h"
 #include <cstdlib>
 
 namespace {
-
-typedef __attribute__((ext_vector_type(2))) float floatx2;
-typedef __attribute__((ext_vector_type(4))) unsigned int uintx4;
-typedef __attribute__((ext_vector_type(8))) _Float16 halfx8;
-typedef __attribute__((ext_vector_type(2))) _Float16 halfx2;
-
-constexpr float SPW_HMAX = 65504.f;
-
-__device__ __forceinline__ void spw_split(float a, unsigned short& h0, unsigned short& h1) {
-  a = __builtin_amdgcn_fmed3f(a, -SPW_HMAX, SPW_HMAX);
-  const _Float16 t0 = (_Float16)a;
-  const _Float16 t1 = (_Float16)(a - (float)t0);
-  h0 = __builtin_bit_cast(unsigned short, t0); h1 = __builtin_bit_cast(unsigned short, t1);
-}
 
 // ---- 1. box sums of dy --------------------------------------------------------------------------------------------------
 // block = (n, co, 8 x 32 low-resolution tile): the processed 18 x 66 high-resolution patch of dy through LDS, nine sums per pixel
@@ -46,16 +32,6 @@ struct SpwDy {
   long Kp;
 };
 
-__device__ __forceinline__ float spw_grad_scale(const float* absmax) {      // h_grad_scale of conv_bx3.hip, / 4 for the box sum
-  const float M = absmax ? *absmax : 0.f;
-  if (!(M > 0.f) || !(M < 3.0e38f)) return 0.25f;
-  int e;
-  (void)frexpf(M, &e);
-  e = 3 - e;
-  e = e < -100 ? -100 : (e > 100 ? 100 : e);
-  return ldexpf(1.f, e);
-}
-
 __global__ __launch_bounds__(256) void k_spw_dysum(const SpwDy p) {
   constexpr int TH = 8, TW = 32, PH = 2 * TH + 2, PW = 2 * TW + 2;
   __shared__ float s_d[PH][PW + 1];
@@ -64,7 +40,7 @@ __global__ __launch_bounds__(256) void k_spw_dysum(const SpwDy p) {
   const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
   const int co = blockIdx.y, n = blockIdx.z;
   const int H = 2 * p.Hl, W = 2 * p.Wl;
-  const float s = spw_grad_scale(p.absmax);
+  const float s = h_grad_scale<3>(p.absmax);      // / 4 for the four addends of a box sum
   if (blockIdx.x == 0 && co == 0 && n == 0 && tid == 0) p.scal[0] = s;
   const size_t plane = (size_t)H * W;
   const float* gb = p.dy.x + ((size_t)n * p.Cout + co) * plane;
@@ -110,7 +86,7 @@ __global__ __launch_bounds__(256) void k_spw_dysum(const SpwDy p) {
     for (int kw = 0; kw < 3; ++kw) {
       const float v = rs[2 - kw] + rs[3 - kw];
       unsigned short h0, h1;
-      spw_split(v, h0, h1);
+      split2h_one(v, h0, h1);
       const size_t row = (size_t)(kh * 3 + kw) * p.Cout + co;
       p.S0[row * p.Kp + k] = h0;
       p.S1[row * p.Kp + k] = h1;
@@ -136,17 +112,8 @@ struct SpwX {
   int N, Cup, HW;
   long Kp;
 };
-__device__ __forceinline__ float spw_act_scale(const float* xb) {
-  float M = xb ? *xb : 0.f;
-  if (!(M * 2.f > 32752.f)) return 2.f;
-  M = fminf(M, 3.0e38f);
-  int e;
-  (void)frexpf(32752.f / M, &e);
-  e = e - 1 < -120 ? -120 : e - 1;
-  return ldexpf(1.f, e);
-}
 __global__ __launch_bounds__(256) void k_spw_xsplit(const SpwX p) {
-  const float s = spw_act_scale(p.xb);
+  const float s = h_act_scale(p.xb, nullptr);
   if (blockIdx.x == 0 && blockIdx.y == 0 && threadIdx.x == 0) p.scal[1] = s;
   const int ci = blockIdx.y;
   float sc = 1.f, sh = 0.f;
@@ -157,7 +124,7 @@ __global__ __launch_bounds__(256) void k_spw_xsplit(const SpwX p) {
     const long n = k / p.HW, q = k - n * p.HW;
     const float v = sc_pro_affine(p.x.x[((size_t)n * p.Cup + ci) * p.HW + q], sc, sh, lo, hi) * s;
     unsigned short h0, h1;
-    spw_split(v, h0, h1);
+    split2h_one(v, h0, h1);
     p.X0[(size_t)ci * p.Kp + k] = h0;
     p.X1[(size_t)ci * p.Kp + k] = h1;
   }
@@ -381,11 +348,7 @@ extern "C" int sc_conv3x3_sp_wgrad(const sc_wgrad_args* a, void* ws, size_t ws_b
     p.M = pl.M; p.Nc = Cup; p.Mp = pl.Mp; p.Np = pl.Np; p.Kp = pl.Kp; p.kstages = pl.kstages;
     dim3 grid(pl.nsl, pl.mtiles, pl.ntiles);
     constexpr int lds2 = 2 * 2 * (256 + 128) * 5 * 16, lds1 = 2 * 2 * (256 + 64) * 5 * 16;
-    static const bool attr_ok = [] {
-      return hipFuncSetAttribute(reinterpret_cast<const void*>(&k_spw_gemm<2>), hipFuncAttributeMaxDynamicSharedMemorySize, lds2) == hipSuccess &&
-             hipFuncSetAttribute(reinterpret_cast<const void*>(&k_spw_gemm<1>), hipFuncAttributeMaxDynamicSharedMemorySize, lds1) == hipSuccess;
-    }();
-    SC_REQUIRE(attr_ok, "sc_conv3x3_sp_wgrad: cannot reserve %d bytes of LDS", lds2);
+    if (int rc = pl.cb == 2 ? sc_lds_limit(&k_spw_gemm<2>, lds2, "sc_conv3x3_sp_wgrad") : sc_lds_limit(&k_spw_gemm<1>, lds1, "sc_conv3x3_sp_wgrad")) return rc;
     if (pl.cb == 2) hipLaunchKernelGGL((k_spw_gemm<2>), grid, dim3(512), lds2, st, p);
     else hipLaunchKernelGGL((k_spw_gemm<1>), grid, dim3(512), lds1, st, p);
     SC_LAUNCH_OK("sc_conv3x3_sp_wgrad(gemm)");

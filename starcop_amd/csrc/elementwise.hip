@@ -6,6 +6,8 @@
 #include "sc_common.h"
 #include <atomic>
 #include <mutex>
+#include <set>
+#include <utility>
 
 // ------------------------------------------------------------------------------------------
 // error plumbing (thread-local message)
@@ -17,6 +19,23 @@ void sc_set_error(const char* fmt, ...) {
   va_end(ap);
 }
 extern "C" const char* sc_last_error(void) { return g_err; }
+
+// The attribute is per device: the record is keyed by (device, kernel), so a process that drives several GPUs raises it on each.
+int sc_lds_limit(const void* kernel, size_t bytes, const char* who) {
+  if (bytes <= 64 * 1024) return SC_OK;
+  static std::mutex mu;
+  static std::set<std::pair<int, const void*>> done;
+  int dev = 0;
+  hipError_t e = hipGetDevice(&dev);
+  if (e == hipSuccess) {
+    std::lock_guard<std::mutex> lock(mu);
+    if (done.count({dev, kernel})) return SC_OK;
+    e = hipFuncSetAttribute(kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+    if (e == hipSuccess) { done.insert({dev, kernel}); return SC_OK; }
+  }
+  sc_set_error("%s: cannot raise the dynamic LDS limit for %zu bytes on device %d: %s", who, bytes, dev, hipGetErrorString(e));
+  return SC_ERR_LAUNCH;
+}
 extern "C" int sc_version(void) { return 100; }
 extern "C" int sc_device_check(void) {
   int dev = 0;

@@ -1826,19 +1826,6 @@ size_t mag1c_lds_bytes(int S) {
   return ((size_t)S * (S + 1) + 11 * VEC + 64 + stg) * sizeof(double);
 }
 
-// the dynamic-LDS limit of a kernel: set once per instantiation (the pointer identifies it); not a stream operation
-template <typename K>
-hipError_t mag1c_lds_attr(K kern, size_t lds) {
-  static const void* done[32];
-  static int ndone = 0;
-  const void* f = reinterpret_cast<const void*>(kern);
-  for (int i = 0; i < ndone; ++i) if (done[i] == f) return hipSuccess;
-  (void)lds;
-  const hipError_t e = hipFuncSetAttribute(f, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-  if (e == hipSuccess && ndone < 32) done[ndone++] = f;
-  return e;
-}
-
 }  // namespace
 
 extern "C" size_t sc_mag1c_workspace_doubles(int G, int S, int64_t npix) {
@@ -1874,17 +1861,16 @@ extern "C" int sc_mag1c_groups(const sc_mag1c_args* a, sc_stream stream) {
   SC_REQUIRE((a->energy == nullptr) == (a->logdet == nullptr), "sc_mag1c_groups: energy and logdet go together");
   size_t lds = mag1c_lds_bytes(a->S);
   hipStream_t st = (hipStream_t)stream;
-  hipError_t e;
+  int rc = SC_OK;
   const bool fast = a->alpha == 0.0;     // no shrinkage: one factorisation per group + Woodbury updates
   if (!a->x_is_f64) {
     // fp32 radiances (both drivers of the reference): the register-tile kernel, one group per CU.  Up to 64 bands: chunks streamed;
     // more: a pair of launches (groups of <= 512 pixels stay in registers, larger ones stream), see k_mag1c_tile
 #define SC_TILE_GO(...)                                                                                                        \
     do {                                                                                                                       \
-      if (e == hipSuccess) e = mag1c_lds_attr(&k_mag1c_tile<__VA_ARGS__>, lds);                                                  \
-      if (e == hipSuccess) hipLaunchKernelGGL((k_mag1c_tile<__VA_ARGS__>), dim3(a->G), dim3(RNT), lds, st, p);                  \
+      if (rc == SC_OK) rc = sc_lds_limit(&k_mag1c_tile<__VA_ARGS__>, lds, "sc_mag1c_groups");                                    \
+      if (rc == SC_OK) hipLaunchKernelGGL((k_mag1c_tile<__VA_ARGS__>), dim3(a->G), dim3(RNT), lds, st, p);                  \
     } while (0)
-    e = hipSuccess;
     if (a->energy) {                 // compute_energy: the streaming instantiations take every group
       if (a->S <= 64) { lds = mag1c_tile_lds_bytes<4>(a->S); if (fast) SC_TILE_GO(4, false, false, true); else SC_TILE_GO(4, false, true, true); }
       else { lds = mag1c_tile_lds_bytes<8>(a->S); if (fast) SC_TILE_GO(8, false, false, true); else SC_TILE_GO(8, false, true, true); }
@@ -1899,21 +1885,21 @@ extern "C" int sc_mag1c_groups(const sc_mag1c_args* a, sc_stream stream) {
     }
 #undef SC_TILE_GO
   } else if (fast) {
-    e = mag1c_lds_attr(&k_mag1c_fast<double, 1024>, lds);
-    if (e == hipSuccess) hipLaunchKernelGGL((k_mag1c_fast<double, 1024>), dim3(a->G), dim3(1024), lds, st, p);
+    rc = sc_lds_limit(&k_mag1c_fast<double, 1024>, lds, "sc_mag1c_groups");
+    if (rc == SC_OK) hipLaunchKernelGGL((k_mag1c_fast<double, 1024>), dim3(a->G), dim3(1024), lds, st, p);
   } else {
     // fp64 radiances, alpha != 0: refactorisation every iteration.  Few bands: 512 threads (3 groups per CU);
     // many bands: the matrix fills the LDS, one group of 1024 threads per CU
 #define SC_MAG1C_GO(T_, NT_, EN_)                                                                                                 \
     do {                                                                                                                       \
-      e = mag1c_lds_attr(&k_mag1c<T_, NT_, EN_>, lds);                                                                          \
-      if (e == hipSuccess) hipLaunchKernelGGL((k_mag1c<T_, NT_, EN_>), dim3(a->G), dim3(NT_), lds, st, p);                     \
+      rc = sc_lds_limit(&k_mag1c<T_, NT_, EN_>, lds, "sc_mag1c_groups");                                                        \
+      if (rc == SC_OK) hipLaunchKernelGGL((k_mag1c<T_, NT_, EN_>), dim3(a->G), dim3(NT_), lds, st, p);                     \
     } while (0)
     if (a->energy) { if (a->S <= 64) SC_MAG1C_GO(double, 512, true); else SC_MAG1C_GO(double, 1024, true); }
     else { if (a->S <= 64) SC_MAG1C_GO(double, 512, false); else SC_MAG1C_GO(double, 1024, false); }
 #undef SC_MAG1C_GO
   }
-  if (e != hipSuccess) { sc_set_error("sc_mag1c_groups: cannot reserve %zu bytes of LDS: %s", lds, hipGetErrorString(e)); return SC_ERR_LAUNCH; }
+  if (rc != SC_OK) return rc;
   SC_LAUNCH_OK("sc_mag1c_groups");
   return SC_OK;
 }

@@ -340,9 +340,7 @@ struct SweepArgs {
 
 template <int MODE, bool VEC>
 bool sweep_launch(const SweepArgs& a) {
-  static const bool ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_pwreg_sweep<MODE, VEC>),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)sweep_smem_bytes(PW_C, PW_C)) == hipSuccess;
-  if (!ok) return false;
+  if (sc_lds_limit(&k_pwreg_sweep<MODE, VEC>, a.smem, "sc_pwreg_train_sweep") != SC_OK) return false;
   hipLaunchKernelGGL((k_pwreg_sweep<MODE, VEC>), dim3(a.nb), dim3(256), a.smem, a.st, a.x, a.yg, a.params, a.d, a.HW, a.tpi, a.ntiles,
                      a.iters, a.part);
   return true;

@@ -7,6 +7,15 @@
 
 void sc_set_error(const char* fmt, ...);
 
+// Call directly in front of the launch of a kernel instantiation with `bytes` of dynamic LDS: above the default 64 KB limit it raises
+// the kernel's limit to gfx950's 160 KB, once per (current device, kernel).  Not a stream operation, so it is legal under graph
+// capture too.  SC_OK, or SC_ERR_LAUNCH with the error set (`who`: the entry point).  Defined in elementwise.hip.
+int sc_lds_limit(const void* kernel, size_t bytes, const char* who);
+template <typename... A>
+inline int sc_lds_limit(void (*kernel)(A...), size_t bytes, const char* who) {
+  return sc_lds_limit(reinterpret_cast<const void*>(kernel), bytes, who);
+}
+
 #define SC_REQUIRE(cond, ...)                 \
   do {                                        \
     if (!(cond)) {                            \

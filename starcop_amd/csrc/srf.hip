@@ -123,9 +123,7 @@ __global__ __launch_bounds__(SRF_WG) void k_srf_strided(SrfD a, int tiles) {
 
 template <bool VEC>
 int launch_bip(const SrfD& d, int tiles, int sp, size_t lds, hipStream_t st) {
-  static const bool attr_ok = hipFuncSetAttribute(reinterpret_cast<const void*>(&k_srf_bip<VEC>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, SRF_LDS_MAX) == hipSuccess;
-  SC_REQUIRE(attr_ok || lds <= 64 * 1024, "sc_srf_bands: cannot raise the LDS limit of the band-contiguous kernel");
+  SC_REQUIRE(sc_lds_limit(&k_srf_bip<VEC>, lds, "sc_srf_bands") == SC_OK, "sc_srf_bands: cannot raise the LDS limit of the band-contiguous kernel");
   hipLaunchKernelGGL(k_srf_bip<VEC>, dim3((unsigned)d.L * (unsigned)tiles), dim3(SRF_WG), lds, st, d, tiles, sp);
   return SC_OK;
 }

@@ -390,7 +390,7 @@ class HyperStarcopUNet(nn.Module):
             torch.distributed.all_reduce(v, op=torch.distributed.ReduceOp.MAX)
             wmax, amax, rmax, omax, switched = (float(x) for x in v.tolist())
         # Round 5: activations can no longer leave the range -- every split convolution scales its fp16 operand from a device-side
-        # bound of its sources (h_act_scale in conv_bx3.hip: |gamma| sqrt(n - 1) + |beta| from sc_bn_finalize in training, the
+        # bound of its sources (h_act_scale in sc_split.h: |gamma| sqrt(n - 1) + |beta| from sc_bn_finalize in training, the
         # recorded maxima for residual sums / in inference), so only the FILTERS (scaled by a fixed 2^8 at pack time) decide `ok`;
         # the activation figures stay in the report (activation_default_scale: the fixed x2 of rounds 1-4 still applies to all).
         #  Inference has no by-construction bound: BatchNorm runs on running statistics and the scales follow the sticky

@@ -91,6 +91,21 @@ def test_inverted_residual_block_eval_one_launch(hip, case):
         assert abs(float(zmax) - float(out.abs().max())) <= 1e-6 * float(out.abs().max())
 
 
+@pytest.mark.skipif(torch.cuda.device_count() < 2, reason="needs two GPUs: the dynamic-LDS limit of a kernel is a per-device attribute")
+def test_inverted_residual_block_eval_on_a_second_device(hip):
+    """launches that need more than 64 KB of dynamic LDS (the stride-2 tiling; Cin > 96), first on device 0, then on device 1 of the
+    same process: the kernel's LDS limit has to be raised on each device, and both must compute the same bits"""
+    for case in ((2, 32, 192, 64, 64, 64, False, "raw", 2), (2, 160, 960, 160, 16, 16, True, "raw")):
+        with torch.cuda.device(0):
+            out0, want, _ = _run(case, seed=77)
+        with torch.cuda.device(1):
+            out1, _, _ = _run(case, seed=77)
+        assert out0.device.index == 0 and out1.device.index == 1
+        assert relerr(out0, want) < 3e-6, relerr(out0, want)
+        assert relerr(out1, want) < 3e-6, relerr(out1, want)
+        assert torch.equal(out0.cpu(), out1.cpu())
+
+
 def test_inverted_residual_block_eval_rejects_what_it_does_not_take(hip):
     lib = _lib.load()
     assert not lib.sc_irb_supported(160, 960, 320, 16, 16, 2)    # stride 2: Cin <= 96 only
