@@ -886,6 +886,50 @@ typedef struct sc_wcut_args {
 int sc_window_cut(const sc_wcut_args* a, sc_stream stream);
 
 /* ------------------------------------------------------------------------- */
+/* Whole-scene cloud masking: the reference's CDModel.predict (starcop/sentinel2/models.py:27-52, 80-89) reflect-pads the scene to a
+ * multiple of 32 and runs it as ONE image; a 10 980 x 10 980 Sentinel-2 tile does not fit that way.  Here the padded scene is walked
+ * in equally shaped windows (sentinel2.scene_windows); one table row describes a window to both kernels below.
+ *   sc_scene_gather : out[i][c][y][x] = (float) src[c][refl(row_off_i + y - pad_top, H)][refl(col_off_i + x - pad_left, W)] [* scale]
+ *                     refl(t, n) = t < 0 ? -t : (t >= n ? 2 (n - 1) - t : t): numpy's "reflect" with ONE reflection, so pads < n.
+ *                     src: (C, H, W) uint16 (elem_bytes 2) or float32 (4), device, read in place through non-negative element
+ *                     strides (a band-interleaved view has col_stride = C); out: dense [n][C][win_h][win_w] float32, 16-byte
+ *                     aligned, win_w a multiple of 4.  scale == 1: no multiply; otherwise exactly one float32 multiply (float)v *
+ *                     scale.  Addresses are 64-bit.  16-byte stores; one 8- / 16-byte load per store where its four source elements
+ *                     are contiguous, inside the image and so aligned, element loads otherwise.  The padded scene is never stored.
+ *   sc_head_conv_fwd_k_mosaic : the class-index path of sc_head_conv_fwd_k (logits == NULL) with a destination table: of batch item
+ *                     i only the core rectangle rows [core_y0, core_y1) x columns [core_x0, core_x1) of its H x W plane is stored,
+ *                     at mosaic[(dst_row + y - core_y0) * pitch + dst_col + x - core_x0].  Same stencil, same FMA order, hence the
+ *                     class bits of sc_head_conv_fwd_k; work-groups whose tile holds no core pixel return before they stage
+ *                     anything.  4-byte stores where four adjacent pixels are wanted and their address is 4-byte aligned, byte
+ *                     stores otherwise.  An empty core (core_y1 <= core_y0 or core_x1 <= core_x0) stores nothing.
+ * The table is given twice, on the device for the kernels and on the host for the checks that run before the launch (windows inside
+ * the reflect-padded scene; cores inside the plane and their destinations inside the mos_h x mos_w mosaic); the kernels additionally
+ * clamp source coordinates into the image and drop stores outside the mosaic, so a device table that differs from the checked one
+ * cannot make them touch foreign memory.  No synchronisation, no allocation, no atomics.                                          */
+typedef struct sc_scene_win {
+  int32_t row_off, col_off;                      /* window origin in the padded scene (sc_scene_gather)       */
+  int32_t core_y0, core_y1, core_x0, core_x1;    /* core rectangle inside the window (mosaic head)            */
+  int32_t dst_row, dst_col;                      /* where the core's first pixel goes in the mosaic           */
+} sc_scene_win;
+typedef struct sc_scene_args {
+  const void* src;                               /* element [0][0][0], device                                 */
+  int32_t elem_bytes;                            /* 2 = uint16, 4 = float32                                   */
+  int32_t C, H, W;
+  int64_t chan_stride, row_stride, col_stride;   /* elements                                                  */
+  int32_t pad_top, pad_left;                     /* reflect pads in front of row 0 / column 0                 */
+  int32_t n, win_h, win_w;                       /* windows of the call and their common shape                */
+  float scale;
+  const sc_scene_win* win;                       /* [n] device                                                */
+  const sc_scene_win* win_host;                  /* the same on the host                                      */
+  float* out;                                    /* [n][C][win_h][win_w] device                               */
+} sc_scene_args;
+int sc_scene_gather(const sc_scene_args* a, sc_stream stream);
+int sc_head_conv_fwd_k_mosaic(const sc_src* in, const float* w /*[K][Cin][3][3]*/, const float* bias /*[K]*/,
+                              uint8_t* mosaic /*[mos_h][pitch]*/, int mos_h, int mos_w, int64_t pitch,
+                              const sc_scene_win* win /*[N] device*/, const sc_scene_win* win_host /*[N] host*/,
+                              int N, int Cin, int K, int H, int W, sc_stream stream);
+
+/* ------------------------------------------------------------------------- */
 /* evaluation masks of the baselines and of run_validation.
  * Thresholded prediction with an optional binary opening by a 3x3 structuring element:
  *   starcop/baselines.py:25-27 binary_opening = dilation(erosion(x)) ; :53-57 Mag1cBaseline.apply_threshold (pred > thr, cross SE)

@@ -20,6 +20,7 @@ Public surface (mirrors the reference):
     (the EMIT driver with its georreferenced=True default); pipeline.emit_granule_predict(georeferenced=True, out_folder=...)
   starcop_amd.model_module_regression.ModelModuleRegression / l1 / mse (the regression twin; get_model serves both modes);
     starcop_amd.pointwise_net.SimpleCNN_v2 / SimpleCNN_v3; features.set_learned_model (the learned band-ratio product)
+  starcop_amd.sentinel2.CDModel (predict / predict_scene: the whole-tile cloud mask) / scene_windows / cloud_mask_file / load_weights
 All compute runs in starcop_amd/libstarcop_hip.so (include/starcop_hip.h); there is no CPU fallback.
 """
 __version__ = "0.1.0"

@@ -147,6 +147,20 @@ class sc_wcut_args(C.Structure):
                 ("clip_hi", C.c_float * WCUT_MAX_PLANES), ("out", C.c_void_p)]
 
 
+class sc_scene_win(C.Structure):
+    """one window of a scene plan (include/starcop_hip.h: sc_scene_win)"""
+    _fields_ = [("row_off", C.c_int32), ("col_off", C.c_int32), ("core_y0", C.c_int32), ("core_y1", C.c_int32),
+                ("core_x0", C.c_int32), ("core_x1", C.c_int32), ("dst_row", C.c_int32), ("dst_col", C.c_int32)]
+
+
+class sc_scene_args(C.Structure):
+    """reflect-padded window gather operands (include/starcop_hip.h: sc_scene_args)"""
+    _fields_ = [("src", C.c_void_p), ("elem_bytes", C.c_int32), ("C", C.c_int32), ("H", C.c_int32), ("W", C.c_int32),
+                ("chan_stride", C.c_int64), ("row_stride", C.c_int64), ("col_stride", C.c_int64),
+                ("pad_top", C.c_int32), ("pad_left", C.c_int32), ("n", C.c_int32), ("win_h", C.c_int32), ("win_w", C.c_int32),
+                ("scale", C.c_float), ("win", C.c_void_p), ("win_host", C.c_void_p), ("out", C.c_void_p)]
+
+
 _vp, _i, _f, _d, _sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/starcop_hip.h declares
@@ -228,6 +242,8 @@ SIGNATURES = {
     "sc_window_stats": (_i, [C.POINTER(sc_winstats_args), _vp, _sz, _vp]),
     "sc_glt_ortho": (_i, [C.POINTER(sc_ortho_args), _vp]),
     "sc_window_cut": (_i, [C.POINTER(sc_wcut_args), _vp]),
+    "sc_scene_gather": (_i, [C.POINTER(sc_scene_args), _vp]),
+    "sc_head_conv_fwd_k_mosaic": (_i, [C.POINTER(sc_src), _vp, _vp, _vp, _i, _i, C.c_int64, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "sc_connected_components": (_i, [_vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "sc_proposed_mask": (_i, [_vp, C.c_int64, _vp, C.c_int64, _f, _i, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "sc_packed_weight_floats_thin16": (_sz, [_i, _i, _i]),

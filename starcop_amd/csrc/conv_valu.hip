@@ -1605,16 +1605,51 @@ __device__ __forceinline__ uint32_t head_argmax(const float* a, int K) {
   return idx;
 }
 
+// Destination of the class indices when only the core rectangle of every batch item is wanted, written straight into a uint8
+// mosaic[h][pitch] (sc_head_conv_fwd_k_mosaic); win == NULL in the plain launches
+struct HeadMosaic {
+  const sc_scene_win* win;      // [N] device
+  uint8_t* mosaic;
+  long long pitch;
+  int h, w;
+};
+
+// loads batch item n's core; false if the TR x TC tile at (y0, x0) holds none of its pixels (the whole work-group leaves then)
+__device__ __forceinline__ bool head_mosaic_tile(const HeadMosaic& mo, int n, int y0, int x0, int TR, int TC, sc_scene_win& q) {
+  q = mo.win[n];
+  return q.core_y1 > q.core_y0 && q.core_x1 > q.core_x0 && y0 < q.core_y1 && y0 + TR > q.core_y0 && x0 < q.core_x1 && x0 + TC > q.core_x0;
+}
+
+// where pixel (y, x) of a window goes in the mosaic, and whether it is stored: inside the core, and inside the mosaic whatever the
+// device table holds
+__device__ __forceinline__ bool head_mosaic_px(const HeadMosaic& mo, const sc_scene_win& q, int y, int x, long long& off) {
+  const long long r = (long long)q.dst_row + y - q.core_y0, c = (long long)q.dst_col + x - q.core_x0;
+  off = r * mo.pitch + c;
+  return y >= q.core_y0 && y < q.core_y1 && x >= q.core_x0 && x < q.core_x1 && r >= 0 && r < mo.h && c >= 0 && c < mo.w;
+}
+
+// the class indices of a thread's four adjacent pixels: one 4-byte store if `word` (all four wanted, cp 4-byte aligned), else a byte
+// store per wanted pixel (bit o of `want`)
+__device__ __forceinline__ void head_store_classes4(uint8_t* cp, const uint32_t (&c)[4], bool word, uint32_t want) {
+  if (word) {
+    *reinterpret_cast<uint32_t*>(cp) = c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24);
+  } else {
+#pragma unroll
+    for (int o = 0; o < 4; ++o) if (want & (1u << o)) cp[o] = (uint8_t)c[o];
+  }
+}
+
 // Cin = 16 (the decoder's last block), K <= KT classes: k_head_fwd16's tile (16 rows x 64 columns, a thread owns 4 adjacent pixels,
 // channels in two passes of 8) with KT x 4 accumulators per thread; the patch values of one (ci, kh) -- a 16-byte and two 4-byte LDS
 // reads -- now feed 12 KT FMAs.  Patch rows as in k_head_fwd16v: left halo at [3], columns at [4, 68), right halo at [68].  VEC: the
 // 16-byte staging of k_head_fwd16v (W % 4 == 0, 16-byte aligned planes), next pass requested before this pass's stencil; otherwise
 // the 4-byte staging of k_head_fwd16.  logits == NULL: nothing but the class index (1 byte per pixel) leaves the launch.
 // lvec / cvec: 16-byte logit stores / 4-byte class stores (W % 4 == 0 and the output's base aligned accordingly).
-template <int KT, bool VEC>
+// MOS: the classes of the core rectangles go into mo.mosaic (logits and classes are NULL); a tile without a core pixel leaves at once.
+template <int KT, bool VEC, bool MOS>
 __global__ __launch_bounds__(256, 2) void k_head_fwdk16(const SrcD in, const float* __restrict__ w, const float* __restrict__ bias,
                                                        float* __restrict__ logits, uint8_t* __restrict__ classes, int K, int H, int W,
-                                                       int lvec, int cvec) {
+                                                       int lvec, int cvec, const HeadMosaic mo) {
   constexpr int CIN = 16, CP = 8, TR = 16, TC = 64, PR = TR + 2, PC = 68, NROW = CP * PR, QW = NROW / 16, NHALO = NROW * 2;
   static_assert(NROW % 16 == 0 && NHALO <= 512, "four waves x QW requests of four rows; two halo elements per thread");
   __shared__ __attribute__((aligned(16))) float s_in[NROW * PC + 4];
@@ -1624,6 +1659,8 @@ __global__ __launch_bounds__(256, 2) void k_head_fwdk16(const SrcD in, const flo
   const int tiles_x = (W + TC - 1) / TC;
   const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
   const int y0 = ty * TR, x0 = tx * TC;
+  sc_scene_win core;
+  if (MOS && !head_mosaic_tile(mo, n, y0, x0, TR, TC, core)) return;
   const float lo = sc_act_lo(in.act), hi = sc_act_hi(in.act);
   const bool raw = in.mode == SC_SRC_RAW;
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
@@ -1773,23 +1810,31 @@ __global__ __launch_bounds__(256, 2) void k_head_fwdk16(const SrcD in, const flo
       }
     }
   }
-  if (classes) {
-    uint32_t c[4];
+  if (MOS || classes) {
+    uint32_t c[4], want = 0;
 #pragma unroll
     for (int o = 0; o < 4; ++o) c[o] = head_argmax<KT, 4>(&acc[0][o], K);
-    uint8_t* cp = classes + (size_t)n * HW + pix;
-    if (cvec) {
-      *reinterpret_cast<uint32_t*>(cp) = c[0] | (c[1] << 8) | (c[2] << 16) | (c[3] << 24);
+    if (MOS) {
+      long long off0, off;
+      head_mosaic_px(mo, core, y, x, off0);
+#pragma unroll
+      for (int o = 0; o < 4; ++o)
+        if (x + o < W && head_mosaic_px(mo, core, y, x + o, off)) want |= 1u << o;
+      uint8_t* cp = mo.mosaic + off0;      // (only the wanted bytes of cp[0..3] are touched)
+      head_store_classes4(cp, c, want == 15u && (reinterpret_cast<uintptr_t>(cp) & 3) == 0, want);
     } else {
 #pragma unroll
-      for (int o = 0; o < 4; ++o) if (x + o < W) cp[o] = (uint8_t)c[o];
+      for (int o = 0; o < 4; ++o) want |= (x + o < W) ? 1u << o : 0u;
+      head_store_classes4(classes + (size_t)n * HW + pix, c, cvec != 0, want);
     }
   }
 }
 
 // any Cin <= 32: k_head_fwd<0>'s tile (8 x 32, one pixel per thread, taps in LDS) with HEADK_MAXK accumulators
+template <bool MOS>
 __global__ __launch_bounds__(256) void k_head_fwdk(const SrcD in, const float* __restrict__ w, const float* __restrict__ bias,
-                                                   float* __restrict__ logits, uint8_t* __restrict__ classes, int Cin, int K, int H, int W) {
+                                                   float* __restrict__ logits, uint8_t* __restrict__ classes, int Cin, int K, int H, int W,
+                                                   const HeadMosaic mo) {
   constexpr int KT = HEADK_MAXK, PR = HT_R + 2, PC = HT_C + 2;
   __shared__ float s_in[HEAD_MAXCI * PR * PC];
   __shared__ float s_w[KT * HEAD_MAXCI * 9];                            // [k][ci][tap]; classes >= K: zeros
@@ -1797,6 +1842,8 @@ __global__ __launch_bounds__(256) void k_head_fwdk(const SrcD in, const float* _
   const int tiles_x = (W + HT_C - 1) / HT_C;
   const int ty = blockIdx.x / tiles_x, tx = blockIdx.x - ty * tiles_x;
   const int y0 = ty * HT_R, x0 = tx * HT_C;
+  sc_scene_win core;
+  if (MOS && !head_mosaic_tile(mo, n, y0, x0, HT_R, HT_C, core)) return;
   for (int i = threadIdx.x; i < KT * Cin * 9; i += 256) s_w[i] = i < K * Cin * 9 ? w[i] : 0.f;
   head_stage_patch<PC, 0>(in, s_in, n, Cin, H, W, y0, x0);
   __syncthreads();
@@ -1821,7 +1868,12 @@ __global__ __launch_bounds__(256) void k_head_fwdk(const SrcD in, const float* _
     for (int k = 0; k < KT; ++k)
       if (k < K) logits[((size_t)n * K + k) * HW + pix] = acc[k];
   }
-  if (classes) classes[(size_t)n * HW + pix] = (uint8_t)head_argmax<KT, 1>(acc, K);
+  if (MOS) {
+    long long off;
+    if (head_mosaic_px(mo, core, y, x, off)) mo.mosaic[off] = (uint8_t)head_argmax<KT, 1>(acc, K);
+  } else if (classes) {
+    classes[(size_t)n * HW + pix] = (uint8_t)head_argmax<KT, 1>(acc, K);
+  }
 }
 
 __global__ __launch_bounds__(256) void k_head_dgrad(const float* __restrict__ dl, const float* __restrict__ w,
@@ -2279,9 +2331,32 @@ extern "C" int sc_head_conv_fwd(const sc_src* in, const float* w, const float* b
 
 template <int KT>
 static void launch_head_fwdk16(bool vec, dim3 grid, hipStream_t st, const SrcD& s, const float* w, const float* bias, float* logits,
-                               uint8_t* classes, int K, int H, int W, int lvec, int cvec) {
-  if (vec) hipLaunchKernelGGL((k_head_fwdk16<KT, true>), grid, dim3(256), 0, st, s, w, bias, logits, classes, K, H, W, lvec, cvec);
-  else hipLaunchKernelGGL((k_head_fwdk16<KT, false>), grid, dim3(256), 0, st, s, w, bias, logits, classes, K, H, W, lvec, cvec);
+                               uint8_t* classes, int K, int H, int W, int lvec, int cvec, const HeadMosaic& mo) {
+  if (mo.win) {
+    if (vec) hipLaunchKernelGGL((k_head_fwdk16<KT, true, true>), grid, dim3(256), 0, st, s, w, bias, logits, classes, K, H, W, lvec, cvec, mo);
+    else hipLaunchKernelGGL((k_head_fwdk16<KT, false, true>), grid, dim3(256), 0, st, s, w, bias, logits, classes, K, H, W, lvec, cvec, mo);
+  } else {
+    if (vec) hipLaunchKernelGGL((k_head_fwdk16<KT, true, false>), grid, dim3(256), 0, st, s, w, bias, logits, classes, K, H, W, lvec, cvec, mo);
+    else hipLaunchKernelGGL((k_head_fwdk16<KT, false, false>), grid, dim3(256), 0, st, s, w, bias, logits, classes, K, H, W, lvec, cvec, mo);
+  }
+}
+
+// the K-class kernels: logits and / or classes (mo.win == NULL), or the cores' classes into mo.mosaic
+static void launch_head_fwdk(const sc_src* in, const float* w, const float* bias, float* logits, uint8_t* classes, const HeadMosaic& mo,
+                             int N, int Cin, int K, int H, int W, hipStream_t st) {
+  if (Cin == 16) {
+    dim3 g16(((W + 63) / 64) * ((H + 15) / 16), 1, N);
+    const bool w4 = W % 4 == 0;
+    const bool vec = w4 && ((uintptr_t)in->x & 15) == 0;
+    const int lvec = w4 && ((uintptr_t)logits & 15) == 0, cvec = w4 && ((uintptr_t)classes & 3) == 0;
+    if (K <= 2) launch_head_fwdk16<2>(vec, g16, st, to_srcd(*in), w, bias, logits, classes, K, H, W, lvec, cvec, mo);
+    else if (K <= 4) launch_head_fwdk16<4>(vec, g16, st, to_srcd(*in), w, bias, logits, classes, K, H, W, lvec, cvec, mo);
+    else launch_head_fwdk16<8>(vec, g16, st, to_srcd(*in), w, bias, logits, classes, K, H, W, lvec, cvec, mo);
+  } else {
+    dim3 grid(((W + HT_C - 1) / HT_C) * ((H + HT_R - 1) / HT_R), 1, N);
+    if (mo.win) hipLaunchKernelGGL(k_head_fwdk<true>, grid, dim3(256), 0, st, to_srcd(*in), w, bias, logits, classes, Cin, K, H, W, mo);
+    else hipLaunchKernelGGL(k_head_fwdk<false>, grid, dim3(256), 0, st, to_srcd(*in), w, bias, logits, classes, Cin, K, H, W, mo);
+  }
 }
 
 extern "C" int sc_head_conv_fwd_k(const sc_src* in, const float* w, const float* bias, float* logits, uint8_t* classes, int N,
@@ -2297,19 +2372,33 @@ extern "C" int sc_head_conv_fwd_k(const sc_src* in, const float* w, const float*
     if (classes && hipMemsetAsync(classes, 0, (size_t)N * H * W, st) != hipSuccess) { sc_set_error("sc_head_conv_fwd_k: memset failed"); return SC_ERR_LAUNCH; }
     return logits ? sc_head_conv_fwd(in, w, bias, logits, N, Cin, H, W, stream) : SC_OK;
   }
-  if (Cin == 16) {
-    dim3 g16(((W + 63) / 64) * ((H + 15) / 16), 1, N);
-    const bool w4 = W % 4 == 0;
-    const bool vec = w4 && ((uintptr_t)in->x & 15) == 0;
-    const int lvec = w4 && ((uintptr_t)logits & 15) == 0, cvec = w4 && ((uintptr_t)classes & 3) == 0;
-    if (K <= 2) launch_head_fwdk16<2>(vec, g16, st, to_srcd(*in), w, bias, logits, classes, K, H, W, lvec, cvec);
-    else if (K <= 4) launch_head_fwdk16<4>(vec, g16, st, to_srcd(*in), w, bias, logits, classes, K, H, W, lvec, cvec);
-    else launch_head_fwdk16<8>(vec, g16, st, to_srcd(*in), w, bias, logits, classes, K, H, W, lvec, cvec);
-  } else {
-    dim3 grid(((W + HT_C - 1) / HT_C) * ((H + HT_R - 1) / HT_R), 1, N);
-    hipLaunchKernelGGL(k_head_fwdk, grid, dim3(256), 0, st, to_srcd(*in), w, bias, logits, classes, Cin, K, H, W);
-  }
+  launch_head_fwdk(in, w, bias, logits, classes, HeadMosaic{nullptr, nullptr, 0, 0, 0}, N, Cin, K, H, W, st);
   SC_LAUNCH_OK("sc_head_conv_fwd_k");
+  return SC_OK;
+}
+
+extern "C" int sc_head_conv_fwd_k_mosaic(const sc_src* in, const float* w, const float* bias, uint8_t* mosaic, int mos_h, int mos_w,
+                                         int64_t pitch, const sc_scene_win* win, const sc_scene_win* win_host, int N, int Cin, int K,
+                                         int H, int W, sc_stream stream) {
+  SC_REQUIRE(in && in->C == Cin, "sc_head_conv_fwd_k_mosaic: source channels != Cin");
+  SC_REQUIRE(Cin >= 1 && Cin <= HEAD_MAXCI, "sc_head_conv_fwd_k_mosaic: Cin must be in [1,%d]", HEAD_MAXCI);
+  SC_REQUIRE(K >= 1 && K <= HEADK_MAXK, "sc_head_conv_fwd_k_mosaic: K must be in [1,%d] (got %d)", HEADK_MAXK, K);
+  SC_REQUIRE((in->mode == SC_SRC_RAW || in->mode == SC_SRC_AFFINE) && in->up == 0, "sc_head_conv_fwd_k_mosaic: unsupported source mode");
+  SC_REQUIRE(w && mosaic && win && win_host && N > 0 && H > 0 && W > 0, "sc_head_conv_fwd_k_mosaic: bad argument");
+  SC_REQUIRE(mos_h > 0 && mos_w > 0 && pitch >= mos_w, "sc_head_conv_fwd_k_mosaic: bad mosaic %d x %d, pitch %lld", mos_h, mos_w, (long long)pitch);
+  SC_REQUIRE((uintptr_t)win % 4 == 0, "sc_head_conv_fwd_k_mosaic: misaligned window table");
+  for (int i = 0; i < N; ++i) {
+    const sc_scene_win& q = win_host[i];
+    if (q.core_y1 <= q.core_y0 || q.core_x1 <= q.core_x0) continue;      // empty core: nothing is stored
+    SC_REQUIRE(q.core_y0 >= 0 && q.core_y1 <= H && q.core_x0 >= 0 && q.core_x1 <= W,
+               "sc_head_conv_fwd_k_mosaic: core %d (rows %d:%d, columns %d:%d) is not inside the %d x %d plane", i, q.core_y0, q.core_y1,
+               q.core_x0, q.core_x1, H, W);
+    SC_REQUIRE(q.dst_row >= 0 && (long long)q.dst_row + (q.core_y1 - q.core_y0) <= mos_h && q.dst_col >= 0 &&
+                   (long long)q.dst_col + (q.core_x1 - q.core_x0) <= mos_w,
+               "sc_head_conv_fwd_k_mosaic: core %d does not fit the %d x %d mosaic at row %d, column %d", i, mos_h, mos_w, q.dst_row, q.dst_col);
+  }
+  launch_head_fwdk(in, w, bias, nullptr, nullptr, HeadMosaic{win, mosaic, (long long)pitch, mos_h, mos_w}, N, Cin, K, H, W, (hipStream_t)stream);
+  SC_LAUNCH_OK("sc_head_conv_fwd_k_mosaic");
   return SC_OK;
 }
 

@@ -597,8 +597,10 @@ class HyperStarcopUNet(nn.Module):
     class _Plan:
         pass
 
-    def _get_plan(self, N, H, W, need_grad, want_logits=True):
-        """want_logits=False (predict_classes): a plan created by this call gets no logits buffer; the first call that wants one adds it"""
+    def _get_plan(self, N, H, W, need_grad, want_logits=True, want_classes=None):
+        """want_logits=False (predict_classes): a plan created by this call gets no logits buffer; the first call that wants one adds it.
+        want_classes (default: not want_logits) likewise for the (N, H, W) class buffer, which predict_classes_into does without."""
+        want_classes = (not want_logits) if want_classes is None else want_classes
         key = (N, H, W)
         plan = self._plans.get(key)
         dev = self._pflat.device
@@ -680,7 +682,7 @@ class HyperStarcopUNet(nn.Module):
             self._plans[key] = plan
         if want_logits and "logits" not in plan.buf:
             plan.buf["logits"] = torch.empty((N, self.classes, H, W), dtype=torch.float32, device=dev)
-        if not want_logits and getattr(plan, "classes", None) is None:
+        if want_classes and getattr(plan, "classes", None) is None:
             plan.classes = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
         if need_grad and not plan.has_grad:
             lib = _lib.load()
@@ -958,9 +960,11 @@ class HyperStarcopUNet(nn.Module):
     def _dy_src(self, plan, t):
         return make_src(plan.grad[t.name], t.C, SRC_BNBWD, act=t.act, cst=plan.cstb[t.name], aux=plan.buf[t.name])
 
-    def _forward_impl(self, x, x_cst, training, need_grad, _recheck=0, head="logits"):
+    def _forward_impl(self, x, x_cst, training, need_grad, _recheck=0, head="logits", mosaic=None):
         """x: (N,C,H,W) fp32 device tensor (raw physical units if x_cst is given, else already normalised).
-        head: "logits" -> plan.buf["logits"] (N,K,H,W); "classes" -> plan.classes (N,H,W) uint8 = argmax over K, no logits stored."""
+        head: "logits" -> plan.buf["logits"] (N,K,H,W); "classes" -> plan.classes (N,H,W) uint8 = argmax over K, no logits stored;
+        "mosaic" -> the classes of every item's core rectangle into mosaic = (uint8 (h, w) tensor, device table, host table, first
+        row), see predict_classes_into: neither logits nor per-item classes are stored."""
         if training and (self.classes > self.MAX_TRAIN_CLASSES or self.in_channels > self.MAX_TRAIN_IN_CHANNELS):
             raise NotImplementedError(
                 f"HyperStarcopUNet(in_channels={self.in_channels}, classes={self.classes}) runs in eval mode only: training needs two "
@@ -976,7 +980,7 @@ class HyperStarcopUNet(nn.Module):
                                "divisible by 32.")
         self._ensure_flat()
         x = x.contiguous().float()
-        plan = self._get_plan(N, H, W, need_grad, want_logits=head == "logits")
+        plan = self._get_plan(N, H, W, need_grad, want_logits=head == "logits", want_classes=head == "classes")
         plan.buf["x"] = x
         plan.x_cst = x_cst
         plan.generation = getattr(plan, "generation", 0) + 1     # activations of an earlier forward of this shape are gone
@@ -1152,7 +1156,12 @@ class HyperStarcopUNet(nn.Module):
                                              plan.fin_amax.data_ptr() + 4 * plan.fin_slot[o.name], st))
             elif ty == "head":
                 s = self._src_of(plan, op["ins"][0])
-                if self.classes == 1 and head == "logits":
+                if head == "mosaic":
+                    mos, tab_dev, tab_host, first = mosaic
+                    check(lib.sc_head_conv_fwd_k_mosaic(C.byref(s), ptr(conv.weight), ptr(conv.bias), ptr(mos), mos.shape[0], mos.shape[1],
+                                                        mos.stride(0), tab_dev.data_ptr() + 32 * first, tab_host.ctypes.data + 32 * first,
+                                                        N, conv.in_channels, self.classes, Ho, Wo, st))
+                elif self.classes == 1 and head == "logits":
                     check(lib.sc_head_conv_fwd(C.byref(s), ptr(conv.weight), ptr(conv.bias), ptr(plan.buf[o.name]),
                                                N, conv.in_channels, Ho, Wo, st))
                 else:       # K classes and / or the fused argmax: exactly one of the two outputs
@@ -1200,7 +1209,7 @@ class HyperStarcopUNet(nn.Module):
                                           f"({self.FP16_MAX_ACT:g}) and was clamped; the forward is redone with the adapted scale.  "
                                           f"Forwards between two checks (range_check_every={self.range_check_every}) are not re-examined: "
                                           f"set range_check_every=1 for data of unknown range")
-                        return self._forward_impl(x, x_cst, training, need_grad, _recheck=_recheck + 1, head=head)
+                        return self._forward_impl(x, x_cst, training, need_grad, _recheck=_recheck + 1, head=head, mosaic=mosaic)
                     self._inference_unrepaired += 1
                     warnings.warn(f"HyperStarcopUNet (inference, precision='fp32'): activations still outside the fp16 range after 6 "
                                   f"re-runs with adapted scales ({worst:.4g}); the returned logits carry operands clamped to "
@@ -1868,6 +1877,27 @@ class HyperStarcopUNet(nn.Module):
             raise RuntimeError("HyperStarcopUNet.predict_classes: eval mode only (call .eval() first)")
         plan = self._forward_impl(x, normalizer_consts, False, False, head="classes")
         return plan.classes.clone()
+
+    @torch.no_grad()
+    def predict_classes_into(self, x, mosaic, table, normalizer_consts=None):
+        """``predict_classes`` for the windows of a scene: of batch item i only the core rectangle is kept, written by the head itself
+        (sc_head_conv_fwd_k_mosaic) into ``mosaic``, a uint8 (h, w) device tensor with unit column stride.  ``table`` = (device int32
+        (n, 8) tensor, the same contiguous int32 numpy array on the host, first row): rows first .. first + N - 1 are the
+        ``sc_scene_win`` of the batch -- core y0, y1, x0, x1 inside the window at [2:6], the core's row and column in the mosaic at
+        [6:8] (sentinel2.scene_table).  No logits and no (N, H, W) class tensor exist.  Eval mode only.  Returns ``mosaic``."""
+        if self.training:
+            raise RuntimeError("HyperStarcopUNet.predict_classes_into: eval mode only (call .eval() first)")
+        import numpy as np
+        tab_dev, tab_host, first = table
+        _lib.require_device(mosaic)
+        if mosaic.dtype != torch.uint8 or mosaic.dim() != 2 or mosaic.stride(1) != 1:
+            raise ValueError("predict_classes_into: mosaic must be a uint8 (h, w) tensor with unit column stride")
+        if (tab_dev.dtype != torch.int32 or not tab_dev.is_contiguous() or tab_host.dtype != np.int32 or not tab_host.flags.c_contiguous
+                or tab_dev.dim() != 2 or tuple(tab_dev.shape) != tuple(tab_host.shape) or tab_dev.shape[1] != 8
+                or first < 0 or first + x.shape[0] > tab_dev.shape[0]):
+            raise ValueError("predict_classes_into: table must be (device int32 (n, 8), the same numpy int32 array, first) with first + N <= n")
+        self._forward_impl(x, normalizer_consts, False, False, head="mosaic", mosaic=(mosaic, tab_dev, tab_host, int(first)))
+        return mosaic
 
 
 class _UNetFunction(torch.autograd.Function):
