@@ -1015,6 +1015,49 @@ int sc_pwreg_finalize(const double* part, int nblocks, const float* params, int 
                       float* grad, double* loss_sum, sc_stream stream);
 
 /* ------------------------------------------------------------------------- */
+/* Validation panels (starcop/plot.py plot_batch, starcop/validation.py:137-153): a figure is a canvas of image panels, each one a
+ * source plane (or three) of a batch tensor turned into 8-bit RGB and enlarged by an integer nearest-neighbour factor.  The canvas is
+ * stored as PNG scanlines: canvas_h rows of 1 + 3 * canvas_w bytes, byte 0 of a row is the filter byte 0, RGB triplets follow, so the
+ * buffer goes to zlib as it is.  Every byte of the canvas is written: pixels outside every panel are white (255).
+ *
+ * Per pixel, all arithmetic in float32 (DESIGN.md "Validation panels" has the derivation from matplotlib):
+ *   SC_PANEL_BAND         v = (float)src; if div != 1: v = v / div.  Not finite -> white.  Else t = (v - vmin) / d with
+ *                         d = (float)((double)vmax - (double)vmin), t = 0 if vmax == vmin; xa = t * 256f; index = 0 if xa < 0,
+ *                         255 if xa >= 256, else trunc(xa); colour = viridis[index] (256 x 3 bytes, starcop_amd/data/viridis8.txt).
+ *   SC_PANEL_RGB          per channel c = min(max(v, 0), 1), byte = trunc(c * 255f); a NaN in any channel -> white.
+ *   SC_PANEL_CATEGORICAL  the colour of the LAST of the n_cat entries whose value equals (float)src; no match -> (0, 0, 0).
+ *
+ *   sc_panel_minmax   out[p] = (min, max) over the finite v of panel p's plane when it is flagged autoscale, (0, 1) if it has none;
+ *                     (vmin, vmax) of the descriptor otherwise, so out holds the range every panel is drawn with.  One launch, one
+ *                     work-group per panel, min/max only (no sums): equal inputs give equal bits.
+ *   sc_render_panels  one launch for the whole figure; an autoscale panel takes its range from minmax[p] (may be NULL when no
+ *                     panel is flagged), which the preceding sc_panel_minmax on the same stream left there -- no host
+ *                     synchronisation in between.
+ * The table is given twice (as for sc_scene_gather): on the device for the kernel, on the host for the checks made before the
+ * launch.  SC_ERR_ARG, with nothing launched, for n_panels outside [1, SC_PANEL_MAX], a null pointer, an unknown dtype or kind,
+ * scale < 1, bad dims or stride, autoscale on a panel that is not a BAND, a div that is 0 or not finite, limits that are not
+ * finite, n_cat outside [0, SC_PANEL_MAX_CAT], a destination rectangle that leaves the canvas, or two rectangles that overlap. */
+#define SC_PANEL_MAX 1024
+#define SC_PANEL_MAX_CAT 8
+enum sc_panel_dtype { SC_PANEL_F32 = 0, SC_PANEL_I64 = 1, SC_PANEL_U8 = 2 };
+enum sc_panel_kind { SC_PANEL_BAND = 0, SC_PANEL_RGB = 1, SC_PANEL_CATEGORICAL = 2 };
+typedef struct sc_panel {
+  const void* src[3];                            /* device planes: one (BAND, CATEGORICAL) or three (RGB: r, g, b)  */
+  int64_t row_stride;                            /* elements between rows of a plane (>= W)                         */
+  int32_t dtype, kind;                           /* enum sc_panel_dtype, enum sc_panel_kind                         */
+  int32_t H, W, scale;                           /* source size; the panel covers H*scale x W*scale canvas pixels   */
+  int32_t dst_y, dst_x;                          /* its top-left canvas pixel                                       */
+  int32_t autoscale, n_cat, reserved;
+  float vmin, vmax, div;                         /* BAND limits (ignored when autoscale) and divisor (1 = none)     */
+  float cat_value[SC_PANEL_MAX_CAT];
+  uint8_t cat_rgb[SC_PANEL_MAX_CAT][4];          /* r, g, b, unused                                                 */
+} sc_panel;
+int sc_panel_minmax(const sc_panel* table_dev, const sc_panel* table_host, int n_panels, float* out_minmax_dev /*[n][2]*/,
+                    sc_stream stream);
+int sc_render_panels(const sc_panel* table_dev, const sc_panel* table_host, int n_panels, const float* minmax_dev /*[n][2]*/,
+                     uint8_t* canvas, int canvas_h, int canvas_w, sc_stream stream);
+
+/* ------------------------------------------------------------------------- */
 /* HOST functions (no device involved): decoders of the on-disk sample format -- one tiled GeoTIFF per product per sample,
  * read by rasterio in the reference (starcop/data/dataset.py:66-76, written by save_cog at sampling_dataset.py:332-355).
  *   sc_tiff_lzw_decode : TIFF 6.0 LZW (GDAL's default COG compression); *written = bytes produced (<= n_out)

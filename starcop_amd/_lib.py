@@ -161,6 +161,20 @@ class sc_scene_args(C.Structure):
                 ("scale", C.c_float), ("win", C.c_void_p), ("win_host", C.c_void_p), ("out", C.c_void_p)]
 
 
+PANEL_MAX, PANEL_MAX_CAT = 1024, 8
+PANEL_F32, PANEL_I64, PANEL_U8 = 0, 1, 2                 # enum sc_panel_dtype
+PANEL_BAND, PANEL_RGB, PANEL_CATEGORICAL = 0, 1, 2       # enum sc_panel_kind
+
+
+class sc_panel(C.Structure):
+    """one image panel of a validation figure (include/starcop_hip.h: sc_panel)"""
+    _fields_ = [("src", C.c_void_p * 3), ("row_stride", C.c_int64), ("dtype", C.c_int32), ("kind", C.c_int32),
+                ("H", C.c_int32), ("W", C.c_int32), ("scale", C.c_int32), ("dst_y", C.c_int32), ("dst_x", C.c_int32),
+                ("autoscale", C.c_int32), ("n_cat", C.c_int32), ("reserved", C.c_int32),
+                ("vmin", C.c_float), ("vmax", C.c_float), ("div", C.c_float),
+                ("cat_value", C.c_float * PANEL_MAX_CAT), ("cat_rgb", (C.c_uint8 * 4) * PANEL_MAX_CAT)]
+
+
 _vp, _i, _f, _d, _sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/starcop_hip.h declares
@@ -298,6 +312,8 @@ SIGNATURES = {
     "sc_pwreg_sweep_blocks": (_i, [_i, _i, _i]),
     "sc_pwreg_train_sweep": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _vp, _vp]),
     "sc_pwreg_finalize": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _d, _vp, _vp, _vp]),
+    "sc_panel_minmax": (_i, [_vp, C.POINTER(sc_panel), _i, _vp, _vp]),
+    "sc_render_panels": (_i, [_vp, C.POINTER(sc_panel), _i, _vp, _vp, _i, _i, _vp]),
     "sc_tiff_lzw_decode": (_i, [_vp, _sz, _vp, _sz, C.POINTER(C.c_size_t)]),
     "sc_tiff_unpredict": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp]),
 }

@@ -58,6 +58,7 @@ class _BandThresholdBaseline(torch.nn.Module):
     def __init__(self, input_products: List[str], band_name: str, threshold: float, use_normalisation: bool,
                  use_morphological_ops: bool):
         super().__init__()
+        self.input_products = list(input_products)
         self.band_baseline = input_products.index(band_name)
         self.baseline_threshold = threshold
         self.element_stronger = torch.nn.Parameter(torch.from_numpy(ELEMENT_STRONGER.copy()), requires_grad=False)

@@ -254,6 +254,28 @@ def write_tiff(path, array, blocksize: int = 128, compress: Optional[str] = "def
             f.write(b + (b"\0" if len(b) & 1 else b""))
 
 
+# ------------------------------------------------------------------------------------------------ PNG
+def write_png(path, scanlines, width: int, height: int, text: Optional[str] = None):
+    """8-bit truecolour PNG from finished scanlines: ``height`` rows of ``1 + 3 * width`` bytes, each a filter byte 0 followed by
+    RGB triplets (what ``sc_render_panels`` leaves in its canvas), so the buffer goes to zlib without a repack.  ``text`` is
+    stored in one tEXt chunk with the keyword ``Comment``; ``plot.Panels.save`` puts the panel names and ranges there as JSON."""
+    data = memoryview(np.ascontiguousarray(np.asarray(scanlines, dtype=np.uint8))).cast("B")
+    width, height = int(width), int(height)
+    if width < 1 or height < 1 or len(data) != height * (1 + 3 * width):
+        raise ValueError(f"write_png: {len(data)} bytes are not {height} scanlines of 1 + 3 * {width} bytes")
+    if any(data[0::1 + 3 * width]):
+        raise ValueError("write_png: every scanline must start with the filter byte 0")
+
+    def chunk(kind: bytes, body: bytes) -> bytes:
+        return struct.pack(">I", len(body)) + kind + body + struct.pack(">I", zlib.crc32(kind + body) & 0xFFFFFFFF)
+    out = [b"\x89PNG\r\n\x1a\n", chunk(b"IHDR", struct.pack(">IIBBBBB", width, height, 8, 2, 0, 0, 0))]
+    if text is not None:
+        out.append(chunk(b"tEXt", b"Comment\0" + text.encode("latin-1")))
+    out += [chunk(b"IDAT", zlib.compress(data)), chunk(b"IEND", b"")]
+    with open(path, "wb") as f:
+        f.write(b"".join(out))
+
+
 # ------------------------------------------------------------------------------------------------ ENVI
 _ENVI_DTYPES = {1: "u1", 2: "i2", 3: "i4", 4: "f4", 5: "f8", 12: "u2", 13: "u4", 14: "i8", 15: "u8"}
 

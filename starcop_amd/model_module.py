@@ -216,7 +216,8 @@ class ModelModule(_Base):
         self.settings_wandb = settings.wandb if "wandb" in settings else None
         self.normalizer = DataNormalizer(settings)
         self.num_classes = self.settings_model.num_classes
-        self.num_channels = len(settings.dataset.input_products)
+        self.input_products = list(settings.dataset.input_products)
+        self.num_channels = len(self.input_products)
         architecture = self.settings_model.model_type
         self.network = configure_architecture(architecture, self.num_channels, self.num_classes, self.settings_model)
         self.lr = self.settings_model.lr

@@ -7,12 +7,13 @@ What is different underneath: the reference updates 1 + T ``torchmetrics.Confusi
 thresholds by default, each a threshold pass + a bincount, and for the morphological baselines two kornia unfold passes)
 and reads ~10 scalars back per tile.  Here the T thresholded (and opened) masks are counted against the label in ONE pass
 over the prediction (``sc_threshold_confusion``), the per-tile matrices stay on the device, and there is a single
-read-back at the end of the loop.  Plotting (``products_plot``) is outside the hot path and is skipped with a warning.
+read-back at the end of the loop.  With ``products_plot`` each tile's figure is drawn on the device (``plot.render_batch``: the
+image panels of ``plot_batch``, no text) and written as ``images/<id>.png``; the metrics do not depend on it.
 """
+import importlib.util
 import json
 import os
 import tempfile
-import warnings
 from numbers import Number
 from typing import Dict, List, Optional, Tuple
 
@@ -24,6 +25,7 @@ from . import _lib, metrics as starcopmetrics
 from ._lib import check, ptr, stream
 
 MAX_T = 32          # thresholds per sc_threshold_confusion launch
+RGB_AVIRIS = ["TOA_AVIRIS_640nm", "TOA_AVIRIS_550nm", "TOA_AVIRIS_460nm"]
 
 
 def to_device(x, device):
@@ -75,8 +77,24 @@ def run_validation(model, dataloader, products_plot: Optional[List[str]] = None,
         thresholds = [0, 1e-3, 1e-2] + np.arange(0.5, .96, .05).tolist() + [.99, .995, .999]
     thresholds = np.sort(thresholds)[-1::-1]                     # high to low (validation.py:41-42)
     T = len(thresholds)
+    products_plot = list(products_plot) if products_plot else []
+    input_products = None
     if products_plot:
-        warnings.warn("run_validation: plotting (products_plot) is not part of the HIP build; skipped")
+        dataset = getattr(dataloader, "dataset", None)
+        if hasattr(dataset, "input_products"):
+            input_products = dataset.input_products
+            # products to plot that the dataset does not deliver yet (validation.py:52-64)
+            if "mag1c" in products_plot and "mag1c" not in input_products:
+                print("Adding mag1c as extra products to dataset for plotting purposes")
+                dataset.add_extra_products(["mag1c"])
+            if "rgb_aviris" in products_plot and not all(b in input_products for b in RGB_AVIRIS):
+                print("RGB aviris not in input. Adding to dataset for plotting purposes")
+                dataset.add_rgb_aviris = True
+        elif hasattr(model, "input_products"):
+            input_products = model.input_products
+        else:
+            raise ValueError("run_validation: products_plot needs the names of the input channels, and neither "
+                             "dataloader.dataset.input_products nor model.input_products exists")
     model.eval()
     device = model.device
 
@@ -114,6 +132,8 @@ def run_validation(model, dataloader, products_plot: Optional[List[str]] = None,
         scalars.append(torch.stack([y_long[0, 0].sum(), plume_data["has_plume"][0].long().reshape(()),
                                     plume_data["pred_classification"][0, 0].long(), pb[0, 0].sum()]))
         ids.append(plume_data["id"][0])
+        if products_plot:
+            _plot_tile(plume_data, input_products, products_plot, show_plots, path_save_results, skip_saving_plots)
 
     if len(ids) == 0:
         raise ValueError("run_validation: empty dataloader")
@@ -182,6 +202,38 @@ def run_validation(model, dataloader, products_plot: Optional[List[str]] = None,
         with open(os.path.join(path_save_results, "results_agg.json"), "w") as fh:
             json.dump(metrics, fh, cls=CustomJSONEncoder)
     return out_data, metrics
+
+
+def _can_show() -> bool:
+    """matplotlib is importable and its backend has a window (or a notebook cell) to show a figure in"""
+    if importlib.util.find_spec("matplotlib") is None:
+        return False
+    import matplotlib
+    try:
+        from matplotlib.backends import BackendFilter, backend_registry
+        headless = backend_registry.list_builtin(BackendFilter.NON_INTERACTIVE)
+    except ImportError:                                      # matplotlib < 3.9
+        headless = ["agg", "cairo", "pdf", "pgf", "ps", "svg", "template"]
+    return matplotlib.get_backend().lower() not in headless
+
+
+def _plot_tile(plume_data, input_products, products_plot, show_plots, path_save_results, skip_saving_plots):
+    """validation.py:137-153: the tile's figure, shown when matplotlib is there to show it and saved as images/<id>.png"""
+    from . import plot as starcoplot
+    panels = starcoplot.render_batch(plume_data, input_products, products_plot)
+    if show_plots and _can_show():
+        import matplotlib.pyplot as plt
+        fig, ax = plt.subplots(1, len(products_plot), figsize=(4 * len(products_plot), 4), tight_layout=True, squeeze=False)
+        for k, name in enumerate(products_plot):
+            ax[0, k].imshow(panels.panel(0, k), interpolation="nearest")
+            ax[0, k].set_title(name)
+        plt.show()
+        plt.close(fig)
+    if path_save_results is not None:
+        path_save_images = os.path.join(path_save_results, "images")
+        os.makedirs(path_save_images, exist_ok=True)
+        if not skip_saving_plots:
+            panels.save(os.path.join(path_save_images, f"{plume_data['id'][0]}.png"))
 
 
 class CustomJSONEncoder(json.JSONEncoder):
