@@ -1057,6 +1057,47 @@ int sc_panel_minmax(const sc_panel* table_dev, const sc_panel* table_host, int n
 int sc_render_panels(const sc_panel* table_dev, const sc_panel* table_host, int n_panels, const float* minmax_dev /*[n][2]*/,
                      uint8_t* canvas, int canvas_h, int canvas_w, sc_stream stream);
 
+/* Per-component statistics of a label image: the plume catalogue (starcop_amd/plumes.py).  Component k of image n is the set of
+ * pixels of labels[n] with value k, 1 <= k <= min(counts[n], M); 0 is background.  Nothing assumes that a value is connected or
+ * that the image comes from sc_connected_components, and values outside [0, min(counts[n], M)] are ignored and never index
+ * memory.  counts is a DEVICE array; M is the row capacity per image the caller chose (>= the largest count it wants reported).
+ * Row n*M + k-1 of every per-component column, and entry (n*M + k-1)*P + q of every per-plane column, receive:
+ *   area (int64)   row_min row_max col_min col_max (int32, inclusive)   sum_row sum_col (int64)
+ *   first_pixel (int64, the smallest raster index r*W + c)   n_other (int64, pixels with other != 0; 0 without `other`)
+ *   per plane q < P, over the FINITE values of the component only: n_finite (int64), sum (fp64), max, min (float32), argmax
+ *   (int64, the smallest raster index whose value compares equal to max); with no finite value: 0, 0, NaN, NaN, -1.
+ * A value in [1, counts[n]] that no pixel carries gives area 0, a zero box, first_pixel -1 and the "no finite value" plane
+ * entries.  Rows at or above counts[n] are zero-filled in every column.
+ * Plane q of image n is the dense H x W float32 block at plane[q] + n*plane_stride[q] (elements), `other` likewise in bytes:
+ * channel c of an (N, C, H, W) tensor is read in place.  N <= 65535, H*W < 2^31, 0 <= P <= SC_CSTATS_MAX_PLANES, M >= 0 (M = 0:
+ * nothing to write, nothing launched); SC_ERR_ARG, before any launch, for bad dims, a null pointer, a plane stride below H*W in
+ * a batch or a workspace that is too small.
+ * Integer atomics for the bounding boxes only; the fp64 sums are added in an order that depends on the label image alone (per
+ * lane in raster order along the component's box, one fixed butterfly, then the row bands of the box in order), so repeated
+ * calls give identical bits and an image gives the same bits alone and inside any batch.  5 launches per call; the work is
+ * proportional to the sum of the areas of the bounding boxes.
+ * work: sc_component_stats_workspace_bytes(N, H, W, M, P) bytes (4 bytes and, at P planes, 40 + 32 P bytes per row, the latter
+ * also per 4096 pixels of an image).                                                                                          */
+#define SC_CSTATS_MAX_PLANES 8
+typedef struct sc_cstats_args {
+  const int32_t* labels;                          /* [N][H][W] device                                              */
+  const int32_t* counts;                          /* [N] device                                                    */
+  int32_t N, H, W, M, P, reserved;
+  const float* plane[SC_CSTATS_MAX_PLANES];       /* element (0, 0) of image 0 of every plane                      */
+  int64_t plane_stride[SC_CSTATS_MAX_PLANES];     /* elements between images                                       */
+  const uint8_t* other;                           /* may be NULL                                                   */
+  int64_t other_stride;                           /* bytes between images                                          */
+  int64_t* area;                                  /* [N][M] columns ...                                            */
+  int32_t *row_min, *row_max, *col_min, *col_max;
+  int64_t *sum_row, *sum_col, *first_pixel, *n_other;
+  int64_t* n_finite;                              /* [N][M][P] columns (may be NULL when P = 0) ...                */
+  double* sum;
+  float *max, *min;
+  int64_t* argmax;
+} sc_cstats_args;
+size_t sc_component_stats_workspace_bytes(int N, int H, int W, int M, int P);
+int sc_component_stats(const sc_cstats_args* a, void* work, size_t work_bytes, sc_stream stream);
+
 /* ------------------------------------------------------------------------- */
 /* HOST functions (no device involved): decoders of the on-disk sample format -- one tiled GeoTIFF per product per sample,
  * read by rasterio in the reference (starcop/data/dataset.py:66-76, written by save_cog at sampling_dataset.py:332-355).

@@ -175,6 +175,21 @@ class sc_panel(C.Structure):
                 ("cat_value", C.c_float * PANEL_MAX_CAT), ("cat_rgb", (C.c_uint8 * 4) * PANEL_MAX_CAT)]
 
 
+CSTATS_MAX_PLANES = 8
+
+
+class sc_cstats_args(C.Structure):
+    """per-component statistics operands (include/starcop_hip.h: sc_cstats_args)"""
+    _fields_ = [("labels", C.c_void_p), ("counts", C.c_void_p),
+                ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("M", C.c_int32), ("P", C.c_int32), ("reserved", C.c_int32),
+                ("plane", C.c_void_p * CSTATS_MAX_PLANES), ("plane_stride", C.c_int64 * CSTATS_MAX_PLANES),
+                ("other", C.c_void_p), ("other_stride", C.c_int64),
+                ("area", C.c_void_p), ("row_min", C.c_void_p), ("row_max", C.c_void_p), ("col_min", C.c_void_p),
+                ("col_max", C.c_void_p), ("sum_row", C.c_void_p), ("sum_col", C.c_void_p), ("first_pixel", C.c_void_p),
+                ("n_other", C.c_void_p), ("n_finite", C.c_void_p), ("sum", C.c_void_p), ("max", C.c_void_p), ("min", C.c_void_p),
+                ("argmax", C.c_void_p)]
+
+
 _vp, _i, _f, _d, _sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/starcop_hip.h declares
@@ -314,6 +329,8 @@ SIGNATURES = {
     "sc_pwreg_finalize": (_i, [_vp, _i, _vp, _i, _i, _i, _i, _d, _vp, _vp, _vp]),
     "sc_panel_minmax": (_i, [_vp, C.POINTER(sc_panel), _i, _vp, _vp]),
     "sc_render_panels": (_i, [_vp, C.POINTER(sc_panel), _i, _vp, _vp, _i, _i, _vp]),
+    "sc_component_stats_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "sc_component_stats": (_i, [C.POINTER(sc_cstats_args), _vp, _sz, _vp]),
     "sc_tiff_lzw_decode": (_i, [_vp, _sz, _vp, _sz, C.POINTER(C.c_size_t)]),
     "sc_tiff_unpredict": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp]),
 }

@@ -228,7 +228,7 @@ def _emit_predict_parts(model, sub, rgb, ratio, template, fill_value, column_ste
 @torch.no_grad()
 def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_lerp_alpha=1e-4, tile=None, halo=RECEPTIVE_HALO,
                          ratio_bands=None, distributed=None, group=None, rows=None, threads=8, strips=True, georeferenced=False,
-                         out_folder=None, geotransform=None, overwrite=False):
+                         out_folder=None, geotransform=None, overwrite=False, plumes=False):
     """The notebook path of the reference end to end FROM THE FILE (notebooks/inference_on_raw_EMIT_nc_file.ipynb cells 8-19:
     ``EMITImage(path)`` -> ``mag1c_emit`` -> RGB bands -> rescale -> ``model`` -> threshold): opens the EMIT L1B radiance granule
     (NetCDF-4) with :mod:`starcop_amd.hdf5_reader`, reads ONLY what the pipeline touches -- the contiguous band slice inside
@@ -244,7 +244,12 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
     value), ``predbinary.tif`` (uint8) and ``rgb.tif`` (3 bands, the RGB planes of the network input), with band descriptions
     and the georeferencing of :func:`starcop_amd.ortho.emit_geo_tags` from the file's root attributes ``geotransform`` /
     ``spatial_ref`` -- ``geotransform=`` overrides the attribute; with neither, the files carry no georeferencing and one warning
-    is issued.  Existing files are skipped unless ``overwrite=True``; the paths written are returned under ``files``."""
+    is issued.  Existing files are skipped unless ``overwrite=True``; the paths written are returned under ``files``.
+
+    ``plumes=True`` adds ``plumes``, the :func:`starcop_amd.plumes.plume_table` of ``pred_binary`` with ``mf`` as mag1c and
+    ``prediction`` as probability -- on the orthorectified products (with ``x`` / ``y`` from the geotransform, when there is one)
+    if ``georeferenced=True``, on the sensor-geometry ones otherwise; pixels that carry the fill value or are not finite do not
+    count.  With ``out_folder`` the table is also written as ``plumes.csv`` (same ``overwrite`` rule) and listed in ``files``."""
     from .hdf5_reader import H5File
     if out_folder is not None:
         if str(out_folder).startswith("gs://"):
@@ -271,7 +276,7 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
         rgb_h = np.stack([plane(i) for i in nearest_bands(wl)])
         ratio_h = [plane(i) for i in nearest_bands(wl, ratio_bands)] if ratio_bands is not None else None
         glt = (f["location/glt_x"].read(), f["location/glt_y"].read()) if ("location/glt_x" in f and "location/glt_y" in f) else (None, None)
-        root = f.attrs("/") if out_folder is not None else {}
+        root = f.attrs("/") if out_folder is not None or (plumes and georeferenced) else {}
     if georeferenced and glt[0] is None:
         raise ValueError(f"{nc_path}: no location/glt_x, location/glt_y to orthorectify with")
 
@@ -284,10 +289,32 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
     if georeferenced:
         out = georeference_products(out, glt[0], glt[1], fill)
     out.update(wavelengths=wl[b0:b1], fwhm=fwhm[b0:b1], glt_x=glt[0], glt_y=glt[1], fill_value=fill)
+    gt = geotransform if geotransform is not None else root.get("geotransform")
+    if plumes:
+        out["plumes"] = _emit_plume_table(out, fill, gt if georeferenced else None)
     if out_folder is not None:
-        gt = geotransform if geotransform is not None else root.get("geotransform")
         out["files"] = _write_emit_products(out, str(out_folder), fill, gt, root.get("spatial_ref"), overwrite)
+        if plumes:
+            import os
+            from .plumes import write_plumes
+            path = os.path.join(str(out_folder), "plumes.csv")
+            if overwrite or not os.path.exists(path):
+                os.makedirs(str(out_folder), exist_ok=True)
+                out["files"].append(write_plumes(out["plumes"], path))
     return out
+
+
+def _emit_plume_table(out, fill, geotransform):
+    """plume table of an EMIT prediction dict: no-data pixels (the fill value, or not finite) of ``mf`` / ``prediction`` become
+    NaN, which the per-component statistics leave out.  In sensor geometry the network output covers the swath cropped to
+    multiples of 32 (its top-left part): ``mf`` is cropped to it"""
+    from .plumes import plume_table
+    nan = torch.tensor(float("nan"), device=out["mf"].device)
+    h, w = out["pred_binary"].shape
+    mf = out["mf"][:h, :w]
+    mf = torch.where(mf == fill, nan, mf)
+    prob = torch.where(out["prediction"] == fill, nan, out["prediction"])
+    return plume_table(out["pred_binary"], mag1c=mf, prob=prob, geotransform=geotransform)
 
 
 EMIT_PRODUCT_FILES = {"mag1c.tif": ("mf", ["CH4 Absorption (ppm x m)"]), "albedo.tif": ("albedo", ["Albedo"]),
