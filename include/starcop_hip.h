@@ -749,6 +749,58 @@ typedef struct sc_srf_args {
 } sc_srf_args;
 int sc_srf_bands(const sc_srf_args* a, sc_stream stream);
 
+/* Anti-aliased downscaling of the simulated bands to the sensor's pixel size: the read.resize(..., anti_aliasing=True,
+ * anti_aliasing_sigma=sigma_bands) that ends starcop/data/aviris.py:262-338 (transform_to_srf), which wraps
+ * skimage.transform.resize(order=1, anti_aliasing=True) = per plane, scipy.ndimage.gaussian_filter followed by scipy.ndimage.zoom(order=1,
+ * grid_mode=True).  That operator is separable and linear in (x, cval), so it is given here as tap tables per axis:
+ *   sc_resize_aa : tmp[p][j][s] = f32( sum_k wy[j][k] * x_p[start_y[j] + k][s] + wcy[j] * cval )        (vertical pass, first)
+ *                  out[p][j][i] = f32( sum_k wx[i][k] * tmp[p][j][start_x[i] + k] + wcx[i] * cval )      (horizontal pass)
+ *                  each product in fp64 (float32 value promoted exactly), added in ascending tap order onto a +0.0 seed, the cval term
+ *                  added last, no fused multiply-add, rounded once to float32 at the end of each pass -- bit-equal to a numpy loop over
+ *                  the taps, identical between calls and between a plane alone and inside a batch.  No atomics.
+ * Input plane p, element (l, s) = x[p*plane_stride + l*line_stride + s*sample_stride] (elements, >= 0): a permuted view or a line range
+ * of a larger buffer is read in place.  Output plane p, line j starts at out + p*out_plane_stride + j*out_line_stride (samples dense).
+ * An axis (sc_resize_axis) carries n_tables tap tables of o outputs: start[t][o] (first input sample of the window), w[t][o][T] (fp64,
+ * rows zero-padded to the common row length T) and wc[t][o] (the weight that goes to cval); taps[t] <= T is the number of leading
+ * entries of table t's rows that are used (NULL: T for every table).  Plane p uses table table_y[p] / table_x[p], so planes with equal
+ * sigma share one.  start, taps and the plane -> table maps are given twice: on the device for the kernels, on the host for the checks
+ * that run before anything is launched.  Downscaling only (o <= n; o == n is a blur, or the identity).
+ * SC_ERR_ARG for bad dims, an output larger than the input, P outside [1, 65535], T outside [1, 256], a tap window that leaves [0, n),
+ * a table index out of range, negative strides, null pointers or a workspace below sc_resize_workspace_bytes(P, oh, W) bytes (the
+ * float32 intermediate).  Two launches per call, all planes in each.                                                            */
+typedef struct sc_resize_axis {
+  int32_t n, o;                /* input and output length of the axis, o <= n           */
+  int32_t n_tables;
+  int32_t T;                   /* row length of w, 1..256                               */
+  const int32_t* start;        /* [n_tables][o] device                                  */
+  const int32_t* taps;         /* [n_tables] device, or NULL                            */
+  const double* w;             /* [n_tables][o][T] device                               */
+  const double* wc;            /* [n_tables][o] device                                  */
+  const int32_t* start_host;   /* the same start / taps on the host                     */
+  const int32_t* taps_host;
+} sc_resize_axis;
+typedef struct sc_resize_args {
+  const float* x;              /* element (0, 0) of plane 0, device                     */
+  int64_t plane_stride;        /* elements                                              */
+  int64_t line_stride;
+  int64_t sample_stride;
+  int32_t P;                   /* planes                                                */
+  float cval;
+  float* out;                  /* float32, device                                       */
+  int64_t out_plane_stride;    /* elements between output planes                        */
+  int64_t out_line_stride;     /* elements between output lines                         */
+  sc_resize_axis y;            /* lines:   n = H, o = oh                                */
+  sc_resize_axis xs;           /* samples: n = W, o = ow                                */
+  const int32_t* table_y;      /* [P] device: table of every plane, per axis            */
+  const int32_t* table_x;
+  const int32_t* table_y_host; /* the same on the host                                  */
+  const int32_t* table_x_host;
+  void* work;                  /* device                                                */
+  size_t work_bytes;
+} sc_resize_args;
+size_t sc_resize_workspace_bytes(int P, int oh, int W);
+int sc_resize_aa(const sc_resize_args* a, sc_stream stream);
+
 /* Window statistics of a mag1c flight line: the table scripts/preprocessing/stats_mag1c.py:24-70 writes (512 x 512 windows at
  * overlap 256) and starcop/data/sampling_dataset.py:112-179, 408-439 samples the no-plume windows from.
  *   sc_window_stats : for each of n_win windows (row_off, col_off, height, width; any sizes, any overlap, duplicates allowed) of one

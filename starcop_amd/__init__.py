@@ -13,7 +13,8 @@ Public surface (mirrors the reference):
     ratio_2c_match_c_from_sums_outlier / weight_mag1c
   starcop_amd.mask_creation.proposed_mask / connected_components / write_label_masks (the labelbinary target)
   starcop_amd.aviris.load_srf_wv3 / load_srf_s2 / transform_to_srf / transform_to_worldview_3 / transform_to_sentinel_2;
-    starcop_amd.pipeline.aviris_as_sensor (the simulated WV3 / S2 bands of an AVIRIS-NG flight line)
+    starcop_amd.pipeline.aviris_as_sensor (the simulated WV3 / S2 bands of an AVIRIS-NG flight line);
+    starcop_amd.resample.resize_antialiased / axis_taps / output_shape_for (those bands at the sensor's pixel size)
   starcop_amd.sampling.window_stats / stats_mag1c (mag1c statistics of every 512 x 512 window of a flight line) /
     mag1c_stats_dataframe / windows_intersect / select_non_overlapping / sampling_no_plumes (which windows become samples)
   starcop_amd.ortho.georeference / emit_geo_tags (orthorectification through a geometry look-up table); starcop_amd.mag1c.mag1c_emit

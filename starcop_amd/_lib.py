@@ -108,6 +108,23 @@ class sc_srf_args(C.Structure):
                 ("has_fill", C.c_int32), ("fill", C.c_float)]
 
 
+class sc_resize_axis(C.Structure):
+    """tap tables of one axis of the anti-aliased resize (include/starcop_hip.h: sc_resize_axis)"""
+    _fields_ = [("n", C.c_int32), ("o", C.c_int32), ("n_tables", C.c_int32), ("T", C.c_int32),
+                ("start", C.c_void_p), ("taps", C.c_void_p), ("w", C.c_void_p), ("wc", C.c_void_p),
+                ("start_host", C.c_void_p), ("taps_host", C.c_void_p)]
+
+
+class sc_resize_args(C.Structure):
+    """anti-aliased resize operands (include/starcop_hip.h: sc_resize_args)"""
+    _fields_ = [("x", C.c_void_p), ("plane_stride", C.c_int64), ("line_stride", C.c_int64), ("sample_stride", C.c_int64),
+                ("P", C.c_int32), ("cval", C.c_float),
+                ("out", C.c_void_p), ("out_plane_stride", C.c_int64), ("out_line_stride", C.c_int64),
+                ("y", sc_resize_axis), ("xs", sc_resize_axis),
+                ("table_y", C.c_void_p), ("table_x", C.c_void_p), ("table_y_host", C.c_void_p), ("table_x_host", C.c_void_p),
+                ("work", C.c_void_p), ("work_bytes", C.c_size_t)]
+
+
 class sc_winstats_args(C.Structure):
     """window-statistics operands (include/starcop_hip.h: sc_winstats_args)"""
     _fields_ = [("x", C.c_void_p), ("row_stride", C.c_int64), ("H", C.c_int32), ("W", C.c_int32),
@@ -267,6 +284,8 @@ SIGNATURES = {
     "sc_mlr_ratio": (_i, [C.POINTER(sc_mlr_args), _vp, _vp, _i, _i, _vp, _vp, _sz, _vp]),
     "sc_label_workspace_bytes": (_sz, [_i, _i, _i]),
     "sc_srf_bands": (_i, [C.POINTER(sc_srf_args), _vp]),
+    "sc_resize_workspace_bytes": (_sz, [_i, _i, _i]),
+    "sc_resize_aa": (_i, [C.POINTER(sc_resize_args), _vp]),
     "sc_window_stats_workspace_bytes": (_sz, [_i]),
     "sc_window_stats": (_i, [C.POINTER(sc_winstats_args), _vp, _sz, _vp]),
     "sc_glt_ortho": (_i, [C.POINTER(sc_ortho_args), _vp]),

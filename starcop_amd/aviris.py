@@ -4,8 +4,9 @@ Mirrors the reference's starcop/data/aviris.py:155-331 (load_srf_s2, load_srf_wv
 transform_to_sentinel_2, transform_to_srf): each simulated band is the spectral response function (SRF) of the sensor band
 resampled to the nearest AVIRIS band, normalised to sum one, applied as a float64 weighted sum over those AVIRIS bands.
 The weights are built on the host (:func:`srf_weights`, the reference's pandas arithmetic); the sums run in libstarcop_hip.so
-(include/starcop_hip.h: sc_srf_bands), all output bands in one pass over the cube.  The file-to-file driver is
-``pipeline.aviris_as_sensor``.
+(include/starcop_hip.h: sc_srf_bands), all output bands in one pass over the cube.  With ``resolution_dst`` and ``resolution_src``
+the bands are then blurred and resampled to the sensor's pixel size (:mod:`starcop_amd.resample`, sc_resize_aa), the reference's
+``read.resize(..., anti_aliasing=True)``.  The file-to-file driver is ``pipeline.aviris_as_sensor``.
 """
 import numpy as np
 import pandas as pd
@@ -166,16 +167,46 @@ class SrfPlan:
         return out
 
 
+def _resample_shape(who, shape, resolution_dst, resolution_src):
+    """None when nothing is to be resampled, else the (oh, ow) of the resampled planes.  Host only: raises before any device use."""
+    if resolution_dst is None:
+        return None
+    if resolution_src is None:
+        raise NotImplementedError(f"{who}: a tensor carries no pixel size (the reference reads aviris.res); pass resolution_src to "
+                                  "resample to resolution_dst, or resolution_dst=None for the AVIRIS grid")
+    from . import resample
+    out_shape = resample.output_shape_for(shape, resolution_src, resolution_dst)
+    if out_shape == tuple(int(v) for v in shape[-2:]):
+        return None
+    if out_shape[0] > shape[-2] or out_shape[1] > shape[-1]:
+        raise ValueError(f"{who}: resolution_dst {resolution_dst} is finer than resolution_src {resolution_src}; only downscaling is "
+                         "supported")
+    return out_shape
+
+
 def transform_to_srf(aviris, bands, srf, resolution_dst=10, bands_nanometers_aviris=None, fill_value_default=0., sigma_bands=None,
-                     verbose=False):
-    """aviris.py:262-331 on the GPU: ``aviris`` is a (C, H, W) float32 device tensor with any strides (``bip.permute(2, 0, 1)`` is
-    read in place) or numpy array; returns the (len(bands), H, W) float32 simulated bands as a device tensor (numpy for numpy).
+                     verbose=False, resolution_src=None, mode="constant"):
+    """aviris.py:262-338 on the GPU: ``aviris`` is a (C, H, W) float32 device tensor with any strides (``bip.permute(2, 0, 1)`` is
+    read in place) or numpy array; returns the (len(bands), oh, ow) float32 simulated bands as a device tensor (numpy for numpy).
     Pixels holding ``fill_value_default`` in any band of a support become ``fill_value_default`` (None: nothing is masked).
-    ``bands_nanometers_aviris`` (the C band centres) is required; resampling to ``resolution_dst`` is not implemented, pass None."""
-    if resolution_dst is not None:
-        raise NotImplementedError("transform_to_srf: resampling to resolution_dst is not implemented; pass resolution_dst=None")
+    ``bands_nanometers_aviris`` (the C band centres) is required.  ``resolution_dst=None`` keeps the AVIRIS grid.  Otherwise
+    ``resolution_src`` (the pixel size of ``aviris``, a number or (y, x); a tensor carries no ``res``) is required and the spectral
+    result is resampled as the reference's ``read.resize(..., anti_aliasing=True, anti_aliasing_sigma=sigma_bands)`` does
+    (:func:`starcop_amd.resample.resize_antialiased`): a Gaussian of ``sigma_bands`` pixels per band (None: (scale - 1) / 2), then a
+    bilinear resample to ``round(n * resolution_src / resolution_dst)`` pixels per axis, border ``mode`` with ``cval =
+    fill_value_default`` (0 for None).  Fill pixels are not masked there: the reference blurs them into their neighbours too.  Equal
+    input and output shapes return the spectral result."""
+    out_shape = _resample_shape("transform_to_srf", aviris.shape, resolution_dst, resolution_src)
     if bands_nanometers_aviris is None:
         raise ValueError("transform_to_srf: bands_nanometers_aviris is required (a tensor carries no band descriptions)")
+    if out_shape is not None:
+        from . import resample
+        if mode not in resample.MODES:
+            raise ValueError(f"transform_to_srf: border mode '{mode}', expected one of {resample.MODES}")
+        if sigma_bands is not None:
+            sigma_bands = np.asarray(sigma_bands, dtype=np.float64)
+            if sigma_bands.shape != (len(bands),) or not np.all(sigma_bands >= 0):
+                raise ValueError(f"transform_to_srf: sigma_bands must hold one non-negative sigma per band, got {sigma_bands}")
     host = isinstance(aviris, np.ndarray)
     x = aviris
     if host:
@@ -193,13 +224,20 @@ def transform_to_srf(aviris, bands, srf, resolution_dst=10, bands_nanometers_avi
         print(f"transform_to_srf: {len(bands)} bands from {len(band)} AVIRIS band weights")
     out = torch.empty((len(bands),) + tuple(x.shape[1:]), dtype=torch.float32, device=x.device)
     SrfPlan(ptrs, band, w, x.device).run(x.permute(1, 2, 0), out, fill_value_default)
+    if out_shape is not None:
+        out = resample.resize_antialiased(out, out_shape, sigma=sigma_bands, mode=mode,
+                                          cval=0.0 if fill_value_default is None else fill_value_default)
     return out.cpu().numpy() if host else out
 
 
-def transform_to_worldview_3(aviris, bands_wv3, resolution_dst=10, bands_nanometers_aviris=None, fill_value_default=0., verbose=False):
-    """aviris.py:224-234: the WV3 SWIR bands ``bands_wv3`` (e.g. ["SWIR1", ...]) with the cached SRF (load_srf_wv3)"""
+def transform_to_worldview_3(aviris, bands_wv3, resolution_dst=10, bands_nanometers_aviris=None, fill_value_default=0., verbose=False,
+                             resolution_src=None):
+    """aviris.py:224-234: the WV3 SWIR bands ``bands_wv3`` (e.g. ["SWIR1", ...]) with the cached SRF (load_srf_wv3); resampled with
+    the default anti-aliasing sigma, as the reference does (sigma_bands=None)"""
+    _resample_shape("transform_to_worldview_3", aviris.shape, resolution_dst, resolution_src)
     return transform_to_srf(aviris, bands_wv3, load_srf_wv3(), resolution_dst=resolution_dst,
-                            bands_nanometers_aviris=bands_nanometers_aviris, fill_value_default=fill_value_default, verbose=verbose)
+                            bands_nanometers_aviris=bands_nanometers_aviris, fill_value_default=fill_value_default, verbose=verbose,
+                            resolution_src=resolution_src)
 
 
 def sentinel_2_srf(sensor="S2A"):
@@ -210,9 +248,18 @@ def sentinel_2_srf(sensor="S2A"):
     return srf
 
 
+def sentinel_2_sigmas(bands_s2, resolution_src):
+    """aviris.py:248-254: the anti-aliasing sigma of every band, ``max((band GSD / max(resolution_src) - 1) / 2, 0)`` AVIRIS pixels"""
+    res = max(abs(float(v)) for v in np.atleast_1d(resolution_src))
+    return np.array([max((BANDS_S2_RESOLUTION[b] / res - 1) / 2, 0) for b in bands_s2])
+
+
 def transform_to_sentinel_2(aviris, bands_s2, resolution_dst=10, sensor="S2A", bands_nanometers_aviris=None, fill_value_default=0.,
-                            verbose=False):
-    """aviris.py:237-259: the S2A or S2B bands ``bands_s2`` (e.g. ["B8A", "B11"]) with the cached joint SRF (load_srf_s2); the
-    anti-aliasing sigmas of the reference only matter for the resampling, which is not implemented"""
+                            verbose=False, resolution_src=None):
+    """aviris.py:237-259: the S2A or S2B bands ``bands_s2`` (e.g. ["B8A", "B11"]) with the cached joint SRF (load_srf_s2); each band is
+    blurred with the sigma of its own ground sampling distance (:func:`sentinel_2_sigmas`) before the resample to ``resolution_dst``"""
+    _resample_shape("transform_to_sentinel_2", aviris.shape, resolution_dst, resolution_src)
+    sigma_bands = sentinel_2_sigmas(bands_s2, resolution_src) if resolution_dst is not None else None
     return transform_to_srf(aviris, bands_s2, sentinel_2_srf(sensor), resolution_dst=resolution_dst,
-                            bands_nanometers_aviris=bands_nanometers_aviris, fill_value_default=fill_value_default, verbose=verbose)
+                            bands_nanometers_aviris=bands_nanometers_aviris, fill_value_default=fill_value_default, verbose=verbose,
+                            sigma_bands=sigma_bands, resolution_src=resolution_src)

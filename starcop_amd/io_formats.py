@@ -386,6 +386,30 @@ def window_geo_tags(info, row_off: int, col_off: int) -> Dict[int, tuple]:
     return out
 
 
+def scaled_geo_tags(tags, sy: float, sx: float) -> Dict[int, tuple]:
+    """Georeferencing tags of a raster resampled onto pixels ``sy`` x ``sx`` times as large (``sy = H / oh``, ``sx = W / ow``, the
+    TRUE ratios, so the full extent maps onto the full extent and the upper-left corner stays where it is).  ``tags``: a ``TiffInfo``
+    or a {tag: (type, values)} dict.  A ModelPixelScale (33550) is multiplied; a ModelTransformation (34264) gets its column vector
+    (per output column) multiplied by ``sx`` and its row vector by ``sy``.  The tiepoint / translation and the geo keys are left
+    alone (a tiepoint that is not at pixel (0, 0) has its pixel coordinates divided instead); every other tag is carried over."""
+    tags = tags.tags if isinstance(tags, TiffInfo) else tags
+    out = dict(tags)
+    sy, sx = float(sy), float(sx)
+    if 33550 in out:
+        t, v = out[33550]
+        out[33550] = (t, (float(v[0]) * sx, float(v[1]) * sy) + tuple(v[2:]))
+        if 33922 in out and (float(out[33922][1][0]) != 0.0 or float(out[33922][1][1]) != 0.0):
+            t, v = out[33922]                                 # a tiepoint off the corner keeps its place on the ground
+            out[33922] = (t, (float(v[0]) / sx, float(v[1]) / sy) + tuple(v[2:]))
+    if 34264 in out:
+        t, v = out[34264]
+        m = [float(e) for e in v]
+        m[0], m[4], m[8] = m[0] * sx, m[4] * sx, m[8] * sx
+        m[1], m[5], m[9] = m[1] * sy, m[5] * sy, m[9] * sy
+        out[34264] = (t, tuple(m))
+    return out
+
+
 def gdal_metadata_tag(tags: Dict[str, object], descriptions: Sequence[str] = ()) -> Dict[int, tuple]:
     """GDAL_METADATA (42112): the XML in which GDAL / rasterio keep dataset tags and band descriptions -- what
     ``save_cog(..., descriptions=[...], tags={...})`` leaves in the reference's products (process_aviris.py:222-232)."""

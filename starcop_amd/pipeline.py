@@ -406,7 +406,7 @@ def _nodata_text(v):
 
 @torch.no_grad()
 def aviris_as_sensor(aviris_img_folder_or_path, folder_dest, sensors=list(BANDS_SENSOR), bands=BANDS_SENSOR, columns_read=50,
-                     path_tiffs_temp=".", disable_pbar=True, device="cuda", lines_per_chunk=None):
+                     path_tiffs_temp=".", disable_pbar=True, device="cuda", lines_per_chunk=None, resolution_dst=None, mode="constant"):
     """``aviris_as_sensor`` of the reference (starcop/process_aviris.py:26-90) on the MI355X: writes
     ``{folder_dest}/{sensor}_{band}.tif`` for every band of ``bands[sensor]`` (WV3 SWIR1..8, S2A / S2B B1..B12) simulated from the
     ENVI radiance ``<name>_img`` of an AVIRIS-NG flight-line folder, skipping files that already exist.  The SRF tables come from the
@@ -417,13 +417,29 @@ def aviris_as_sensor(aviris_img_folder_or_path, folder_dest, sensors=list(BANDS_
     missing band of every sensor.  Band centres come from the header (nanometers), the fill value from its ``data ignore value``
     (none: nothing is masked and no nodata tag is written).  Outputs: float32 (lines, samples), tiled 128 x 128, the radiance file's
     georeferencing, GDAL_NODATA = the fill value, the band name as description.  ``columns_read``, ``path_tiffs_temp`` and
-    ``disable_pbar`` are accepted for the reference's signature and ignored.  Returns the list of files written."""
+    ``disable_pbar`` are accepted for the reference's signature and ignored.  Returns the list of files written.
+
+    ``resolution_dst=None`` (the reference's own call) writes every band on the AVIRIS grid.  A number resamples every band to pixels
+    of that size, ``"native"`` every Sentinel-2 band to its own 10 / 20 / 60 m (a WV3 sensor then raises ValueError): the whole
+    (bands, lines, samples) device buffer is resampled before the read-back, one ``sc_resize_aa`` call per resolution, as
+    ``aviris.transform_to_sentinel_2`` / ``transform_to_worldview_3`` resample (Sentinel-2 bands blurred with the sigma of their own
+    ground sampling distance, WV3 bands with the default of the scale; border ``mode``, ``cval`` = the fill value or 0), and only
+    the small planes cross to the host.  The source pixel size is the header's ``map info`` x / y size (ValueError without one); the
+    files carry the source's georeferencing with the pixel scaled by the true ratios lines / output lines and samples / output
+    samples (``io_formats.scaled_geo_tags``), so the upper-left corner and the full extent stay exact."""
     import os
     from concurrent.futures import ThreadPoolExecutor
-    from . import aviris, io_formats as io
+    from . import aviris, io_formats as io, resample
     for sensor in sensors:
         if sensor != "WV3" and not str(sensor).startswith("S2"):
             raise NotImplementedError(f"Sensor {sensor} not known. Expected sensors [WV3, S2A, S2B]")
+    native = isinstance(resolution_dst, str)
+    if native and resolution_dst != "native":
+        raise ValueError(f"resolution_dst '{resolution_dst}': expected None, a pixel size or 'native'")
+    if native and "WV3" in sensors:
+        raise ValueError("resolution_dst='native' is defined for the Sentinel-2 sensors only (WV3 bands have no table of native pixel sizes)")
+    if resolution_dst is not None and mode not in resample.MODES:
+        raise ValueError(f"border mode '{mode}': expected one of {resample.MODES}")
     src = str(aviris_img_folder_or_path)
     if src.endswith(".tif"):
         raise NotImplementedError(f"{src}: only ENVI flight-line folders are supported, not GeoTIFF radiance")
@@ -453,17 +469,41 @@ def aviris_as_sensor(aviris_img_folder_or_path, folder_dest, sensors=list(BANDS_
     fill = header.get("data ignore value")
     fill = float(fill) if fill is not None else None
 
-    ptr_parts, band_parts, w_parts = [np.zeros(1, np.int32)], [], []
-    for sensor in dict.fromkeys(s for s, _, _ in todo):
-        names = [b for s, b, _ in todo if s == sensor]
-        srf = aviris.load_srf_wv3() if sensor == "WV3" else aviris.sentinel_2_srf(sensor)
-        p, b, w = aviris.srf_weights(names, srf, meta["wavelengths"])
-        ptr_parts.append(p[1:] + ptr_parts[-1][-1])
-        band_parts.append(b)
-        w_parts.append(w)
-    plan = aviris.SrfPlan(np.concatenate(ptr_parts), np.concatenate(band_parts), np.concatenate(w_parts), device)
-
     L, S, B = cube.shape
+    # resampling: the planes of one target pixel size are made neighbours in the device buffer (a stable sort of `todo`), so that each
+    # group is one slice of it; everything that can be refused is refused here, before the cube is streamed
+    groups = []                                              # (first plane, last plane + 1, (oh, ow) or None, sigmas (n, 2))
+    if resolution_dst is not None:
+        mi = header.get("map info")
+        try:
+            res_src = (abs(float(mi[6])), abs(float(mi[5])))              # (y, x) pixel size
+        except (TypeError, IndexError, ValueError):
+            raise ValueError(f"{envi_path}: no map info with a pixel size in the header; resolution_dst needs the source's") from None
+        res_band = [float(aviris.BANDS_S2_RESOLUTION[b]) if native else float(resolution_dst) for _, b, _ in todo]
+        todo = [todo[j] for j in sorted(range(len(todo)), key=lambda j: res_band[j])]
+        res_band = sorted(res_band)
+        for k0 in range(len(todo)):
+            if k0 and res_band[k0] == res_band[k0 - 1]:
+                continue
+            k1 = k0 + res_band[k0:].count(res_band[k0])
+            shape = resample.output_shape_for((L, S), res_src, res_band[k0])
+            if shape[0] > L or shape[1] > S:
+                raise ValueError(f"{envi_path}: pixels of {res_src} m cannot be resampled to the finer {res_band[k0]} m; only "
+                                 "downscaling is supported")
+            sig = np.array([(aviris.sentinel_2_sigmas([b], res_src)[0],) * 2 if s != "WV3" else
+                            (resample.default_sigma(L, shape[0]), resample.default_sigma(S, shape[1])) for s, b, _ in todo[k0:k1]])
+            groups.append((k0, k1, None if shape == (L, S) else shape, sig))
+
+    rows = [None] * len(todo)                                # the CSR row of every output plane, in the order of `todo`
+    for sensor in dict.fromkeys(s for s, _, _ in todo):
+        js = [j for j, t in enumerate(todo) if t[0] == sensor]
+        srf = aviris.load_srf_wv3() if sensor == "WV3" else aviris.sentinel_2_srf(sensor)
+        p, b, w = aviris.srf_weights([todo[j][1] for j in js], srf, meta["wavelengths"])
+        for i, j in enumerate(js):
+            rows[j] = (b[p[i]:p[i + 1]], w[p[i]:p[i + 1]])
+    ptrs = np.concatenate([[0], np.cumsum([len(b) for b, _ in rows])]).astype(np.int32)
+    plan = aviris.SrfPlan(ptrs, np.concatenate([b for b, _ in rows]), np.concatenate([w for _, w in rows]), device)
+
     perm = tuple(int(v) for v in np.argsort([-s for s in cube.strides], kind="stable"))    # memory order of (line, sample, band)
     inv = tuple(int(v) for v in np.argsort(perm))
     if lines_per_chunk is None:
@@ -496,15 +536,26 @@ def aviris_as_sensor(aviris_img_folder_or_path, folder_dest, sensors=list(BANDS_
         plan.run(dev.permute(inv), out[:, l0:l0 + n], fill)
         consumed[i].record(compute)
         used[i] = True
-    result = out.cpu().numpy()
-
     geo = io.envi_geo_tags(header)
     if fill is not None:
         geo[42113] = (2, (_nodata_text(fill),))
+    if resolution_dst is None:
+        result = out.cpu().numpy()
+        tags = [geo] * len(todo)
+    else:
+        result, tags = [], []
+        for k0, k1, shape, sig in groups:
+            if shape is None:                                # already at this pixel size: the spectral result, as transform_to_srf
+                small, g = out[k0:k1], geo
+            else:
+                small = resample.resize_antialiased(out[k0:k1], shape, sigma=sig, mode=mode, cval=0.0 if fill is None else fill)
+                g = io.scaled_geo_tags(geo, L / shape[0], S / shape[1])
+            result.extend(small.cpu().numpy())
+            tags.extend([g] * (k1 - k0))
 
     def write(j):
         _, band, path = todo[j]
-        io.write_tiff(path, result[j], blocksize=128, extra_tags={**geo, **io.gdal_metadata_tag({}, [band])})
+        io.write_tiff(path, result[j], blocksize=128, extra_tags={**tags[j], **io.gdal_metadata_tag({}, [band])})
         return path
     with ThreadPoolExecutor(max_workers=min(8, len(todo))) as pool:
         return list(pool.map(write, range(len(todo))))
