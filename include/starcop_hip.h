@@ -981,6 +981,63 @@ int sc_head_conv_fwd_k_mosaic(const sc_src* in, const float* w /*[K][Cin][3][3]*
                               const sc_scene_win* win /*[N] device*/, const sc_scene_win* win_host /*[N] host*/,
                               int N, int Cin, int K, int H, int W, sc_stream stream);
 
+/* Whole flight lines through the binary plume model (ModelModule.predict_scene): the same window table, three more entry points.
+ *   sc_scene_gather_planes : sc_scene_gather for 1 <= P <= SC_SCENE_MAX_PLANES float32 planes that each have their own base pointer
+ *                     and non-negative element strides (three bands of one (H, W, 3) buffer are three planes with column stride 3),
+ *                     with the per-plane operation of sc_window_cut applied to every element in sc_window_cut's order:
+ *                       ops_p & SC_WCUT_FILL and the element's BIT PATTERN == fill_bits_p : 0.0f
+ *                       else if ops_p & SC_WCUT_SCALE : v * scale_p                  (one float32 multiply, one rounding)
+ *                       then if ops_p & SC_WCUT_CLIP  : v < lo ? lo : v, then v > hi ? hi : v   (numpy.clip: NaN stays NaN)
+ *                     (the fill is compared as bits here -- -0.0 does not match +0.0, a NaN pattern matches itself -- so that it is
+ *                     the test sc_scene_core_counts and the mosaic head make.)  out: dense [n][P][win_h][win_w] float32, 16-byte
+ *                     aligned, win_w a multiple of 4; 16-byte stores; one 16-byte load per store where its four sources are
+ *                     contiguous, inside the image and so aligned, element loads otherwise.  A plane with ops == 0 passes its bits
+ *                     through: what sc_scene_gather (scale 1) gives for the same plane.
+ *   sc_scene_core_counts : counts[i] (int32) = number of pixels of window i's core DESTINATION rectangle -- rows dst_row .. dst_row +
+ *                     core_y1 - core_y0, columns likewise -- of one float32 plane whose bits differ from fill_bits; 0 for an empty
+ *                     core.  counts is overwritten.  Integer sums (one integer atomic per work-group): the result does not depend
+ *                     on the launch geometry.  A core may hold at most 2^31 - 1 pixels.
+ *   sc_head_conv_fwd_mosaic_prob : the 1-class head (sc_head_conv_fwd: Cin <= 32, RAW / AFFINE, no upsample) with the destination
+ *                     table of sc_head_conv_fwd_k_mosaic.  Per core pixel z = the logit of sc_head_conv_fwd (same stencil and FMA
+ *                     order, hence its bits whichever of its kernels the shape selects), p = 1.f / (1.f + expf(-z)), m = p > 0.5f
+ *                     (sc_threshold_masks with ge0 = 0); p goes to the float32 mosaic `prob` (pitch in elements), m to the uint8
+ *                     mosaic `mask`; either may be NULL, not both.  valid != NULL: a float32 plane addressed like the mosaics
+ *                     (valid[r * valid_row_stride + c * valid_col_stride] for mosaic pixel (r, c)); where its bits equal fill_bits
+ *                     the pixel gets `nodata` and 0 instead.  Logits are never stored; tiles without a core pixel leave before
+ *                     they stage anything; 16- / 4-byte stores where four adjacent pixels are wanted and aligned, element stores
+ *                     otherwise.
+ * Checks and guarantees are those of the two functions above: everything is validated on the host copy of the table before a launch
+ * (SC_ERR_ARG otherwise), the kernels clamp reads into the planes and drop stores outside the mosaics / the image whatever the
+ * device table holds.  No allocation, no synchronisation, no floating-point atomics, 64-bit addresses.                           */
+#define SC_SCENE_MAX_PLANES 16
+typedef struct sc_scene_planes_args {
+  int32_t P, H, W;                               /* planes (1..16) and their common size                      */
+  int32_t pad_top, pad_left;                     /* reflect pads in front of row 0 / column 0                 */
+  int32_t n, win_h, win_w;                       /* windows of the call and their common shape                */
+  const float* src[SC_SCENE_MAX_PLANES];         /* element [0][0] of every plane, device                     */
+  int64_t row_stride[SC_SCENE_MAX_PLANES];       /* elements                                                  */
+  int64_t col_stride[SC_SCENE_MAX_PLANES];
+  uint32_t ops[SC_SCENE_MAX_PLANES];             /* SC_WCUT_FILL | SC_WCUT_SCALE | SC_WCUT_CLIP               */
+  uint32_t fill_bits[SC_SCENE_MAX_PLANES];       /* bit pattern of the fill value                             */
+  float scale[SC_SCENE_MAX_PLANES];
+  float clip_lo[SC_SCENE_MAX_PLANES];
+  float clip_hi[SC_SCENE_MAX_PLANES];
+  const sc_scene_win* win;                       /* [n] device                                                */
+  const sc_scene_win* win_host;                  /* the same on the host                                      */
+  float* out;                                    /* [n][P][win_h][win_w] device                               */
+} sc_scene_planes_args;
+int sc_scene_gather_planes(const sc_scene_planes_args* a, sc_stream stream);
+int sc_scene_core_counts(const float* plane, int64_t row_stride, int64_t col_stride, int H, int W, uint32_t fill_bits,
+                         const sc_scene_win* win /*[n] device*/, const sc_scene_win* win_host /*[n] host*/, int n,
+                         int32_t* counts /*[n] device*/, sc_stream stream);
+int sc_head_conv_fwd_mosaic_prob(const sc_src* in, const float* w /*[1][Cin][3][3]*/, const float* bias /*[1]*/,
+                                 float* prob /*[mos_h][prob_pitch] or NULL*/, int64_t prob_pitch,
+                                 uint8_t* mask /*[mos_h][mask_pitch] or NULL*/, int64_t mask_pitch, int mos_h, int mos_w,
+                                 const float* valid /*or NULL*/, int64_t valid_row_stride, int64_t valid_col_stride,
+                                 uint32_t fill_bits, float nodata,
+                                 const sc_scene_win* win /*[N] device*/, const sc_scene_win* win_host /*[N] host*/,
+                                 int N, int Cin, int H, int W, sc_stream stream);
+
 /* ------------------------------------------------------------------------- */
 /* evaluation masks of the baselines and of run_validation.
  * Thresholded prediction with an optional binary opening by a 3x3 structuring element:

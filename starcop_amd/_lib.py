@@ -178,6 +178,20 @@ class sc_scene_args(C.Structure):
                 ("scale", C.c_float), ("win", C.c_void_p), ("win_host", C.c_void_p), ("out", C.c_void_p)]
 
 
+SCENE_MAX_PLANES = 16
+
+
+class sc_scene_planes_args(C.Structure):
+    """per-plane reflect-padded window gather operands (include/starcop_hip.h: sc_scene_planes_args)"""
+    _fields_ = [("P", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("pad_top", C.c_int32), ("pad_left", C.c_int32),
+                ("n", C.c_int32), ("win_h", C.c_int32), ("win_w", C.c_int32),
+                ("src", C.c_void_p * SCENE_MAX_PLANES), ("row_stride", C.c_int64 * SCENE_MAX_PLANES),
+                ("col_stride", C.c_int64 * SCENE_MAX_PLANES), ("ops", C.c_uint32 * SCENE_MAX_PLANES),
+                ("fill_bits", C.c_uint32 * SCENE_MAX_PLANES), ("scale", C.c_float * SCENE_MAX_PLANES),
+                ("clip_lo", C.c_float * SCENE_MAX_PLANES), ("clip_hi", C.c_float * SCENE_MAX_PLANES),
+                ("win", C.c_void_p), ("win_host", C.c_void_p), ("out", C.c_void_p)]
+
+
 PANEL_MAX, PANEL_MAX_CAT = 1024, 8
 PANEL_F32, PANEL_I64, PANEL_U8 = 0, 1, 2                 # enum sc_panel_dtype
 PANEL_BAND, PANEL_RGB, PANEL_CATEGORICAL = 0, 1, 2       # enum sc_panel_kind
@@ -292,6 +306,10 @@ SIGNATURES = {
     "sc_window_cut": (_i, [C.POINTER(sc_wcut_args), _vp]),
     "sc_scene_gather": (_i, [C.POINTER(sc_scene_args), _vp]),
     "sc_head_conv_fwd_k_mosaic": (_i, [C.POINTER(sc_src), _vp, _vp, _vp, _i, _i, C.c_int64, _vp, _vp, _i, _i, _i, _i, _i, _vp]),
+    "sc_scene_gather_planes": (_i, [C.POINTER(sc_scene_planes_args), _vp]),
+    "sc_scene_core_counts": (_i, [_vp, C.c_int64, C.c_int64, _i, _i, C.c_uint32, _vp, _vp, _i, _vp, _vp]),
+    "sc_head_conv_fwd_mosaic_prob": (_i, [C.POINTER(sc_src), _vp, _vp, _vp, C.c_int64, _vp, C.c_int64, _i, _i, _vp, C.c_int64, C.c_int64,
+                                          C.c_uint32, _f, _vp, _vp, _i, _i, _i, _i, _vp]),
     "sc_connected_components": (_i, [_vp, _i, _vp, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "sc_proposed_mask": (_i, [_vp, C.c_int64, _vp, C.c_int64, _f, _i, _vp, _vp, _sz, _i, _i, _i, _vp]),
     "sc_packed_weight_floats_thin16": (_sz, [_i, _i, _i]),

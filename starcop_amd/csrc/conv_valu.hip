@@ -1608,11 +1608,31 @@ __device__ __forceinline__ uint32_t head_argmax(const float* a, int K) {
 // Destination of the class indices when only the core rectangle of every batch item is wanted, written straight into a uint8
 // mosaic[h][pitch] (sc_head_conv_fwd_k_mosaic); win == NULL in the plain launches
 struct HeadMosaic {
+  static constexpr bool prob_out = false;
   const sc_scene_win* win;      // [N] device
   uint8_t* mosaic;
   long long pitch;
   int h, w;
 };
+
+// The 1-class form (sc_head_conv_fwd_mosaic_prob): probability and / or mask of the cores instead of class indices.  `mosaic` is
+// the uint8 mask (or NULL), `prob` the float32 mosaic (or NULL); valid != NULL: the float32 plane whose fill pixels get nodata / 0.
+struct HeadProbMosaic : HeadMosaic {
+  static constexpr bool prob_out = true;
+  float* prob;
+  long long prob_pitch;
+  const uint32_t* valid;
+  long long vrs, vcs;
+  uint32_t fill;
+  float nodata;
+};
+
+// sigmoid and threshold of sc_threshold_masks (ge0 = 0) for mosaic pixel (r, c); a fill pixel of the valid plane gets nodata / 0
+__device__ __forceinline__ void head_prob_px(const HeadProbMosaic& mo, float z, long long r, long long c, float& p, uint32_t& m) {
+  p = 1.f / (1.f + expf(-z));
+  m = p > 0.5f ? 1u : 0u;
+  if (mo.valid && mo.valid[r * mo.vrs + c * mo.vcs] == mo.fill) { p = mo.nodata; m = 0u; }
+}
 
 // loads batch item n's core; false if the TR x TC tile at (y0, x0) holds none of its pixels (the whole work-group leaves then)
 __device__ __forceinline__ bool head_mosaic_tile(const HeadMosaic& mo, int n, int y0, int x0, int TR, int TC, sc_scene_win& q) {
@@ -1646,11 +1666,14 @@ __device__ __forceinline__ void head_store_classes4(uint8_t* cp, const uint32_t 
 // the 4-byte staging of k_head_fwd16.  logits == NULL: nothing but the class index (1 byte per pixel) leaves the launch.
 // lvec / cvec: 16-byte logit stores / 4-byte class stores (W % 4 == 0 and the output's base aligned accordingly).
 // MOS: the classes of the core rectangles go into mo.mosaic (logits and classes are NULL); a tile without a core pixel leaves at once.
-template <int KT, bool VEC, bool MOS>
+// MO = HeadProbMosaic (KT = 1, MOS): the accumulators are the logits of k_head_fwd16 / k_head_fwd16v (same order of the same FMAs);
+// their sigmoid and mask go into mo.prob / mo.mosaic, 16- and 4-byte stores where all four pixels are wanted and the address allows.
+template <int KT, bool VEC, bool MOS, class MO = HeadMosaic>
 __global__ __launch_bounds__(256, 2) void k_head_fwdk16(const SrcD in, const float* __restrict__ w, const float* __restrict__ bias,
                                                        float* __restrict__ logits, uint8_t* __restrict__ classes, int K, int H, int W,
-                                                       int lvec, int cvec, const HeadMosaic mo) {
+                                                       int lvec, int cvec, const MO mo) {
   constexpr int CIN = 16, CP = 8, TR = 16, TC = 64, PR = TR + 2, PC = 68, NROW = CP * PR, QW = NROW / 16, NHALO = NROW * 2;
+  static_assert(!MO::prob_out || (KT == 1 && MOS), "the probability mosaic is the 1-class head's");
   static_assert(NROW % 16 == 0 && NHALO <= 512, "four waves x QW requests of four rows; two halo elements per thread");
   __shared__ __attribute__((aligned(16))) float s_in[NROW * PC + 4];
   __shared__ __attribute__((aligned(16))) float s_w[KT * CIN * 12];      // 9 taps per (class, channel), padded to 12; classes >= K: zeros
@@ -1795,6 +1818,36 @@ __global__ __launch_bounds__(256, 2) void k_head_fwdk16(const SrcD in, const flo
   }
   const int y = y0 + py, x = x0 + 4 * pxg;
   if (y >= H || x >= W) return;
+  if constexpr (MO::prob_out) {
+    long long off0, off;
+    uint32_t want = 0, m[4];
+    float p[4];
+    head_mosaic_px(mo, core, y, x, off0);
+    const long long r = (long long)core.dst_row + y - core.core_y0, c = (long long)core.dst_col + x - core.core_x0;
+#pragma unroll
+    for (int o = 0; o < 4; ++o) {
+      p[o] = 0.f; m[o] = 0u;
+      if (x + o < W && head_mosaic_px(mo, core, y, x + o, off)) {
+        want |= 1u << o;
+        head_prob_px(mo, acc[0][o], r, c + o, p[o], m[o]);
+      }
+    }
+    if (!want) return;
+    if (mo.prob) {
+      float* pp = mo.prob + r * mo.prob_pitch + c;      // (only the wanted elements of pp[0..3] are touched)
+      if (want == 15u && (reinterpret_cast<uintptr_t>(pp) & 15) == 0) {
+        *reinterpret_cast<float4*>(pp) = make_float4(p[0], p[1], p[2], p[3]);
+      } else {
+#pragma unroll
+        for (int o = 0; o < 4; ++o) if (want & (1u << o)) pp[o] = p[o];
+      }
+    }
+    if (mo.mosaic) {
+      uint8_t* cp = mo.mosaic + off0;
+      head_store_classes4(cp, m, want == 15u && (reinterpret_cast<uintptr_t>(cp) & 3) == 0, want);
+    }
+    return;
+  }
   const size_t HW = (size_t)H * W, pix = (size_t)y * W + x;
   if (logits) {
 #pragma unroll
@@ -1831,11 +1884,13 @@ __global__ __launch_bounds__(256, 2) void k_head_fwdk16(const SrcD in, const flo
 }
 
 // any Cin <= 32: k_head_fwd<0>'s tile (8 x 32, one pixel per thread, taps in LDS) with HEADK_MAXK accumulators
-template <bool MOS>
+// (MO = HeadProbMosaic: KT = 1, the logit of k_head_fwd<0>; its sigmoid / mask go to the mosaics, one pixel per thread)
+template <bool MOS, int KT = HEADK_MAXK, class MO = HeadMosaic>
 __global__ __launch_bounds__(256) void k_head_fwdk(const SrcD in, const float* __restrict__ w, const float* __restrict__ bias,
                                                    float* __restrict__ logits, uint8_t* __restrict__ classes, int Cin, int K, int H, int W,
-                                                   const HeadMosaic mo) {
-  constexpr int KT = HEADK_MAXK, PR = HT_R + 2, PC = HT_C + 2;
+                                                   const MO mo) {
+  constexpr int PR = HT_R + 2, PC = HT_C + 2;
+  static_assert(!MO::prob_out || (KT == 1 && MOS), "the probability mosaic is the 1-class head's");
   __shared__ float s_in[HEAD_MAXCI * PR * PC];
   __shared__ float s_w[KT * HEAD_MAXCI * 9];                            // [k][ci][tap]; classes >= K: zeros
   const int n = blockIdx.z;
@@ -1868,7 +1923,17 @@ __global__ __launch_bounds__(256) void k_head_fwdk(const SrcD in, const float* _
     for (int k = 0; k < KT; ++k)
       if (k < K) logits[((size_t)n * K + k) * HW + pix] = acc[k];
   }
-  if (MOS) {
+  if constexpr (MO::prob_out) {
+    long long off;
+    if (head_mosaic_px(mo, core, y, x, off)) {
+      const long long r = (long long)core.dst_row + y - core.core_y0, c = (long long)core.dst_col + x - core.core_x0;
+      float p;
+      uint32_t m;
+      head_prob_px(mo, acc[0], r, c, p, m);
+      if (mo.prob) mo.prob[r * mo.prob_pitch + c] = p;
+      if (mo.mosaic) mo.mosaic[off] = (uint8_t)m;
+    }
+  } else if (MOS) {
     long long off;
     if (head_mosaic_px(mo, core, y, x, off)) mo.mosaic[off] = (uint8_t)head_argmax<KT, 1>(acc, K);
   } else if (classes) {
@@ -2399,6 +2464,49 @@ extern "C" int sc_head_conv_fwd_k_mosaic(const sc_src* in, const float* w, const
   }
   launch_head_fwdk(in, w, bias, nullptr, nullptr, HeadMosaic{win, mosaic, (long long)pitch, mos_h, mos_w}, N, Cin, K, H, W, (hipStream_t)stream);
   SC_LAUNCH_OK("sc_head_conv_fwd_k_mosaic");
+  return SC_OK;
+}
+
+extern "C" int sc_head_conv_fwd_mosaic_prob(const sc_src* in, const float* w, const float* bias, float* prob, int64_t prob_pitch,
+                                            uint8_t* mask, int64_t mask_pitch, int mos_h, int mos_w, const float* valid,
+                                            int64_t valid_row_stride, int64_t valid_col_stride, uint32_t fill_bits, float nodata,
+                                            const sc_scene_win* win, const sc_scene_win* win_host, int N, int Cin, int H, int W,
+                                            sc_stream stream) {
+  SC_REQUIRE(in && in->C == Cin, "sc_head_conv_fwd_mosaic_prob: source channels != Cin");
+  SC_REQUIRE(Cin >= 1 && Cin <= HEAD_MAXCI, "sc_head_conv_fwd_mosaic_prob: Cin must be in [1,%d]", HEAD_MAXCI);
+  SC_REQUIRE((in->mode == SC_SRC_RAW || in->mode == SC_SRC_AFFINE) && in->up == 0, "sc_head_conv_fwd_mosaic_prob: unsupported source mode");
+  SC_REQUIRE(w && in->x && win && win_host && N > 0 && N <= 65535 && H > 0 && W > 0, "sc_head_conv_fwd_mosaic_prob: bad argument");
+  SC_REQUIRE(prob || mask, "sc_head_conv_fwd_mosaic_prob: at least one of prob / mask must be given");
+  SC_REQUIRE(mos_h > 0 && mos_w > 0 && (!prob || prob_pitch >= mos_w) && (!mask || mask_pitch >= mos_w),
+             "sc_head_conv_fwd_mosaic_prob: bad mosaic %d x %d, pitches %lld / %lld", mos_h, mos_w, (long long)prob_pitch, (long long)mask_pitch);
+  SC_REQUIRE((uintptr_t)win % 4 == 0 && (uintptr_t)prob % 4 == 0 && (uintptr_t)valid % 4 == 0, "sc_head_conv_fwd_mosaic_prob: misaligned pointer");
+  SC_REQUIRE(!valid || (valid_row_stride >= 0 && valid_col_stride >= 0), "sc_head_conv_fwd_mosaic_prob: negative stride of the valid plane");
+  for (int i = 0; i < N; ++i) {
+    const sc_scene_win& q = win_host[i];
+    if (q.core_y1 <= q.core_y0 || q.core_x1 <= q.core_x0) continue;      // empty core: nothing is stored
+    SC_REQUIRE(q.core_y0 >= 0 && q.core_y1 <= H && q.core_x0 >= 0 && q.core_x1 <= W,
+               "sc_head_conv_fwd_mosaic_prob: core %d (rows %d:%d, columns %d:%d) is not inside the %d x %d plane", i, q.core_y0, q.core_y1,
+               q.core_x0, q.core_x1, H, W);
+    SC_REQUIRE(q.dst_row >= 0 && (long long)q.dst_row + (q.core_y1 - q.core_y0) <= mos_h && q.dst_col >= 0 &&
+                   (long long)q.dst_col + (q.core_x1 - q.core_x0) <= mos_w,
+               "sc_head_conv_fwd_mosaic_prob: core %d does not fit the %d x %d mosaic at row %d, column %d", i, mos_h, mos_w, q.dst_row, q.dst_col);
+  }
+  HeadProbMosaic mo;
+  mo.win = win; mo.mosaic = mask; mo.pitch = (long long)mask_pitch; mo.h = mos_h; mo.w = mos_w;
+  mo.prob = prob; mo.prob_pitch = (long long)prob_pitch;
+  mo.valid = reinterpret_cast<const uint32_t*>(valid); mo.vrs = (long long)valid_row_stride; mo.vcs = (long long)valid_col_stride;
+  mo.fill = fill_bits; mo.nodata = nodata;
+  hipStream_t st = (hipStream_t)stream;
+  if (Cin == 16) {
+    dim3 g16(((W + 63) / 64) * ((H + 15) / 16), 1, N);
+    const bool vec = (W % 4 == 0) && ((uintptr_t)in->x & 15) == 0;
+    if (vec) hipLaunchKernelGGL((k_head_fwdk16<1, true, true, HeadProbMosaic>), g16, dim3(256), 0, st, to_srcd(*in), w, bias, nullptr, nullptr, 1, H, W, 0, 0, mo);
+    else hipLaunchKernelGGL((k_head_fwdk16<1, false, true, HeadProbMosaic>), g16, dim3(256), 0, st, to_srcd(*in), w, bias, nullptr, nullptr, 1, H, W, 0, 0, mo);
+  } else {
+    dim3 grid(((W + HT_C - 1) / HT_C) * ((H + HT_R - 1) / HT_R), 1, N);
+    hipLaunchKernelGGL((k_head_fwdk<true, 1, HeadProbMosaic>), grid, dim3(256), 0, st, to_srcd(*in), w, bias, nullptr, nullptr, Cin, 1, H, W, mo);
+  }
+  SC_LAUNCH_OK("sc_head_conv_fwd_mosaic_prob");
   return SC_OK;
 }
 

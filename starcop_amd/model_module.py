@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn
 
-from . import _lib, metrics
+from . import _lib, mag1c, metrics
 from ._lib import check, ptr, stream
 from .network import HyperStarcopUNet
 from .normalizer import DataNormalizer
@@ -373,6 +373,116 @@ class ModelModule(_Base):
             if was:
                 self.train(True)
         return out[0]
+
+    @torch.no_grad()
+    def predict_scene(self, planes, fill_value=None, scales=None, clips=None, tile=None, halo=None, batch=None, skip_empty=True,
+                      nodata=mag1c.NODATA):
+        """
+            planes: the raw products of a whole scene, one (H, W) float32 plane per ``input_products`` entry: a list of device
+                tensors or of numpy arrays (or one (C, H, W) tensor / array), any non-negative strides -- three bands of one
+                (H, W, 3) buffer are read in place
+            fill_value: the no-data value of the products (one number, or one per plane; None: none).  Such elements enter the
+                network as 0 (as ``WindowDataset`` prepares samples), and the pixels where the FIRST plane holds it get ``nodata``
+                in ``prediction`` and 0 in ``pred_binary``
+            scales, clips: per plane (entries may be None) the float32 multiplier of the other elements and the (lo, hi) they are
+                clipped to afterwards: the acquisition-date factor and clip of ``window_dataset.product_ops``
+            tile, halo: the window plan, ``sentinel2.scene_windows(H, W, tile, halo)`` (defaults ``sentinel2.SCENE_TILE``,
+                ``RECEPTIVE_HALO``: with ``halo`` >= 320 the logits behind every pixel equal the whole-scene forward's)
+            batch: windows per forward (default: the most with batch x window pixels <= 16 x 512^2)
+            skip_empty: with a ``fill_value``, windows whose core holds no data pixel of the first plane are neither cut nor run
+                (one ``sc_scene_core_counts`` launch and one read-back of n ints decide)
+
+        Sliding-window form of ``predict`` for flight lines that do not fit as one image.  ``sc_scene_gather_planes`` builds each
+        batch of network inputs from the products' own planes; ``normalize_x`` stays fused into the stem; the head writes the
+        sigmoid and the mask of every window's core straight into the results (``HyperStarcopUNet.predict_masks_into``).  No padded
+        scene, no logits, no per-window outputs.
+
+        Returns:
+            {"prediction": (H, W) float32, "pred_binary": (H, W) uint8, "windows": n, "windows_run": k} -- numpy arrays for numpy
+            planes, device tensors for device tensors
+        """
+        from . import sentinel2
+        if isinstance(planes, (np.ndarray, torch.Tensor)):
+            if len(planes.shape) != 3:
+                raise ValueError(f"ModelModule.predict_scene: expected (C, H, W) or a list of (H, W) planes, got shape {tuple(planes.shape)}")
+            planes = [planes[c] for c in range(planes.shape[0])]
+        planes = list(planes)
+        C_ = self.num_channels
+        if len(planes) != C_:
+            raise ValueError(f"ModelModule.predict_scene: {len(planes)} planes for the {C_} input products {self.input_products}")
+        is_np = all(isinstance(p, np.ndarray) for p in planes)
+        if not is_np and not all(isinstance(p, torch.Tensor) for p in planes):
+            raise TypeError("ModelModule.predict_scene: planes must be all numpy arrays or all device tensors")
+        for p in planes:
+            if p.dtype != (np.float32 if is_np else torch.float32):
+                raise TypeError(f"ModelModule.predict_scene: planes must be float32, got {p.dtype}")
+            if len(p.shape) != 2 or tuple(p.shape) != tuple(planes[0].shape):
+                raise ValueError(f"ModelModule.predict_scene: planes must be (H, W) of one shape, got {[tuple(q.shape) for q in planes]}")
+
+        def per_plane(name, v):
+            if v is None:
+                return [None] * C_
+            v = list(v)
+            if len(v) != C_:
+                raise ValueError(f"ModelModule.predict_scene: {name} needs one entry per plane ({C_}), got {len(v)}")
+            return v
+        fills = [fill_value] * C_ if fill_value is None or np.isscalar(fill_value) else per_plane("fill_value", fill_value)
+        scales, clips = per_plane("scales", scales), per_plane("clips", clips)
+        H, W = (int(v) for v in planes[0].shape)
+        plan = sentinel2.scene_windows(H, W, sentinel2.SCENE_TILE if tile is None else tile, sentinel2.RECEPTIVE_HALO if halo is None else halo)
+        if self.num_classes != 1:
+            raise ValueError(f"ModelModule.predict_scene: the binary model only (num_classes={self.num_classes})")
+        dev = self.device
+        if dev.type != "cuda":
+            raise _lib.StarcopHipError(f"ModelModule.predict_scene runs on a gfx950 GPU only; this model is on {dev}")
+        if is_np:
+            planes = [torch.from_numpy(np.ascontiguousarray(p) if any(st < 0 for st in p.strides) else p).to(dev) for p in planes]
+        for p in planes:
+            _lib.require_device(p)
+        wh, ww = plan.window
+        table = sentinel2.scene_table(plan)
+        n = table.shape[0]
+        table_dev = torch.from_numpy(table).to(dev)
+        masked = fills[0] is not None
+        if masked:
+            prediction = torch.full((H, W), float(nodata), dtype=torch.float32, device=dev)
+            pred_binary = torch.zeros((H, W), dtype=torch.uint8, device=dev)
+        else:
+            prediction = torch.empty((H, W), dtype=torch.float32, device=dev)
+            pred_binary = torch.empty((H, W), dtype=torch.uint8, device=dev)
+        if masked and skip_empty:
+            counts = sentinel2.scene_core_counts(planes[0], fills[0], table_dev, table).cpu().numpy()
+            run = np.flatnonzero(counts > 0)
+            if run.shape[0] < n:
+                table = np.ascontiguousarray(table[run])
+                table_dev = torch.from_numpy(table).to(dev) if run.shape[0] else None
+        else:
+            run = np.arange(n)
+        k_run = int(run.shape[0])
+        if k_run:
+            if batch is None:
+                batch = max(1, sentinel2.SCENE_BATCH_PIXELS // (wh * ww))
+            batch = max(1, min(int(batch), k_run))
+            was = self.training
+            if was:
+                self.eval()
+            try:
+                cst = self.normalizer.consts(dev)
+                bufs = {}
+                for first in range(0, k_run, batch):
+                    k = min(batch, k_run - first)
+                    if k not in bufs:
+                        bufs[k] = torch.empty((k, C_, wh, ww), dtype=torch.float32, device=dev)
+                    x = sentinel2.scene_gather_planes(planes, (plan.pad_rows[0], plan.pad_cols[0]), table_dev, table, first, k, plan.window,
+                                                      fills, scales, clips, out=bufs[k])
+                    self.network.predict_masks_into(x, prediction, pred_binary, (table_dev, table, first), cst,
+                                                    valid=planes[0] if masked else None, fill_value=fills[0], nodata=nodata)
+            finally:
+                if was:
+                    self.train(True)
+        if is_np:
+            prediction, pred_binary = prediction.cpu().numpy(), pred_binary.cpu().numpy()
+        return {"prediction": prediction, "pred_binary": pred_binary, "windows": int(n), "windows_run": k_run}
 
     # ---------------------------------------------------------------------------------------------
     # fused training step: forward + loss + backward + (all-reduce) + Adam with no autograd graph.

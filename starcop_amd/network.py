@@ -964,7 +964,9 @@ class HyperStarcopUNet(nn.Module):
         """x: (N,C,H,W) fp32 device tensor (raw physical units if x_cst is given, else already normalised).
         head: "logits" -> plan.buf["logits"] (N,K,H,W); "classes" -> plan.classes (N,H,W) uint8 = argmax over K, no logits stored;
         "mosaic" -> the classes of every item's core rectangle into mosaic = (uint8 (h, w) tensor, device table, host table, first
-        row), see predict_classes_into: neither logits nor per-item classes are stored."""
+        row), see predict_classes_into: neither logits nor per-item classes are stored; "probmosaic" -> sigmoid and mask of the
+        cores of the 1-class head into mosaic = (prob or None, mask or None, device table, host table, first row, valid plane or
+        None, fill bits, nodata), see predict_masks_into: likewise nothing else is stored."""
         if training and (self.classes > self.MAX_TRAIN_CLASSES or self.in_channels > self.MAX_TRAIN_IN_CHANNELS):
             raise NotImplementedError(
                 f"HyperStarcopUNet(in_channels={self.in_channels}, classes={self.classes}) runs in eval mode only: training needs two "
@@ -1161,6 +1163,15 @@ class HyperStarcopUNet(nn.Module):
                     check(lib.sc_head_conv_fwd_k_mosaic(C.byref(s), ptr(conv.weight), ptr(conv.bias), ptr(mos), mos.shape[0], mos.shape[1],
                                                         mos.stride(0), tab_dev.data_ptr() + 32 * first, tab_host.ctypes.data + 32 * first,
                                                         N, conv.in_channels, self.classes, Ho, Wo, st))
+                elif head == "probmosaic":
+                    prob, mask, tab_dev, tab_host, first, valid, fill_bits, nodata = mosaic
+                    ref = prob if prob is not None else mask
+                    check(lib.sc_head_conv_fwd_mosaic_prob(
+                        C.byref(s), ptr(conv.weight), ptr(conv.bias), ptr(prob), prob.stride(0) if prob is not None else 0,
+                        ptr(mask), mask.stride(0) if mask is not None else 0, ref.shape[0], ref.shape[1],
+                        ptr(valid), valid.stride(0) if valid is not None else 0, valid.stride(1) if valid is not None else 0,
+                        fill_bits, nodata, tab_dev.data_ptr() + 32 * first, tab_host.ctypes.data + 32 * first,
+                        N, conv.in_channels, Ho, Wo, st))
                 elif self.classes == 1 and head == "logits":
                     check(lib.sc_head_conv_fwd(C.byref(s), ptr(conv.weight), ptr(conv.bias), ptr(plan.buf[o.name]),
                                                N, conv.in_channels, Ho, Wo, st))
@@ -1898,6 +1909,46 @@ class HyperStarcopUNet(nn.Module):
             raise ValueError("predict_classes_into: table must be (device int32 (n, 8), the same numpy int32 array, first) with first + N <= n")
         self._forward_impl(x, normalizer_consts, False, False, head="mosaic", mosaic=(mosaic, tab_dev, tab_host, int(first)))
         return mosaic
+
+    @torch.no_grad()
+    def predict_masks_into(self, x, prob, mask, table, normalizer_consts=None, valid=None, fill_value=None, nodata=-9999.0):
+        """The binary model over the windows of a scene: of batch item i only the core rectangle is kept, and the head itself
+        (sc_head_conv_fwd_mosaic_prob) writes ``sigmoid(logit)`` into ``prob`` (float32 (h, w) device tensor, unit column stride) and
+        ``sigmoid(logit) > 0.5`` into ``mask`` (uint8, likewise) -- the values ``masks_from_logits`` derives from the eval forward's
+        logits.  Either of ``prob`` / ``mask`` may be None, not both.  ``table`` as for ``predict_classes_into``.  ``valid``: an
+        (h, w) float32 device plane (any non-negative strides) whose pixels with the bits of float32(``fill_value``) get
+        ``nodata`` / 0 instead.  No logits and no per-window tensors exist.  Eval mode, ``classes == 1`` only.  Returns (prob, mask)."""
+        if self.training:
+            raise RuntimeError("HyperStarcopUNet.predict_masks_into: eval mode only (call .eval() first)")
+        if self.classes != 1:
+            raise ValueError(f"HyperStarcopUNet.predict_masks_into: the probability head is the 1-class model's (classes={self.classes})")
+        import numpy as np
+        tab_dev, tab_host, first = table
+        if prob is None and mask is None:
+            raise ValueError("predict_masks_into: at least one of prob / mask must be given")
+        shapes = set()
+        for name, t, dt in (("prob", prob, torch.float32), ("mask", mask, torch.uint8)):
+            if t is None:
+                continue
+            _lib.require_device(t)
+            if t.dtype != dt or t.dim() != 2 or t.stride(1) != 1:
+                raise ValueError(f"predict_masks_into: {name} must be a {dt} (h, w) tensor with unit column stride")
+            shapes.add(tuple(t.shape))
+        if len(shapes) != 1:
+            raise ValueError("predict_masks_into: prob and mask must have one shape")
+        fill_bits = 0
+        if valid is not None:
+            _lib.require_device(valid)
+            if valid.dtype != torch.float32 or tuple(valid.shape) not in shapes or fill_value is None:
+                raise ValueError("predict_masks_into: valid must be a float32 plane of the mosaics' shape, with a fill_value")
+            fill_bits = int(np.array(fill_value, dtype=np.float32).view(np.uint32))
+        if (tab_dev.dtype != torch.int32 or not tab_dev.is_contiguous() or tab_host.dtype != np.int32 or not tab_host.flags.c_contiguous
+                or tab_dev.dim() != 2 or tuple(tab_dev.shape) != tuple(tab_host.shape) or tab_dev.shape[1] != 8
+                or first < 0 or first + x.shape[0] > tab_dev.shape[0]):
+            raise ValueError("predict_masks_into: table must be (device int32 (n, 8), the same numpy int32 array, first) with first + N <= n")
+        self._forward_impl(x, normalizer_consts, False, False, head="probmosaic",
+                           mosaic=(prob, mask, tab_dev, tab_host, int(first), valid, fill_bits, float(nodata)))
+        return prob, mask
 
 
 class _UNetFunction(torch.autograd.Function):

@@ -6,7 +6,9 @@ The reference spreads this over its drivers and notebooks; the steps and their o
     starcop/emit_tools/emit_dataset.py:62-106 -> ``model(x)`` -> sigmoid > 0.5;
     optionally orthorectified through the granule's GLT and written as GeoTIFFs (``georeferenced=True``, ``out_folder``);
   * AVIRIS-NG (configs[2]): ``run_mag1c`` (starcop/process_aviris.py:189-219: per detector column, alpha = 0) and the
-    pre-computed RGB products -> ``padded_predict``.
+    pre-computed RGB products -> ``padded_predict``; here ``aviris_scene_predict`` goes from the ENVI flight line to ``pred.tif`` /
+    ``predbinary.tif`` / the plume table in one call (``aviris_scene_mag1c`` when there is no ``mag1c.tif``, the RGB bands read
+    from the radiance cube, ``ModelModule.predict_scene`` for lines that do not fit as one image).
 Everything stays on the device between the stages; with ``torch.distributed`` initialised the column blocks of the
 matched filter and the scenes are independent work items (``column_range`` / ``parallel.sharded_map``): no collective on
 the data path.
@@ -366,6 +368,21 @@ def aviris_scene_mag1c(aviris_img_folder, mf_filename, albedo_filename=None, use
     keys), GDAL_NODATA, the band description and the dataset tags ``wavelengths`` (the kept band centres) and ``mag1c=acfwl1mf``.
     The target spectrum is cast to the radiance dtype as the reference does (:199).  Returns (mf, albedo) device tensors.
     The radiance slice is uploaded once from the memmap through pinned memory; everything after that stays on the device."""
+    from . import io_formats as io
+    mf, alb, meta, wl, keep = _aviris_mag1c(aviris_img_folder, use_wavelength_range, device)
+    tags = io.envi_geo_tags(meta["header"])                               # transform + crs of the radiance file
+    tags[42113] = (2, (str(mag1c.NODATA),))                               # GDAL_NODATA, as fill_value_default=NODATA
+    tags.update(extra_tags or {})
+    md = {"wavelengths": wl[keep], "mag1c": "acfwl1mf"}
+    io.write_tiff(mf_filename, mf.cpu().numpy(), blocksize=128,
+                  extra_tags={**tags, **io.gdal_metadata_tag(md, ["CH4 Absorption (ppm x m)"])})
+    if albedo_filename is not None:
+        io.write_tiff(albedo_filename, alb.cpu().numpy(), blocksize=128, extra_tags={**tags, **io.gdal_metadata_tag(md, ["Albedo"])})
+    return mf, alb
+
+
+def _aviris_mag1c(aviris_img_folder, use_wavelength_range, device):
+    """the matched filter of :func:`aviris_scene_mag1c` without the files -> (mf, albedo, ENVI meta, band centres, kept bands)"""
     import os
     from . import io_formats as io
     folder = aviris_img_folder.rstrip("/")
@@ -382,15 +399,168 @@ def aviris_scene_mag1c(aviris_img_folder, mf_filename, albedo_filename=None, use
     x = (host.pin_memory() if torch.cuda.is_available() else host).to(device, non_blocking=True)
     groups = np.abs(np.asarray(glt[..., 0])).astype(np.int64)
     mf, alb = mag1c.func_by_groups(mag1c.Filter(spec, num_iter=30), x, groups, mask=groups != 0, max_group=int(groups.max()))
-    tags = io.envi_geo_tags(meta["header"])                               # transform + crs of the radiance file
-    tags[42113] = (2, (str(mag1c.NODATA),))                               # GDAL_NODATA, as fill_value_default=NODATA
-    tags.update(extra_tags or {})
-    md = {"wavelengths": wl[keep], "mag1c": "acfwl1mf"}
-    io.write_tiff(mf_filename, mf.cpu().numpy(), blocksize=128,
-                  extra_tags={**tags, **io.gdal_metadata_tag(md, ["CH4 Absorption (ppm x m)"])})
-    if albedo_filename is not None:
-        io.write_tiff(albedo_filename, alb.cpu().numpy(), blocksize=128, extra_tags={**tags, **io.gdal_metadata_tag(md, ["Albedo"])})
-    return mf, alb
+    return mf, alb, meta, wl, keep
+
+
+def aviris_scene_products(input_products, normalize_by_acquisition_date=True):
+    """what :func:`aviris_scene_predict` reads for a model's ``input_products``: [("mag1c", None) | ("band", centre in nm)].
+    ``mag1c`` is the matched filter; ``TOA_AVIRIS_{w}nm`` (``{w}nm`` when not normalising by the acquisition date) the radiance
+    band nearest to ``w`` nm, the names ``window_dataset.save_name`` gives them.  Anything else: NotImplementedError."""
+    import re
+    pat = r"TOA_AVIRIS_(\d+(?:\.\d+)?)nm" if normalize_by_acquisition_date else r"(\d+(?:\.\d+)?)nm"
+    out = []
+    for name in input_products:
+        m = re.fullmatch(pat, name)
+        if name == "mag1c":
+            out.append(("mag1c", None))
+        elif m:
+            out.append(("band", float(m.group(1))))
+        else:
+            raise NotImplementedError(f"aviris_scene_predict: input product {name!r} cannot be derived from an AVIRIS-NG flight line "
+                                      f"(mag1c and {'TOA_AVIRIS_{w}nm' if normalize_by_acquisition_date else '{w}nm'} can)")
+    return out
+
+
+def _envi_geotransform(header):
+    """(GDAL geotransform, pixel area in m2) of an ENVI ``map info`` without rotation; (None, None) otherwise.  The area only
+    for UTM (metres)."""
+    mi = header.get("map info")
+    if not isinstance(mi, list) or len(mi) < 7:
+        return None, None
+    try:
+        xr, yr, e0, n0, px, py = (float(v) for v in mi[1:7])
+    except ValueError:
+        return None, None
+    if any(v.lower().replace(" ", "").startswith("rotation=") and float(v.split("=")[1]) != 0.0 for v in mi[7:]):
+        return None, None
+    return (e0 - (xr - 1.0) * px, px, 0.0, n0 + (yr - 1.0) * py, 0.0, -py), (px * py if mi[0].strip().lower() == "utm" else None)
+
+
+AVIRIS_PRODUCT_FILES = {"pred.tif": ("prediction", ["Plume probability"]), "predbinary.tif": ("pred_binary", ["Plume mask"])}
+
+
+@torch.no_grad()
+def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=None, toa_correction_factor=None, solar_altitude=None,
+                         normalize_by_acquisition_date=True, tile=None, halo=None, batch=None, plumes=False, overwrite=False,
+                         device="cuda"):
+    """An orthorectified AVIRIS-NG flight line through the plume model, file to file: ``{folder}/{name}_img`` (ENVI radiance,
+    float32) -> the network's input products -> ``model.predict_scene`` -> (with ``out_folder``) ``pred.tif`` / ``predbinary.tif``.
+
+    The channels follow ``model.input_products`` (:func:`aviris_scene_products`).  ``mag1c`` is read from ``mag1c_path``, else
+    from ``{folder}/mag1c.tif`` when it exists, else computed as :func:`aviris_scene_mag1c` does (needs ``{name}_glt``; written to
+    ``{out_folder}/mag1c.tif`` when ``out_folder`` is given); its no-data pixels enter the network as 0 and it is clipped to
+    [0, 10000] (``window_dataset.product_ops``).  A radiance band is the band of the cube whose centre is nearest to the product's
+    wavelength, as ``WindowDataset`` picks it: the bands are read from the memmap as one strided host read, uploaded as ONE pinned
+    (H, W, k) buffer and read in place; the header's ``data ignore value`` enters as 0, everything else is multiplied by the
+    acquisition-date factor -- ``toa_correction_factor``, or ``aviris.observation_date_correction_factor(date, solar_altitude)``
+    with the date parsed from the ``angYYYYMMDDtHHMMSS`` folder name; with ``normalize_by_acquisition_date`` and neither: ValueError.
+
+    Returns the dict of ``predict_scene`` (device tensors) plus ``mf``; ``plumes=True`` adds ``plumes``, the
+    ``plumes.plume_table`` of the mask with ``mf`` and ``prediction`` and the geotransform / pixel area of the ENVI ``map info``.
+    With ``out_folder``: ``pred.tif`` (float32, GDAL_NODATA = ``mag1c.NODATA``) and ``predbinary.tif`` (uint8), BLOCKSIZE 128, the
+    radiance file's georeferencing, band descriptions; ``plumes.csv`` with ``plumes=True``; existing files are skipped unless
+    ``overwrite``; the paths written come back under ``files``."""
+    import datetime
+    import os
+    import re
+    from . import aviris
+    from . import io_formats as io
+    from .sampling import _nodata
+    products = aviris_scene_products(model.input_products, normalize_by_acquisition_date)
+    for path in (out_folder, mag1c_path, aviris_img_folder):
+        if path is not None and str(path).startswith("gs://"):
+            raise NotImplementedError(f"{path}: Google Cloud Storage is not supported; pass a local path")
+    folder = str(aviris_img_folder).rstrip("/")
+    name = os.path.basename(folder)
+    factor = None
+    if normalize_by_acquisition_date and any(kind == "band" for kind, _ in products):
+        if toa_correction_factor is not None:
+            factor = float(toa_correction_factor)
+        elif solar_altitude is not None:
+            m = re.search(r"ang(\d{8})t(\d{6})", name)
+            if m is None:
+                raise ValueError(f"aviris_scene_predict: no acquisition date (angYYYYMMDDtHHMMSS) in the folder name {name!r}; pass toa_correction_factor=")
+            when = datetime.datetime.strptime(m.group(1) + m.group(2), "%Y%m%d%H%M%S").replace(tzinfo=datetime.timezone.utc)
+            factor = float(aviris.observation_date_correction_factor(when, float(solar_altitude)))
+        else:
+            raise ValueError("aviris_scene_predict: the acquisition-date factor needs toa_correction_factor= or solar_altitude= (degrees; "
+                             "aviris.observation_date_correction_factor), or normalize_by_acquisition_date=False")
+    rdn, meta = io.open_envi(os.path.join(folder, f"{name}_img"))
+    if meta["wavelengths"] is None:
+        raise ValueError(f"{folder}/{name}_img: the ENVI header has no wavelengths")
+    if rdn.dtype.itemsize != 4 or rdn.dtype.kind != "f":
+        raise NotImplementedError(f"{folder}/{name}_img: {rdn.dtype} radiance is not supported (float32)")
+    header = meta["header"]
+    ignore = header.get("data ignore value")
+    ignore = float(ignore) if ignore is not None else None
+    dev = torch.device(device)
+    files = []
+    # ---- the planes, in the order of input_products
+    centres = [w for kind, w in products if kind == "band"]
+    cube = None
+    if centres:
+        bands = np.argmin(np.abs(np.asarray(centres, dtype=np.float64)[:, None] - meta["wavelengths"]), axis=1)
+        host = torch.from_numpy(np.ascontiguousarray(rdn[:, :, bands], dtype=np.float32))        # one strided read of the memmap
+        cube = (host.pin_memory() if torch.cuda.is_available() else host).to(dev, non_blocking=True)
+    mf, mf_fill = None, float(mag1c.NODATA)
+    if any(kind == "mag1c" for kind, _ in products):
+        path = mag1c_path if mag1c_path is not None else os.path.join(folder, "mag1c.tif")
+        if mag1c_path is not None or os.path.exists(path):
+            info = io.tiff_info(path)
+            a = io.read_tiff(path, info=info)
+            a = a[0] if a.ndim == 3 else a
+            if a.dtype != np.float32:
+                raise ValueError(f"{path}: mag1c must be float32, got {a.dtype}")
+            nod = _nodata(info)
+            mf_fill = float(nod) if nod is not None else mf_fill
+            mf = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+        else:
+            mf, alb, _, wl, keep = _aviris_mag1c(folder, mag1c.DEFAULT_WAVELENGTH_RANGE, dev)
+            if out_folder is not None:
+                mpath = os.path.join(str(out_folder), "mag1c.tif")
+                if overwrite or not os.path.exists(mpath):
+                    os.makedirs(str(out_folder), exist_ok=True)
+                    tags = io.envi_geo_tags(header)
+                    tags[42113] = (2, (str(mag1c.NODATA),))
+                    md = {"wavelengths": wl[keep], "mag1c": "acfwl1mf"}
+                    io.write_tiff(mpath, mf.cpu().numpy(), blocksize=128,
+                                  extra_tags={**tags, **io.gdal_metadata_tag(md, ["CH4 Absorption (ppm x m)"])})
+                    files.append(mpath)
+        if tuple(mf.shape) != tuple(rdn.shape[:2]):
+            raise ValueError(f"aviris_scene_predict: mag1c is {tuple(mf.shape)}, the radiance {tuple(rdn.shape[:2])}")
+    planes, fills, scales, clips = [], [], [], []
+    j = 0
+    for kind, _ in products:
+        if kind == "mag1c":
+            planes.append(mf); fills.append(mf_fill); scales.append(None); clips.append((0.0, 10_000.0))
+        else:
+            planes.append(cube[:, :, j]); fills.append(ignore); scales.append(factor); clips.append(None)
+            j += 1
+    out = model.predict_scene(planes, fill_value=fills, scales=scales, clips=clips, tile=tile, halo=halo, batch=batch)
+    out["mf"] = mf
+    gt, area = _envi_geotransform(header)
+    if plumes:
+        from .plumes import plume_table
+        out["plumes"] = plume_table(out["pred_binary"], mag1c=mf, prob=out["prediction"], geotransform=gt, pixel_area_m2=area)
+    if out_folder is not None:
+        geo = io.envi_geo_tags(header)
+        nodata = {42113: (2, (_nodata_text(mag1c.NODATA),))}
+        for fname, (key, desc) in AVIRIS_PRODUCT_FILES.items():
+            path = os.path.join(str(out_folder), fname)
+            if not overwrite and os.path.exists(path):
+                continue
+            os.makedirs(str(out_folder), exist_ok=True)
+            tags = {**geo, **(nodata if key == "prediction" else {}), **io.gdal_metadata_tag({}, desc)}
+            io.write_tiff(path, out[key].cpu().numpy(), blocksize=128, extra_tags=tags)
+            files.append(path)
+        if plumes:
+            from .plumes import write_plumes
+            path = os.path.join(str(out_folder), "plumes.csv")
+            if overwrite or not os.path.exists(path):
+                os.makedirs(str(out_folder), exist_ok=True)
+                files.append(write_plumes(out["plumes"], path))
+        out["files"] = files
+    return out
 
 
 BANDS_S2 = ["B1", "B2", "B3", "B4", "B5", "B6", "B7", "B8", "B8A", "B9", "B10", "B11", "B12"]

@@ -26,7 +26,8 @@ from .padding import find_padding, padded_predict       # same arithmetic as mod
 from .pipeline import RECEPTIVE_HALO
 
 __all__ = ["INTERPRETATION_CLOUDSEN12", "load_weights", "find_padding", "padded_predict", "CDModel", "RECEPTIVE_HALO", "SCENE_TILE",
-           "ScenePlan", "scene_windows", "scene_table", "scene_gather", "cloud_mask_file"]
+           "ScenePlan", "scene_windows", "scene_table", "scene_gather", "scene_gather_planes", "scene_core_counts", "float_bits",
+           "cloud_mask_file"]
 
 INTERPRETATION_CLOUDSEN12 = ["clear", "Thick cloud", "Thin cloud", "Cloud shadow"]      # models.py:11
 
@@ -115,6 +116,80 @@ def scene_gather(src, pads, table_dev, table_host, first, n, window, scale=1.0, 
     a.win_host = table_host.ctypes.data + 32 * first
     a.out = out.data_ptr()
     _lib.check(_lib.load().sc_scene_gather(C.byref(a), _lib.stream()))
+    return out
+
+
+def _check_table(who, table_dev, table_host, first, n):
+    if (table_dev.dtype != torch.int32 or not table_dev.is_contiguous() or table_host.dtype != np.int32 or not table_host.flags.c_contiguous
+            or table_dev.dim() != 2 or tuple(table_dev.shape) != tuple(table_host.shape) or table_dev.shape[1] != 8
+            or first < 0 or n < 1 or first + n > table_dev.shape[0]):
+        raise ValueError(f"{who}: the table must be a device int32 (m, 8) tensor and the same numpy int32 array, first + n <= m")
+
+
+def float_bits(value):
+    """bit pattern of ``float32(value)``: how the plume-scene kernels compare a fill value"""
+    return int(np.array(value, dtype=np.float32).view(np.uint32))
+
+
+def scene_gather_planes(planes, pads, table_dev, table_host, first, n, window, fills=None, scales=None, clips=None, out=None):
+    """``sc_scene_gather_planes``: windows [first, first + n) of the table out of P <= 16 float32 device planes of one (H, W) shape,
+    each read in place through its own pointer and non-negative strides -> (n, P, wh, ww) float32.  Per plane (entries may be
+    None): ``fills`` -- elements with the bits of float32(fill) become 0; ``scales`` -- else one float32 multiply by float32(scale);
+    ``clips`` -- then (lo, hi) as ``numpy.clip``: the order of ``window_dataset.window_cut``."""
+    P = len(planes)
+    if not 1 <= P <= _lib.SCENE_MAX_PLANES:
+        raise ValueError(f"scene_gather_planes: {P} planes (1 .. {_lib.SCENE_MAX_PLANES} expected)")
+    H, W = (int(v) for v in planes[0].shape[-2:])
+    for p in planes:
+        if not isinstance(p, torch.Tensor) or p.dim() != 2 or p.dtype != torch.float32 or tuple(p.shape) != (H, W):
+            raise TypeError("scene_gather_planes: every plane must be an (H, W) float32 tensor of one shape")
+        _lib.require_device(p)
+    _check_table("scene_gather_planes", table_dev, table_host, first, n)
+    wh, ww = window
+    dev = planes[0].device
+    if out is None:
+        out = torch.empty((n, P, wh, ww), dtype=torch.float32, device=dev)
+    elif out.dtype != torch.float32 or not out.is_contiguous() or out.numel() != n * P * wh * ww or out.device != dev:
+        raise ValueError("scene_gather_planes: out must be a dense float32 (n, P, wh, ww) tensor on the planes' device")
+    a = _lib.sc_scene_planes_args()
+    a.P, a.H, a.W = P, H, W
+    a.pad_top, a.pad_left = int(pads[0]), int(pads[1])
+    a.n, a.win_h, a.win_w = int(n), int(wh), int(ww)
+    for i, p in enumerate(planes):
+        a.src[i] = p.data_ptr()
+        a.row_stride[i], a.col_stride[i] = p.stride()
+        fill, scale, clip = (seq[i] if seq is not None else None for seq in (fills, scales, clips))
+        ops = 0
+        if fill is not None:
+            ops |= _lib.WCUT_FILL
+            a.fill_bits[i] = float_bits(fill)
+        if scale is not None:
+            ops |= _lib.WCUT_SCALE
+            a.scale[i] = float(np.float32(scale))
+        if clip is not None:
+            ops |= _lib.WCUT_CLIP
+            a.clip_lo[i], a.clip_hi[i] = float(clip[0]), float(clip[1])
+        a.ops[i] = ops
+    a.win = table_dev.data_ptr() + 32 * first
+    a.win_host = table_host.ctypes.data + 32 * first
+    a.out = out.data_ptr()
+    _lib.check(_lib.load().sc_scene_gather_planes(C.byref(a), _lib.stream()))
+    return out
+
+
+def scene_core_counts(plane, fill, table_dev, table_host, out=None):
+    """``sc_scene_core_counts``: for every row of the table the number of pixels in the window's core destination rectangle of the
+    (H, W) float32 device ``plane`` whose bits differ from float32(fill) -> int32 (n,) device tensor (no synchronisation)."""
+    if not isinstance(plane, torch.Tensor) or plane.dim() != 2 or plane.dtype != torch.float32:
+        raise TypeError("scene_core_counts: plane must be an (H, W) float32 tensor")
+    _lib.require_device(plane)
+    n = int(table_host.shape[0])
+    _check_table("scene_core_counts", table_dev, table_host, 0, n)
+    if out is None:
+        out = torch.empty((n,), dtype=torch.int32, device=plane.device)
+    _lib.check(_lib.load().sc_scene_core_counts(plane.data_ptr(), plane.stride(0), plane.stride(1), plane.shape[0], plane.shape[1],
+                                                float_bits(fill), table_dev.data_ptr(), table_host.ctypes.data, n, out.data_ptr(),
+                                                _lib.stream()))
     return out
 
 
