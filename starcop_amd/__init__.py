@@ -22,6 +22,7 @@ Public surface (mirrors the reference):
   starcop_amd.model_module_regression.ModelModuleRegression / l1 / mse (the regression twin; get_model serves both modes);
     starcop_amd.pointwise_net.SimpleCNN_v2 / SimpleCNN_v3; features.set_learned_model (the learned band-ratio product)
   starcop_amd.sentinel2.CDModel (predict / predict_scene: the whole-tile cloud mask) / scene_windows / cloud_mask_file / load_weights
+  starcop_amd.scene.scene_windows / scene_table / table_rows / window_batches (the window plan of both predict_scene; sentinel2 re-exports it)
 All compute runs in starcop_amd/libstarcop_hip.so (include/starcop_hip.h); there is no CPU fallback.
 """
 __version__ = "0.1.0"

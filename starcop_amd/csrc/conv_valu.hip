@@ -8,6 +8,7 @@
 // (the 13-band, 4-class cloud detector of starcop/sentinel2/models.py:63-78).
 #include <type_traits>
 #include "sc_common.h"
+#include "sc_scene.h"
 #ifndef SC_HEAD_RB
 #define SC_HEAD_RB 18     // patch rows (x2 loads) a wave keeps in flight while staging the head forward tile
 #endif
@@ -2452,16 +2453,7 @@ extern "C" int sc_head_conv_fwd_k_mosaic(const sc_src* in, const float* w, const
   SC_REQUIRE(w && mosaic && win && win_host && N > 0 && H > 0 && W > 0, "sc_head_conv_fwd_k_mosaic: bad argument");
   SC_REQUIRE(mos_h > 0 && mos_w > 0 && pitch >= mos_w, "sc_head_conv_fwd_k_mosaic: bad mosaic %d x %d, pitch %lld", mos_h, mos_w, (long long)pitch);
   SC_REQUIRE((uintptr_t)win % 4 == 0, "sc_head_conv_fwd_k_mosaic: misaligned window table");
-  for (int i = 0; i < N; ++i) {
-    const sc_scene_win& q = win_host[i];
-    if (q.core_y1 <= q.core_y0 || q.core_x1 <= q.core_x0) continue;      // empty core: nothing is stored
-    SC_REQUIRE(q.core_y0 >= 0 && q.core_y1 <= H && q.core_x0 >= 0 && q.core_x1 <= W,
-               "sc_head_conv_fwd_k_mosaic: core %d (rows %d:%d, columns %d:%d) is not inside the %d x %d plane", i, q.core_y0, q.core_y1,
-               q.core_x0, q.core_x1, H, W);
-    SC_REQUIRE(q.dst_row >= 0 && (long long)q.dst_row + (q.core_y1 - q.core_y0) <= mos_h && q.dst_col >= 0 &&
-                   (long long)q.dst_col + (q.core_x1 - q.core_x0) <= mos_w,
-               "sc_head_conv_fwd_k_mosaic: core %d does not fit the %d x %d mosaic at row %d, column %d", i, mos_h, mos_w, q.dst_row, q.dst_col);
-  }
+  if (int e = sc_scene_check_cores("sc_head_conv_fwd_k_mosaic", win_host, N, H, W, mos_h, mos_w)) return e;
   launch_head_fwdk(in, w, bias, nullptr, nullptr, HeadMosaic{win, mosaic, (long long)pitch, mos_h, mos_w}, N, Cin, K, H, W, (hipStream_t)stream);
   SC_LAUNCH_OK("sc_head_conv_fwd_k_mosaic");
   return SC_OK;
@@ -2481,16 +2473,7 @@ extern "C" int sc_head_conv_fwd_mosaic_prob(const sc_src* in, const float* w, co
              "sc_head_conv_fwd_mosaic_prob: bad mosaic %d x %d, pitches %lld / %lld", mos_h, mos_w, (long long)prob_pitch, (long long)mask_pitch);
   SC_REQUIRE((uintptr_t)win % 4 == 0 && (uintptr_t)prob % 4 == 0 && (uintptr_t)valid % 4 == 0, "sc_head_conv_fwd_mosaic_prob: misaligned pointer");
   SC_REQUIRE(!valid || (valid_row_stride >= 0 && valid_col_stride >= 0), "sc_head_conv_fwd_mosaic_prob: negative stride of the valid plane");
-  for (int i = 0; i < N; ++i) {
-    const sc_scene_win& q = win_host[i];
-    if (q.core_y1 <= q.core_y0 || q.core_x1 <= q.core_x0) continue;      // empty core: nothing is stored
-    SC_REQUIRE(q.core_y0 >= 0 && q.core_y1 <= H && q.core_x0 >= 0 && q.core_x1 <= W,
-               "sc_head_conv_fwd_mosaic_prob: core %d (rows %d:%d, columns %d:%d) is not inside the %d x %d plane", i, q.core_y0, q.core_y1,
-               q.core_x0, q.core_x1, H, W);
-    SC_REQUIRE(q.dst_row >= 0 && (long long)q.dst_row + (q.core_y1 - q.core_y0) <= mos_h && q.dst_col >= 0 &&
-                   (long long)q.dst_col + (q.core_x1 - q.core_x0) <= mos_w,
-               "sc_head_conv_fwd_mosaic_prob: core %d does not fit the %d x %d mosaic at row %d, column %d", i, mos_h, mos_w, q.dst_row, q.dst_col);
-  }
+  if (int e = sc_scene_check_cores("sc_head_conv_fwd_mosaic_prob", win_host, N, H, W, mos_h, mos_w)) return e;
   HeadProbMosaic mo;
   mo.win = win; mo.mosaic = mask; mo.pitch = (long long)mask_pitch; mo.h = mos_h; mo.w = mos_w;
   mo.prob = prob; mo.prob_pitch = (long long)prob_pitch;

@@ -15,6 +15,7 @@
 #include <limits.h>
 
 #include "sc_common.h"
+#include "sc_scene.h"
 
 namespace {
 
@@ -198,13 +199,8 @@ extern "C" int sc_scene_gather_planes(const sc_scene_planes_args* a, sc_stream s
   SC_REQUIRE(a->out && a->win && a->win_host, "sc_scene_gather_planes: null pointer");
   SC_REQUIRE(a->P >= 1 && a->P <= SP_PMAX, "sc_scene_gather_planes: P=%d outside [1, %d]", a->P, SP_PMAX);
   SC_REQUIRE(a->H >= 1 && a->W >= 1, "sc_scene_gather_planes: bad scene dims %d x %d", a->H, a->W);
-  SC_REQUIRE(a->pad_top >= 0 && a->pad_top < a->H && a->pad_left >= 0 && a->pad_left < a->W,
-             "sc_scene_gather_planes: reflect padding (%d, %d) needs the image (%d x %d) to be larger than the pad", a->pad_top, a->pad_left,
-             a->H, a->W);
-  SC_REQUIRE(a->n >= 1 && a->n <= (1 << 20), "sc_scene_gather_planes: n=%d outside [1, 2^20]", a->n);
-  SC_REQUIRE(a->win_h >= 1 && a->win_w >= 4 && a->win_w % 4 == 0 && (long long)a->win_h * a->win_w < (1ll << 31),
-             "sc_scene_gather_planes: bad window size %d x %d (the width must be a multiple of 4)", a->win_h, a->win_w);
-  SC_REQUIRE((uintptr_t)a->out % 16 == 0 && (uintptr_t)a->win % 4 == 0, "sc_scene_gather_planes: misaligned output or window table");
+  if (int e = sc_scene_check_gather("sc_scene_gather_planes", a->H, a->W, a->pad_top, a->pad_left, a->n, a->win_h, a->win_w, a->out, a->win, a->win_host))
+    return e;
   PlanesD d;
   for (int p = 0; p < SP_PMAX; ++p) {
     const bool on = p < a->P;
@@ -226,13 +222,6 @@ extern "C" int sc_scene_gather_planes(const sc_scene_planes_args* a, sc_stream s
     d.scale[p] = on ? a->scale[p] : 1.f;
     d.lo[p] = on ? a->clip_lo[p] : 0.f;
     d.hi[p] = on ? a->clip_hi[p] : 0.f;
-  }
-  for (int i = 0; i < a->n; ++i) {
-    const sc_scene_win& q = a->win_host[i];
-    SC_REQUIRE(q.row_off >= 0 && q.col_off >= 0 && (long long)q.row_off + a->win_h - a->pad_top <= 2ll * a->H - 1 &&
-                   (long long)q.col_off + a->win_w - a->pad_left <= 2ll * a->W - 1,
-               "sc_scene_gather_planes: window %d (row %d, col %d, %d x %d) leaves the reflect-padded scene (pads must stay below the image size)",
-               i, q.row_off, q.col_off, a->win_h, a->win_w);
   }
   d.win = a->win; d.out = a->out;
   d.P = a->P; d.H = a->H; d.W = a->W; d.pad_top = a->pad_top; d.pad_left = a->pad_left;
@@ -284,21 +273,9 @@ extern "C" int sc_scene_gather(const sc_scene_args* a, sc_stream stream) {
   SC_REQUIRE(a->C >= 1 && a->H >= 1 && a->W >= 1, "sc_scene_gather: bad scene dims %d x %d x %d", a->C, a->H, a->W);
   SC_REQUIRE(a->chan_stride >= 0 && a->row_stride >= 0 && a->col_stride >= 0, "sc_scene_gather: negative stride");
   SC_REQUIRE((uintptr_t)a->src % a->elem_bytes == 0, "sc_scene_gather: the source is not aligned to its %d-byte elements", a->elem_bytes);
-  SC_REQUIRE(a->pad_top >= 0 && a->pad_top < a->H && a->pad_left >= 0 && a->pad_left < a->W,
-             "sc_scene_gather: reflect padding (%d, %d) needs the image (%d x %d) to be larger than the pad", a->pad_top, a->pad_left, a->H, a->W);
-  SC_REQUIRE(a->n >= 1 && a->n <= (1 << 20), "sc_scene_gather: n=%d outside [1, 2^20]", a->n);
-  SC_REQUIRE(a->win_h >= 1 && a->win_w >= 4 && a->win_w % 4 == 0 && (long long)a->win_h * a->win_w < (1ll << 31),
-             "sc_scene_gather: bad window size %d x %d (the width must be a multiple of 4)", a->win_h, a->win_w);
-  SC_REQUIRE((uintptr_t)a->out % 16 == 0 && (uintptr_t)a->win % 4 == 0, "sc_scene_gather: misaligned output or window table");
   SC_REQUIRE(a->scale == a->scale, "sc_scene_gather: scale is NaN");
-  for (int i = 0; i < a->n; ++i) {
-    const sc_scene_win& q = a->win_host[i];
-    // one reflection: rows -pad_top .. 2H - 2 - pad_top of the padded scene exist, i.e. the bottom / right pad is below H / W too
-    SC_REQUIRE(q.row_off >= 0 && q.col_off >= 0 && (long long)q.row_off + a->win_h - a->pad_top <= 2ll * a->H - 1 &&
-                   (long long)q.col_off + a->win_w - a->pad_left <= 2ll * a->W - 1,
-               "sc_scene_gather: window %d (row %d, col %d, %d x %d) leaves the reflect-padded scene (pads must stay below the image size)",
-               i, q.row_off, q.col_off, a->win_h, a->win_w);
-  }
+  if (int e = sc_scene_check_gather("sc_scene_gather", a->H, a->W, a->pad_top, a->pad_left, a->n, a->win_h, a->win_w, a->out, a->win, a->win_host))
+    return e;
   SceneD d;
   d.src = a->src; d.win = a->win; d.out = a->out;
   d.cs = a->chan_stride; d.rs = a->row_stride; d.xs = a->col_stride;

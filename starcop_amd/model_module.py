@@ -20,7 +20,7 @@ import numpy as np
 import torch
 import torch.nn
 
-from . import _lib, mag1c, metrics
+from . import _lib, mag1c, metrics, scene
 from ._lib import check, ptr, stream
 from .network import HyperStarcopUNet
 from .normalizer import DataNormalizer
@@ -386,8 +386,8 @@ class ModelModule(_Base):
                 in ``prediction`` and 0 in ``pred_binary``
             scales, clips: per plane (entries may be None) the float32 multiplier of the other elements and the (lo, hi) they are
                 clipped to afterwards: the acquisition-date factor and clip of ``window_dataset.product_ops``
-            tile, halo: the window plan, ``sentinel2.scene_windows(H, W, tile, halo)`` (defaults ``sentinel2.SCENE_TILE``,
-                ``RECEPTIVE_HALO``: with ``halo`` >= 320 the logits behind every pixel equal the whole-scene forward's)
+            tile, halo: the window plan, ``scene.scene_windows(H, W, tile, halo)`` (None: the defaults ``scene.SCENE_TILE``,
+                ``scene.RECEPTIVE_HALO``: with ``halo`` >= 320 the logits behind every pixel equal the whole-scene forward's)
             batch: windows per forward (default: the most with batch x window pixels <= 16 x 512^2)
             skip_empty: with a ``fill_value``, windows whose core holds no data pixel of the first plane are neither cut nor run
                 (one ``sc_scene_core_counts`` launch and one read-back of n ints decide)
@@ -401,7 +401,6 @@ class ModelModule(_Base):
             {"prediction": (H, W) float32, "pred_binary": (H, W) uint8, "windows": n, "windows_run": k} -- numpy arrays for numpy
             planes, device tensors for device tensors
         """
-        from . import sentinel2
         if isinstance(planes, (np.ndarray, torch.Tensor)):
             if len(planes.shape) != 3:
                 raise ValueError(f"ModelModule.predict_scene: expected (C, H, W) or a list of (H, W) planes, got shape {tuple(planes.shape)}")
@@ -429,7 +428,7 @@ class ModelModule(_Base):
         fills = [fill_value] * C_ if fill_value is None or np.isscalar(fill_value) else per_plane("fill_value", fill_value)
         scales, clips = per_plane("scales", scales), per_plane("clips", clips)
         H, W = (int(v) for v in planes[0].shape)
-        plan = sentinel2.scene_windows(H, W, sentinel2.SCENE_TILE if tile is None else tile, sentinel2.RECEPTIVE_HALO if halo is None else halo)
+        plan = scene.scene_windows(H, W, scene.SCENE_TILE if tile is None else tile, scene.RECEPTIVE_HALO if halo is None else halo)
         if self.num_classes != 1:
             raise ValueError(f"ModelModule.predict_scene: the binary model only (num_classes={self.num_classes})")
         dev = self.device
@@ -439,8 +438,7 @@ class ModelModule(_Base):
             planes = [torch.from_numpy(np.ascontiguousarray(p) if any(st < 0 for st in p.strides) else p).to(dev) for p in planes]
         for p in planes:
             _lib.require_device(p)
-        wh, ww = plan.window
-        table = sentinel2.scene_table(plan)
+        table = scene.scene_table(plan)
         n = table.shape[0]
         table_dev = torch.from_numpy(table).to(dev)
         masked = fills[0] is not None
@@ -451,7 +449,7 @@ class ModelModule(_Base):
             prediction = torch.empty((H, W), dtype=torch.float32, device=dev)
             pred_binary = torch.empty((H, W), dtype=torch.uint8, device=dev)
         if masked and skip_empty:
-            counts = sentinel2.scene_core_counts(planes[0], fills[0], table_dev, table).cpu().numpy()
+            counts = scene.scene_core_counts(planes[0], fills[0], table_dev, table).cpu().numpy()
             run = np.flatnonzero(counts > 0)
             if run.shape[0] < n:
                 table = np.ascontiguousarray(table[run])
@@ -460,21 +458,14 @@ class ModelModule(_Base):
             run = np.arange(n)
         k_run = int(run.shape[0])
         if k_run:
-            if batch is None:
-                batch = max(1, sentinel2.SCENE_BATCH_PIXELS // (wh * ww))
-            batch = max(1, min(int(batch), k_run))
             was = self.training
             if was:
                 self.eval()
             try:
                 cst = self.normalizer.consts(dev)
-                bufs = {}
-                for first in range(0, k_run, batch):
-                    k = min(batch, k_run - first)
-                    if k not in bufs:
-                        bufs[k] = torch.empty((k, C_, wh, ww), dtype=torch.float32, device=dev)
-                    x = sentinel2.scene_gather_planes(planes, (plan.pad_rows[0], plan.pad_cols[0]), table_dev, table, first, k, plan.window,
-                                                      fills, scales, clips, out=bufs[k])
+                for first, k, buf in scene.window_batches(k_run, plan.window, C_, dev, batch):
+                    x = scene.scene_gather_planes(planes, (plan.pad_rows[0], plan.pad_cols[0]), table_dev, table, first, k, plan.window,
+                                                  fills, scales, clips, out=buf)
                     self.network.predict_masks_into(x, prediction, pred_binary, (table_dev, table, first), cst,
                                                     valid=planes[0] if masked else None, fill_value=fills[0], nodata=nodata)
             finally:

@@ -17,6 +17,7 @@ are applied by the consumer while it stages tiles into LDS, nearest x2 upsamplin
 concat are address arithmetic in the consumer, and the backward pass applies the BatchNorm /
 activation backward the same way (g, y -> dy on load).
 """
+import collections
 import ctypes as C
 import math
 import os
@@ -24,7 +25,7 @@ import os
 import torch
 import torch.nn as nn
 
-from . import _lib
+from . import _lib, scene
 from ._lib import (ACT_NONE, ACT_RELU, ACT_RELU6, SC_CST, sc_irb_args, sc_irt_args, SRC_AFFINE, SRC_BNBWD, SRC_NORM, SRC_RAW, STAT_BNBWD, sc_wgrad_pending,
                    PACK_PW3, PACK_SP, PACK_SPD, PACK_THIN16, STAT_PW3, STAT_CONV1, STAT_CONV1K, STAT_CONV3, STAT_DW, STAT_STEM, TERMS_F16X2, check, make_src, ptr, sc_bn_tail, sc_bnr_args,
                    sc_conv_args, sc_wgrad_args, stream)
@@ -33,6 +34,9 @@ MBV2_SETTINGS = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2),
                  (6, 96, 3, 1), (6, 160, 3, 2), (6, 320, 1, 1))
 DECODER_CHANNELS = (256, 128, 64, 32, 16)
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
+# where the head of a scene batch writes its cores (_forward_impl(head="mosaic" | "probmosaic")): win / win_host = scene.table_rows of the
+# batch; classes: the uint8 mosaic of "mosaic"; prob / mask (either may be None) / valid / fill_bits / nodata: those of "probmosaic"
+HeadMosaic = collections.namedtuple("HeadMosaic", "win win_host classes prob mask valid fill_bits nodata", defaults=(None,) * 4 + (0, 0.0))
 
 
 # ----------------------------------------------------------------------------------------------
@@ -963,10 +967,9 @@ class HyperStarcopUNet(nn.Module):
     def _forward_impl(self, x, x_cst, training, need_grad, _recheck=0, head="logits", mosaic=None):
         """x: (N,C,H,W) fp32 device tensor (raw physical units if x_cst is given, else already normalised).
         head: "logits" -> plan.buf["logits"] (N,K,H,W); "classes" -> plan.classes (N,H,W) uint8 = argmax over K, no logits stored;
-        "mosaic" -> the classes of every item's core rectangle into mosaic = (uint8 (h, w) tensor, device table, host table, first
-        row), see predict_classes_into: neither logits nor per-item classes are stored; "probmosaic" -> sigmoid and mask of the
-        cores of the 1-class head into mosaic = (prob or None, mask or None, device table, host table, first row, valid plane or
-        None, fill bits, nodata), see predict_masks_into: likewise nothing else is stored."""
+        "mosaic" -> the classes of every item's core rectangle into ``mosaic.classes``, see predict_classes_into: neither logits nor
+        per-item classes are stored; "probmosaic" -> sigmoid and mask of the cores of the 1-class head into ``mosaic.prob`` /
+        ``mosaic.mask``, see predict_masks_into: likewise nothing else is stored.  ``mosaic``: a :class:`HeadMosaic`."""
         if training and (self.classes > self.MAX_TRAIN_CLASSES or self.in_channels > self.MAX_TRAIN_IN_CHANNELS):
             raise NotImplementedError(
                 f"HyperStarcopUNet(in_channels={self.in_channels}, classes={self.classes}) runs in eval mode only: training needs two "
@@ -1159,18 +1162,18 @@ class HyperStarcopUNet(nn.Module):
             elif ty == "head":
                 s = self._src_of(plan, op["ins"][0])
                 if head == "mosaic":
-                    mos, tab_dev, tab_host, first = mosaic
+                    mos = mosaic.classes
                     check(lib.sc_head_conv_fwd_k_mosaic(C.byref(s), ptr(conv.weight), ptr(conv.bias), ptr(mos), mos.shape[0], mos.shape[1],
-                                                        mos.stride(0), tab_dev.data_ptr() + 32 * first, tab_host.ctypes.data + 32 * first,
+                                                        mos.stride(0), mosaic.win, mosaic.win_host,
                                                         N, conv.in_channels, self.classes, Ho, Wo, st))
                 elif head == "probmosaic":
-                    prob, mask, tab_dev, tab_host, first, valid, fill_bits, nodata = mosaic
+                    prob, mask, valid = mosaic.prob, mosaic.mask, mosaic.valid
                     ref = prob if prob is not None else mask
                     check(lib.sc_head_conv_fwd_mosaic_prob(
                         C.byref(s), ptr(conv.weight), ptr(conv.bias), ptr(prob), prob.stride(0) if prob is not None else 0,
                         ptr(mask), mask.stride(0) if mask is not None else 0, ref.shape[0], ref.shape[1],
                         ptr(valid), valid.stride(0) if valid is not None else 0, valid.stride(1) if valid is not None else 0,
-                        fill_bits, nodata, tab_dev.data_ptr() + 32 * first, tab_host.ctypes.data + 32 * first,
+                        mosaic.fill_bits, mosaic.nodata, mosaic.win, mosaic.win_host,
                         N, conv.in_channels, Ho, Wo, st))
                 elif self.classes == 1 and head == "logits":
                     check(lib.sc_head_conv_fwd(C.byref(s), ptr(conv.weight), ptr(conv.bias), ptr(plan.buf[o.name]),
@@ -1895,19 +1898,14 @@ class HyperStarcopUNet(nn.Module):
         (sc_head_conv_fwd_k_mosaic) into ``mosaic``, a uint8 (h, w) device tensor with unit column stride.  ``table`` = (device int32
         (n, 8) tensor, the same contiguous int32 numpy array on the host, first row): rows first .. first + N - 1 are the
         ``sc_scene_win`` of the batch -- core y0, y1, x0, x1 inside the window at [2:6], the core's row and column in the mosaic at
-        [6:8] (sentinel2.scene_table).  No logits and no (N, H, W) class tensor exist.  Eval mode only.  Returns ``mosaic``."""
+        [6:8] (scene.scene_table).  No logits and no (N, H, W) class tensor exist.  Eval mode only.  Returns ``mosaic``."""
         if self.training:
             raise RuntimeError("HyperStarcopUNet.predict_classes_into: eval mode only (call .eval() first)")
-        import numpy as np
-        tab_dev, tab_host, first = table
         _lib.require_device(mosaic)
         if mosaic.dtype != torch.uint8 or mosaic.dim() != 2 or mosaic.stride(1) != 1:
             raise ValueError("predict_classes_into: mosaic must be a uint8 (h, w) tensor with unit column stride")
-        if (tab_dev.dtype != torch.int32 or not tab_dev.is_contiguous() or tab_host.dtype != np.int32 or not tab_host.flags.c_contiguous
-                or tab_dev.dim() != 2 or tuple(tab_dev.shape) != tuple(tab_host.shape) or tab_dev.shape[1] != 8
-                or first < 0 or first + x.shape[0] > tab_dev.shape[0]):
-            raise ValueError("predict_classes_into: table must be (device int32 (n, 8), the same numpy int32 array, first) with first + N <= n")
-        self._forward_impl(x, normalizer_consts, False, False, head="mosaic", mosaic=(mosaic, tab_dev, tab_host, int(first)))
+        win, win_host = scene.table_rows("predict_classes_into", *table, x.shape[0])
+        self._forward_impl(x, normalizer_consts, False, False, head="mosaic", mosaic=HeadMosaic(win, win_host, classes=mosaic))
         return mosaic
 
     @torch.no_grad()
@@ -1922,8 +1920,6 @@ class HyperStarcopUNet(nn.Module):
             raise RuntimeError("HyperStarcopUNet.predict_masks_into: eval mode only (call .eval() first)")
         if self.classes != 1:
             raise ValueError(f"HyperStarcopUNet.predict_masks_into: the probability head is the 1-class model's (classes={self.classes})")
-        import numpy as np
-        tab_dev, tab_host, first = table
         if prob is None and mask is None:
             raise ValueError("predict_masks_into: at least one of prob / mask must be given")
         shapes = set()
@@ -1941,13 +1937,10 @@ class HyperStarcopUNet(nn.Module):
             _lib.require_device(valid)
             if valid.dtype != torch.float32 or tuple(valid.shape) not in shapes or fill_value is None:
                 raise ValueError("predict_masks_into: valid must be a float32 plane of the mosaics' shape, with a fill_value")
-            fill_bits = int(np.array(fill_value, dtype=np.float32).view(np.uint32))
-        if (tab_dev.dtype != torch.int32 or not tab_dev.is_contiguous() or tab_host.dtype != np.int32 or not tab_host.flags.c_contiguous
-                or tab_dev.dim() != 2 or tuple(tab_dev.shape) != tuple(tab_host.shape) or tab_dev.shape[1] != 8
-                or first < 0 or first + x.shape[0] > tab_dev.shape[0]):
-            raise ValueError("predict_masks_into: table must be (device int32 (n, 8), the same numpy int32 array, first) with first + N <= n")
+            fill_bits = scene.float_bits(fill_value)
+        win, win_host = scene.table_rows("predict_masks_into", *table, x.shape[0])
         self._forward_impl(x, normalizer_consts, False, False, head="probmosaic",
-                           mosaic=(prob, mask, tab_dev, tab_host, int(first), valid, fill_bits, float(nodata)))
+                           mosaic=HeadMosaic(win, win_host, prob=prob, mask=mask, valid=valid, fill_bits=fill_bits, nodata=float(nodata)))
         return prob, mask
 
 

@@ -19,6 +19,7 @@ import torch
 from . import mag1c
 from .features import emit_to_aviris_input
 from .model_module import masks_from_logits
+from .scene import RECEPTIVE_HALO       # noqa: F401  (re-exported: the halo of scene_tiles / tiled_logits too)
 
 EMIT_MAG1C_RANGE_NM = (2122.0, 2488.0)          # mag1c_emit.py:40-43
 RGB_NM = (640.0, 550.0, 460.0)
@@ -27,12 +28,6 @@ RGB_NM = (640.0, 550.0, 460.0)
 def nearest_bands(wavelengths, targets=RGB_NM):
     w = np.asarray(wavelengths, dtype=np.float64)
     return [int(np.argmin(np.abs(w - t))) for t in targets]
-
-
-# Receptive field of smp.Unet('mobilenet_v2'): encoder 3x3 convolutions at strides 1..32 reach 490 px, the decoder
-# adds 126 -> a logit depends on inputs at most 308 px away.  Halo >= 320 (a multiple of 32, the network's stride) therefore makes a
-# tile's core logits IDENTICAL to the whole-scene forward in eval mode (BatchNorm is affine there); smaller halos are an approximation.
-RECEPTIVE_HALO = 320
 
 
 def scene_tiles(H, W, tile=512, halo=RECEPTIVE_HALO, strips=False):

@@ -1,5 +1,5 @@
-"""Host side of the whole-scene cloud mask: the window plan of sentinel2.scene_windows and the argument checks of
-CDModel.predict_scene (no GPU)."""
+"""Host side of the whole-scene cloud mask: the window plan of scene.scene_windows (under its sentinel2 spelling), the table check
+and batch loop of starcop_amd.scene and the argument checks of CDModel.predict_scene (no GPU)."""
 import itertools
 
 import numpy as np
@@ -118,3 +118,69 @@ def test_struct_layouts_match_the_c_compiler(tmp_path):
     a = _lib.sc_scene_args
     assert got == [32, _lib.sc_scene_win.dst_row.offset, ctypes.sizeof(a), a.chan_stride.offset, a.pad_top.offset, a.scale.offset,
                    a.win.offset, a.out.offset]
+
+
+def test_moved_names_are_the_scene_module_s():
+    """sentinel2 / pipeline re-export the window machinery of starcop_amd.scene: the same objects, not copies"""
+    from starcop_amd import pipeline, scene
+    moved = [name for name in sentinel2.__all__ if hasattr(scene, name)]
+    assert set(moved) >= {"RECEPTIVE_HALO", "SCENE_TILE", "ScenePlan", "scene_windows", "scene_table", "scene_gather", "scene_gather_planes",
+                          "scene_core_counts", "float_bits"}
+    for name in moved:
+        assert getattr(sentinel2, name) is getattr(scene, name), name
+    assert sentinel2.SCENE_BATCH_PIXELS is scene.SCENE_BATCH_PIXELS
+    assert pipeline.RECEPTIVE_HALO is scene.RECEPTIVE_HALO
+
+
+def test_window_batches():
+    from starcop_amd import scene
+    cpu = torch.device("cpu")
+    got = list(scene.window_batches(5, (64, 96), 3, cpu, batch=2))
+    assert [(first, k) for first, k, _ in got] == [(0, 2), (2, 2), (4, 1)]
+    for _, k, buf in got:
+        assert buf.shape == (k, 3, 64, 96) and buf.dtype == torch.float32 and buf.device == cpu
+    assert got[0][2] is got[1][2] and got[2][2] is not got[0][2]
+    # batch=None: the most windows below SCENE_BATCH_PIXELS, clamped to [1, n]
+    per = scene.SCENE_BATCH_PIXELS // (64 * 96)
+    assert per > 5 and [(f, k) for f, k, _ in scene.window_batches(5, (64, 96), 1, cpu)] == [(0, 5)]
+    assert [(f, k) for f, k, _ in scene.window_batches(per + 3, (64, 96), 1, cpu)] == [(0, per), (per, 3)]
+    big = (4096, 2048)                              # one window above the pixel budget: still one per batch
+    assert scene.SCENE_BATCH_PIXELS // (big[0] * big[1]) == 0
+    assert [(f, k) for f, k, _ in scene.window_batches(2, big, 1, torch.device("meta"))] == [(0, 1), (1, 1)]
+    assert [(f, k) for f, k, _ in scene.window_batches(3, (32, 32), 1, cpu, batch=0)] == [(0, 1), (1, 1), (2, 1)]
+    assert [(f, k) for f, k, _ in scene.window_batches(3, (32, 32), 1, cpu, batch=99)] == [(0, 3)]
+
+
+def test_table_rows():
+    import ctypes
+    from starcop_amd import _lib, scene
+    host = scene.scene_table(scene.scene_windows(150, 217, 64, 32))         # (12, 8)
+    dev = torch.from_numpy(host.copy())
+    bad = [(dev.to(torch.int64), host, 0, 1), (torch.from_numpy(np.zeros((12, 16), np.int32))[:, ::2], host, 0, 1),
+           (dev[:, :7].contiguous(), np.ascontiguousarray(host[:, :7]), 0, 1), (dev, host[:11], 0, 1), (dev, host, -1, 1), (dev, host, 8, 5),
+           (dev, host.astype(np.int64), 0, 1), (dev, host, 0, 0)]
+    for who in ("scene_gather", "predict_masks_into"):
+        for args in bad:
+            with pytest.raises(ValueError, match=f"^{who}: the table must be"):
+                scene.table_rows(who, *args)
+    row = ctypes.sizeof(_lib.sc_scene_win)
+    for first, n in ((0, 12), (5, 7), (11, 1)):
+        assert scene.table_rows("t", dev, host, first, n) == (dev.data_ptr() + first * row, host.ctypes.data + first * row)
+
+
+def test_scene_module_imports_nothing_above_it():
+    """scene.py sits below network / model_module / pipeline / sentinel2 (they import it), and model_module imports it at module level"""
+    import ast
+    import inspect
+    from starcop_amd import model_module, scene
+
+    def imported(tree):
+        for node in ast.walk(tree):
+            if isinstance(node, ast.ImportFrom):
+                yield from ([node.module] if node.module else [a.name for a in node.names])
+            elif isinstance(node, ast.Import):
+                yield from (a.name.split(".")[-1] for a in node.names)
+    assert not {"network", "model_module", "pipeline", "sentinel2"} & set(imported(ast.parse(inspect.getsource(scene))))
+    mm = ast.parse(inspect.getsource(model_module))
+    assert "scene" in set(imported(ast.Module(body=[n for n in mm.body if isinstance(n, (ast.Import, ast.ImportFrom))], type_ignores=[])))
+    assert "sentinel2" not in set(imported(mm))
