@@ -1207,6 +1207,58 @@ typedef struct sc_cstats_args {
 size_t sc_component_stats_workspace_bytes(int N, int H, int W, int M, int P);
 int sc_component_stats(const sc_cstats_args* a, void* work, size_t work_bytes, sc_stream stream);
 
+/* Outlines of the components of a label image: polygon rings per plume (starcop_amd/plumes.py: component_outlines).  labels is
+ * one int32 H x W image, 0 (and anything below) background, component k the pixels of value k.  The outline of k is made of
+ * directed unit edges on the (H+1) x (W+1) lattice of pixel corners (corner (r, c) = the upper-left corner of pixel (r, c)),
+ * one for every side of a pixel of value k whose neighbour is not k or lies outside, directed so that k is on the RIGHT (row axis
+ * down): top (r,c)->(r,c+1), right (r,c+1)->(r+1,c+1), bottom (r+1,c+1)->(r+1,c), left (r+1,c)->(r,c).  Edges are numbered in
+ * raster order of their pixel, then top, right, bottom, left.  The successor of an edge is the edge of the same value that leaves
+ * its end corner; where two pixels of k meet diagonally with neither of the other two being k, connectivity 2 turns left (crosses
+ * to the diagonal pixel), connectivity 1 turns right.  The cycles of the successor are the rings; a ring's signed doubled area is
+ * sum(col_i * row_{i+1} - col_{i+1} * row_i): > 0 an exterior, < 0 a hole.  A ring may touch itself at such a corner.
+ * The call is made in stages, the caller's scans and sort between them (all buffers device memory, one stream):
+ *   SC_OUTLINE_COUNT   cnt[H*W] <- boundary sides per pixel.       caller: prefix = inclusive scan of cnt, E = prefix[H*W-1]
+ *   SC_OUTLINE_TRACE   successors, ceil(log2 E) + 1 pointer-doubling launches, areas.  keys[E] <- (value << 33 | hole << 32 | the
+ *                      ring's smallest edge) at that edge, INT64_MAX elsewhere; stats[2] <- {rings R, corner vertices}
+ *                                                                  caller: sorted_keys = the R smallest keys in ascending order
+ *   SC_OUTLINE_RINGS   ring_label[R], ring_area2[R], ring_len[R] (edges of the ring) in that order: value, exterior first, first
+ *                      edge.                                       caller: ring_start[R+1] = exclusive scan of ring_len
+ *   SC_OUTLINE_SCATTER ordered[E][2] <- (row, col) of the start corner of every edge, ring after ring, each from its smallest
+ *                      edge on; ordered_keep[E] <- 1 where the incoming and the outgoing edge differ in direction.
+ *                                                                  caller: keep_prefix = inclusive scan of ordered_keep
+ *   SC_OUTLINE_COMPACT vertices[V][2] <- the kept corners; ring_offsets[R+1] <- their ring boundaries (V = stats[1]).
+ * With every vertex wanted, `ordered` and `ring_start` are the result and COMPACT is not called.  E = 0 needs no call after COUNT.
+ * work: sc_component_outlines_workspace_bytes(H, W, E) bytes, the same buffer from TRACE to the last stage; cnt and prefix are
+ * the only per-pixel buffers (8 bytes per pixel).  SC_ERR_ARG, before any launch, when 4*H*W >= 2^31 (the workspace size is then
+ * 0), for a connectivity other than 1 or 2, a null pointer the stage needs, counts out of range or a workspace that is too
+ * small.  Integer arithmetic and integer atomic adds only: repeated calls give identical bytes.  No launch waits on another
+ * work-group: every doubling round is its own launch.                                                                       */
+enum sc_outline_stage { SC_OUTLINE_COUNT = 0, SC_OUTLINE_TRACE = 1, SC_OUTLINE_RINGS = 2, SC_OUTLINE_SCATTER = 3, SC_OUTLINE_COMPACT = 4 };
+typedef struct sc_outline_args {
+  const int32_t* labels;                          /* [H][W]                                                        */
+  int32_t H, W, connectivity, reserved;
+  int64_t E, R, V;                                /* edges (from TRACE on), rings (from RINGS on), vertices (COMPACT) */
+  int32_t* cnt;                                   /* [H*W]                                                         */
+  const int32_t* prefix;                          /* [H*W] inclusive scan of cnt                                   */
+  void* work;
+  size_t work_bytes;
+  int64_t* keys;                                  /* [E]                                                           */
+  int32_t* stats;                                 /* [2]                                                           */
+  const int64_t* sorted_keys;                     /* [R]                                                           */
+  int32_t* ring_label;                            /* [R]                                                           */
+  int64_t* ring_area2;                            /* [R]                                                           */
+  int64_t* ring_len;                              /* [R]                                                           */
+  const int64_t* ring_start;                      /* [R+1]                                                         */
+  int32_t* ordered;                               /* [E][2]                                                        */
+  int32_t* ordered_keep;                          /* [E]                                                           */
+  const int32_t* keep_prefix;                     /* [E] inclusive scan of ordered_keep                            */
+  int32_t* vertices;                              /* [V][2]                                                        */
+  int64_t* ring_offsets;                          /* [R+1]                                                         */
+} sc_outline_args;
+size_t sc_component_outlines_workspace_bytes(int H, int W, int64_t E);
+int sc_component_outlines_rounds(int64_t E);      /* pointer-doubling launches of TRACE for E edges                 */
+int sc_component_outlines(const sc_outline_args* a, int stage, sc_stream stream);
+
 /* ------------------------------------------------------------------------- */
 /* HOST functions (no device involved): decoders of the on-disk sample format -- one tiled GeoTIFF per product per sample,
  * read by rasterio in the reference (starcop/data/dataset.py:66-76, written by save_cog at sampling_dataset.py:332-355).

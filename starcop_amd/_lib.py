@@ -221,6 +221,19 @@ class sc_cstats_args(C.Structure):
                 ("argmax", C.c_void_p)]
 
 
+OUTLINE_COUNT, OUTLINE_TRACE, OUTLINE_RINGS, OUTLINE_SCATTER, OUTLINE_COMPACT = range(5)       # enum sc_outline_stage
+
+
+class sc_outline_args(C.Structure):
+    """component-outline operands (include/starcop_hip.h: sc_outline_args)"""
+    _fields_ = [("labels", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("connectivity", C.c_int32), ("reserved", C.c_int32),
+                ("E", C.c_int64), ("R", C.c_int64), ("V", C.c_int64), ("cnt", C.c_void_p), ("prefix", C.c_void_p),
+                ("work", C.c_void_p), ("work_bytes", C.c_size_t), ("keys", C.c_void_p), ("stats", C.c_void_p),
+                ("sorted_keys", C.c_void_p), ("ring_label", C.c_void_p), ("ring_area2", C.c_void_p), ("ring_len", C.c_void_p),
+                ("ring_start", C.c_void_p), ("ordered", C.c_void_p), ("ordered_keep", C.c_void_p), ("keep_prefix", C.c_void_p),
+                ("vertices", C.c_void_p), ("ring_offsets", C.c_void_p)]
+
+
 _vp, _i, _f, _d, _sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/starcop_hip.h declares
@@ -368,6 +381,9 @@ SIGNATURES = {
     "sc_render_panels": (_i, [_vp, C.POINTER(sc_panel), _i, _vp, _vp, _i, _i, _vp]),
     "sc_component_stats_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "sc_component_stats": (_i, [C.POINTER(sc_cstats_args), _vp, _sz, _vp]),
+    "sc_component_outlines_workspace_bytes": (_sz, [_i, _i, C.c_int64]),
+    "sc_component_outlines_rounds": (_i, [C.c_int64]),
+    "sc_component_outlines": (_i, [C.POINTER(sc_outline_args), _i, _vp]),
     "sc_tiff_lzw_decode": (_i, [_vp, _sz, _vp, _sz, C.POINTER(C.c_size_t)]),
     "sc_tiff_unpredict": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp]),
 }

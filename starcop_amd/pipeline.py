@@ -225,7 +225,7 @@ def _emit_predict_parts(model, sub, rgb, ratio, template, fill_value, column_ste
 @torch.no_grad()
 def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_lerp_alpha=1e-4, tile=None, halo=RECEPTIVE_HALO,
                          ratio_bands=None, distributed=None, group=None, rows=None, threads=8, strips=True, georeferenced=False,
-                         out_folder=None, geotransform=None, overwrite=False, plumes=False):
+                         out_folder=None, geotransform=None, overwrite=False, plumes=False, plume_outlines=False):
     """The notebook path of the reference end to end FROM THE FILE (notebooks/inference_on_raw_EMIT_nc_file.ipynb cells 8-19:
     ``EMITImage(path)`` -> ``mag1c_emit`` -> RGB bands -> rescale -> ``model`` -> threshold): opens the EMIT L1B radiance granule
     (NetCDF-4) with :mod:`starcop_amd.hdf5_reader`, reads ONLY what the pipeline touches -- the contiguous band slice inside
@@ -246,13 +246,17 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
     ``plumes=True`` adds ``plumes``, the :func:`starcop_amd.plumes.plume_table` of ``pred_binary`` with ``mf`` as mag1c and
     ``prediction`` as probability -- on the orthorectified products (with ``x`` / ``y`` from the geotransform, when there is one)
     if ``georeferenced=True``, on the sensor-geometry ones otherwise; pixels that carry the fill value or are not finite do not
-    count.  With ``out_folder`` the table is also written as ``plumes.csv`` (same ``overwrite`` rule) and listed in ``files``."""
+    count.  With ``out_folder`` the table is also written as ``plumes.csv`` (same ``overwrite`` rule) and listed in ``files``.
+    ``plume_outlines=True`` (with ``plumes=True``) adds ``plume_outlines``, the :func:`starcop_amd.plumes.plume_outlines` of the same
+    mask in the same coordinates, and with ``out_folder`` writes ``plumes.geojson``, one Polygon per row of the table."""
     from .hdf5_reader import H5File
     if out_folder is not None:
         if str(out_folder).startswith("gs://"):
             raise NotImplementedError(f"{out_folder}: writing to Google Cloud Storage is not supported")
         if not georeferenced:
             raise ValueError("emit_granule_predict: out_folder writes the orthorectified products; pass georeferenced=True")
+    if plume_outlines and not plumes:
+        raise ValueError("emit_granule_predict: plume_outlines=True needs plumes=True")
     if georeferenced and rows is not None:
         raise ValueError("emit_granule_predict: georeferenced=True needs the whole granule (rows=None): the GLT indexes all of its lines")
     dev = model.device
@@ -289,16 +293,28 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
     gt = geotransform if geotransform is not None else root.get("geotransform")
     if plumes:
         out["plumes"] = _emit_plume_table(out, fill, gt if georeferenced else None)
+        if plume_outlines:
+            from .plumes import plume_outlines as outlines_of
+            out["plume_outlines"] = outlines_of(out["pred_binary"], geotransform=gt if georeferenced else None)
     if out_folder is not None:
         out["files"] = _write_emit_products(out, str(out_folder), fill, gt, root.get("spatial_ref"), overwrite)
         if plumes:
-            import os
-            from .plumes import write_plumes
-            path = os.path.join(str(out_folder), "plumes.csv")
-            if overwrite or not os.path.exists(path):
-                os.makedirs(str(out_folder), exist_ok=True)
-                out["files"].append(write_plumes(out["plumes"], path))
+            out["files"] += _write_plume_files(out, str(out_folder), overwrite)
     return out
+
+
+def _write_plume_files(out, folder, overwrite):
+    """``plumes.csv`` and, with outlines, ``plumes.geojson`` (polygons) of a prediction dict -> the paths written"""
+    import os
+    from .plumes import write_plumes
+    files = []
+    todo = [("plumes.csv", None)] + ([("plumes.geojson", out["plume_outlines"])] if "plume_outlines" in out else [])
+    for name, outlines in todo:
+        path = os.path.join(folder, name)
+        if overwrite or not os.path.exists(path):
+            os.makedirs(folder, exist_ok=True)
+            files.append(write_plumes(out["plumes"], path, outlines=outlines))
+    return files
 
 
 def _emit_plume_table(out, fill, geotransform):
@@ -437,7 +453,7 @@ AVIRIS_PRODUCT_FILES = {"pred.tif": ("prediction", ["Plume probability"]), "pred
 @torch.no_grad()
 def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=None, toa_correction_factor=None, solar_altitude=None,
                          normalize_by_acquisition_date=True, tile=None, halo=None, batch=None, plumes=False, overwrite=False,
-                         device="cuda"):
+                         device="cuda", plume_outlines=False):
     """An orthorectified AVIRIS-NG flight line through the plume model, file to file: ``{folder}/{name}_img`` (ENVI radiance,
     float32) -> the network's input products -> ``model.predict_scene`` -> (with ``out_folder``) ``pred.tif`` / ``predbinary.tif``.
 
@@ -454,13 +470,17 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
     ``plumes.plume_table`` of the mask with ``mf`` and ``prediction`` and the geotransform / pixel area of the ENVI ``map info``.
     With ``out_folder``: ``pred.tif`` (float32, GDAL_NODATA = ``mag1c.NODATA``) and ``predbinary.tif`` (uint8), BLOCKSIZE 128, the
     radiance file's georeferencing, band descriptions; ``plumes.csv`` with ``plumes=True``; existing files are skipped unless
-    ``overwrite``; the paths written come back under ``files``."""
+    ``overwrite``; the paths written come back under ``files``.  ``plume_outlines=True`` (with ``plumes=True``) adds
+    ``plume_outlines``, the ``plumes.plume_outlines`` of the mask with the same geotransform, and writes ``plumes.geojson``, one
+    Polygon per row of the table, next to ``plumes.csv``."""
     import datetime
     import os
     import re
     from . import aviris
     from . import io_formats as io
     from .sampling import _nodata
+    if plume_outlines and not plumes:
+        raise ValueError("aviris_scene_predict: plume_outlines=True needs plumes=True")
     products = aviris_scene_products(model.input_products, normalize_by_acquisition_date)
     for path in (out_folder, mag1c_path, aviris_img_folder):
         if path is not None and str(path).startswith("gs://"):
@@ -537,6 +557,9 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
     if plumes:
         from .plumes import plume_table
         out["plumes"] = plume_table(out["pred_binary"], mag1c=mf, prob=out["prediction"], geotransform=gt, pixel_area_m2=area)
+        if plume_outlines:
+            from .plumes import plume_outlines as outlines_of
+            out["plume_outlines"] = outlines_of(out["pred_binary"], geotransform=gt)
     if out_folder is not None:
         geo = io.envi_geo_tags(header)
         nodata = {42113: (2, (_nodata_text(mag1c.NODATA),))}
@@ -549,11 +572,7 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
             io.write_tiff(path, out[key].cpu().numpy(), blocksize=128, extra_tags=tags)
             files.append(path)
         if plumes:
-            from .plumes import write_plumes
-            path = os.path.join(str(out_folder), "plumes.csv")
-            if overwrite or not os.path.exists(path):
-                os.makedirs(str(out_folder), exist_ok=True)
-                files.append(write_plumes(out["plumes"], path))
+            files += _write_plume_files(out, str(out_folder), overwrite)
         out["files"] = files
     return out
 

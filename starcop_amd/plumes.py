@@ -3,7 +3,9 @@
 ``component_stats`` reduces value planes per labelled component in libstarcop_hip.so (include/starcop_hip.h: sc_component_stats);
 ``plume_table`` labels a mask (``mask_creation.connected_components``), reduces mag1c / probability / a second mask per
 component in one call and returns one pandas row per plume; ``match_plumes`` counts detected, spurious and missed plumes between
-a predicted and a labelled mask; ``write_plumes`` writes a table as CSV or GeoJSON.
+a predicted and a labelled mask; ``component_outlines`` traces the polygon rings of every component (sc_component_outlines),
+``plume_outlines`` turns a mask into closed (x, y) rings per plume; ``write_plumes`` writes a table as CSV or GeoJSON (Points, or
+Polygons with the outlines).
 """
 import json
 
@@ -228,10 +230,183 @@ def match_plumes(pred_mask, label_mask, connectivity=2, min_overlap_px=1, min_ar
             "precision": float(metrics.precision(cm)), "recall": float(metrics.recall(cm))}
 
 
-def write_plumes(table, path):
-    """``.csv``: the table as it is (no index column).  ``.geojson``: one Point feature per plume at (``x``, ``y``) -- the table
-    must carry them, i.e. come from ``plume_table(..., geotransform=...)`` -- with every other column as a property and the
-    bounding box as ``bbox_px`` = [row_min, col_min, row_max, col_max]."""
+OUTLINE_FIELDS = ("vertices", "ring_offsets", "ring_label", "ring_area2")
+
+
+def _empty_outlines(dev):
+    return {"vertices": torch.zeros((0, 2), dtype=torch.int32, device=dev), "ring_offsets": torch.zeros(1, dtype=torch.int64, device=dev),
+            "ring_label": torch.zeros(0, dtype=torch.int32, device=dev), "ring_area2": torch.zeros(0, dtype=torch.int64, device=dev)}
+
+
+def _outlines_one(lab, connectivity, collinear):
+    """the stages of ``sc_component_outlines`` on one (H, W) int32 image, the scans and the sort of the ring keys between them"""
+    lib = _lib.load()
+    dev = lab.device
+    H, W = lab.shape
+
+    def i32(n):
+        return torch.empty(n, dtype=torch.int32, device=dev)
+
+    def i64(n):
+        return torch.empty(n, dtype=torch.int64, device=dev)
+    a = _lib.sc_outline_args()
+    a.labels, a.H, a.W, a.connectivity = lab.data_ptr(), H, W, int(connectivity)
+    if 4 * H * W >= 2 ** 31 or H * W == 0:                       # refused before anything is allocated: the call has the message
+        check(lib.sc_component_outlines(a, _lib.OUTLINE_COUNT, stream()))
+    cnt = i32(H * W)
+    a.cnt = cnt.data_ptr()
+    check(lib.sc_component_outlines(a, _lib.OUTLINE_COUNT, stream()))
+    prefix = torch.cumsum(cnt, 0, dtype=torch.int32)
+    E = int(prefix[-1].item())                                   # read-back: sizes every buffer below
+    if E == 0:
+        return _empty_outlines(dev)
+    wb = lib.sc_component_outlines_workspace_bytes(H, W, E)
+    work = torch.empty(wb, dtype=torch.uint8, device=dev)
+    keys, stats = i64(E), i32(2)
+    a.E, a.prefix, a.work, a.work_bytes, a.keys, a.stats = E, prefix.data_ptr(), work.data_ptr(), wb, keys.data_ptr(), stats.data_ptr()
+    check(lib.sc_component_outlines(a, _lib.OUTLINE_TRACE, stream()))
+    R, V = (int(v) for v in stats.cpu().tolist())                # read-back: rings and corner vertices
+    skeys = torch.sort(keys).values[:R].contiguous()
+    out = {"ring_label": i32(R), "ring_area2": i64(R)}
+    ring_len, ring_start = i64(R), torch.zeros(R + 1, dtype=torch.int64, device=dev)
+    a.R, a.sorted_keys, a.ring_len = R, skeys.data_ptr(), ring_len.data_ptr()
+    a.ring_label, a.ring_area2 = out["ring_label"].data_ptr(), out["ring_area2"].data_ptr()
+    check(lib.sc_component_outlines(a, _lib.OUTLINE_RINGS, stream()))
+    torch.cumsum(ring_len, 0, out=ring_start[1:])
+    ordered, okeep = torch.empty((E, 2), dtype=torch.int32, device=dev), i32(E)
+    a.ring_start, a.ordered, a.ordered_keep = ring_start.data_ptr(), ordered.data_ptr(), okeep.data_ptr()
+    check(lib.sc_component_outlines(a, _lib.OUTLINE_SCATTER, stream()))
+    if collinear:
+        out.update(vertices=ordered, ring_offsets=ring_start)
+        return out
+    kprefix = torch.cumsum(okeep, 0, dtype=torch.int32)
+    out.update(vertices=torch.empty((V, 2), dtype=torch.int32, device=dev), ring_offsets=i64(R + 1))
+    a.V, a.keep_prefix, a.vertices, a.ring_offsets = V, kprefix.data_ptr(), out["vertices"].data_ptr(), out["ring_offsets"].data_ptr()
+    check(lib.sc_component_outlines(a, _lib.OUTLINE_COMPACT, stream()))
+    return out
+
+
+def component_outlines(labels, counts=None, connectivity=2, collinear=False):
+    """Polygon rings of every component of a label image (``sc_component_outlines``; include/starcop_hip.h has the edge
+    numbering and the turning rule).
+
+    ``labels``: device int32 (H, W) or (N, H, W) as ``connected_components`` returns them: 0 background, component k the pixels of
+    value k.  ``counts`` (an int, an (N,) tensor or None) is accepted as ``component_stats`` accepts it and only checked for its
+    length: every positive value has its outline traced.  ``connectivity`` must be the one the image was labelled with: at a
+    corner where two pixels of a component meet diagonally, 2 passes to the diagonal pixel, 1 stays on its own.
+
+    Returns, per image (a dict for (H, W), a list of dicts for (N, H, W)), device tensors ``vertices`` (V, 2) int32 (row, column)
+    of pixel CORNERS (corner (r, c) is the upper-left corner of pixel (r, c)), ``ring_offsets`` (R+1,) int64 (ring i is
+    ``vertices[ring_offsets[i]:ring_offsets[i+1]]``, not closed), ``ring_label`` (R,) int32 and ``ring_area2`` (R,) int64, the
+    signed doubled area sum(col_i * row_{i+1} - col_{i+1} * row_i): positive for an exterior, negative for a hole.  A ring has
+    its component on the right of the direction of travel (row axis down).  Rings are ordered by label, the exterior first,
+    then by their first edge in raster order.  ``collinear=False`` drops every vertex that lies on a straight run; the ring then
+    starts at the first corner at or after its first edge.  A ring may touch itself at a corner where two pixels of the component
+    meet diagonally: with connectivity 2 the ring around both passes through that corner twice, with connectivity 1 a hole
+    ring whose background is pinched there does.  That is how GDAL's polygonize leaves such rings too; they are not repaired.
+    Integers throughout: two calls give identical bytes."""
+    if not isinstance(labels, torch.Tensor):
+        raise ValueError("component_outlines: labels must be a device tensor (plume_outlines takes numpy masks)")
+    if connectivity not in (1, 2):
+        raise ValueError(f"component_outlines: connectivity {connectivity!r} (1 or 2)")
+    lab = _as_batch(labels, "component_outlines: labels")
+    if counts is not None and not isinstance(counts, int) and counts.numel() != lab.shape[0]:
+        raise ValueError(f"component_outlines: {counts.numel()} counts for {lab.shape[0]} images")
+    _lib.require_device(lab)
+    if lab.dtype != torch.int32:
+        lab = lab.to(torch.int32)
+    lab = lab.contiguous()
+    res = [_outlines_one(lab[n], connectivity, bool(collinear)) for n in range(lab.shape[0])]
+    return res[0] if labels.dim() == 2 else res
+
+
+def _gt6(geotransform, who):
+    gt = [float(v) for v in np.asarray(geotransform, dtype=np.float64).ravel()]
+    if len(gt) != 6:
+        raise ValueError(f"{who}: geotransform must have 6 numbers, got {len(gt)}")
+    if gt[2] != 0.0 or gt[4] != 0.0:
+        raise NotImplementedError(f"{who}: rotated geotransform (terms {gt[2]}, {gt[4]}) is not supported")
+    return gt
+
+
+def polygons_from_rings(vertices, ring_offsets, ring_label, ring_area2, geotransform=None, min_area=1, item=0):
+    """The host half of ``plume_outlines``: the four arrays of ``component_outlines`` (numpy) -> ``{(item, label): [ring, ...]}``,
+    every ring a closed (n+1, 2) float64 array of (x, y), the exterior first, then the holes.  x = gt0 + col * gt1 and
+    y = gt3 + row * gt5 (corners: no + 0.5); without a geotransform (x, y) = (col, row).  Components of fewer than ``min_area``
+    pixels (half the sum of their rings' ``ring_area2``) are left out.  No device involved."""
+    v = np.asarray(vertices, dtype=np.float64).reshape(-1, 2)
+    off = np.asarray(ring_offsets, dtype=np.int64)
+    lab = np.asarray(ring_label, dtype=np.int64)
+    a2 = np.asarray(ring_area2, dtype=np.int64)
+    if geotransform is not None:
+        gt = _gt6(geotransform, "plume_outlines")
+        xy = np.stack([gt[0] + v[:, 1] * gt[1], gt[3] + v[:, 0] * gt[5]], 1)
+    else:
+        xy = np.stack([v[:, 1], v[:, 0]], 1)
+    out = {}
+    i, R = 0, lab.size
+    while i < R:
+        j = i
+        while j < R and lab[j] == lab[i]:
+            j += 1
+        if a2[i] <= 0:
+            raise ValueError(f"polygons_from_rings: the first ring of label {lab[i]} is not an exterior")
+        if int(a2[i:j].sum()) // 2 >= max(int(min_area), 1):
+            out[(int(item), int(lab[i]))] = [np.concatenate([xy[off[q]:off[q + 1]], xy[off[q]:off[q] + 1]]) for q in range(i, j)]
+        i = j
+    return out
+
+
+def plume_outlines(mask, connectivity=2, min_area=1, geotransform=None):
+    """Polygons of the plumes of ``mask != 0``, an (H, W) or (N, H, W) mask, numpy or device: labels the mask as ``plume_table``
+    does (same ``plume_id``), traces every component on the device (``component_outlines``, corners only) and reads the rings
+    back in one copy.  Returns ``{(item, plume_id): [ring, ...]}`` as ``polygons_from_rings`` gives them."""
+    shape = tuple(mask.shape)
+    if len(shape) not in (2, 3):
+        raise ValueError(f"plume_outlines: expected an (H, W) or (N, H, W) mask, got {shape}")
+    if geotransform is not None:
+        _gt6(geotransform, "plume_outlines")
+    m = _to_device(mask)
+    labels, counts = connected_components(m, connectivity=connectivity)
+    res = component_outlines(labels, counts, connectivity=connectivity, collinear=False)
+    res = [res] if isinstance(res, dict) else res
+    flat = torch.cat([r[f].reshape(-1).to(torch.int64) for r in res for f in OUTLINE_FIELDS]).cpu().numpy()      # the one read-back
+    out, at = {}, 0
+    for n, r in enumerate(res):
+        arrs = []
+        for f in OUTLINE_FIELDS:
+            k = r[f].numel()
+            arrs.append(flat[at:at + k])
+            at += k
+        out.update(polygons_from_rings(*arrs, geotransform=geotransform, min_area=min_area, item=n))
+    return out
+
+
+def _shoelace(ring):
+    """signed doubled area of a closed (n+1, 2) ring of (x, y), taken about its first vertex"""
+    x, y = ring[:, 0] - ring[0, 0], ring[:, 1] - ring[0, 1]
+    return float(np.sum(x[:-1] * y[1:] - x[1:] * y[:-1]))
+
+
+def _properties(row):
+    props = {}
+    for c, v in row.items():
+        if c in ("x", "y"):
+            continue
+        v = v.item() if hasattr(v, "item") else v
+        props[c] = None if isinstance(v, float) and not np.isfinite(v) else v
+    props["bbox_px"] = [int(row["row_min"]), int(row["col_min"]), int(row["row_max"]), int(row["col_max"])]
+    return props
+
+
+def write_plumes(table, path, outlines=None):
+    """``.csv``: the table as it is (no index column; ``outlines`` is ignored).  ``.geojson``: one Point feature per plume at
+    (``x``, ``y``) -- the table must carry them, i.e. come from ``plume_table(..., geotransform=...)`` -- with every other column
+    as a property and the bounding box as ``bbox_px`` = [row_min, col_min, row_max, col_max].  With ``outlines`` (the dict of
+    ``plume_outlines`` of the same mask) every feature is a Polygon instead, looked up by (``item``, ``plume_id``), with the same
+    properties; a row without an outline is a ValueError.  Rings are wound as RFC 7946 asks, the exterior counter-clockwise
+    and the holes clockwise in (x, y) -- reversed where the geotransform flips an axis (north up) -- and the coordinates stay in
+    the raster's reference system."""
     path = str(path)
     if path.startswith("gs://"):
         raise NotImplementedError(f"{path}: writing to Google Cloud Storage is not supported")
@@ -240,19 +415,24 @@ def write_plumes(table, path):
         return path
     if not path.endswith(".geojson"):
         raise ValueError(f"write_plumes: {path}: expected a .csv or .geojson path")
-    if "x" not in table.columns or "y" not in table.columns:
+    if outlines is None and ("x" not in table.columns or "y" not in table.columns):
         raise ValueError("write_plumes: a .geojson needs the x / y columns (plume_table(..., geotransform=...))")
     feats = []
     for row in table.to_dict("records"):
-        props = {}
-        for c, v in row.items():
-            if c in ("x", "y"):
-                continue
-            v = v.item() if hasattr(v, "item") else v
-            props[c] = None if isinstance(v, float) and not np.isfinite(v) else v
-        props["bbox_px"] = [int(row["row_min"]), int(row["col_min"]), int(row["row_max"]), int(row["col_max"])]
-        feats.append({"type": "Feature", "geometry": {"type": "Point", "coordinates": [float(row["x"]), float(row["y"])]},
-                      "properties": props})
+        if outlines is None:
+            geom = {"type": "Point", "coordinates": [float(row["x"]), float(row["y"])]}
+        else:
+            key = (int(row["item"]), int(row["plume_id"]))
+            if key not in outlines:
+                raise ValueError(f"write_plumes: no outline for item {key[0]}, plume {key[1]}")
+            rings = []
+            for q, ring in enumerate(outlines[key]):
+                ring = np.asarray(ring, dtype=np.float64)
+                if (_shoelace(ring) < 0) == (q == 0):            # exterior clockwise, or a hole counter-clockwise
+                    ring = ring[::-1]
+                rings.append(ring.tolist())
+            geom = {"type": "Polygon", "coordinates": rings}
+        feats.append({"type": "Feature", "geometry": geom, "properties": _properties(row)})
     with open(path, "w") as f:
         json.dump({"type": "FeatureCollection", "features": feats}, f)
     return path
