@@ -407,6 +407,14 @@ int sc_dwconv3x3_wgrad(const sc_src* dy, const sc_src* in, double* dw_acc /*[C][
  * output once instead of twice and saves the (dx, y_in) pass of the expansion's BatchNorm backward. */
 int sc_dwconv3x3_bwd_fused(const sc_src* dy, const sc_src* in, const float* w, float* dx, double* dw_acc, double* in_sums,
                            int N, int C, int Hin, int Win, int stride, sc_stream stream);
+/* HOST: the kernel variant a depthwise entry point launches for a shape.  op: 0 = sc_dwconv3x3_fwd / _fwd_bn, 1 = _dgrad, 2 = _wgrad,
+ * 3 = _bwd_fused; aligned16: whether every tensor pointer the entry point tests for 16-byte alignment passes (in->x and out for 0;
+ * dy->x, dy->aux, in->x and dx for 3; ignored for 1 and 2).  -1 = the entry point rejects the arguments (stride outside {1, 2}; odd
+ * sizes at stride 2 for op 3), 9000 + PS = the wave-per-plane kernel for PS x PS planes (PS = 16; 32 only with STARCOP_DW_P32 set),
+ * else 1000 * stride + 10 * TW + V4: TW = tile width 64 | 32 | 16 (64 x 32, 32 x 32, 16 x 16 pixels per work-group, by the width of
+ * the plane the work-groups tile: the output for ops 0 and 2, the input for 1 and 3), V4 = 1 for float4 staging, 0 for element-wise
+ * staging (always 0 for ops 1 and 2).  The entry points dispatch on this value. */
+int sc_dw_variant(int op, int N, int C, int Hin, int Win, int stride, int aligned16);
 int sc_cast_f64_f32(const double* in, float* out, size_t n, sc_stream stream);
 /* the same for n_descs (in, out, n) triples in one launch; descs_dev: DEVICE array (static for a plan: the caller builds it once).
  * The depthwise filter gradients of a backward walk (fp64 accumulators of sc_dwconv3x3_bwd_fused -> the flat fp32 gradient). */

@@ -2138,28 +2138,65 @@ int head_blocks(int N, int H, int W) {
 
 }  // namespace
 
-#define SC_DW_DISPATCH4(KERNEL, V4_, W_, GRID, ...)                                                                     \
+// The depthwise launchers dispatch on the code of dw_variant below: 1000 * stride + 10 * TW + V4 (tile shape by plane width:
+// (TW, R) = (64, 8) -> 64x32, (32, 4) -> 32x32, (16, 1) -> 16x16 pixels per block).  SC_DW_DISPATCH4: kernels with a staging form (V4);
+// SC_DW_DISPATCH: kernels without one (their codes end in 0).
+#define SC_DW_DISPATCH4(KERNEL, CODE_, GRID, ...)                                                                       \
   do {                                                                                                                  \
-    const int tw_ = sc_dw_tile_w(W_);                                                                                   \
-    if (stride == 1 && tw_ == 64) hipLaunchKernelGGL((KERNEL<1, 64, 8, V4_>), GRID, dim3(256), 0, st, __VA_ARGS__);     \
-    else if (stride == 1 && tw_ == 32) hipLaunchKernelGGL((KERNEL<1, 32, 4, V4_>), GRID, dim3(256), 0, st, __VA_ARGS__);\
-    else if (stride == 1) hipLaunchKernelGGL((KERNEL<1, 16, 1, V4_>), GRID, dim3(256), 0, st, __VA_ARGS__);             \
-    else if (tw_ == 64) hipLaunchKernelGGL((KERNEL<2, 64, 8, V4_>), GRID, dim3(256), 0, st, __VA_ARGS__);               \
-    else if (tw_ == 32) hipLaunchKernelGGL((KERNEL<2, 32, 4, V4_>), GRID, dim3(256), 0, st, __VA_ARGS__);               \
-    else hipLaunchKernelGGL((KERNEL<2, 16, 1, V4_>), GRID, dim3(256), 0, st, __VA_ARGS__);                              \
+    switch (CODE_) {                                                                                                    \
+      case 1641: hipLaunchKernelGGL((KERNEL<1, 64, 8, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;              \
+      case 1640: hipLaunchKernelGGL((KERNEL<1, 64, 8, false>), GRID, dim3(256), 0, st, __VA_ARGS__); break;             \
+      case 1321: hipLaunchKernelGGL((KERNEL<1, 32, 4, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;              \
+      case 1320: hipLaunchKernelGGL((KERNEL<1, 32, 4, false>), GRID, dim3(256), 0, st, __VA_ARGS__); break;             \
+      case 1161: hipLaunchKernelGGL((KERNEL<1, 16, 1, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;              \
+      case 1160: hipLaunchKernelGGL((KERNEL<1, 16, 1, false>), GRID, dim3(256), 0, st, __VA_ARGS__); break;             \
+      case 2641: hipLaunchKernelGGL((KERNEL<2, 64, 8, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;              \
+      case 2640: hipLaunchKernelGGL((KERNEL<2, 64, 8, false>), GRID, dim3(256), 0, st, __VA_ARGS__); break;             \
+      case 2321: hipLaunchKernelGGL((KERNEL<2, 32, 4, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;              \
+      case 2320: hipLaunchKernelGGL((KERNEL<2, 32, 4, false>), GRID, dim3(256), 0, st, __VA_ARGS__); break;             \
+      case 2161: hipLaunchKernelGGL((KERNEL<2, 16, 1, true>), GRID, dim3(256), 0, st, __VA_ARGS__); break;              \
+      case 2160: hipLaunchKernelGGL((KERNEL<2, 16, 1, false>), GRID, dim3(256), 0, st, __VA_ARGS__); break;             \
+      default: sc_set_error("depthwise dispatch: no kernel for variant %d", (int)(CODE_)); return SC_ERR_LAUNCH;        \
+    }                                                                                                                   \
   } while (0)
 
-// tile shape by plane width: (TW, R) = (64, 8) -> 64x32, (32, 4) -> 32x32, (16, 1) -> 16x16 outputs per block
-#define SC_DW_DISPATCH(KERNEL, W_, GRID, ...)                                                                      \
+#define SC_DW_DISPATCH(KERNEL, CODE_, GRID, ...)                                                                   \
   do {                                                                                                             \
-    const int tw_ = sc_dw_tile_w(W_);                                                                              \
-    if (stride == 1 && tw_ == 64) hipLaunchKernelGGL((KERNEL<1, 64, 8>), GRID, dim3(256), 0, st, __VA_ARGS__);     \
-    else if (stride == 1 && tw_ == 32) hipLaunchKernelGGL((KERNEL<1, 32, 4>), GRID, dim3(256), 0, st, __VA_ARGS__);\
-    else if (stride == 1) hipLaunchKernelGGL((KERNEL<1, 16, 1>), GRID, dim3(256), 0, st, __VA_ARGS__);             \
-    else if (tw_ == 64) hipLaunchKernelGGL((KERNEL<2, 64, 8>), GRID, dim3(256), 0, st, __VA_ARGS__);               \
-    else if (tw_ == 32) hipLaunchKernelGGL((KERNEL<2, 32, 4>), GRID, dim3(256), 0, st, __VA_ARGS__);               \
-    else hipLaunchKernelGGL((KERNEL<2, 16, 1>), GRID, dim3(256), 0, st, __VA_ARGS__);                              \
+    switch (CODE_) {                                                                                               \
+      case 1640: hipLaunchKernelGGL((KERNEL<1, 64, 8>), GRID, dim3(256), 0, st, __VA_ARGS__); break;               \
+      case 1320: hipLaunchKernelGGL((KERNEL<1, 32, 4>), GRID, dim3(256), 0, st, __VA_ARGS__); break;               \
+      case 1160: hipLaunchKernelGGL((KERNEL<1, 16, 1>), GRID, dim3(256), 0, st, __VA_ARGS__); break;               \
+      case 2640: hipLaunchKernelGGL((KERNEL<2, 64, 8>), GRID, dim3(256), 0, st, __VA_ARGS__); break;               \
+      case 2320: hipLaunchKernelGGL((KERNEL<2, 32, 4>), GRID, dim3(256), 0, st, __VA_ARGS__); break;               \
+      case 2160: hipLaunchKernelGGL((KERNEL<2, 16, 1>), GRID, dim3(256), 0, st, __VA_ARGS__); break;               \
+      default: sc_set_error("depthwise dispatch: no kernel for variant %d", (int)(CODE_)); return SC_ERR_LAUNCH;   \
+    }                                                                                                              \
   } while (0)
+
+// Which instantiation a depthwise launch gets, without touching the GPU.  op: 0 = forward (sc_dwconv3x3_fwd / _fwd_bn), 1 = dgrad,
+// 2 = wgrad, 3 = bwd_fused.  -1 for what the entry point rejects, 9000 + PS for the wave-per-plane kernels (PS = 16, or 32 behind
+// STARCOP_DW_P32), else 1000 * stride + 10 * TW + V4 (V4: float4 staging; always 0 for dgrad and wgrad).  The tile width follows
+// the plane the work-groups tile: the output for forward and wgrad, the input for dgrad and bwd_fused.  al_v4: the tensors the
+// float4 staging reads are 16-byte aligned; al_plane: so are those the plane kernels also access as float4 (out, dx).
+static int dw_variant(int op, int N, int C, int Hin, int Win, int stride, bool al_v4, bool al_plane) {
+  if (op < 0 || op > 3 || N < 1 || C < 1 || Hin < 1 || Win < 1) return -1;
+  if (stride != 1 && stride != 2) return -1;
+  if (op == 3 && stride == 2 && (Hin % 2 != 0 || Win % 2 != 0)) return -1;
+  const int Wout = (Win - 1) / stride + 1;
+  const int tw = sc_dw_tile_w((op == 0 || op == 2) ? Wout : Win);
+  if (op == 1 || op == 2) return 1000 * stride + 10 * tw;
+  // float4 staging where every patch row is 16-byte aligned
+  const bool v4 = al_v4 && Win % 4 == 0 && (op == 0 || Wout % 4 == 0);
+  // (32 x 32 planes through the plane kernels measured SLOWER than the work-group-per-plane form -- backward 50 -> 63 us, forward
+  // 22 -> 27 us on features.12: 16 pixels per lane, 43 KB of LDS per work-group -- so it is opt-in: STARCOP_DW_P32=1)
+  static const bool p32_env = [] { const char* e = getenv("STARCOP_DW_P32"); return e && atoi(e) != 0; }();
+  const bool plane_ok = (op == 0 ? al_v4 : v4) && al_plane && stride == 1 && Hin == Win && ((long)N * C) % 4 == 0;
+  if (plane_ok && (Hin == 16 || (p32_env && Hin == 32))) return 9000 + Hin;      // a wave per plane
+  return 1000 * stride + 10 * tw + (v4 ? 1 : 0);
+}
+extern "C" int sc_dw_variant(int op, int N, int C, int Hin, int Win, int stride, int aligned16) {
+  return dw_variant(op, N, C, Hin, Win, stride, aligned16 != 0, aligned16 != 0);
+}
 
 static inline long dw_tiles(int H, int W) {
   const int tw = sc_dw_tile_w(W), th = sc_dw_tile_h(W);
@@ -2196,22 +2233,14 @@ static int dwconv3x3_fwd(const sc_src* in, const float* w, float* out, int N, in
     tail.arrivals = (int)(N * dw_tiles(Hout, Wout));          // statistics rows per channel (sc_stat_rows(SC_STAT_DW, ..))
     tail.count = (double)N * Hout * Wout;
   }
-  constexpr bool p16_env = true;
-  // (32 x 32 planes through the same kernel measured SLOWER than the work-group-per-plane form -- backward 50 -> 63 us, forward
-  // 22 -> 27 us on features.12: 16 pixels per lane, 43 KB of LDS per work-group -- so it is opt-in: STARCOP_DW_P32=1)
-  static const bool p32_env = [] { const char* e = getenv("STARCOP_DW_P32"); return e && atoi(e) != 0; }();
-  const bool plane_ok = stride == 1 && Hin == Win && ((long)N * C) % 4 == 0 && (((uintptr_t)in->x | (uintptr_t)out) & 15) == 0;
-  if (plane_ok && ((p16_env && Hin == 16) || (p16_env && p32_env && Hin == 32))) {      // a wave per plane
-    if (Hin == 16) hipLaunchKernelGGL(k_dw_fwd_plane<16>, dim3((unsigned)((long)N * C / 4)), dim3(256), 0, st, to_srcd(*in), w, out, C, stats, tail);
+  const int variant = dw_variant(0, N, C, Hin, Win, stride, (((uintptr_t)in->x) & 15) == 0, (((uintptr_t)out) & 15) == 0);
+  if (variant >= 9000) {      // a wave per plane
+    if (variant == 9016) hipLaunchKernelGGL(k_dw_fwd_plane<16>, dim3((unsigned)((long)N * C / 4)), dim3(256), 0, st, to_srcd(*in), w, out, C, stats, tail);
     else hipLaunchKernelGGL(k_dw_fwd_plane<32>, dim3((unsigned)((long)N * C / 4)), dim3(256), 0, st, to_srcd(*in), w, out, C, stats, tail);
     SC_LAUNCH_OK("sc_dwconv3x3_fwd");
     return SC_OK;
   }
-  constexpr bool v4_env = true;
-  if (v4_env && Win % 4 == 0 && (((uintptr_t)in->x) & 15) == 0)
-    SC_DW_DISPATCH4(k_dw_fwd, true, Wout, grid, to_srcd(*in), w, out, N * C, C, Hin, Win, Hout, Wout, stats, tail);
-  else
-    SC_DW_DISPATCH4(k_dw_fwd, false, Wout, grid, to_srcd(*in), w, out, N * C, C, Hin, Win, Hout, Wout, stats, tail);
+  SC_DW_DISPATCH4(k_dw_fwd, variant, grid, to_srcd(*in), w, out, N * C, C, Hin, Win, Hout, Wout, stats, tail);
   SC_LAUNCH_OK("sc_dwconv3x3_fwd");
   return SC_OK;
 }
@@ -2225,7 +2254,7 @@ extern "C" int sc_dwconv3x3_dgrad(const sc_src* dy, const float* w, float* dx, i
   const int Hout = (Hin - 1) / stride + 1, Wout = (Win - 1) / stride + 1;
   hipStream_t st = (hipStream_t)stream;
   dim3 grid((unsigned)dw_tiles(Hin, Win), C, N);
-  SC_DW_DISPATCH(k_dw_dgrad, Win, grid, to_srcd(*dy), w, dx, accum, C, Hin, Win, Hout, Wout);
+  SC_DW_DISPATCH(k_dw_dgrad, dw_variant(1, N, C, Hin, Win, stride, true, true), grid, to_srcd(*dy), w, dx, accum, C, Hin, Win, Hout, Wout);
   SC_LAUNCH_OK("sc_dwconv3x3_dgrad");
   return SC_OK;
 }
@@ -2241,7 +2270,7 @@ extern "C" int sc_dwconv3x3_wgrad(const sc_src* dy, const sc_src* in, double* dw
   const long T = (long)N * dw_tiles(Hout, Wout);
   const long want = 4096 / C > 0 ? 4096 / C : 1;
   dim3 grid((unsigned)(T < want ? T : want), C);
-  SC_DW_DISPATCH(k_dw_wgrad, Wout, grid, to_srcd(*dy), to_srcd(*in), dw_acc, N, C, Hin, Win, Hout, Wout, 0);
+  SC_DW_DISPATCH(k_dw_wgrad, dw_variant(2, N, C, Hin, Win, stride, true, true), grid, to_srcd(*dy), to_srcd(*in), dw_acc, N, C, Hin, Win, Hout, Wout, 0);
   SC_LAUNCH_OK("sc_dwconv3x3_wgrad");
   return SC_OK;
 }
@@ -2260,23 +2289,15 @@ extern "C" int sc_dwconv3x3_bwd_fused(const sc_src* dy, const sc_src* in, const 
   const long planes8 = ((long)N * C + 7) / 8 * 8;
   SC_REQUIRE(planes8 * dw_tiles(Hin, Win) < (1L << 31), "sc_dwconv3x3_bwd_fused: grid too large");
   dim3 grid((unsigned)(planes8 * dw_tiles(Hin, Win)));
-  // float4 staging where every patch row is 16-byte aligned (SC_DW_V4=0 forces the element-wise form)
-  constexpr bool v4_env = true;
-  const bool v4 = v4_env && Win % 4 == 0 && Wout % 4 == 0 &&
-                  ((((uintptr_t)dy->x) | ((uintptr_t)dy->aux) | ((uintptr_t)in->x)) & 15) == 0;
-  constexpr bool p16_env = true;
-  // (32 x 32 planes through the same kernel measured SLOWER than the work-group-per-plane form -- backward 50 -> 63 us, forward
-  // 22 -> 27 us on features.12: 16 pixels per lane, 43 KB of LDS per work-group -- so it is opt-in: STARCOP_DW_P32=1)
-  static const bool p32_env = [] { const char* e = getenv("STARCOP_DW_P32"); return e && atoi(e) != 0; }();
-  const bool plane_ok = v4 && stride == 1 && Hin == Win && ((long)N * C) % 4 == 0 && ((uintptr_t)dx & 15) == 0;
-  if (plane_ok && ((p16_env && Hin == 16) || (p16_env && p32_env && Hin == 32))) {      // a wave per plane
-    if (Hin == 16) hipLaunchKernelGGL(k_dw_bwd_plane<16>, dim3((unsigned)((long)N * C / 4)), dim3(256), 0, st, to_srcd(*dy), to_srcd(*in), w, dx, dw_acc, in_sums, C);
+  const int variant = dw_variant(3, N, C, Hin, Win, stride, ((((uintptr_t)dy->x) | ((uintptr_t)dy->aux) | ((uintptr_t)in->x)) & 15) == 0,
+                                 ((uintptr_t)dx & 15) == 0);
+  if (variant >= 9000) {      // a wave per plane
+    if (variant == 9016) hipLaunchKernelGGL(k_dw_bwd_plane<16>, dim3((unsigned)((long)N * C / 4)), dim3(256), 0, st, to_srcd(*dy), to_srcd(*in), w, dx, dw_acc, in_sums, C);
     else hipLaunchKernelGGL(k_dw_bwd_plane<32>, dim3((unsigned)((long)N * C / 4)), dim3(256), 0, st, to_srcd(*dy), to_srcd(*in), w, dx, dw_acc, in_sums, C);
     SC_LAUNCH_OK("sc_dwconv3x3_bwd_fused");
     return SC_OK;
   }
-  if (v4) SC_DW_DISPATCH4(k_dw_bwd, true, Win, grid, to_srcd(*dy), to_srcd(*in), w, dx, dw_acc, in_sums, N * C, C, Hin, Win, Hout, Wout);
-  else SC_DW_DISPATCH4(k_dw_bwd, false, Win, grid, to_srcd(*dy), to_srcd(*in), w, dx, dw_acc, in_sums, N * C, C, Hin, Win, Hout, Wout);
+  SC_DW_DISPATCH4(k_dw_bwd, variant, grid, to_srcd(*dy), to_srcd(*in), w, dx, dw_acc, in_sums, N * C, C, Hin, Win, Hout, Wout);
   SC_LAUNCH_OK("sc_dwconv3x3_bwd_fused");
   return SC_OK;
 }
@@ -2528,7 +2549,7 @@ extern "C" int sc_head_conv_wgrad(const float* dlogits, const sc_src* in, float*
   const long T = (long)N * dw_tiles(Hout, Wout);
   const long want = 4096 / Cin > 0 ? 4096 / Cin : 1;
   dim3 grid((unsigned)(T < want ? T : want), Cin);
-  SC_DW_DISPATCH(k_dw_wgrad, Wout, grid, dy, to_srcd(*in), acc, N, Cin, H, W, Hout, Wout, 1);
+  SC_DW_DISPATCH(k_dw_wgrad, dw_variant(2, N, Cin, H, W, stride, true, true), grid, dy, to_srcd(*in), acc, N, Cin, H, W, Hout, Wout, 1);
   SC_LAUNCH_OK("sc_head_conv_wgrad");
   const size_t npx = (size_t)N * H * W;
   hipLaunchKernelGGL(k_sum_f32_to_f64, dim3((unsigned)((npx + 4095) / 4096 > 512 ? 512 : (npx + 4095) / 4096)), dim3(256), 0, st, dlogits, npx, acc + Cin * 9);
