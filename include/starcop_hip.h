@@ -1267,6 +1267,49 @@ size_t sc_component_outlines_workspace_bytes(int H, int W, int64_t E);
 int sc_component_outlines_rounds(int64_t E);      /* pointer-doubling launches of TRACE for E edges                 */
 int sc_component_outlines(const sc_outline_args* a, int stage, sc_stream stream);
 
+/* Polygons -> label image: the inverse of sc_component_outlines (starcop_amd/plumes.py: rasterize_polygons).  P polygons, each a
+ * set of rings given as directed edges (x0, y0) -> (x1, y1) in PIXEL coordinates, float64, x along the columns and y along the
+ * rows: pixel (r, c) covers [c, c+1) x [r, r+1), its centre is (c + 0.5, r + 0.5).  The caller closes every ring (the closing
+ * edge is in the list); winding is irrelevant.  out is one int32 H x W image, 0 where no polygon covers the pixel.
+ *   coverage   even-odd over ALL edges of a polygon: exteriors, holes, the parts of a multi-polygon and rings that touch
+ *              themselves need no distinction.
+ *   crossing   an edge crosses the scanline of row r, yc = r + 0.5 (exact in float64), iff (y0 <= yc) != (y1 <= yc): horizontal
+ *              edges never cross, a vertex on a scanline counts once.
+ *   abscissa   xs = x0 + ((yc - y0) * (x1 - x0)) / (y1 - y0) in float64, every operation rounded on its own -- subtract,
+ *              multiply, divide, add -- with no fused multiply-add (the file is compiled with contraction off).
+ *   toggle     the crossing toggles pixel c of row r iff xs <= c + 0.5; a pixel is covered when its toggle count is odd.  A
+ *              top-left rule: the square (2.5, 2.5) .. (6.5, 6.5) covers rows 2..5 and columns 2..5, not 6.  Away from ties this
+ *              is GDAL's default burn (pixel centre inside, no ALL_TOUCHED).
+ *   order      polygon i (0-based) burns i + 1; where polygons overlap the one later in the list wins (integer atomicMax of
+ *              i + 1: independent of scheduling, two calls give identical bytes).  With values != NULL a second launch maps
+ *              i + 1 -> values[i] in place (any int32, repeats allowed); NULL leaves 1..P.
+ *   clipping   vertices may lie anywhere (|coordinate| < 2^31, finite: the caller checks); each polygon carries a box of rows
+ *              [r0, r1) and columns [c0, c1) inside the raster that contains every pixel it can toggle, one column to spare for
+ *              the rounding of xs.  A crossing left of the box toggles the whole box row, one right of it nothing.
+ * The polygon table is given twice (as for sc_scene_gather): on the device for the kernel, on the host for the checks made before
+ * the launch.  job0 is the running sum of the rows r1 - r0 of the polygons before it that have a non-empty box and at least one
+ * edge: one wave per (polygon, row).  There is no cap on crossings per row, edges per polygon or polygons per call beyond int32
+ * indexing: E < 2^31, jobs < 2^31, H*W < 2^31.  SC_ERR_ARG, before any launch, for bad dims, a null pointer, an edge range outside
+ * [0, E], a box that leaves the raster or a job0 that is not that running sum.  P = 0 or no job: out is cleared, nothing is
+ * launched.  Work: sum over polygons of box rows x (edges + box columns / 64) -- meant for plumes (hundreds of polygons, boxes of
+ * tens to hundreds of pixels), tolerable for a scene footprint (1e4 edges x 1e4 rows).  Integer atomics only (LDS xor, global
+ * max); no work-group waits on another.                                                                                      */
+typedef struct sc_rast_poly {
+  int32_t e0, e1;                                 /* its edges: [e0, e1) of the edge array                         */
+  int32_t r0, r1, c0, c1;                         /* clipped box: rows [r0, r1), columns [c0, c1)                  */
+  int32_t job0, reserved;
+} sc_rast_poly;
+typedef struct sc_rast_args {
+  const double* edges;                            /* [E][4] device: x0, y0, x1, y1; 16-byte aligned                */
+  const sc_rast_poly* polys;                      /* [P] device                                                    */
+  const sc_rast_poly* polys_host;                 /* [P] host, the same table                                      */
+  const int32_t* values;                          /* [P] device, or NULL for 1..P                                  */
+  int32_t* out;                                   /* [H][W] device                                                 */
+  int64_t E;
+  int32_t P, H, W, reserved;
+} sc_rast_args;
+int sc_rasterize_polygons(const sc_rast_args* a, sc_stream stream);
+
 /* ------------------------------------------------------------------------- */
 /* HOST functions (no device involved): decoders of the on-disk sample format -- one tiled GeoTIFF per product per sample,
  * read by rasterio in the reference (starcop/data/dataset.py:66-76, written by save_cog at sampling_dataset.py:332-355).

@@ -234,7 +234,19 @@ class sc_outline_args(C.Structure):
                 ("vertices", C.c_void_p), ("ring_offsets", C.c_void_p)]
 
 
-_vp, _i, _f, _d, _sz = C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
+class sc_rast_poly(C.Structure):
+    """one polygon of a rasterize call (include/starcop_hip.h: sc_rast_poly)"""
+    _fields_ = [("e0", C.c_int32), ("e1", C.c_int32), ("r0", C.c_int32), ("r1", C.c_int32), ("c0", C.c_int32), ("c1", C.c_int32),
+                ("job0", C.c_int32), ("reserved", C.c_int32)]
+
+
+class sc_rast_args(C.Structure):
+    """polygon-rasterize operands (include/starcop_hip.h: sc_rast_args)"""
+    _fields_ = [("edges", C.c_void_p), ("polys", C.c_void_p), ("polys_host", C.c_void_p), ("values", C.c_void_p), ("out", C.c_void_p),
+                ("E", C.c_int64), ("P", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("reserved", C.c_int32)]
+
+
+_vp, _i, _f, _d, _sz =C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/starcop_hip.h declares
 SIGNATURES = {
@@ -385,6 +397,7 @@ SIGNATURES = {
     "sc_component_outlines_workspace_bytes": (_sz, [_i, _i, C.c_int64]),
     "sc_component_outlines_rounds": (_i, [C.c_int64]),
     "sc_component_outlines": (_i, [C.POINTER(sc_outline_args), _i, _vp]),
+    "sc_rasterize_polygons": (_i, [C.POINTER(sc_rast_args), _vp]),
     "sc_tiff_lzw_decode": (_i, [_vp, _sz, _vp, _sz, C.POINTER(C.c_size_t)]),
     "sc_tiff_unpredict": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp]),
 }

@@ -225,7 +225,8 @@ def _emit_predict_parts(model, sub, rgb, ratio, template, fill_value, column_ste
 @torch.no_grad()
 def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_lerp_alpha=1e-4, tile=None, halo=RECEPTIVE_HALO,
                          ratio_bands=None, distributed=None, group=None, rows=None, threads=8, strips=True, georeferenced=False,
-                         out_folder=None, geotransform=None, overwrite=False, plumes=False, plume_outlines=False):
+                         out_folder=None, geotransform=None, overwrite=False, plumes=False, plume_outlines=False,
+                         label_polygons=None):
     """The notebook path of the reference end to end FROM THE FILE (notebooks/inference_on_raw_EMIT_nc_file.ipynb cells 8-19:
     ``EMITImage(path)`` -> ``mag1c_emit`` -> RGB bands -> rescale -> ``model`` -> threshold): opens the EMIT L1B radiance granule
     (NetCDF-4) with :mod:`starcop_amd.hdf5_reader`, reads ONLY what the pipeline touches -- the contiguous band slice inside
@@ -248,7 +249,13 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
     if ``georeferenced=True``, on the sensor-geometry ones otherwise; pixels that carry the fill value or are not finite do not
     count.  With ``out_folder`` the table is also written as ``plumes.csv`` (same ``overwrite`` rule) and listed in ``files``.
     ``plume_outlines=True`` (with ``plumes=True``) adds ``plume_outlines``, the :func:`starcop_amd.plumes.plume_outlines` of the same
-    mask in the same coordinates, and with ``out_folder`` writes ``plumes.geojson``, one Polygon per row of the table."""
+    mask in the same coordinates, and with ``out_folder`` writes ``plumes.geojson``, one Polygon per row of the table.
+
+    ``label_polygons`` (a ``.geojson`` path for :func:`starcop_amd.plumes.read_plumes`, or polygons as
+    :func:`starcop_amd.plumes.rasterize_polygons` takes them, in the coordinates of the geotransform; needs ``georeferenced=True``,
+    there is no grid to burn into otherwise) adds ``label_mask``, the polygons burnt into the product grid (device uint8), and
+    ``plume_match``, :func:`starcop_amd.plumes.match_plumes_polygons` of ``pred_binary`` against them; with ``out_folder`` the
+    mask is written as ``label.tif`` like ``predbinary.tif``."""
     from .hdf5_reader import H5File
     if out_folder is not None:
         if str(out_folder).startswith("gs://"):
@@ -257,6 +264,8 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
             raise ValueError("emit_granule_predict: out_folder writes the orthorectified products; pass georeferenced=True")
     if plume_outlines and not plumes:
         raise ValueError("emit_granule_predict: plume_outlines=True needs plumes=True")
+    if label_polygons is not None and not georeferenced:
+        raise ValueError("emit_granule_predict: label_polygons are burnt into the orthorectified grid; pass georeferenced=True")
     if georeferenced and rows is not None:
         raise ValueError("emit_granule_predict: georeferenced=True needs the whole granule (rows=None): the GLT indexes all of its lines")
     dev = model.device
@@ -277,7 +286,7 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
         rgb_h = np.stack([plane(i) for i in nearest_bands(wl)])
         ratio_h = [plane(i) for i in nearest_bands(wl, ratio_bands)] if ratio_bands is not None else None
         glt = (f["location/glt_x"].read(), f["location/glt_y"].read()) if ("location/glt_x" in f and "location/glt_y" in f) else (None, None)
-        root = f.attrs("/") if out_folder is not None or (plumes and georeferenced) else {}
+        root = f.attrs("/") if out_folder is not None or ((plumes or label_polygons is not None) and georeferenced) else {}
     if georeferenced and glt[0] is None:
         raise ValueError(f"{nc_path}: no location/glt_x, location/glt_y to orthorectify with")
 
@@ -296,11 +305,43 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
         if plume_outlines:
             from .plumes import plume_outlines as outlines_of
             out["plume_outlines"] = outlines_of(out["pred_binary"], geotransform=gt if georeferenced else None)
+    if label_polygons is not None:
+        _burn_label_polygons(out, label_polygons, gt)
     if out_folder is not None:
         out["files"] = _write_emit_products(out, str(out_folder), fill, gt, root.get("spatial_ref"), overwrite)
+        if label_polygons is not None:
+            from .ortho import emit_geo_tags
+            geo = emit_geo_tags(gt, root.get("spatial_ref")) if gt is not None else {}
+            out["files"] += _write_label_tif(out, str(out_folder), geo, overwrite)
         if plumes:
             out["files"] += _write_plume_files(out, str(out_folder), overwrite)
     return out
+
+
+def _burn_label_polygons(out, label_polygons, geotransform):
+    """``label_mask`` and ``plume_match`` of a prediction dict: the polygons (a ``.geojson`` path or polygons) burnt into the grid
+    of ``pred_binary`` once, the same image scored"""
+    import os
+    from . import plumes as pl
+    if isinstance(label_polygons, (str, os.PathLike)):
+        label_polygons = pl.read_plumes(label_polygons)[1]
+    polys, _ = pl._polygon_list(label_polygons)
+    pred = out["pred_binary"]
+    burnt = pl.rasterize_polygons(polys, tuple(pred.shape), geotransform=geotransform)
+    out["label_mask"] = (burnt != 0).to(torch.uint8)
+    out["plume_match"] = pl._match_burnt(pred, burnt, len(polys), 2, 1, 1)
+
+
+def _write_label_tif(out, folder, geo_tags, overwrite):
+    """``label.tif`` like ``predbinary.tif``: uint8, BLOCKSIZE 128, the products' georeferencing -> the paths written"""
+    import os
+    from . import io_formats as io
+    path = os.path.join(folder, "label.tif")
+    if not overwrite and os.path.exists(path):
+        return []
+    os.makedirs(folder, exist_ok=True)
+    io.write_tiff(path, out["label_mask"].cpu().numpy(), blocksize=128, extra_tags={**geo_tags, **io.gdal_metadata_tag({}, ["Plume label"])})
+    return [path]
 
 
 def _write_plume_files(out, folder, overwrite):
@@ -453,7 +494,7 @@ AVIRIS_PRODUCT_FILES = {"pred.tif": ("prediction", ["Plume probability"]), "pred
 @torch.no_grad()
 def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=None, toa_correction_factor=None, solar_altitude=None,
                          normalize_by_acquisition_date=True, tile=None, halo=None, batch=None, plumes=False, overwrite=False,
-                         device="cuda", plume_outlines=False):
+                         device="cuda", plume_outlines=False, label_polygons=None):
     """An orthorectified AVIRIS-NG flight line through the plume model, file to file: ``{folder}/{name}_img`` (ENVI radiance,
     float32) -> the network's input products -> ``model.predict_scene`` -> (with ``out_folder``) ``pred.tif`` / ``predbinary.tif``.
 
@@ -472,7 +513,10 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
     radiance file's georeferencing, band descriptions; ``plumes.csv`` with ``plumes=True``; existing files are skipped unless
     ``overwrite``; the paths written come back under ``files``.  ``plume_outlines=True`` (with ``plumes=True``) adds
     ``plume_outlines``, the ``plumes.plume_outlines`` of the mask with the same geotransform, and writes ``plumes.geojson``, one
-    Polygon per row of the table, next to ``plumes.csv``."""
+    Polygon per row of the table, next to ``plumes.csv``.  ``label_polygons`` (a ``.geojson`` path for ``plumes.read_plumes``, or
+    polygons as ``plumes.rasterize_polygons`` takes them, in the coordinates of the ``map info``) adds ``label_mask``, the
+    polygons burnt into the flight line's grid (device uint8), and ``plume_match``, the ``plumes.match_plumes_polygons`` of the
+    mask against them, and writes ``label.tif`` like ``predbinary.tif``."""
     import datetime
     import os
     import re
@@ -560,6 +604,8 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
         if plume_outlines:
             from .plumes import plume_outlines as outlines_of
             out["plume_outlines"] = outlines_of(out["pred_binary"], geotransform=gt)
+    if label_polygons is not None:
+        _burn_label_polygons(out, label_polygons, gt)
     if out_folder is not None:
         geo = io.envi_geo_tags(header)
         nodata = {42113: (2, (_nodata_text(mag1c.NODATA),))}
@@ -571,6 +617,8 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
             tags = {**geo, **(nodata if key == "prediction" else {}), **io.gdal_metadata_tag({}, desc)}
             io.write_tiff(path, out[key].cpu().numpy(), blocksize=128, extra_tags=tags)
             files.append(path)
+        if label_polygons is not None:
+            files += _write_label_tif(out, str(out_folder), geo, overwrite)
         if plumes:
             files += _write_plume_files(out, str(out_folder), overwrite)
         out["files"] = files

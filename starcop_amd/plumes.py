@@ -5,7 +5,8 @@
 component in one call and returns one pandas row per plume; ``match_plumes`` counts detected, spurious and missed plumes between
 a predicted and a labelled mask; ``component_outlines`` traces the polygon rings of every component (sc_component_outlines),
 ``plume_outlines`` turns a mask into closed (x, y) rings per plume; ``write_plumes`` writes a table as CSV or GeoJSON (Points, or
-Polygons with the outlines).
+Polygons with the outlines).  The other way: ``read_plumes`` reads such a GeoJSON back, ``rasterize_polygons`` burns polygons
+into a label image on the raster grid (sc_rasterize_polygons), ``match_plumes_polygons`` scores a mask against polygons.
 """
 import json
 
@@ -436,3 +437,222 @@ def write_plumes(table, path, outlines=None):
     with open(path, "w") as f:
         json.dump({"type": "FeatureCollection", "features": feats}, f)
     return path
+
+
+def read_plumes(path):
+    """The inverse of ``write_plumes`` for a ``.geojson`` FeatureCollection -> ``(table, polygons)``: ``table`` a DataFrame of the
+    features' properties, one row per feature in file order; ``polygons`` a list aligned with the rows, for a ``Polygon`` its rings
+    and for a ``MultiPolygon`` the rings of all its parts in one list (float64 (n, 2) arrays of (x, y), closed as the file has
+    them), ``None`` for a ``Point``.  Any other geometry is a ValueError.  The coordinates are taken as the raster's reference
+    system: nothing is reprojected.  ``rasterize_polygons`` takes the list as it is (``None`` burns nothing)."""
+    import pandas as pd
+    path = str(path)
+    if path.startswith("gs://"):
+        raise NotImplementedError(f"{path}: reading from Google Cloud Storage is not supported")
+    if not path.endswith(".geojson"):
+        raise ValueError(f"read_plumes: {path}: expected a .geojson path")
+    with open(path) as f:
+        doc = json.load(f)
+    if not isinstance(doc, dict) or doc.get("type") != "FeatureCollection":
+        raise ValueError(f"read_plumes: {path}: not a GeoJSON FeatureCollection")
+    props, polygons = [], []
+    for k, feat in enumerate(doc.get("features", [])):
+        geom = feat.get("geometry") or {}
+        kind = geom.get("type")
+        if kind == "Point":
+            polygons.append(None)
+        elif kind == "Polygon":
+            polygons.append([np.asarray(r, dtype=np.float64)[:, :2] for r in geom["coordinates"]])
+        elif kind == "MultiPolygon":
+            polygons.append([np.asarray(r, dtype=np.float64)[:, :2] for part in geom["coordinates"] for r in part])
+        else:
+            raise ValueError(f"read_plumes: {path}: feature {k} has geometry {kind!r} (Point, Polygon or MultiPolygon)")
+        props.append(dict(feat.get("properties") or {}))
+    return pd.DataFrame(props), polygons
+
+
+RAST_COORD_LIMIT = 2.0 ** 31
+
+
+def _polygon_list(polygons, item=0):
+    """a sequence of ring lists, or the dict of ``plume_outlines`` -> (list of ring lists, their default burn values)"""
+    if isinstance(polygons, dict):
+        keys = [k for k in polygons if int(k[0]) == int(item)]
+        return [polygons[k] for k in keys], [int(k[1]) for k in keys]
+    polys = list(polygons)
+    return polys, list(range(1, len(polys) + 1))
+
+
+def polygon_edges(polygons, shape, geotransform=None):
+    """The host half of ``rasterize_polygons``: a list of ring lists -> ``(edges, table)`` as ``sc_rasterize_polygons`` takes
+    them.  ``edges``: float64 (E, 4), (x0, y0, x1, y1) in pixel coordinates, every ring closed (the closing edge is added when the
+    last vertex differs from the first).  ``table``: int32 (P, 8), per polygon its edge range, the clipped box rows [r0, r1) and
+    columns [c0, c1) -- every pixel the polygon can toggle, a pixel to spare on each side -- and the first job index
+    (include/starcop_hip.h: sc_rast_poly).  With ``geotransform`` the rings are (x, y) and become col = (x - gt0) / gt1,
+    row = (y - gt3) / gt5 in float64; without, they are (col, row).  An entry that is ``None`` has no edges.  ValueError for
+    coordinates that are not finite or reach 2^31 in magnitude, rings of fewer than 3 distinct positions and H * W >= 2^31;
+    NotImplementedError for a rotated geotransform.  No device involved."""
+    H, W = (int(v) for v in shape)
+    if H <= 0 or W <= 0 or H * W >= 2 ** 31:
+        raise ValueError(f"rasterize_polygons: bad shape {(H, W)} (positive, H * W < 2^31)")
+    gt = _gt6(geotransform, "rasterize_polygons") if geotransform is not None else None
+    if gt is not None and (gt[1] == 0.0 or gt[5] == 0.0):
+        raise ValueError(f"rasterize_polygons: geotransform with a zero pixel size ({gt[1]}, {gt[5]})")
+    # every ring of every polygon in one (N, 2) array: the checks, the closing edges and the boxes are whole-array operations
+    rings, ring_poly = [], []
+    for i, poly in enumerate(polygons):
+        for q, ring in enumerate(poly if poly is not None else ()):
+            a = np.asarray(ring, dtype=np.float64)
+            if a.ndim != 2 or a.shape[1] != 2:
+                raise ValueError(f"rasterize_polygons: polygon {i}, ring {q}: expected an (n, 2) array, got {a.shape}")
+            if len(a) < 3:
+                raise ValueError(f"rasterize_polygons: polygon {i}, ring {q}: fewer than 3 distinct positions")
+            rings.append(a)
+            ring_poly.append(i)
+    P = len(polygons)
+    table = np.zeros((P, 8), dtype=np.int32)
+    if not rings:
+        return np.zeros((0, 4), dtype=np.float64), table
+    ring_poly = np.asarray(ring_poly, dtype=np.int64)
+    n = np.array([len(a) for a in rings], dtype=np.int64)
+    start = np.concatenate([[0], np.cumsum(n)])
+    A = np.concatenate(rings)
+    rid = np.repeat(np.arange(len(rings)), n)
+
+    def refuse(bad_vertex, what):
+        k = int(rid[np.nonzero(bad_vertex)[0][0]])
+        i = int(ring_poly[k])
+        raise ValueError(f"rasterize_polygons: polygon {i}, ring {k - int(np.searchsorted(ring_poly, i))}: {what}")
+    finite = np.isfinite(A).all(1)
+    if gt is not None and finite.all():
+        A = np.stack([(A[:, 0] - gt[0]) / gt[1], (A[:, 1] - gt[3]) / gt[5]], 1)
+    ok = np.isfinite(A).all(1) & (np.abs(A) < RAST_COORD_LIMIT).all(1)
+    if not ok.all():
+        refuse(~ok, "coordinates must be finite and below 2^31 in magnitude (pixel units)")
+    # at least 3 distinct positions: some vertex differs from the first one and from the first that differs from it
+    idx = np.arange(len(A))
+    off0 = (A != A[start[:-1]][rid]).any(1)
+    second = np.minimum.reduceat(np.where(off0, idx, len(A)), start[:-1])
+    off1 = off0 & (A != A[np.minimum(second, len(A) - 1)][rid]).any(1)
+    enough = np.logical_or.reduceat(off1, start[:-1])
+    if not enough.all():
+        refuse(~enough[rid], "fewer than 3 distinct positions")
+    # vertex j -> its successor in the ring, the last one back to the first; a ring that is closed already has no such edge
+    nxt = idx + 1
+    last = start[1:] - 1
+    nxt[last] = start[:-1]
+    keep = np.ones(len(A), dtype=bool)
+    keep[last] = (A[last] != A[start[:-1]]).any(1)
+    edges = np.ascontiguousarray(np.concatenate([A, A[nxt]], 1)[keep])
+    ring_edges = n - 1 + keep[last]
+    first_ring = np.searchsorted(ring_poly, np.arange(P + 1))              # ring_poly is non-decreasing
+    e_at = np.concatenate([[0], np.cumsum(ring_edges)])
+    table[:, 0], table[:, 1] = e_at[first_ring[:-1]], e_at[first_ring[1:]]
+    has = first_ring[1:] > first_ring[:-1]
+    lo = np.minimum.reduceat(A, start[first_ring[:-1][has]])
+    hi = np.maximum.reduceat(A, start[first_ring[:-1][has]])
+    # rows whose scanline an edge can cross and columns a crossing can land in, one to spare: a box that is too large costs time
+    # only, the rule is applied per edge on the device
+    r0, r1 = np.clip(np.floor(lo[:, 1] - 0.5), 0, H), np.clip(np.ceil(hi[:, 1] - 0.5) + 1, 0, H)
+    c0, c1 = np.clip(np.floor(lo[:, 0] - 0.5) - 1, 0, W), np.clip(np.ceil(hi[:, 0] - 0.5) + 2, 0, W)
+    box = np.stack([r0, r1, c0, c1], 1).astype(np.int32)
+    box[(r1 <= r0) | (c1 <= c0)] = 0
+    table[has, 2:6] = box
+    rows = (table[:, 3] - table[:, 2]).astype(np.int64)
+    job0 = np.concatenate([[0], np.cumsum(rows)])
+    E, jobs = len(edges), int(job0[-1])
+    if E >= 2 ** 31 or jobs >= 2 ** 31:
+        raise ValueError(f"rasterize_polygons: {E} edges, {jobs} (polygon, row) jobs: both must stay below 2^31")
+    table[:, 6] = job0[:-1]
+    return edges, table
+
+
+def _align256(n):
+    return (int(n) + 255) // 256 * 256
+
+
+def rasterize_upload(edges, table, values=None, device="cuda"):
+    """``polygon_edges`` output (and int32 ``values``, or None for 1..P) -> the operands of ``rasterize_launch``: edges, table and
+    values packed into one buffer and uploaded in ONE copy"""
+    E, P = len(edges), len(table)
+    off_t = _align256(E * 32)
+    off_v = off_t + _align256(P * 32)
+    buf = np.zeros(off_v + _align256(P * 4) + 256, dtype=np.uint8)
+    buf[:E * 32] = edges.view(np.uint8).reshape(-1)
+    buf[off_t:off_t + P * 32] = table.view(np.uint8).reshape(-1)
+    if values is not None:
+        buf[off_v:off_v + P * 4] = np.ascontiguousarray(values, dtype=np.int32).view(np.uint8)
+    _lib.require_device()
+    return {"buffer": torch.from_numpy(buf).to(device), "table": table, "E": E, "off_table": off_t,
+            "off_values": off_v if values is not None else None}
+
+
+def rasterize_launch(ops, shape, out=None):
+    """one ``sc_rasterize_polygons`` call on uploaded operands -> device int32 (H, W)"""
+    H, W = (int(v) for v in shape)
+    buf, table = ops["buffer"], ops["table"]
+    if out is None:
+        out = torch.empty((H, W), dtype=torch.int32, device=buf.device)
+    a = _lib.sc_rast_args()
+    base = buf.data_ptr()
+    a.edges, a.polys, a.polys_host = base, base + ops["off_table"], table.ctypes.data
+    a.values = base + ops["off_values"] if ops["off_values"] is not None else None
+    a.out, a.E, a.P, a.H, a.W = out.data_ptr(), ops["E"], len(table), H, W
+    check(_lib.load().sc_rasterize_polygons(a, stream()))
+    return out
+
+
+def rasterize_polygons(polygons, shape, geotransform=None, values=None, item=0):
+    """Burn polygons into a label image on the device, the inverse of ``plume_outlines`` (``sc_rasterize_polygons``;
+    include/starcop_hip.h has the rule): -> device int32 (H, W), 0 where no polygon covers the pixel.
+
+    ``polygons``: a sequence of ring lists (every ring an (n, 2) array, n >= 3, closed or not, any winding; ``None`` burns
+    nothing), or the dict ``{(item, plume_id): [ring, ...]}`` of ``plume_outlines``, iterated in its order, of which only the keys
+    of ``item`` are burnt.  With ``geotransform`` (GDAL 6-tuple, north up; a rotated one is a NotImplementedError) the rings are
+    (x, y) and are converted on the host in float64, col = (x - gt0) / gt1 and row = (y - gt3) / gt5; without, they are (col, row):
+    pixel (r, c) covers [c, c+1) x [r, r+1).  Coverage is even-odd over all rings of a polygon (exterior and holes, the parts of a
+    MultiPolygon), a pixel belongs to a polygon when its centre is inside, centres on the outline by a top-left rule.  Polygon i
+    burns ``values[i]`` (int32; default i + 1, for the dict its ``plume_id``); where polygons overlap the later one wins.
+    Vertices may lie anywhere outside the raster.  Two calls give identical bytes."""
+    polys, default = _polygon_list(polygons, item)
+    H, W = (int(v) for v in shape)
+    edges, table = polygon_edges(polys, (H, W), geotransform)
+    P = len(polys)
+    vals = np.asarray(default if values is None else values).reshape(-1)
+    if vals.size != P:
+        raise ValueError(f"rasterize_polygons: {vals.size} values for {P} polygons")
+    if P and (vals.dtype.kind not in "iu" or vals.min() < -2 ** 31 or vals.max() >= 2 ** 31):
+        raise ValueError("rasterize_polygons: values must be integers in the int32 range")
+    _lib.require_device()
+    if P == 0 or not (table[:, 3] > table[:, 2]).any():
+        return torch.zeros((H, W), dtype=torch.int32, device="cuda")
+    identity = np.array_equal(vals, np.arange(1, P + 1))
+    return rasterize_launch(rasterize_upload(edges, table, None if identity else vals.astype(np.int32)), (H, W))
+
+
+def _match_burnt(pred_mask, burnt, P, connectivity, min_overlap_px, min_area):
+    pred = plume_table(pred_mask, label_mask=(burnt != 0).to(torch.uint8), connectivity=connectivity, min_area=min_area)
+    other = _to_device(pred_mask, burnt.device)
+    st = component_stats(burnt, P, other=other, M=P)
+    lab = table_from_stats(_read_back(st), [P], burnt.shape[-1], with_other=True, min_area=min_area)
+    tp = int((pred["overlap_px"] >= min_overlap_px).sum())
+    fp = len(pred) - tp
+    fn = int((lab["overlap_px"] < min_overlap_px).sum())
+    cm = torch.tensor([[0, fp], [fn, tp]], dtype=torch.float64)
+    return {"pred": pred, "label": lab, "tp": tp, "fp": fp, "fn": fn,
+            "precision": float(metrics.precision(cm)), "recall": float(metrics.recall(cm))}
+
+
+def match_plumes_polygons(pred_mask, polygons, geotransform=None, connectivity=2, min_overlap_px=1, min_area=1):
+    """``match_plumes`` against labelled POLYGONS (a sequence of ring lists or the dict of ``plume_outlines``, as
+    ``rasterize_polygons`` takes them; with ``geotransform`` in its coordinates): the polygons are burnt with values 1..P on the
+    grid of ``pred_mask`` ((H, W), numpy or device) and the labelled objects are the polygons themselves, not the connected
+    components of their union -- two polygons that share an edge stay two.  The ``label`` table is ``component_stats`` of the burnt
+    image against ``pred_mask``, one row per polygon that burnt at least ``min_area`` pixels (``plume_id`` = its position + 1);
+    the ``pred`` table is ``plume_table(pred_mask, label_mask=burnt != 0)``.  Returns the dict ``match_plumes`` returns."""
+    shape = tuple(pred_mask.shape)
+    if len(shape) != 2:
+        raise ValueError(f"match_plumes_polygons: expected an (H, W) mask, got {shape}")
+    polys, _ = _polygon_list(polygons)
+    burnt = rasterize_polygons(polys, shape, geotransform=geotransform)
+    return _match_burnt(pred_mask, burnt, len(polys), connectivity, min_overlap_px, min_area)
