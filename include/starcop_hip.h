@@ -1310,6 +1310,63 @@ typedef struct sc_rast_args {
 } sc_rast_args;
 int sc_rasterize_polygons(const sc_rast_args* a, sc_stream stream);
 
+/* Cloud-Optimized GeoTIFF products (starcop_amd/cog.py: write_cog; the reference's georeader.save_cog): overview pyramid, TIFF
+ * tiles and the search for empty tiles on the device.  An image is (nb, h, w), uint8 (elem_bytes 1) or float32 (4), 1 <= nb <= 4,
+ * read in place through non-negative element strides: an (h, w, nb) interleaved view has col_stride = nb.  Samples are compared
+ * and moved as BIT PATTERNS: with has_nodata, a sample whose bits equal nodata_bits is nodata (-0.0 is not 0.0).
+ *   sc_overview_reduce  halves the image `levels` (1..3) times in one launch: dst[k] is dense (nb, ceil(h / 2^(k+1)),
+ *       ceil(w / 2^(k+1))).  Pixel (r, c) of a level is made from pixels (2r + i, 2c + j), i, j in {0, 1}, of the level before
+ *       that lie inside it; every band on its own.  A sample is valid unless it is NaN (float32) or nodata.
+ *         SC_COG_AVERAGE float32: (float)(S / count), S the float64 sum of the valid samples in the order (0,0), (0,1), (1,0),
+ *                                 (1,1) (a single sample is its own sum), one rounding per operation; none valid: nodata, or
+ *                                 the NaN 0x7FC00000 without one.
+ *                        uint8:   (2 S + count) / (2 count) in integers; none valid: nodata.
+ *         SC_COG_NEAREST          the bits of pixel (2r, 2c).
+ *         SC_COG_MODE    uint8:   the most frequent valid value, the smallest of equally frequent ones; none valid: nodata.
+ *       Level k + 1 is computed from the stored bits of level k: a launch of three levels equals three launches of one.  A
+ *       work-group owns an aligned 64 x 64 source block and keeps the intermediate levels in LDS.  16-byte loads where
+ *       col_stride = 1, the run lies inside the image and its address is 16-byte aligned; 16-byte stores where the level's width
+ *       is a multiple of the vector and dst[k] is 16-byte aligned; element accesses otherwise.
+ *   sc_tiff_tile_flags  flags[tile] = 1 where every in-image sample of every band of the bs x bs tile (row-major tile order) has
+ *       the bits of the fill value -- nodata_bits with has_nodata, else 0 -- and 0 otherwise.  Padding does not count.
+ *   sc_tiff_pack_tiles  tile t with slots[t] >= 0 is written to out + slots[t] * bs * bs * nb * elem_bytes as TIFF tile bytes:
+ *       [bs][bs][nb] chunky little-endian samples, zero beyond the image edge, then the predictor per tile row: 1 none; 2 (uint8)
+ *       byte k of a row minus byte k - nb, modulo 256; 3 (float32, TIFF Technical Note 3) the 4 * bs * nb bytes of a row ordered
+ *       by significance, most significant byte of every sample first, then byte k minus byte k - nb over the whole row.  Tiles
+ *       with slot -1 are not touched.  The slot table is given twice, on the device for the kernel and on the host for the
+ *       checks made before the launch: every slot is -1 or inside [0, n_slots), no slot is given twice, out_bytes holds
+ *       n_slots tiles, and the device table is read back and compared (one stream synchronisation).  n_slots = 0 launches nothing.
+ * bs is a multiple of 16 with bs * nb * elem_bytes <= 32768; out is 16-byte aligned.  Addresses are 64-bit.  SC_ERR_ARG, before
+ * any launch, for anything else.  No floating-point atomics: two calls give identical bytes.                                      */
+#define SC_COG_MAX_BANDS 4
+enum sc_cog_resampling { SC_COG_AVERAGE = 0, SC_COG_NEAREST = 1, SC_COG_MODE = 2 };
+typedef struct sc_cog_image {
+  const void* data;                               /* element [0][0][0], device                                     */
+  int32_t elem_bytes;                             /* 1 = uint8, 4 = float32                                        */
+  int32_t nb, h, w;
+  int64_t band_stride, row_stride, col_stride;    /* elements                                                      */
+  int32_t has_nodata;
+  uint32_t nodata_bits;                           /* bit pattern of the nodata value (low elem_bytes bytes)        */
+} sc_cog_image;
+typedef struct sc_overview_args {
+  sc_cog_image src;
+  int32_t resampling;                             /* enum sc_cog_resampling                                        */
+  int32_t levels;                                 /* 1..3                                                          */
+  void* dst[3];                                   /* dense (nb, h_k, w_k) per level, device                        */
+} sc_overview_args;
+typedef struct sc_tiff_pack_args {
+  sc_cog_image src;
+  int32_t bs, predictor;
+  int32_t n_slots, reserved;
+  const int32_t* slots;                           /* [tiles] device: slot of each tile, -1 = do not write          */
+  const int32_t* slots_host;                      /* the same on the host                                          */
+  void* out;                                      /* [n_slots][bs][bs][nb] samples, device                         */
+  size_t out_bytes;
+} sc_tiff_pack_args;
+int sc_overview_reduce(const sc_overview_args* a, sc_stream stream);
+int sc_tiff_tile_flags(const sc_cog_image* src, int bs, uint8_t* flags /*[tiles] device*/, sc_stream stream);
+int sc_tiff_pack_tiles(const sc_tiff_pack_args* a, sc_stream stream);
+
 /* ------------------------------------------------------------------------- */
 /* HOST functions (no device involved): decoders of the on-disk sample format -- one tiled GeoTIFF per product per sample,
  * read by rasterio in the reference (starcop/data/dataset.py:66-76, written by save_cog at sampling_dataset.py:332-355).

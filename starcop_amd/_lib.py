@@ -246,6 +246,28 @@ class sc_rast_args(C.Structure):
                 ("E", C.c_int64), ("P", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("reserved", C.c_int32)]
 
 
+COG_MAX_BANDS = 4
+COG_AVERAGE, COG_NEAREST, COG_MODE = 0, 1, 2             # enum sc_cog_resampling
+
+
+class sc_cog_image(C.Structure):
+    """a (nb, h, w) image read in place (include/starcop_hip.h: sc_cog_image)"""
+    _fields_ = [("data", C.c_void_p), ("elem_bytes", C.c_int32), ("nb", C.c_int32), ("h", C.c_int32), ("w", C.c_int32),
+                ("band_stride", C.c_int64), ("row_stride", C.c_int64), ("col_stride", C.c_int64),
+                ("has_nodata", C.c_int32), ("nodata_bits", C.c_uint32)]
+
+
+class sc_overview_args(C.Structure):
+    """overview-pyramid operands (include/starcop_hip.h: sc_overview_args)"""
+    _fields_ = [("src", sc_cog_image), ("resampling", C.c_int32), ("levels", C.c_int32), ("dst", C.c_void_p * 3)]
+
+
+class sc_tiff_pack_args(C.Structure):
+    """TIFF tile-packing operands (include/starcop_hip.h: sc_tiff_pack_args)"""
+    _fields_ = [("src", sc_cog_image), ("bs", C.c_int32), ("predictor", C.c_int32), ("n_slots", C.c_int32), ("reserved", C.c_int32),
+                ("slots", C.c_void_p), ("slots_host", C.c_void_p), ("out", C.c_void_p), ("out_bytes", C.c_size_t)]
+
+
 _vp, _i, _f, _d, _sz =C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/starcop_hip.h declares
@@ -398,6 +420,9 @@ SIGNATURES = {
     "sc_component_outlines_rounds": (_i, [C.c_int64]),
     "sc_component_outlines": (_i, [C.POINTER(sc_outline_args), _i, _vp]),
     "sc_rasterize_polygons": (_i, [C.POINTER(sc_rast_args), _vp]),
+    "sc_overview_reduce": (_i, [C.POINTER(sc_overview_args), _vp]),
+    "sc_tiff_tile_flags": (_i, [C.POINTER(sc_cog_image), _i, _vp, _vp]),
+    "sc_tiff_pack_tiles": (_i, [C.POINTER(sc_tiff_pack_args), _vp]),
     "sc_tiff_lzw_decode": (_i, [_vp, _sz, _vp, _sz, C.POINTER(C.c_size_t)]),
     "sc_tiff_unpredict": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp]),
 }

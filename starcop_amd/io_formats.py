@@ -11,7 +11,10 @@ What the reference reads and writes on this path:
 ``read_tiff`` decodes classic (32-bit offset) TIFFs, tiled or stripped, 8/16/32/64-bit unsigned / signed / float samples,
 chunky or planar multi-band, compression none / deflate / LZW with predictor 1, 2 or 3, either byte order, and reads only the
 blocks a window touches (the first IFD = full resolution of a COG).  ``write_tiff`` writes tiled (BLOCKSIZE 128), deflate or
-uncompressed files that carry the GeoTIFF tags handed to it, so a round trip keeps the georeferencing.  ``open_envi`` parses an
+uncompressed files that carry the GeoTIFF tags handed to it, so a round trip keeps the georeferencing.  ``write_tiff_levels`` lays
+finished tiles out as a Cloud-Optimized GeoTIFF (IFDs first, overviews, sparse tiles; ``starcop_amd.cog`` packs the tiles on the
+device), ``tiff_info(path, ifd=k)`` / ``tiff_ifd_count`` reach its overviews and ``cog_layout_problems`` checks the layout rules.
+``open_envi`` parses an
 ENVI header and returns the cube as a (lines, samples, bands) memmap view plus wavelengths / fwhm.  ``load_tileset`` reads the
 sample folders of a split into pinned host buffers and uploads them asynchronously into a ``ResidentTileSet``.
 LZW and the predictors are undone by host C++ in libstarcop_hip.so (sc_tiff_lzw_decode / sc_tiff_unpredict): a Python loop
@@ -46,18 +49,52 @@ class TiffInfo:
         return {t: v for t, v in self.tags.items() if t in GEO_TAGS}
 
 
-def tiff_info(path) -> TiffInfo:
+def _tiff_header(f, path):
+    """-> (byte order, offset of the first IFD) of an open classic TIFF"""
+    head = f.read(8)
+    bo = {b"II": "<", b"MM": ">"}.get(head[:2])
+    if bo is None:
+        raise ValueError(f"{path}: not a TIFF file")
+    magic, ifd = struct.unpack(bo + "HI", head[2:8])
+    if magic == 43:
+        raise NotImplementedError(f"{path}: BigTIFF is not supported (STARCOP samples are classic TIFFs of ~1 MB)")
+    if magic != 42:
+        raise ValueError(f"{path}: bad TIFF magic {magic}")
+    return bo, ifd
+
+
+def _ifd_offsets(f, path):
+    """-> (byte order, [offset of every IFD of the chain])"""
+    bo, off = _tiff_header(f, path)
+    offs = []
+    while off and len(offs) < 65536:
+        if off in offs:
+            raise ValueError(f"{path}: the IFD chain loops")
+        offs.append(off)
+        f.seek(off)
+        n, = struct.unpack(bo + "H", f.read(2))
+        f.seek(off + 2 + 12 * n)
+        off, = struct.unpack(bo + "I", f.read(4))
+    return bo, offs
+
+
+def tiff_ifd_count(path) -> int:
+    """number of IFDs (images: the full resolution and its overviews) of a TIFF file"""
     with open(path, "rb") as f:
-        head = f.read(8)
-        bo = {b"II": "<", b"MM": ">"}.get(head[:2])
-        if bo is None:
-            raise ValueError(f"{path}: not a TIFF file")
-        magic, ifd = struct.unpack(bo + "HI", head[2:8])
-        if magic == 43:
-            raise NotImplementedError(f"{path}: BigTIFF is not supported (STARCOP samples are classic TIFFs of ~1 MB)")
-        if magic != 42:
-            raise ValueError(f"{path}: bad TIFF magic {magic}")
-        f.seek(ifd)
+        return len(_ifd_offsets(f, path)[1])
+
+
+def tiff_info(path, ifd: int = 0) -> TiffInfo:
+    """``ifd``: which image of the file (0 = the full resolution of a COG, k = its k-th overview); IndexError past the last"""
+    with open(path, "rb") as f:
+        if ifd == 0:
+            bo, off = _tiff_header(f, path)
+        else:
+            bo, offs = _ifd_offsets(f, path)
+            if not 0 <= ifd < len(offs):
+                raise IndexError(f"{path}: IFD {ifd} of a file with {len(offs)}")
+            off = offs[ifd]
+        f.seek(off)
         n, = struct.unpack(bo + "H", f.read(2))
         raw = f.read(12 * n)
         info = TiffInfo()
@@ -252,6 +289,227 @@ def write_tiff(path, array, blocksize: int = 128, compress: Optional[str] = "def
             f.write(data + (b"\0" if len(data) & 1 else b""))
         for b in blocks:
             f.write(b + (b"\0" if len(b) & 1 else b""))
+
+
+_MAIN_ONLY_TAGS = (33550, 33922, 34264, 34735, 34736, 34737, 42112)       # georeferencing and GDAL metadata: IFD 0 of a COG only
+
+
+def _pack_tag(typ, vals):
+    if typ == 2:
+        return vals[0].encode("latin-1") + b"\0"
+    return struct.pack("<" + _TYPES[typ][0][0] * len(vals), *vals)
+
+
+def write_tiff_levels(path, levels, dtype, bands: int = 1, blocksize: int = 128, compress: Optional[str] = "deflate", predictor: int = 1,
+                      extra_tags: Optional[Dict[int, tuple]] = None) -> int:
+    """Finished tiles -> a classic little-endian TIFF in Cloud-Optimized GeoTIFF order.  Pure host code: the tiles arrive encoded.
+
+    ``levels`` = [((h, w), payloads), ...], the full resolution first, then every overview, each ceil(previous / 2); ``payloads``
+    lists the tiles of a level row-major: ``bytes`` as they go into the file (a [blocksize][blocksize][bands] chunky little-endian
+    tile after ``predictor`` and ``compress``), or None for a tile that is absent.  ``extra_tags`` are the tags of the main image.
+
+    Layout: the header, IFD 0 at offset 8 and its out-of-line values, then one IFD per overview (NewSubfileType = 1; the same tile
+    size, sample format, compression and predictor; GDAL_NODATA repeated; the georeferencing and the GDAL metadata stay on the main
+    image) each followed by its values, and only then tile bytes: the smallest overview first, the full resolution last, row-major
+    inside a level.  An absent tile has offset = byte count = 0 (GDAL's sparse form, which ``read_tiff`` reads as nodata).  No
+    GDAL structural-metadata block is written: it would declare block leaders that are not there.  A file that would pass 4 GiB
+    raises NotImplementedError (BigTIFF).  Returns the file size."""
+    dt = np.dtype(dtype)
+    kind = {"u": 1, "i": 2, "f": 3}.get(dt.kind)
+    if kind is None or dt.itemsize not in (1, 2, 4, 8):
+        raise ValueError(f"write_tiff_levels: unsupported dtype {dt}")
+    if blocksize <= 0 or blocksize % 16:
+        raise ValueError("write_tiff_levels: TIFF tile sizes must be multiples of 16")
+    comp = {None: 1, "none": 1, "deflate": 8}.get(compress)
+    if comp is None:
+        raise ValueError(f"write_tiff_levels: compress must be None or 'deflate' (got {compress!r})")
+    if predictor not in (1, 2, 3) or (predictor == 2 and kind == 3) or (predictor == 3 and kind != 3):
+        raise ValueError(f"write_tiff_levels: predictor {predictor} on {dt} samples")
+    levels = [((int(h), int(w)), list(tiles)) for (h, w), tiles in levels]
+    if not levels:
+        raise ValueError("write_tiff_levels: no image")
+    nb = int(bands)
+    for k, ((h, w), tiles) in enumerate(levels):
+        if h < 1 or w < 1 or len(tiles) != (-(-h // blocksize)) * (-(-w // blocksize)):
+            raise ValueError(f"write_tiff_levels: level {k} is {h} x {w} with {len(tiles)} tiles of {blocksize}")
+        if k and (h, w) != (-(-levels[k - 1][0][0] // 2), -(-levels[k - 1][0][1] // 2)):
+            raise ValueError(f"write_tiff_levels: level {k} is {h} x {w}, not half of {levels[k - 1][0]}")
+    extra = {int(t): v for t, v in (extra_tags or {}).items()}
+    ifds = []
+    for k, ((h, w), tiles) in enumerate(levels):
+        e = {256: (4, (w,)), 257: (4, (h,)), 258: (3, (8 * dt.itemsize,) * nb), 259: (3, (comp,)), 262: (3, (1,)), 277: (3, (nb,)),
+             284: (3, (1,)), 322: (4, (blocksize,)), 323: (4, (blocksize,)), 339: (3, (kind,) * nb),
+             324: (4, (0,) * len(tiles)), 325: (4, tuple(0 if t is None else len(t) for t in tiles))}
+        if k:
+            e[254] = (4, (1,))                          # NewSubfileType: a reduced-resolution image
+        if predictor != 1:
+            e[317] = (3, (predictor,))
+        if nb > 1:
+            e[338] = (3, (0,) * (nb - 1))
+        for tag, tv in extra.items():
+            if tag not in e and tag not in (254, 317, 273, 279, 278) and (k == 0 or tag == 42113):
+                e[tag] = tv
+        ifds.append(e)
+    # pass 1: where every IFD and every out-of-line value goes
+    pos = 8
+    plan = []
+    for e in ifds:
+        start = pos
+        pos += 2 + 12 * len(e) + 4
+        ool = {}
+        for tag in sorted(e):
+            n = len(_pack_tag(*e[tag]))
+            if n > 4:
+                ool[tag] = pos
+                pos += n + (n & 1)
+        plan.append((start, ool))
+    # pass 2: the tiles, the smallest overview first
+    for k in range(len(levels) - 1, -1, -1):
+        offs = []
+        for t in levels[k][1]:
+            offs.append(0 if t is None else pos)
+            if t is not None:
+                if len(t) == 0:
+                    raise ValueError("write_tiff_levels: an empty tile payload (None marks an absent tile)")
+                pos += len(t) + (len(t) & 1)
+        ifds[k][324] = (4, tuple(offs))
+    if pos > 0xFFFFFFFF:
+        raise NotImplementedError(f"{path}: {pos} bytes do not fit a classic TIFF (BigTIFF is not supported)")
+    with open(path, "wb") as f:
+        f.write(struct.pack("<2sHI", b"II", 42, 8))
+        for k, e in enumerate(ifds):
+            start, ool = plan[k]
+            assert f.tell() == start, (k, f.tell(), start)
+            f.write(struct.pack("<H", len(e)))
+            for tag in sorted(e):
+                typ, vals = e[tag]
+                data = _pack_tag(typ, vals)
+                cnt = len(data) if typ == 2 else len(vals) // len(_TYPES[typ][0])
+                if tag in ool:
+                    f.write(struct.pack("<HHII", tag, typ, cnt, ool[tag]))
+                else:
+                    f.write(struct.pack("<HHI4s", tag, typ, cnt, data.ljust(4, b"\0")))
+            f.write(struct.pack("<I", plan[k + 1][0] if k + 1 < len(ifds) else 0))
+            for tag in sorted(ool):
+                data = _pack_tag(*e[tag])
+                assert f.tell() == ool[tag], (tag, f.tell(), ool[tag])
+                f.write(data + (b"\0" if len(data) & 1 else b""))
+        for k in range(len(levels) - 1, -1, -1):
+            for t in levels[k][1]:
+                if t is not None:
+                    f.write(t)
+                    if len(t) & 1:
+                        f.write(b"\0")
+        assert f.tell() == pos, (f.tell(), pos)
+    return pos
+
+
+def _raw_ifds(path):
+    """every IFD of a little- or big-endian classic TIFF as it lies in the file -> (byte order, [{"offset", "end", "next",
+    "entries": {tag: {"type", "count", "pos": file position of the 12-byte entry, "value_offset": position of an out-of-line value
+    or None, "nbytes", "values"}}}])"""
+    out = []
+    with open(path, "rb") as f:
+        bo, offs = _ifd_offsets(f, path)
+        for off in offs:
+            f.seek(off)
+            n, = struct.unpack(bo + "H", f.read(2))
+            raw = f.read(12 * n)
+            nxt, = struct.unpack(bo + "I", f.read(4))
+            entries = {}
+            for i in range(n):
+                tag, typ, cnt, val = struct.unpack(bo + "HHI4s", raw[12 * i:12 * i + 12])
+                if typ not in _TYPES:
+                    continue
+                code, size = _TYPES[typ]
+                nbytes = size * cnt
+                voff = None
+                if nbytes <= 4:
+                    data = val[:nbytes]
+                else:
+                    voff, = struct.unpack(bo + "I", val)
+                    f.seek(voff)
+                    data = f.read(nbytes)
+                vals = (data.rstrip(b"\0").decode("latin-1"),) if typ == 2 else struct.unpack(bo + code[0] * (cnt * len(code)), data)
+                entries[tag] = {"type": typ, "count": cnt, "pos": off + 2 + 12 * i, "value_offset": voff, "nbytes": nbytes, "values": vals}
+            out.append({"offset": off, "end": off + 2 + 12 * n + 4, "next": nxt, "entries": entries})
+    return bo, out
+
+
+def cog_layout_problems(path):
+    """The layout rules of a Cloud-Optimized GeoTIFF as ``write_tiff_levels`` writes it -> a list of sentences, empty for a
+    conforming file: classic little-endian TIFF, IFD 0 at offset 8, every IFD behind the one before it, every image tiled, every
+    overview marked with NewSubfileType bit 0, ceil(previous / 2) in size and alike in tile size, samples, compression, predictor
+    and GDAL_NODATA, georeferencing and GDAL metadata on the main image only, every IFD and every out-of-line value in front of the
+    first tile byte, tile data ascending from the smallest overview to the full resolution and row-major inside a level, absent
+    tiles with offset = byte count = 0."""
+    problems = []
+    try:
+        bo, ifds = _raw_ifds(path)
+    except (ValueError, NotImplementedError, struct.error) as e:
+        return [f"not a readable classic TIFF: {e}"]
+    if bo != "<":
+        problems.append("the file is big-endian")
+    if not ifds:
+        return problems + ["the file has no IFD"]
+    if ifds[0]["offset"] != 8:
+        problems.append(f"IFD 0 is at offset {ifds[0]['offset']}, not 8")
+
+    def val(e, tag, default=None):
+        return e[tag]["values"] if tag in e else default
+    first_tile = None
+    runs = []
+    for k, d in enumerate(ifds):
+        e = d["entries"]
+        if k and d["offset"] <= ifds[k - 1]["offset"]:
+            problems.append(f"IFD {k} at offset {d['offset']} does not follow IFD {k - 1} at {ifds[k - 1]['offset']}")
+        if 322 not in e or 323 not in e or 324 not in e or 325 not in e:
+            problems.append(f"IFD {k} is not tiled")
+            continue
+        offs, cnts = e[324]["values"], e[325]["values"]
+        h, w, bh, bw = val(e, 257)[0], val(e, 256)[0], val(e, 323)[0], val(e, 322)[0]
+        if len(offs) != len(cnts) or len(offs) != (-(-h // bh)) * (-(-w // bw)) * (val(e, 277, (1,))[0] if val(e, 284, (1,))[0] == 2 else 1):
+            problems.append(f"IFD {k}: {len(offs)} tile offsets and {len(cnts)} byte counts for a {h} x {w} image of {bh} x {bw} tiles")
+        if any((o == 0) != (c == 0) for o, c in zip(offs, cnts)):
+            problems.append(f"IFD {k}: an absent tile must have offset = byte count = 0")
+        runs.append((k, [o for o in offs if o]))
+        for o in offs:
+            if o and (first_tile is None or o < first_tile):
+                first_tile = o
+        sub = val(e, 254, (0,))[0]
+        if k == 0:
+            if sub & 1:
+                problems.append("IFD 0 is marked as a reduced-resolution image (NewSubfileType)")
+            continue
+        m = ifds[0]["entries"]
+        p = ifds[k - 1]["entries"]
+        if not sub & 1:
+            problems.append(f"IFD {k}: NewSubfileType is missing or lacks the reduced-resolution bit")
+        if 256 in p and 257 in p and (h, w) != (-(-val(p, 257)[0] // 2), -(-val(p, 256)[0] // 2)):
+            problems.append(f"IFD {k} is {h} x {w}, not half of the {val(p, 257)[0]} x {val(p, 256)[0]} of IFD {k - 1}")
+        for tag, name in ((322, "tile width"), (323, "tile length"), (258, "bits per sample"), (339, "sample format"), (277, "samples per pixel"),
+                          (259, "compression"), (317, "predictor"), (284, "planar configuration"), (42113, "GDAL_NODATA")):
+            if val(e, tag) != val(m, tag):
+                problems.append(f"IFD {k}: {name} {val(e, tag)} differs from the main image's {val(m, tag)}")
+        for tag in _MAIN_ONLY_TAGS:
+            if tag in e:
+                problems.append(f"IFD {k} carries tag {tag}, which belongs to the main image only")
+    if first_tile is not None:
+        for k, d in enumerate(ifds):
+            if d["end"] > first_tile:
+                problems.append(f"IFD {k} ends at {d['end']}, behind the first tile byte at {first_tile}")
+            for tag, t in d["entries"].items():
+                if t["value_offset"] is not None and t["value_offset"] + t["nbytes"] > first_tile:
+                    problems.append(f"IFD {k}: the values of tag {tag} at {t['value_offset']} lie behind the first tile byte at {first_tile}")
+    last = 0
+    for k, offs in reversed(runs):
+        for i, o in enumerate(offs):
+            if o <= last:
+                problems.append(f"IFD {k}: tile data at {o} is not behind {last}: tiles go row-major, the smallest overview first and "
+                                f"the full resolution last")
+                break
+            last = o
+    return problems
 
 
 # ------------------------------------------------------------------------------------------------ PNG

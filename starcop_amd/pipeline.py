@@ -226,7 +226,7 @@ def _emit_predict_parts(model, sub, rgb, ratio, template, fill_value, column_ste
 def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_lerp_alpha=1e-4, tile=None, halo=RECEPTIVE_HALO,
                          ratio_bands=None, distributed=None, group=None, rows=None, threads=8, strips=True, georeferenced=False,
                          out_folder=None, geotransform=None, overwrite=False, plumes=False, plume_outlines=False,
-                         label_polygons=None):
+                         label_polygons=None, cog=False):
     """The notebook path of the reference end to end FROM THE FILE (notebooks/inference_on_raw_EMIT_nc_file.ipynb cells 8-19:
     ``EMITImage(path)`` -> ``mag1c_emit`` -> RGB bands -> rescale -> ``model`` -> threshold): opens the EMIT L1B radiance granule
     (NetCDF-4) with :mod:`starcop_amd.hdf5_reader`, reads ONLY what the pipeline touches -- the contiguous band slice inside
@@ -255,7 +255,11 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
     :func:`starcop_amd.plumes.rasterize_polygons` takes them, in the coordinates of the geotransform; needs ``georeferenced=True``,
     there is no grid to burn into otherwise) adds ``label_mask``, the polygons burnt into the product grid (device uint8), and
     ``plume_match``, :func:`starcop_amd.plumes.match_plumes_polygons` of ``pred_binary`` against them; with ``out_folder`` the
-    mask is written as ``label.tif`` like ``predbinary.tif``."""
+    mask is written as ``label.tif`` like ``predbinary.tif``.
+
+    ``cog=True`` (or a dict of :func:`starcop_amd.cog.write_cog` keyword arguments) writes every raster as a Cloud-Optimized
+    GeoTIFF -- tiled, with an overview pyramid, empty tiles left out -- straight from the device tensors; the default leaves the
+    files as they were."""
     from .hdf5_reader import H5File
     if out_folder is not None:
         if str(out_folder).startswith("gs://"):
@@ -308,14 +312,27 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
     if label_polygons is not None:
         _burn_label_polygons(out, label_polygons, gt)
     if out_folder is not None:
-        out["files"] = _write_emit_products(out, str(out_folder), fill, gt, root.get("spatial_ref"), overwrite)
+        out["files"] = _write_emit_products(out, str(out_folder), fill, gt, root.get("spatial_ref"), overwrite, cog)
         if label_polygons is not None:
             from .ortho import emit_geo_tags
             geo = emit_geo_tags(gt, root.get("spatial_ref")) if gt is not None else {}
-            out["files"] += _write_label_tif(out, str(out_folder), geo, overwrite)
+            out["files"] += _write_label_tif(out, str(out_folder), geo, overwrite, cog)
         if plumes:
             out["files"] += _write_plume_files(out, str(out_folder), overwrite)
     return out
+
+
+def _write_raster(path, tensor, tags, cog=False, nodata=None):
+    """one raster product of a scene run: ``write_tiff`` of the host copy, or with ``cog`` (True, or a dict of ``cog.write_cog``
+    keyword arguments) a Cloud-Optimized GeoTIFF straight from the device tensor -- tiles and overviews are made on the device,
+    float32 products averaged, uint8 ones by mode, and only the tiles that are stored cross to the host"""
+    from . import io_formats as io
+    if not cog:
+        io.write_tiff(path, tensor.cpu().numpy(), blocksize=128, extra_tags=tags)
+        return
+    from .cog import write_cog
+    kw = {"blocksize": 128, **(cog if isinstance(cog, dict) else {})}
+    write_cog(path, tensor, nodata=nodata, extra_tags=tags, **kw)
 
 
 def _burn_label_polygons(out, label_polygons, geotransform):
@@ -332,7 +349,7 @@ def _burn_label_polygons(out, label_polygons, geotransform):
     out["plume_match"] = pl._match_burnt(pred, burnt, len(polys), 2, 1, 1)
 
 
-def _write_label_tif(out, folder, geo_tags, overwrite):
+def _write_label_tif(out, folder, geo_tags, overwrite, cog=False):
     """``label.tif`` like ``predbinary.tif``: uint8, BLOCKSIZE 128, the products' georeferencing -> the paths written"""
     import os
     from . import io_formats as io
@@ -340,7 +357,7 @@ def _write_label_tif(out, folder, geo_tags, overwrite):
     if not overwrite and os.path.exists(path):
         return []
     os.makedirs(folder, exist_ok=True)
-    io.write_tiff(path, out["label_mask"].cpu().numpy(), blocksize=128, extra_tags={**geo_tags, **io.gdal_metadata_tag({}, ["Plume label"])})
+    _write_raster(path, out["label_mask"], {**geo_tags, **io.gdal_metadata_tag({}, ["Plume label"])}, cog)
     return [path]
 
 
@@ -376,7 +393,7 @@ EMIT_PRODUCT_FILES = {"mag1c.tif": ("mf", ["CH4 Absorption (ppm x m)"]), "albedo
                       "rgb.tif": ("rgb", ["Red (640 nm)", "Green (550 nm)", "Blue (460 nm)"])}
 
 
-def _write_emit_products(out, folder, fill, geotransform, spatial_ref, overwrite):
+def _write_emit_products(out, folder, fill, geotransform, spatial_ref, overwrite, cog=False):
     """the orthorectified products of :func:`emit_granule_predict` -> GeoTIFFs in ``folder``; returns the paths written"""
     import os
     import warnings
@@ -397,13 +414,15 @@ def _write_emit_products(out, folder, fill, geotransform, spatial_ref, overwrite
     md = {"wavelengths": out["wavelengths"], "mag1c": "acrwl1mf"}
     written = []
     for path, key, desc in todo:
-        a = out[key].cpu().numpy()
         if key == "pred_binary":
             tags = {**geo, **io.gdal_metadata_tag({}, desc)}
-            a = a.astype(np.uint8)
         else:
             tags = {**geo, **nodata, **io.gdal_metadata_tag(md if key in ("mf", "albedo") else {}, desc)}
-        io.write_tiff(path, a, blocksize=128, extra_tags=tags)
+        if cog:
+            _write_raster(path, out[key].to(torch.uint8) if key == "pred_binary" else out[key], tags, cog, None if key == "pred_binary" else fill)
+        else:
+            a = out[key].cpu().numpy()
+            io.write_tiff(path, a.astype(np.uint8) if key == "pred_binary" else a, blocksize=128, extra_tags=tags)
         written.append(path)
     return written
 
@@ -494,7 +513,7 @@ AVIRIS_PRODUCT_FILES = {"pred.tif": ("prediction", ["Plume probability"]), "pred
 @torch.no_grad()
 def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=None, toa_correction_factor=None, solar_altitude=None,
                          normalize_by_acquisition_date=True, tile=None, halo=None, batch=None, plumes=False, overwrite=False,
-                         device="cuda", plume_outlines=False, label_polygons=None):
+                         device="cuda", plume_outlines=False, label_polygons=None, cog=False):
     """An orthorectified AVIRIS-NG flight line through the plume model, file to file: ``{folder}/{name}_img`` (ENVI radiance,
     float32) -> the network's input products -> ``model.predict_scene`` -> (with ``out_folder``) ``pred.tif`` / ``predbinary.tif``.
 
@@ -516,7 +535,12 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
     Polygon per row of the table, next to ``plumes.csv``.  ``label_polygons`` (a ``.geojson`` path for ``plumes.read_plumes``, or
     polygons as ``plumes.rasterize_polygons`` takes them, in the coordinates of the ``map info``) adds ``label_mask``, the
     polygons burnt into the flight line's grid (device uint8), and ``plume_match``, the ``plumes.match_plumes_polygons`` of the
-    mask against them, and writes ``label.tif`` like ``predbinary.tif``."""
+    mask against them, and writes ``label.tif`` like ``predbinary.tif``.
+
+    ``cog=True`` (or a dict of :func:`starcop_amd.cog.write_cog` keyword arguments) writes every raster of the call --
+    ``pred.tif``, ``predbinary.tif``, ``label.tif`` and a ``mag1c.tif`` it computes -- as a Cloud-Optimized GeoTIFF straight from
+    the device tensor: tiles, overviews (average for float32, mode for uint8) and the search for empty tiles run on the device.
+    The default leaves every byte of the files as it was."""
     import datetime
     import os
     import re
@@ -582,8 +606,7 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
                     tags = io.envi_geo_tags(header)
                     tags[42113] = (2, (str(mag1c.NODATA),))
                     md = {"wavelengths": wl[keep], "mag1c": "acfwl1mf"}
-                    io.write_tiff(mpath, mf.cpu().numpy(), blocksize=128,
-                                  extra_tags={**tags, **io.gdal_metadata_tag(md, ["CH4 Absorption (ppm x m)"])})
+                    _write_raster(mpath, mf, {**tags, **io.gdal_metadata_tag(md, ["CH4 Absorption (ppm x m)"])}, cog, mag1c.NODATA)
                     files.append(mpath)
         if tuple(mf.shape) != tuple(rdn.shape[:2]):
             raise ValueError(f"aviris_scene_predict: mag1c is {tuple(mf.shape)}, the radiance {tuple(rdn.shape[:2])}")
@@ -615,10 +638,10 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
                 continue
             os.makedirs(str(out_folder), exist_ok=True)
             tags = {**geo, **(nodata if key == "prediction" else {}), **io.gdal_metadata_tag({}, desc)}
-            io.write_tiff(path, out[key].cpu().numpy(), blocksize=128, extra_tags=tags)
+            _write_raster(path, out[key], tags, cog, mag1c.NODATA if key == "prediction" else None)
             files.append(path)
         if label_polygons is not None:
-            files += _write_label_tif(out, str(out_folder), geo, overwrite)
+            files += _write_label_tif(out, str(out_folder), geo, overwrite, cog)
         if plumes:
             files += _write_plume_files(out, str(out_folder), overwrite)
         out["files"] = files

@@ -125,14 +125,28 @@ class CDModel(torch.nn.Module):
         return mosaic.cpu().numpy() if is_np else mosaic
 
 
-def cloud_mask_file(src_tif, dst_tif, model, **kw):
+def cloud_mask_file(src_tif, dst_tif, model, cog=False, **kw):
     """13-band GeoTIFF -> uint8 cloud-mask GeoTIFF (``model.predict_scene(bands, **kw)``): 128 x 128 blocks, the source's
-    georeferencing tags, band description "cloudmask" and the class names in the GDAL metadata.  Returns the (H, W) mask."""
+    georeferencing tags, band description "cloudmask" and the class names in the GDAL metadata.  Returns the (H, W) mask.
+    ``cog=True`` (or a dict of ``cog.write_cog`` keyword arguments) keeps the mask on the device and writes it as a
+    Cloud-Optimized GeoTIFF -- tiles and mode-resampled overviews made on the device, all-zero tiles left out; the default
+    leaves every byte of the file as it was."""
     from . import io_formats
     info = io_formats.tiff_info(src_tif)
     bands = io_formats.read_tiff(src_tif, info=info)
-    mask = model.predict_scene(bands, **kw)
+    if cog:
+        from .cog import write_cog
+        if bands.dtype == np.uint16:
+            on_dev = torch.from_numpy(bands.view(np.int16)).to(model.device).view(torch.uint16)
+        else:
+            on_dev = torch.from_numpy(bands).to(model.device)
+        mask = model.predict_scene(on_dev, **kw)
+    else:
+        mask = model.predict_scene(bands, **kw)
     tags = {t: v for t, v in info.geo_tags().items() if t not in (42112, 42113)}       # (the source's metadata / nodata describe its bands)
     tags.update(io_formats.gdal_metadata_tag({f"class_{i}": name for i, name in enumerate(INTERPRETATION_CLOUDSEN12)}, ["cloudmask"]))
+    if cog:
+        write_cog(dst_tif, mask, extra_tags=tags, **{"blocksize": 128, **(cog if isinstance(cog, dict) else {})})
+        return mask.cpu().numpy()
     io_formats.write_tiff(dst_tif, mask, blocksize=128, extra_tags=tags)
     return mask
