@@ -16,13 +16,20 @@ the data path.
 import numpy as np
 import torch
 
-from . import mag1c
+from . import mag1c, products
 from .features import emit_to_aviris_input
 from .model_module import masks_from_logits
+from .products import nodata_text
 from .scene import RECEPTIVE_HALO       # noqa: F401  (re-exported: the halo of scene_tiles / tiled_logits too)
 
 EMIT_MAG1C_RANGE_NM = (2122.0, 2488.0)          # mag1c_emit.py:40-43
 RGB_NM = (640.0, 550.0, 460.0)
+
+
+def _upload_pinned(array, device):
+    """host array -> device tensor through pinned memory, without waiting for the copy"""
+    h = torch.from_numpy(array)
+    return (h.pin_memory() if torch.cuda.is_available() else h).to(device, non_blocking=True)
 
 
 def nearest_bands(wavelengths, targets=RGB_NM):
@@ -293,138 +300,31 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
         root = f.attrs("/") if out_folder is not None or ((plumes or label_polygons is not None) and georeferenced) else {}
     if georeferenced and glt[0] is None:
         raise ValueError(f"{nc_path}: no location/glt_x, location/glt_y to orthorectify with")
-
-    def up(a):
-        h = torch.from_numpy(a)
-        return (h.pin_memory() if torch.cuda.is_available() else h).to(dev, non_blocking=True)
     template = mag1c.generate_template_from_bands(wl[b0:b1], fwhm[b0:b1])
-    out = _emit_predict_parts(model, up(sub_h), up(rgb_h), tuple(up(a) for a in ratio_h) if ratio_h else None, template, fill, column_step,
+    ratio = tuple(_upload_pinned(a, dev) for a in ratio_h) if ratio_h else None
+    out = _emit_predict_parts(model, _upload_pinned(sub_h, dev), _upload_pinned(rgb_h, dev), ratio, template, fill, column_step,
                               num_iter, covariance_lerp_alpha, None, tile, halo, distributed, group, strips)
     if georeferenced:
         out = georeference_products(out, glt[0], glt[1], fill)
     out.update(wavelengths=wl[b0:b1], fwhm=fwhm[b0:b1], glt_x=glt[0], glt_y=glt[1], fill_value=fill)
     gt = geotransform if geotransform is not None else root.get("geotransform")
+    mf = prob = None
     if plumes:
-        out["plumes"] = _emit_plume_table(out, fill, gt if georeferenced else None)
-        if plume_outlines:
-            from .plumes import plume_outlines as outlines_of
-            out["plume_outlines"] = outlines_of(out["pred_binary"], geotransform=gt if georeferenced else None)
-    if label_polygons is not None:
-        _burn_label_polygons(out, label_polygons, gt)
+        # pixels that carry the fill value become NaN, which the per-plume statistics leave out; in sensor geometry the network
+        # output covers the swath cropped to multiples of 32 (its top-left part): mf is cropped to it
+        nan = torch.tensor(float("nan"), device=out["mf"].device)
+        h, w = out["pred_binary"].shape
+        mf = out["mf"][:h, :w]
+        mf, prob = torch.where(mf == fill, nan, mf), torch.where(out["prediction"] == fill, nan, out["prediction"])
+    products.annotate(out, out["pred_binary"], mf, prob, gt if georeferenced else None, None, plumes, plume_outlines, label_polygons)
     if out_folder is not None:
-        out["files"] = _write_emit_products(out, str(out_folder), fill, gt, root.get("spatial_ref"), overwrite, cog)
-        if label_polygons is not None:
-            from .ortho import emit_geo_tags
-            geo = emit_geo_tags(gt, root.get("spatial_ref")) if gt is not None else {}
-            out["files"] += _write_label_tif(out, str(out_folder), geo, overwrite, cog)
-        if plumes:
-            out["files"] += _write_plume_files(out, str(out_folder), overwrite)
+        from .ortho import emit_geo_tags
+        geo = emit_geo_tags(gt, root.get("spatial_ref")) if gt is not None else {}
+        out["files"] = products.write_rasters(
+            out, products.EMIT_RASTERS, str(out_folder), overwrite, geo, fill, {"wavelengths": out["wavelengths"], "mag1c": "acrwl1mf"}, cog,
+            "emit_granule_predict: the granule has no geotransform attribute and none was passed: the GeoTIFFs are written without georeferencing")
+        out["files"] += products.write_annotations(out, str(out_folder), overwrite, geo, cog)
     return out
-
-
-def _write_raster(path, tensor, tags, cog=False, nodata=None):
-    """one raster product of a scene run: ``write_tiff`` of the host copy, or with ``cog`` (True, or a dict of ``cog.write_cog``
-    keyword arguments) a Cloud-Optimized GeoTIFF straight from the device tensor -- tiles and overviews are made on the device,
-    float32 products averaged, uint8 ones by mode, and only the tiles that are stored cross to the host"""
-    from . import io_formats as io
-    if not cog:
-        io.write_tiff(path, tensor.cpu().numpy(), blocksize=128, extra_tags=tags)
-        return
-    from .cog import write_cog
-    kw = {"blocksize": 128, **(cog if isinstance(cog, dict) else {})}
-    write_cog(path, tensor, nodata=nodata, extra_tags=tags, **kw)
-
-
-def _burn_label_polygons(out, label_polygons, geotransform):
-    """``label_mask`` and ``plume_match`` of a prediction dict: the polygons (a ``.geojson`` path or polygons) burnt into the grid
-    of ``pred_binary`` once, the same image scored"""
-    import os
-    from . import plumes as pl
-    if isinstance(label_polygons, (str, os.PathLike)):
-        label_polygons = pl.read_plumes(label_polygons)[1]
-    polys, _ = pl._polygon_list(label_polygons)
-    pred = out["pred_binary"]
-    burnt = pl.rasterize_polygons(polys, tuple(pred.shape), geotransform=geotransform)
-    out["label_mask"] = (burnt != 0).to(torch.uint8)
-    out["plume_match"] = pl._match_burnt(pred, burnt, len(polys), 2, 1, 1)
-
-
-def _write_label_tif(out, folder, geo_tags, overwrite, cog=False):
-    """``label.tif`` like ``predbinary.tif``: uint8, BLOCKSIZE 128, the products' georeferencing -> the paths written"""
-    import os
-    from . import io_formats as io
-    path = os.path.join(folder, "label.tif")
-    if not overwrite and os.path.exists(path):
-        return []
-    os.makedirs(folder, exist_ok=True)
-    _write_raster(path, out["label_mask"], {**geo_tags, **io.gdal_metadata_tag({}, ["Plume label"])}, cog)
-    return [path]
-
-
-def _write_plume_files(out, folder, overwrite):
-    """``plumes.csv`` and, with outlines, ``plumes.geojson`` (polygons) of a prediction dict -> the paths written"""
-    import os
-    from .plumes import write_plumes
-    files = []
-    todo = [("plumes.csv", None)] + ([("plumes.geojson", out["plume_outlines"])] if "plume_outlines" in out else [])
-    for name, outlines in todo:
-        path = os.path.join(folder, name)
-        if overwrite or not os.path.exists(path):
-            os.makedirs(folder, exist_ok=True)
-            files.append(write_plumes(out["plumes"], path, outlines=outlines))
-    return files
-
-
-def _emit_plume_table(out, fill, geotransform):
-    """plume table of an EMIT prediction dict: no-data pixels (the fill value, or not finite) of ``mf`` / ``prediction`` become
-    NaN, which the per-component statistics leave out.  In sensor geometry the network output covers the swath cropped to
-    multiples of 32 (its top-left part): ``mf`` is cropped to it"""
-    from .plumes import plume_table
-    nan = torch.tensor(float("nan"), device=out["mf"].device)
-    h, w = out["pred_binary"].shape
-    mf = out["mf"][:h, :w]
-    mf = torch.where(mf == fill, nan, mf)
-    prob = torch.where(out["prediction"] == fill, nan, out["prediction"])
-    return plume_table(out["pred_binary"], mag1c=mf, prob=prob, geotransform=geotransform)
-
-
-EMIT_PRODUCT_FILES = {"mag1c.tif": ("mf", ["CH4 Absorption (ppm x m)"]), "albedo.tif": ("albedo", ["Albedo"]),
-                      "pred.tif": ("prediction", ["Plume probability"]), "predbinary.tif": ("pred_binary", ["Plume mask"]),
-                      "rgb.tif": ("rgb", ["Red (640 nm)", "Green (550 nm)", "Blue (460 nm)"])}
-
-
-def _write_emit_products(out, folder, fill, geotransform, spatial_ref, overwrite, cog=False):
-    """the orthorectified products of :func:`emit_granule_predict` -> GeoTIFFs in ``folder``; returns the paths written"""
-    import os
-    import warnings
-    from . import io_formats as io
-    from .ortho import emit_geo_tags
-    todo = [(os.path.join(folder, name), key, desc) for name, (key, desc) in EMIT_PRODUCT_FILES.items()]
-    todo = [t for t in todo if overwrite or not os.path.exists(t[0])]
-    if not todo:
-        return []
-    os.makedirs(folder, exist_ok=True)
-    if geotransform is None:
-        warnings.warn("emit_granule_predict: the granule has no geotransform attribute and none was passed: the GeoTIFFs are "
-                      "written without georeferencing")
-        geo = {}
-    else:
-        geo = emit_geo_tags(geotransform, spatial_ref)
-    nodata = {42113: (2, (_nodata_text(fill),))}
-    md = {"wavelengths": out["wavelengths"], "mag1c": "acrwl1mf"}
-    written = []
-    for path, key, desc in todo:
-        if key == "pred_binary":
-            tags = {**geo, **io.gdal_metadata_tag({}, desc)}
-        else:
-            tags = {**geo, **nodata, **io.gdal_metadata_tag(md if key in ("mf", "albedo") else {}, desc)}
-        if cog:
-            _write_raster(path, out[key].to(torch.uint8) if key == "pred_binary" else out[key], tags, cog, None if key == "pred_binary" else fill)
-        else:
-            a = out[key].cpu().numpy()
-            io.write_tiff(path, a.astype(np.uint8) if key == "pred_binary" else a, blocksize=128, extra_tags=tags)
-        written.append(path)
-    return written
 
 
 @torch.no_grad()
@@ -440,20 +340,16 @@ def aviris_scene_mag1c(aviris_img_folder, mf_filename, albedo_filename=None, use
     The target spectrum is cast to the radiance dtype as the reference does (:199).  Returns (mf, albedo) device tensors.
     The radiance slice is uploaded once from the memmap through pinned memory; everything after that stays on the device."""
     from . import io_formats as io
-    mf, alb, meta, wl, keep = _aviris_mag1c(aviris_img_folder, use_wavelength_range, device)
-    tags = io.envi_geo_tags(meta["header"])                               # transform + crs of the radiance file
-    tags[42113] = (2, (str(mag1c.NODATA),))                               # GDAL_NODATA, as fill_value_default=NODATA
-    tags.update(extra_tags or {})
-    md = {"wavelengths": wl[keep], "mag1c": "acfwl1mf"}
-    io.write_tiff(mf_filename, mf.cpu().numpy(), blocksize=128,
-                  extra_tags={**tags, **io.gdal_metadata_tag(md, ["CH4 Absorption (ppm x m)"])})
-    if albedo_filename is not None:
-        io.write_tiff(albedo_filename, alb.cpu().numpy(), blocksize=128, extra_tags={**tags, **io.gdal_metadata_tag(md, ["Albedo"])})
+    mf, alb, meta, md = _aviris_mag1c(aviris_img_folder, use_wavelength_range, device)
+    geo = io.envi_geo_tags(meta["header"])                                # transform + crs of the radiance file
+    for row, path, image in ((products.MAG1C, mf_filename, mf), (products.ALBEDO, albedo_filename, alb)):
+        if path is not None:                                              # GDAL_NODATA, as fill_value_default=NODATA
+            products.write_raster(path, image, products.raster_tags(row, geo, mag1c.NODATA, md, extra_tags))
     return mf, alb
 
 
 def _aviris_mag1c(aviris_img_folder, use_wavelength_range, device):
-    """the matched filter of :func:`aviris_scene_mag1c` without the files -> (mf, albedo, ENVI meta, band centres, kept bands)"""
+    """the matched filter of :func:`aviris_scene_mag1c` without the files -> (mf, albedo, ENVI meta, the dataset tags of its products)"""
     import os
     from . import io_formats as io
     folder = aviris_img_folder.rstrip("/")
@@ -466,11 +362,10 @@ def _aviris_mag1c(aviris_img_folder, use_wavelength_range, device):
     assert idx[-1] - idx[0] + 1 == idx.shape[0], "Not all indexes included. Can't be a slice!"
     target = mag1c.generate_template_from_bands(centers=wl, fwhm=meta["fwhm"])
     spec = target.astype(rdn.dtype)[keep, 1]           # process_aviris.py:199: the template in the cube's dtype
-    host = torch.from_numpy(np.ascontiguousarray(rdn[..., idx[0]:idx[-1] + 1], dtype=np.float32))
-    x = (host.pin_memory() if torch.cuda.is_available() else host).to(device, non_blocking=True)
+    x = _upload_pinned(np.ascontiguousarray(rdn[..., idx[0]:idx[-1] + 1], dtype=np.float32), device)
     groups = np.abs(np.asarray(glt[..., 0])).astype(np.int64)
     mf, alb = mag1c.func_by_groups(mag1c.Filter(spec, num_iter=30), x, groups, mask=groups != 0, max_group=int(groups.max()))
-    return mf, alb, meta, wl, keep
+    return mf, alb, meta, {"wavelengths": wl[keep], "mag1c": "acfwl1mf"}
 
 
 def aviris_scene_products(input_products, normalize_by_acquisition_date=True):
@@ -505,9 +400,6 @@ def _envi_geotransform(header):
     if any(v.lower().replace(" ", "").startswith("rotation=") and float(v.split("=")[1]) != 0.0 for v in mi[7:]):
         return None, None
     return (e0 - (xr - 1.0) * px, px, 0.0, n0 + (yr - 1.0) * py, 0.0, -py), (px * py if mi[0].strip().lower() == "utm" else None)
-
-
-AVIRIS_PRODUCT_FILES = {"pred.tif": ("prediction", ["Plume probability"]), "predbinary.tif": ("pred_binary", ["Plume mask"])}
 
 
 @torch.no_grad()
@@ -549,14 +441,14 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
     from .sampling import _nodata
     if plume_outlines and not plumes:
         raise ValueError("aviris_scene_predict: plume_outlines=True needs plumes=True")
-    products = aviris_scene_products(model.input_products, normalize_by_acquisition_date)
+    inputs = aviris_scene_products(model.input_products, normalize_by_acquisition_date)
     for path in (out_folder, mag1c_path, aviris_img_folder):
         if path is not None and str(path).startswith("gs://"):
             raise NotImplementedError(f"{path}: Google Cloud Storage is not supported; pass a local path")
     folder = str(aviris_img_folder).rstrip("/")
     name = os.path.basename(folder)
     factor = None
-    if normalize_by_acquisition_date and any(kind == "band" for kind, _ in products):
+    if normalize_by_acquisition_date and any(kind == "band" for kind, _ in inputs):
         if toa_correction_factor is not None:
             factor = float(toa_correction_factor)
         elif solar_altitude is not None:
@@ -577,16 +469,15 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
     ignore = header.get("data ignore value")
     ignore = float(ignore) if ignore is not None else None
     dev = torch.device(device)
-    files = []
+    files, geo = [], io.envi_geo_tags(header) if out_folder is not None else None
     # ---- the planes, in the order of input_products
-    centres = [w for kind, w in products if kind == "band"]
+    centres = [w for kind, w in inputs if kind == "band"]
     cube = None
     if centres:
         bands = np.argmin(np.abs(np.asarray(centres, dtype=np.float64)[:, None] - meta["wavelengths"]), axis=1)
-        host = torch.from_numpy(np.ascontiguousarray(rdn[:, :, bands], dtype=np.float32))        # one strided read of the memmap
-        cube = (host.pin_memory() if torch.cuda.is_available() else host).to(dev, non_blocking=True)
+        cube = _upload_pinned(np.ascontiguousarray(rdn[:, :, bands], dtype=np.float32), dev)     # one strided read of the memmap
     mf, mf_fill = None, float(mag1c.NODATA)
-    if any(kind == "mag1c" for kind, _ in products):
+    if any(kind == "mag1c" for kind, _ in inputs):
         path = mag1c_path if mag1c_path is not None else os.path.join(folder, "mag1c.tif")
         if mag1c_path is not None or os.path.exists(path):
             info = io.tiff_info(path)
@@ -598,21 +489,14 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
             mf_fill = float(nod) if nod is not None else mf_fill
             mf = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
         else:
-            mf, alb, _, wl, keep = _aviris_mag1c(folder, mag1c.DEFAULT_WAVELENGTH_RANGE, dev)
+            mf, _, _, md = _aviris_mag1c(folder, mag1c.DEFAULT_WAVELENGTH_RANGE, dev)
             if out_folder is not None:
-                mpath = os.path.join(str(out_folder), "mag1c.tif")
-                if overwrite or not os.path.exists(mpath):
-                    os.makedirs(str(out_folder), exist_ok=True)
-                    tags = io.envi_geo_tags(header)
-                    tags[42113] = (2, (str(mag1c.NODATA),))
-                    md = {"wavelengths": wl[keep], "mag1c": "acfwl1mf"}
-                    _write_raster(mpath, mf, {**tags, **io.gdal_metadata_tag(md, ["CH4 Absorption (ppm x m)"])}, cog, mag1c.NODATA)
-                    files.append(mpath)
+                files += products.write_rasters({"mf": mf}, (products.MAG1C,), str(out_folder), overwrite, geo, mag1c.NODATA, md, cog)
         if tuple(mf.shape) != tuple(rdn.shape[:2]):
             raise ValueError(f"aviris_scene_predict: mag1c is {tuple(mf.shape)}, the radiance {tuple(rdn.shape[:2])}")
     planes, fills, scales, clips = [], [], [], []
     j = 0
-    for kind, _ in products:
+    for kind, _ in inputs:
         if kind == "mag1c":
             planes.append(mf); fills.append(mf_fill); scales.append(None); clips.append((0.0, 10_000.0))
         else:
@@ -621,30 +505,10 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
     out = model.predict_scene(planes, fill_value=fills, scales=scales, clips=clips, tile=tile, halo=halo, batch=batch)
     out["mf"] = mf
     gt, area = _envi_geotransform(header)
-    if plumes:
-        from .plumes import plume_table
-        out["plumes"] = plume_table(out["pred_binary"], mag1c=mf, prob=out["prediction"], geotransform=gt, pixel_area_m2=area)
-        if plume_outlines:
-            from .plumes import plume_outlines as outlines_of
-            out["plume_outlines"] = outlines_of(out["pred_binary"], geotransform=gt)
-    if label_polygons is not None:
-        _burn_label_polygons(out, label_polygons, gt)
+    products.annotate(out, out["pred_binary"], mf, out["prediction"], gt, area, plumes, plume_outlines, label_polygons)
     if out_folder is not None:
-        geo = io.envi_geo_tags(header)
-        nodata = {42113: (2, (_nodata_text(mag1c.NODATA),))}
-        for fname, (key, desc) in AVIRIS_PRODUCT_FILES.items():
-            path = os.path.join(str(out_folder), fname)
-            if not overwrite and os.path.exists(path):
-                continue
-            os.makedirs(str(out_folder), exist_ok=True)
-            tags = {**geo, **(nodata if key == "prediction" else {}), **io.gdal_metadata_tag({}, desc)}
-            _write_raster(path, out[key], tags, cog, mag1c.NODATA if key == "prediction" else None)
-            files.append(path)
-        if label_polygons is not None:
-            files += _write_label_tif(out, str(out_folder), geo, overwrite, cog)
-        if plumes:
-            files += _write_plume_files(out, str(out_folder), overwrite)
-        out["files"] = files
+        files += products.write_rasters(out, products.AVIRIS_RASTERS, str(out_folder), overwrite, geo, mag1c.NODATA, cog=cog)
+        out["files"] = files + products.write_annotations(out, str(out_folder), overwrite, geo, cog)
     return out
 
 
@@ -653,10 +517,6 @@ BANDS_WV3 = ["SWIR1", "SWIR2", "SWIR3", "SWIR4", "SWIR5", "SWIR6", "SWIR7", "SWI
 BANDS_SENSOR = {"S2A": BANDS_S2, "S2B": BANDS_S2, "WV3": BANDS_WV3}
 
 _NANOMETERS = ("nanometers", "nanometer", "nm")
-
-
-def _nodata_text(v):
-    return f"{float(v):.9g}"
 
 
 @torch.no_grad()
@@ -793,7 +653,7 @@ def aviris_as_sensor(aviris_img_folder_or_path, folder_dest, sensors=list(BANDS_
         used[i] = True
     geo = io.envi_geo_tags(header)
     if fill is not None:
-        geo[42113] = (2, (_nodata_text(fill),))
+        geo[42113] = (2, (nodata_text(fill),))
     if resolution_dst is None:
         result = out.cpu().numpy()
         tags = [geo] * len(todo)

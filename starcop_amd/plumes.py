@@ -630,7 +630,12 @@ def rasterize_polygons(polygons, shape, geotransform=None, values=None, item=0):
     return rasterize_launch(rasterize_upload(edges, table, None if identity else vals.astype(np.int32)), (H, W))
 
 
-def _match_burnt(pred_mask, burnt, P, connectivity, min_overlap_px, min_area):
+def burn_and_match(pred_mask, polygons, geotransform=None, connectivity=2, min_overlap_px=1, min_area=1):
+    """The polygons burnt with values 1..P on the grid of ``pred_mask`` and that image scored against the mask -> (burnt, device
+    int32 (H, W); the dict ``match_plumes_polygons`` returns) -- for callers that keep the burnt image as a label mask."""
+    polys, _ = _polygon_list(polygons)
+    P = len(polys)
+    burnt = rasterize_polygons(polys, tuple(pred_mask.shape), geotransform=geotransform)
     pred = plume_table(pred_mask, label_mask=(burnt != 0).to(torch.uint8), connectivity=connectivity, min_area=min_area)
     other = _to_device(pred_mask, burnt.device)
     st = component_stats(burnt, P, other=other, M=P)
@@ -639,8 +644,8 @@ def _match_burnt(pred_mask, burnt, P, connectivity, min_overlap_px, min_area):
     fp = len(pred) - tp
     fn = int((lab["overlap_px"] < min_overlap_px).sum())
     cm = torch.tensor([[0, fp], [fn, tp]], dtype=torch.float64)
-    return {"pred": pred, "label": lab, "tp": tp, "fp": fp, "fn": fn,
-            "precision": float(metrics.precision(cm)), "recall": float(metrics.recall(cm))}
+    return burnt, {"pred": pred, "label": lab, "tp": tp, "fp": fp, "fn": fn,
+                   "precision": float(metrics.precision(cm)), "recall": float(metrics.recall(cm))}
 
 
 def match_plumes_polygons(pred_mask, polygons, geotransform=None, connectivity=2, min_overlap_px=1, min_area=1):
@@ -650,9 +655,6 @@ def match_plumes_polygons(pred_mask, polygons, geotransform=None, connectivity=2
     components of their union -- two polygons that share an edge stay two.  The ``label`` table is ``component_stats`` of the burnt
     image against ``pred_mask``, one row per polygon that burnt at least ``min_area`` pixels (``plume_id`` = its position + 1);
     the ``pred`` table is ``plume_table(pred_mask, label_mask=burnt != 0)``.  Returns the dict ``match_plumes`` returns."""
-    shape = tuple(pred_mask.shape)
-    if len(shape) != 2:
-        raise ValueError(f"match_plumes_polygons: expected an (H, W) mask, got {shape}")
-    polys, _ = _polygon_list(polygons)
-    burnt = rasterize_polygons(polys, shape, geotransform=geotransform)
-    return _match_burnt(pred_mask, burnt, len(polys), connectivity, min_overlap_px, min_area)
+    if len(pred_mask.shape) != 2:
+        raise ValueError(f"match_plumes_polygons: expected an (H, W) mask, got {tuple(pred_mask.shape)}")
+    return burn_and_match(pred_mask, polygons, geotransform, connectivity, min_overlap_px, min_area)[1]

@@ -1,0 +1,116 @@
+"""What a scene run leaves behind: the raster files of a prediction dict and its plume annotations, for
+``pipeline.emit_granule_predict``, ``pipeline.aviris_scene_predict`` / ``aviris_scene_mag1c`` and ``sentinel2.cloud_mask_file``.
+
+Host side only.  Which files a run writes is data (``Raster`` rows), which of them are written and with which tags is decided by
+``plan_rasters`` without a device, and every file goes through ``write_raster``: ``io_formats.write_tiff`` of the host copy, or
+(the only place that imports :mod:`starcop_amd.cog`) a Cloud-Optimized GeoTIFF straight from the device tensor."""
+import os
+import warnings
+from typing import NamedTuple
+
+import numpy as np
+import torch
+
+from . import io_formats as io
+
+
+class Raster(NamedTuple):
+    name: str               # file name in the output folder
+    key: str                # key of the image in the prediction dict
+    bands: tuple            # band descriptions
+    nodata: bool            # carries GDAL_NODATA (and hands the value to the COG writer)
+    mag1c_tags: bool        # carries the dataset tags of the matched filter: wavelengths, mag1c=...
+    uint8: bool             # stored as uint8 whatever the dtype in the dict
+
+
+MAG1C = Raster("mag1c.tif", "mf", ("CH4 Absorption (ppm x m)",), True, True, False)
+ALBEDO = Raster("albedo.tif", "albedo", ("Albedo",), True, True, False)
+PRED = Raster("pred.tif", "prediction", ("Plume probability",), True, False, False)
+PREDBINARY = Raster("predbinary.tif", "pred_binary", ("Plume mask",), False, False, True)
+RGB = Raster("rgb.tif", "rgb", ("Red (640 nm)", "Green (550 nm)", "Blue (460 nm)"), True, False, False)
+LABEL = Raster("label.tif", "label_mask", ("Plume label",), False, False, True)
+EMIT_RASTERS = (MAG1C, ALBEDO, PRED, PREDBINARY, RGB)
+AVIRIS_RASTERS = (PRED, PREDBINARY)
+
+
+def nodata_text(v):
+    return f"{float(v):.9g}"
+
+
+def raster_tags(row, geo_tags, nodata=None, mag1c_md=None, extra_tags=None):
+    """the tags of one file, in the order they are laid out in it: georeferencing, GDAL_NODATA, ``extra_tags``, GDAL_METADATA"""
+    tags = {**(geo_tags or {}), **({42113: (2, (nodata_text(nodata),))} if row.nodata else {}), **(extra_tags or {})}
+    return {**tags, **io.gdal_metadata_tag(mag1c_md if row.mag1c_tags else {}, list(row.bands))}
+
+
+def plan_rasters(table, folder, overwrite=False, geo_tags=None, nodata=None, mag1c_md=None, no_geo_warning=None):
+    """The files of ``table`` a run will write into ``folder`` -- all with ``overwrite``, else those that do not exist -- in table
+    order: [(path, key, tags, nodata for the COG writer)].  ``no_geo_warning``: issued once when something will be written and
+    ``geo_tags`` is empty.  Touches the file system with ``os.path.exists`` only."""
+    plan = []
+    for row in table:
+        path = os.path.join(folder, row.name)
+        if overwrite or not os.path.exists(path):
+            plan.append((path, row.key, raster_tags(row, geo_tags, nodata, mag1c_md), nodata if row.nodata else None))
+    if plan and not geo_tags and no_geo_warning:
+        warnings.warn(no_geo_warning)
+    return plan
+
+
+def write_raster(path, image, tags, cog=False, nodata=None):
+    """one raster product, BLOCKSIZE 128, from a device tensor or a numpy array: ``write_tiff`` of the host copy, or with ``cog``
+    (True, or a dict of ``cog.write_cog`` keyword arguments) a Cloud-Optimized GeoTIFF -- tiles and overviews are made on the
+    device, float32 products averaged, uint8 ones by mode, and only the tiles that are stored cross to the host"""
+    if not cog:
+        io.write_tiff(path, image.cpu().numpy() if isinstance(image, torch.Tensor) else image, blocksize=128, extra_tags=tags)
+        return
+    from .cog import write_cog
+    write_cog(path, image, nodata=nodata, extra_tags=tags, **{"blocksize": 128, **(cog if isinstance(cog, dict) else {})})
+
+
+def write_rasters(out, table, folder, overwrite=False, geo_tags=None, nodata=None, mag1c_md=None, cog=False, no_geo_warning=None):
+    """the plan of ``plan_rasters`` carried out on the images of ``out``; the folder is created when something is written into it.
+    An image that is not uint8 yet is cast where it lives: on the host for the plain file, on the device for the COG.
+    Returns the paths written, in table order."""
+    plan = plan_rasters(table, folder, overwrite, geo_tags, nodata, mag1c_md, no_geo_warning)
+    if plan:
+        os.makedirs(folder, exist_ok=True)
+    as_uint8 = {row.key for row in table if row.uint8}
+    for path, key, tags, cog_nodata in plan:
+        image = out[key]
+        if key in as_uint8 and image.dtype != torch.uint8:
+            image = image.to(torch.uint8) if cog else image.cpu().numpy().astype(np.uint8)
+        write_raster(path, image, tags, cog, cog_nodata)
+    return [p[0] for p in plan]
+
+
+def annotate(out, mask, mf, prob, geotransform=None, pixel_area_m2=None, plumes=False, plume_outlines=False, label_polygons=None):
+    """The plume annotations of a prediction dict, as asked for: ``plumes`` (``plumes.plume_table`` of ``mask`` with ``mf`` as mag1c
+    and ``prob`` as probability), ``plume_outlines`` of the same mask in the same coordinates, and for ``label_polygons`` (a
+    ``.geojson`` path or polygons) ``label_mask``, the polygons burnt into the grid of ``mask`` (device uint8), and ``plume_match``,
+    the same burnt image scored against the mask."""
+    from . import plumes as pl
+    if plumes:
+        out["plumes"] = pl.plume_table(mask, mag1c=mf, prob=prob, geotransform=geotransform, pixel_area_m2=pixel_area_m2)
+        if plume_outlines:
+            out["plume_outlines"] = pl.plume_outlines(mask, geotransform=geotransform)
+    if label_polygons is not None:
+        if isinstance(label_polygons, (str, os.PathLike)):
+            label_polygons = pl.read_plumes(label_polygons)[1]
+        burnt, match = pl.burn_and_match(mask, label_polygons, geotransform)
+        out["label_mask"], out["plume_match"] = (burnt != 0).to(torch.uint8), match
+
+
+def write_annotations(out, folder, overwrite=False, geo_tags=None, cog=False):
+    """what ``annotate`` added, as files: ``label.tif`` like ``predbinary.tif``, ``plumes.csv`` and, with outlines,
+    ``plumes.geojson`` (one Polygon per row of the table) -> the paths written"""
+    from .plumes import write_plumes
+    files = write_rasters(out, (LABEL,), folder, overwrite, geo_tags, cog=cog) if "label_mask" in out else []
+    todo = [("plumes.csv", None)] if "plumes" in out else []
+    todo += [("plumes.geojson", out["plume_outlines"])] if "plume_outlines" in out else []
+    for name, outlines in todo:
+        path = os.path.join(folder, name)
+        if overwrite or not os.path.exists(path):
+            os.makedirs(folder, exist_ok=True)
+            files.append(write_plumes(out["plumes"], path, outlines=outlines))
+    return files

@@ -131,22 +131,15 @@ def cloud_mask_file(src_tif, dst_tif, model, cog=False, **kw):
     ``cog=True`` (or a dict of ``cog.write_cog`` keyword arguments) keeps the mask on the device and writes it as a
     Cloud-Optimized GeoTIFF -- tiles and mode-resampled overviews made on the device, all-zero tiles left out; the default
     leaves every byte of the file as it was."""
-    from . import io_formats
+    from . import io_formats, products
     info = io_formats.tiff_info(src_tif)
     bands = io_formats.read_tiff(src_tif, info=info)
-    if cog:
-        from .cog import write_cog
-        if bands.dtype == np.uint16:
-            on_dev = torch.from_numpy(bands.view(np.int16)).to(model.device).view(torch.uint16)
-        else:
-            on_dev = torch.from_numpy(bands).to(model.device)
-        mask = model.predict_scene(on_dev, **kw)
-    else:
-        mask = model.predict_scene(bands, **kw)
+    if cog and bands.dtype == np.uint16:                      # the COG is made from the device mask: the bands go there first
+        bands = torch.from_numpy(bands.view(np.int16)).to(model.device).view(torch.uint16)
+    elif cog:
+        bands = torch.from_numpy(bands).to(model.device)
+    mask = model.predict_scene(bands, **kw)
     tags = {t: v for t, v in info.geo_tags().items() if t not in (42112, 42113)}       # (the source's metadata / nodata describe its bands)
     tags.update(io_formats.gdal_metadata_tag({f"class_{i}": name for i, name in enumerate(INTERPRETATION_CLOUDSEN12)}, ["cloudmask"]))
-    if cog:
-        write_cog(dst_tif, mask, extra_tags=tags, **{"blocksize": 128, **(cog if isinstance(cog, dict) else {})})
-        return mask.cpu().numpy()
-    io_formats.write_tiff(dst_tif, mask, blocksize=128, extra_tags=tags)
-    return mask
+    products.write_raster(dst_tif, mask, tags, cog)
+    return mask.cpu().numpy() if cog else mask

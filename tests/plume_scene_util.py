@@ -98,3 +98,34 @@ def write_flight_line(folder, cube, wavelengths, fill=FILL, map_info=MAP_INFO):
                 f"wavelength = {{ {', '.join(f'{v:.4f}' for v in wavelengths)} }}\n"
                 f"map info = {map_info}\ndata ignore value = {fill:g}\n")
     return str(folder)
+
+
+def write_mag1c_flight_line(parent, nl=96, ns=40, seed=5):
+    """the flight line the matched filter is tested on, as ``{parent}/ang20190101t000000_rdn/<name>_img`` + ``<name>_glt`` (ENVI,
+    BIP): 101 bands on a 5 nm grid from 2000 to 2500 nm (74 of them inside [2122, 2488] nm and outside the bad-band windows), a
+    weak CH4 signal in a rectangle, 23 detector groups that vary along a row AND down, a no-data border of 5 lines and negative
+    (interpolated) indices; a rotated ``map info`` and no data ignore value.  -> (folder, cube, glt, wl, fwhm, target)"""
+    from starcop_amd import mag1c
+    rng = np.random.default_rng(seed)
+    wl = np.linspace(2000.0, 2500.0, 101)
+    fwhm = np.full_like(wl, 5.6)
+    target = mag1c.generate_template_from_bands(wl, fwhm)[:, 1]
+    cube = (rng.uniform(1, 6, size=wl.size) * (1 + 0.05 * rng.standard_normal((nl, ns, wl.size)))).astype(np.float32)
+    k = np.zeros((nl, ns)); k[30:50, 10:20] = 2e-5
+    cube = (cube * (1 + k[..., None] * np.nan_to_num(target))).astype(np.float32)
+    glt = np.zeros((nl, ns, 2), dtype=np.int32)
+    glt[..., 0] = (np.arange(ns)[None, :] + (np.arange(nl)[:, None] // 8)) % 23 + 1      # orthorectified: detector sample varies along a row AND down
+    glt[:5, :, 0] = 0                                                                    # no-data border
+    glt[..., 0] *= np.where(rng.random((nl, ns)) < 0.5, 1, -1)                           # interpolated pixels carry a negative index
+    glt[..., 1] = np.arange(nl)[:, None]
+    name = "ang20190101t000000_rdn"
+    folder = os.path.join(str(parent), name)
+    os.makedirs(folder)
+    for suffix, arr, dt, extra in (("img", cube, 4, f"wavelength = {{ {', '.join(f'{v:.4f}' for v in wl)} }}\nfwhm = {{ {', '.join(f'{v:.2f}' for v in fwhm)} }}\n"
+                                    "map info = {UTM, 1, 1, 500000.0, 4100000.0, 5.0, 5.0, 11, North, WGS-84, units=Meters, rotation=-12.0}\n"),
+                                   ("glt", glt, 3, "")):
+        arr.tofile(os.path.join(folder, f"{name}_{suffix}"))
+        with open(os.path.join(folder, f"{name}_{suffix}.hdr"), "w") as f:
+            f.write(f"ENVI\nsamples = {ns}\nlines = {nl}\nbands = {arr.shape[2]}\nheader offset = 0\n"
+                    f"data type = {dt}\ninterleave = bip\nbyte order = 0\n{extra}")
+    return folder, cube, glt, wl, fwhm, target

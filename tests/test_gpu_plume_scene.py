@@ -368,3 +368,36 @@ def test_aviris_scene_predict_files(hip, tmp_path):
     a = pipeline.aviris_scene_predict(model, folder, solar_altitude=50.0, tile=32, halo=32)
     b = pipeline.aviris_scene_predict(model, folder, toa_correction_factor=f, tile=32, halo=32)
     assert "files" not in a and torch.equal(a["prediction"], b["prediction"]) and not torch.equal(a["prediction"], out["prediction"])
+
+
+def test_aviris_scene_predict_computes_and_writes_mag1c(hip, tmp_path):
+    """no mag1c.tif beside the cube: the matched filter runs from ``<name>_glt`` (96 x 40 x 101 bands, 23 detector groups: every
+    group has more pixels than the 74 kept bands; tile 32 / halo 32 cut it into 3 x 2 cores of one 96 x 64 window) and ``{out_folder}/mag1c.tif`` is the
+    file ``aviris_scene_mag1c`` writes, byte for byte, plain; as a COG the same pixels and tags"""
+    from test_gpu_cog import _same_product
+    folder = U.write_mag1c_flight_line(tmp_path)[0]
+    assert not os.path.exists(os.path.join(folder, "mag1c.tif"))
+    model = _model(bias=-0.93)
+    kw = dict(toa_correction_factor=1.037, tile=32, halo=32)
+    want_path = str(tmp_path / "want_mag1c.tif")
+    want_mf, _ = pipeline.aviris_scene_mag1c(folder, want_path)
+    names = ["mag1c.tif", "pred.tif", "predbinary.tif"]
+
+    def read(sub):
+        return [open(str(tmp_path / sub / n), "rb").read() for n in names]
+    out = pipeline.aviris_scene_predict(model, folder, str(tmp_path / "a"), **kw)
+    assert out["files"] == [str(tmp_path / "a" / n) for n in names]
+    first = read("a")
+    assert first[0] == open(want_path, "rb").read()
+    assert out["mf"].dtype == want_mf.dtype == torch.float32 and torch.equal(out["mf"].view(torch.int32), want_mf.view(torch.int32))
+    stamp = {p: os.stat(p).st_mtime_ns for p in out["files"]}
+    again = pipeline.aviris_scene_predict(model, folder, str(tmp_path / "a"), **kw)
+    assert again["files"] == [] and {p: os.stat(p).st_mtime_ns for p in stamp} == stamp
+    c = pipeline.aviris_scene_predict(model, folder, str(tmp_path / "c"), cog=dict(overview_min_size=32), **kw)
+    assert c["files"] == [str(tmp_path / "c" / n) for n in names]
+    info = _same_product(str(tmp_path / "c" / "mag1c.tif"), str(tmp_path / "a" / "mag1c.tif"))
+    plain = io_formats.tiff_info(str(tmp_path / "a" / "mag1c.tif"))
+    assert info.tags[42113] == plain.tags[42113] and info.tags[42113][1] == ("-9999",)
+    assert info.tags[42112] == plain.tags[42112] and '<Item name="mag1c">acfwl1mf</Item>' in info.tags[42112][1][0]
+    pipeline.aviris_scene_predict(model, folder, str(tmp_path / "b"), **kw)
+    assert read("b") == first
