@@ -886,6 +886,57 @@ typedef struct sc_ortho_args {
 } sc_ortho_args;
 int sc_glt_ortho(const sc_ortho_args* a, sc_stream stream);
 
+/* Reprojection of rasters between grids (the warp), for P planes in one launch.  For every pixel (r, c) of the destination grid:
+ *   (x, y) = dst_gt applied to the pixel centre (c + 0.5, r + 0.5)     [GDAL order: x = gt[0] + col*gt[1] + row*gt[2],
+ *                                                                                   y = gt[3] + col*gt[4] + row*gt[5]]
+ *   (x, y) : destination CRS -> source CRS.  CRS codes: equal codes on both sides (0 included) = same CRS, affine only; otherwise
+ *            each side is 4326 (WGS-84 longitude / latitude, degrees) or 32601..32660 / 32701..32760 (WGS-84 UTM north / south).
+ *            Transverse Mercator is the Krueger series to order n^6 (Karney 2011, alpha / beta coefficients), complex Clenshaw
+ *            summation, the conformal latitude inverted with a fixed number of Newton steps; zone A -> zone B goes through
+ *            longitude / latitude.  A point further than 30 degrees of longitude from the central meridian of a UTM side, a latitude
+ *            beyond +-90 and a result that is not finite are outside the source.
+ *   (u, v) = src_inv applied to (x, y): u = inv[0] + x*inv[1] + y*inv[2], v = inv[3] + x*inv[4] + y*inv[5] -- the inverse of the
+ *            source's geotransform, inverted by the caller in float64 (so either side may be rotated); outside unless
+ *            0 <= u < src_w and 0 <= v < src_h.
+ *   SC_WARP_NEAREST  : out[p][r][c] = src_p[floor(v)][floor(u)], copied as a word of elem_bytes (1, 2, 4 or 8; one width per call);
+ *                      nodata_bits[p] (its low elem_bytes) when outside -- bit-equal to a numpy gather for every dtype.
+ *   SC_WARP_BILINEAR : float32 planes (elem_bytes = 4).  With fx = u - 0.5 - floor(u - 0.5) and fy likewise the four pixels around
+ *                      (u - 0.5, v - 0.5) are weighed (1 - fx | fx) * (1 - fy | fy) in fp64; a sample counts when it lies inside the
+ *                      raster, is not NaN and is not nodata_bits[p] (compared as bits) and has a weight > 0; the sum is divided by the
+ *                      weight of the samples that count and rounded once to float32.  The pixel is nodata when it is outside or its
+ *                      NEAREST source pixel does not count: both modes have the same valid pixels.
+ * All of it in fp64, once per pixel and not once per plane.  Source plane p is read in place: element (row, col) = src[p] +
+ * (row*row_stride[p] + col*col_stride[p]) elements, strides >= 0, every plane src_h x src_w.  out: dense [P][out_h][out_w].
+ * coords (device, may be NULL): float64 [2][out_h][out_w], (u, v) of every pixel, NaN for "outside"; a call with P = 0 writes only
+ * this.  *oob_count (device, may be NULL; the caller zeroes it) is incremented once per pixel outside the source.  16-byte stores
+ * (4 float32 pixels per thread) when out_w is a multiple of 4 (2 for 8-byte elements) and out is aligned to the store.
+ * SC_ERR_ARG for a null or misaligned pointer, P outside [0, 32] (0 only with coords), non-positive shapes, out_h*out_w >= 2^31, an
+ * unsupported elem_bytes / resampling / CRS pair, bilinear on another width than 4, a negative stride, a singular or non-finite
+ * geotransform.  No LDS, no other atomics: repeated calls give identical bits.                                                  */
+#define SC_WARP_MAX_PLANES 32
+#define SC_WARP_NEAREST 0
+#define SC_WARP_BILINEAR 1
+#define SC_WARP_UNBOUNDED 1   /* flags, coordinates-only calls: (u, v) outside the raster are written, NaN only where the projection fails */
+typedef struct sc_warp_args {
+  double dst_gt[6];                              /* geotransform of the destination grid, GDAL order           */
+  double src_inv[6];                             /* world -> source pixel coordinates (see above)               */
+  int32_t dst_crs, src_crs;                      /* 0, 4326, 326zz, 327zz                                      */
+  int32_t out_h, out_w;
+  int32_t src_h, src_w;
+  int32_t P;                                     /* planes, 0..32                                              */
+  int32_t elem_bytes;                            /* 1, 2, 4 or 8 (ignored with P = 0)                          */
+  int32_t resampling;                            /* SC_WARP_NEAREST, SC_WARP_BILINEAR                          */
+  int32_t flags;                                 /* SC_WARP_UNBOUNDED: P = 0 only                              */
+  const void* src[SC_WARP_MAX_PLANES];           /* element (0, 0) of every plane, device                      */
+  int64_t row_stride[SC_WARP_MAX_PLANES];        /* elements                                                   */
+  int64_t col_stride[SC_WARP_MAX_PLANES];
+  uint64_t nodata_bits[SC_WARP_MAX_PLANES];      /* raw bit pattern of every plane's no-data value             */
+  void* out;                                     /* [P][out_h][out_w] device (NULL with P = 0)                 */
+  double* coords;                                /* [2][out_h][out_w] device, or NULL                          */
+  uint64_t* oob_count;                           /* device, or NULL                                            */
+} sc_warp_args;
+int sc_warp(const sc_warp_args* a, sc_stream stream);
+
 /* Cutting the sampled windows of a flight line into dense sample tensors: the reads of WindowDataset.__getitem__,
  * starcop/data/sampling_dataset.py:259-303 -- RasterioReader.read_from_window(window, boundless=True).load(boundless=True) at :266,
  * nodata -> 0 at :269-271, the acquisition-date multiply at :285 / :289 and np.clip at :287 / :293 -- for every window of a chunk

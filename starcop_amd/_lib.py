@@ -147,6 +147,20 @@ class sc_ortho_args(C.Structure):
                 ("out", C.c_void_p), ("oob_count", C.c_void_p)]
 
 
+WARP_MAX_PLANES = 32
+WARP_NEAREST, WARP_BILINEAR, WARP_UNBOUNDED = 0, 1, 1
+
+
+class sc_warp_args(C.Structure):
+    """reprojection operands (include/starcop_hip.h: sc_warp_args)"""
+    _fields_ = [("dst_gt", C.c_double * 6), ("src_inv", C.c_double * 6), ("dst_crs", C.c_int32), ("src_crs", C.c_int32),
+                ("out_h", C.c_int32), ("out_w", C.c_int32), ("src_h", C.c_int32), ("src_w", C.c_int32), ("P", C.c_int32),
+                ("elem_bytes", C.c_int32), ("resampling", C.c_int32), ("flags", C.c_int32),
+                ("src", C.c_void_p * WARP_MAX_PLANES), ("row_stride", C.c_int64 * WARP_MAX_PLANES),
+                ("col_stride", C.c_int64 * WARP_MAX_PLANES), ("nodata_bits", C.c_uint64 * WARP_MAX_PLANES),
+                ("out", C.c_void_p), ("coords", C.c_void_p), ("oob_count", C.c_void_p)]
+
+
 WCUT_MAX_PLANES = 64
 WCUT_FILL, WCUT_SCALE, WCUT_CLIP = 1, 2, 4
 
@@ -350,6 +364,7 @@ SIGNATURES = {
     "sc_window_stats_workspace_bytes": (_sz, [_i]),
     "sc_window_stats": (_i, [C.POINTER(sc_winstats_args), _vp, _sz, _vp]),
     "sc_glt_ortho": (_i, [C.POINTER(sc_ortho_args), _vp]),
+    "sc_warp": (_i, [C.POINTER(sc_warp_args), _vp]),
     "sc_window_cut": (_i, [C.POINTER(sc_wcut_args), _vp]),
     "sc_scene_gather": (_i, [C.POINTER(sc_scene_args), _vp]),
     "sc_head_conv_fwd_k_mosaic": (_i, [C.POINTER(sc_src), _vp, _vp, _vp, _i, _i, C.c_int64, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

@@ -1,0 +1,326 @@
+// Reprojection of rasters between grids (the warp): for every pixel (r, c) of a destination grid
+//   1. world coordinates of the pixel centre (c + 0.5, r + 0.5) through the destination's 6-term affine geotransform,
+//   2. destination CRS -> source CRS: nothing (same CRS), WGS-84 UTM -> longitude / latitude, longitude / latitude -> UTM, or zone A ->
+//      zone B through longitude / latitude.  Transverse Mercator is the Krueger series in the third flattening n to order n^6 (Karney
+//      2011, "Transverse Mercator with an accuracy of a few nanometers", eq. 35 / 36: the alpha and beta coefficients), summed with a
+//      complex Clenshaw recurrence; the conformal latitude is inverted with a FIXED number of Newton steps (no data-dependent loop),
+//   3. source pixel coordinates (u, v) through the inverse of the source's affine (inverted on the host in float64),
+//   4. sampling of P planes: `nearest` copies element (floor(v), floor(u)) as a 1-, 2-, 4- or 8-byte word (bit-equal to a numpy gather
+//      for every dtype); `bilinear` (float32) weighs the four pixels around (u - 0.5, v - 0.5) in fp64, leaves out samples that lie
+//      outside the raster, are NaN or carry the plane's no-data bit pattern, divides by the weight of those that count and rounds once.
+//   Footprint rule of both modes: the pixel gets the plane's no-data when (u, v) is outside [0, W) x [0, H), when the projection has
+//   no finite result or leaves the 30 degrees around the zone's central meridian; `bilinear` also when the NEAREST source pixel does
+//   not count -- so bilinear and nearest of one plane have the same valid pixels and data never bleeds into fill.
+// everything in fp64, all of it once per pixel and not once per plane (as sc_glt_ortho reads its GLT words once).
+//   Mapping: the two-dimensional tiles of ortho.hip, because the source side is a gather: a work-group of 256 threads owns 16 rows x
+//   64 pixels, a thread 4 consecutive pixels of a row (one 16-byte store per float32 plane; 2 pixels = 16 bytes for 8-byte elements).
+//   A thread never owns more than 4 pixels: each costs two fp64 series with ~20 transcendental calls, and 16 unrolled copies of that
+//   for one-byte elements would not fit the instruction cache -- a uint8 mask is stored as 4-byte words instead.  When the width is
+//   not a multiple of the vector (or a pointer is not aligned to the store) the same kernel runs with one pixel per thread and tiles
+//   of 4 rows x 64 pixels.  No LDS; the only atomic is the optional count of pixels outside the source: two calls give the same bytes.
+#include <limits.h>
+#include <math.h>
+
+#include <cmath>
+
+#include "sc_common.h"
+
+namespace {
+
+constexpr int WARP_PMAX = SC_WARP_MAX_PLANES;
+constexpr int WARP_WG = 256;
+constexpr double WARP_DEG = 0.017453292519943295769;      // radians per degree
+constexpr double WARP_MAX_DLON = 30.0;                    // degrees from the central meridian beyond which a point is outside
+constexpr int WARP_NEWTON = 3;                            // steps of the conformal-latitude inversion: 2 reach the last place for |lat| < 89.999, one spare
+
+struct Krueger {
+  double e, e2m, ka;                             // first eccentricity, 1 - e^2, k0 * rectifying radius
+  double alp[6], bet[6];
+};
+
+struct WarpD {
+  double gt[6], inv[6];
+  Krueger k;
+  double dst_lon0, dst_fn, src_lon0, src_fn;     // central meridian (degrees) and false northing of a UTM side
+  int route;                                     // bit 0: destination is UTM (inverse first), bit 1: source is UTM (forward after)
+  int H, W, sh, sw, P, tiles_x;
+  int unbounded;                                 // coordinates only: (u, v) outside the source raster are kept
+  void* out;
+  double* coords;
+  unsigned long long* oob;
+  const void* src[WARP_PMAX];
+  long long rs[WARP_PMAX], cs[WARP_PMAX];
+  unsigned long long nod[WARP_PMAX];
+};
+
+template <class T, int V>
+struct alignas((V * sizeof(T) >= 16) ? 16 : V * sizeof(T)) Pack {
+  T v[V];
+};
+
+// sum_j c[j-1] sin(2 j (xi + i eta)), j = 1..6 -> (real, imaginary) part
+__device__ __forceinline__ void clenshaw_sin(const double* c, double xi, double eta, double& re, double& im) {
+  double s0, c0;
+  sincos(2.0 * xi, &s0, &c0);
+  const double sh0 = sinh(2.0 * eta), ch0 = cosh(2.0 * eta);
+  const double ar = 2.0 * c0 * ch0, ai = -2.0 * s0 * sh0;              // 2 cos(2 zeta)
+  double y1r = 0.0, y1i = 0.0, y2r = 0.0, y2i = 0.0;
+#pragma unroll
+  for (int j = 5; j >= 0; --j) {
+    const double yr = c[j] + ar * y1r - ai * y1i - y2r;
+    const double yi = ar * y1i + ai * y1r - y2i;
+    y2r = y1r; y2i = y1i; y1r = yr; y1i = yi;
+  }
+  const double zr = s0 * ch0, zi = c0 * sh0;                           // sin(2 zeta)
+  re = zr * y1r - zi * y1i;
+  im = zr * y1i + zi * y1r;
+}
+
+// tangent of the conformal latitude from the tangent of the geographic one (Karney 2011 eq. 7-9)
+__device__ __forceinline__ double taup_of(double tau, double e) {
+  const double t1 = sqrt(1.0 + tau * tau);
+  const double sig = sinh(e * atanh(e * tau / t1));
+  return tau * sqrt(1.0 + sig * sig) - sig * t1;
+}
+
+// longitude / latitude in degrees -> easting / northing; false outside 30 degrees of the central meridian or |lat| > 90
+__device__ __forceinline__ bool tm_forward(const Krueger& k, double lon0, double fn, double lon, double lat, double& E, double& N) {
+  const double dl = remainder(lon - lon0, 360.0);
+  if (!(fabs(dl) <= WARP_MAX_DLON) || !(fabs(lat) <= 90.0)) return false;
+  const double taup = taup_of(tan(lat * WARP_DEG), k.e);
+  double sl, cl;
+  sincos(dl * WARP_DEG, &sl, &cl);
+  const double xip = atan2(taup, cl), etap = asinh(sl / sqrt(taup * taup + cl * cl));
+  double dx, de;
+  clenshaw_sin(k.alp, xip, etap, dx, de);
+  E = 500000.0 + k.ka * (etap + de);
+  N = fn + k.ka * (xip + dx);
+  return true;
+}
+
+// easting / northing -> longitude / latitude in degrees; false outside 30 degrees of the central meridian
+__device__ __forceinline__ bool tm_inverse(const Krueger& k, double lon0, double fn, double E, double N, double& lon, double& lat) {
+  const double xi = (N - fn) / k.ka, eta = (E - 500000.0) / k.ka;
+  double dx, de;
+  clenshaw_sin(k.bet, xi, eta, dx, de);
+  const double xip = xi - dx, etap = eta - de;
+  double sx, cx;
+  sincos(xip, &sx, &cx);
+  const double shp = sinh(etap);
+  const double taup = sx / sqrt(shp * shp + cx * cx);
+  const double lam = atan2(shp, cx);
+  double tau = taup / k.e2m;
+#pragma unroll
+  for (int i = 0; i < WARP_NEWTON; ++i) {
+    const double ta = taup_of(tau, k.e);
+    tau += (taup - ta) * (1.0 + k.e2m * tau * tau) / (k.e2m * sqrt(1.0 + ta * ta) * sqrt(1.0 + tau * tau));
+  }
+  lat = atan(tau) / WARP_DEG;
+  lon = lon0 + lam / WARP_DEG;
+  return fabs(lam) <= WARP_MAX_DLON * WARP_DEG;
+}
+
+// source pixel coordinates of the centre of destination pixel (r, c); NaN when the point is outside the source
+__device__ __forceinline__ bool source_uv(const WarpD& a, int r, long long c, double& u, double& v) {
+  const double px = (double)c + 0.5, py = (double)r + 0.5;
+  double x = a.gt[0] + px * a.gt[1] + py * a.gt[2];
+  double y = a.gt[3] + px * a.gt[4] + py * a.gt[5];
+  bool ok = true;
+  if (a.route & 1) ok = tm_inverse(a.k, a.dst_lon0, a.dst_fn, x, y, x, y);
+  if (a.route & 2) ok = tm_forward(a.k, a.src_lon0, a.src_fn, x, y, x, y) && ok;
+  u = a.inv[0] + x * a.inv[1] + y * a.inv[2];
+  v = a.inv[3] + x * a.inv[4] + y * a.inv[5];
+  const bool inside = u >= 0.0 && u < (double)a.sw && v >= 0.0 && v < (double)a.sh;      // false for NaN and infinities
+  ok = ok && (inside || (a.unbounded && fabs(u) < INFINITY && fabs(v) < INFINITY));
+  if (!ok) u = v = __builtin_nan("");
+  return ok;
+}
+
+// a float32 sample takes part in an interpolation: not the plane's no-data pattern and not NaN
+__device__ __forceinline__ bool counts(uint32_t bits, uint32_t nod) { return bits != nod && (bits & 0x7FFFFFFFu) <= 0x7F800000u; }
+
+// grid.x = tiles_y * tiles_x tiles of TY rows x TX * V pixels.  BIL: bilinear (T = uint32_t, the bits of a float32)
+template <class T, int V, bool BIL>
+__global__ __launch_bounds__(WARP_WG) void k_warp(WarpD a) {
+  constexpr int TX = V == 1 ? 64 : 16, TY = WARP_WG / TX;
+  const int by = blockIdx.x / a.tiles_x, bx = blockIdx.x - by * a.tiles_x;
+  const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
+  const long long x0 = ((long long)bx * TX + tx) * V;
+  const int y = by * TY + ty;
+  if (y >= a.H || x0 >= a.W) return;              // W % V == 0 on the vector path: a thread's V pixels are inside the row or all outside
+  const size_t pix = (size_t)y * a.W + (size_t)x0;
+  const size_t plane = (size_t)a.H * a.W;
+  double u[V], v[V];
+  bool in[V];
+  unsigned bad = 0;
+#pragma unroll
+  for (int e = 0; e < V; ++e) {
+    in[e] = source_uv(a, y, x0 + e, u[e], v[e]);
+    bad += in[e] ? 0u : 1u;
+  }
+  if (bad && a.oob) atomicAdd(a.oob, (unsigned long long)bad);
+  if (a.coords) {
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      a.coords[pix + e] = u[e];
+      a.coords[plane + pix + e] = v[e];
+    }
+  }
+  if (a.P == 0) return;
+  long long sx[V], sy[V];                         // the nearest source pixel (0 where there is none: never dereferenced)
+#pragma unroll
+  for (int e = 0; e < V; ++e) {
+    sx[e] = in[e] ? (long long)floor(u[e]) : 0;
+    sy[e] = in[e] ? (long long)floor(v[e]) : 0;
+  }
+  T* o = static_cast<T*>(a.out) + pix;
+  for (int p = 0; p < a.P; ++p) {                 // p is uniform: the plane's descriptor comes in scalar registers
+    const T* s = static_cast<const T*>(a.src[p]);
+    const long long rs = a.rs[p], cs = a.cs[p];
+    const T nod = (T)a.nod[p];
+    Pack<T, V> r;
+#pragma unroll
+    for (int e = 0; e < V; ++e) {
+      T val = nod;
+      if (in[e]) val = s[sy[e] * rs + sx[e] * cs];
+      if constexpr (BIL) {
+        if (in[e] && counts(val, nod)) {
+          const double ub = u[e] - 0.5, vb = v[e] - 0.5;
+          const double fx0 = floor(ub), fy0 = floor(vb);
+          const double fx = ub - fx0, fy = vb - fy0;
+          const long long ix = (long long)fx0, iy = (long long)fy0;
+          double acc = 0.0, wsum = 0.0;
+#pragma unroll
+          for (int k = 0; k < 4; ++k) {           // (row, column) offsets (0, 0), (0, 1), (1, 0), (1, 1)
+            const long long xx = ix + (k & 1), yy = iy + (k >> 1);
+            const double w = ((k & 1) ? fx : 1.0 - fx) * ((k >> 1) ? fy : 1.0 - fy);
+            if (w > 0.0 && xx >= 0 && xx < a.sw && yy >= 0 && yy < a.sh) {
+              const uint32_t b = s[yy * rs + xx * cs];
+              if (counts(b, nod)) {
+                acc += w * (double)__uint_as_float(b);
+                wsum += w;
+              }
+            }
+          }
+          val = __float_as_uint((float)(acc / wsum));      // wsum >= 0.25: the nearest pixel counts and has at least that weight
+        } else {
+          val = nod;
+        }
+      }
+      r.v[e] = val;
+    }
+    *reinterpret_cast<Pack<T, V>*>(o + (size_t)p * plane) = r;
+  }
+}
+
+template <class T, int V, bool BIL>
+int launch(const WarpD& d0, bool vec, hipStream_t st) {
+  WarpD d = d0;
+  const int tw = vec ? 16 * V : 64, th = vec ? WARP_WG / 16 : WARP_WG / 64;
+  d.tiles_x = (d.W + tw - 1) / tw;
+  const long long tiles = (long long)d.tiles_x * ((d.H + th - 1) / th);
+  SC_REQUIRE(tiles <= INT_MAX, "sc_warp: grid too large for one launch");
+  if (vec) hipLaunchKernelGGL((k_warp<T, V, BIL>), dim3((unsigned)tiles), dim3(WARP_WG), 0, st, d);
+  else hipLaunchKernelGGL((k_warp<T, 1, BIL>), dim3((unsigned)tiles), dim3(WARP_WG), 0, st, d);
+  return SC_OK;
+}
+
+// 0 = affine only, 1 = WGS-84 geographic, 2 = WGS-84 UTM (zone and hemisphere set), -1 = not a code this operator knows
+int crs_kind(int code, double& lon0, double& fn) {
+  lon0 = fn = 0.0;
+  if (code == 4326) return 1;
+  const bool north = code >= 32601 && code <= 32660, south = code >= 32701 && code <= 32760;
+  if (!north && !south) return -1;
+  lon0 = 6.0 * (code % 100) - 183.0;
+  fn = south ? 10000000.0 : 0.0;
+  return 2;
+}
+
+void krueger_wgs84(Krueger& k) {
+  const double a = 6378137.0, f = 1.0 / 298.257223563, k0 = 0.9996;
+  const double n = f / (2.0 - f), n2 = n * n, n3 = n2 * n, n4 = n3 * n, n5 = n4 * n, n6 = n5 * n;
+  k.e = sqrt(f * (2.0 - f));
+  k.e2m = (1.0 - f) * (1.0 - f);
+  k.ka = k0 * a / (1.0 + n) * (1.0 + n2 / 4.0 + n4 / 64.0 + n6 / 256.0);
+  k.alp[0] = n / 2 - 2 * n2 / 3 + 5 * n3 / 16 + 41 * n4 / 180 - 127 * n5 / 288 + 7891 * n6 / 37800;
+  k.alp[1] = 13 * n2 / 48 - 3 * n3 / 5 + 557 * n4 / 1440 + 281 * n5 / 630 - 1983433 * n6 / 1935360;
+  k.alp[2] = 61 * n3 / 240 - 103 * n4 / 140 + 15061 * n5 / 26880 + 167603 * n6 / 181440;
+  k.alp[3] = 49561 * n4 / 161280 - 179 * n5 / 168 + 6601661 * n6 / 7257600;
+  k.alp[4] = 34729 * n5 / 80640 - 3418889 * n6 / 1995840;
+  k.alp[5] = 212378941 * n6 / 319334400;
+  k.bet[0] = n / 2 - 2 * n2 / 3 + 37 * n3 / 96 - n4 / 360 - 81 * n5 / 512 + 96199 * n6 / 604800;
+  k.bet[1] = n2 / 48 + n3 / 15 - 437 * n4 / 1440 + 46 * n5 / 105 - 1118711 * n6 / 3870720;
+  k.bet[2] = 17 * n3 / 480 - 37 * n4 / 840 - 209 * n5 / 4480 + 5569 * n6 / 90720;
+  k.bet[3] = 4397 * n4 / 161280 - 11 * n5 / 504 - 830251 * n6 / 7257600;
+  k.bet[4] = 4583 * n5 / 161280 - 108847 * n6 / 3991680;
+  k.bet[5] = 20648693 * n6 / 638668800;
+}
+
+}  // namespace
+
+extern "C" int sc_warp(const sc_warp_args* a, sc_stream stream) {
+  SC_REQUIRE(a, "sc_warp: null arguments");
+  SC_REQUIRE(a->P >= 0 && a->P <= WARP_PMAX, "sc_warp: P=%d outside [0, %d]", a->P, WARP_PMAX);
+  SC_REQUIRE(a->P > 0 || a->coords, "sc_warp: nothing to write (P = 0 and no coordinate output)");
+  SC_REQUIRE(a->P == 0 || a->out, "sc_warp: null output pointer");
+  SC_REQUIRE(a->out_h >= 1 && a->out_w >= 1 && a->src_h >= 1 && a->src_w >= 1, "sc_warp: bad dims out %d x %d, source %d x %d",
+             a->out_h, a->out_w, a->src_h, a->src_w);
+  SC_REQUIRE((long long)a->out_h * a->out_w < (1LL << 31), "sc_warp: %d x %d output pixels do not fit 31 bits", a->out_h, a->out_w);
+  const int eb = a->P ? a->elem_bytes : 4;
+  SC_REQUIRE(eb == 1 || eb == 2 || eb == 4 || eb == 8, "sc_warp: element width %d (1, 2, 4 or 8 bytes expected)", eb);
+  SC_REQUIRE(a->resampling == SC_WARP_NEAREST || a->resampling == SC_WARP_BILINEAR, "sc_warp: resampling %d (0 = nearest, 1 = bilinear)",
+             a->resampling);
+  SC_REQUIRE((a->flags & ~SC_WARP_UNBOUNDED) == 0 && (a->flags == 0 || a->P == 0),
+             "sc_warp: flags %d (SC_WARP_UNBOUNDED, and only with P = 0: planes are never read outside the raster)", a->flags);
+  const bool bil = a->P > 0 && a->resampling == SC_WARP_BILINEAR;
+  SC_REQUIRE(!bil || eb == 4, "sc_warp: bilinear resampling is defined for float32 planes, not %d-byte elements", eb);
+  SC_REQUIRE((uintptr_t)a->out % eb == 0 && (uintptr_t)a->coords % 8 == 0 && (uintptr_t)a->oob_count % 8 == 0,
+             "sc_warp: misaligned output, coordinate or counter pointer");
+  WarpD d;
+  for (int i = 0; i < 6; ++i) {
+    SC_REQUIRE(std::isfinite(a->dst_gt[i]) && std::isfinite(a->src_inv[i]), "sc_warp: geotransform term %d is not finite", i);
+    d.gt[i] = a->dst_gt[i];
+    d.inv[i] = a->src_inv[i];
+  }
+  SC_REQUIRE(a->dst_gt[1] * a->dst_gt[5] - a->dst_gt[2] * a->dst_gt[4] != 0.0, "sc_warp: the destination geotransform is singular");
+  SC_REQUIRE(a->src_inv[1] * a->src_inv[5] - a->src_inv[2] * a->src_inv[4] != 0.0, "sc_warp: the inverse source geotransform is singular");
+  d.route = 0;
+  d.dst_lon0 = d.dst_fn = d.src_lon0 = d.src_fn = 0.0;
+  if (a->dst_crs != a->src_crs) {                 // equal codes (0 included): affine only
+    const int kd = crs_kind(a->dst_crs, d.dst_lon0, d.dst_fn), ks = crs_kind(a->src_crs, d.src_lon0, d.src_fn);
+    SC_REQUIRE(kd > 0 && ks > 0, "sc_warp: CRS pair %d -> %d (0 with 0, else 4326 or 32601..32660 / 32701..32760 on both sides)",
+               a->dst_crs, a->src_crs);
+    d.route = (kd == 2 ? 1 : 0) | (ks == 2 ? 2 : 0);
+  } else {
+    SC_REQUIRE(a->dst_crs >= 0, "sc_warp: negative CRS code %d", a->dst_crs);
+  }
+  krueger_wgs84(d.k);
+  d.H = a->out_h; d.W = a->out_w; d.sh = a->src_h; d.sw = a->src_w; d.P = a->P; d.tiles_x = 0;
+  d.unbounded = a->flags & SC_WARP_UNBOUNDED;
+  d.out = a->out; d.coords = a->coords; d.oob = (unsigned long long*)a->oob_count;
+  for (int p = 0; p < WARP_PMAX; ++p) {
+    const bool on = p < a->P;
+    if (on) {
+      SC_REQUIRE(a->src[p], "sc_warp: null source plane %d", p);
+      SC_REQUIRE((uintptr_t)a->src[p] % eb == 0, "sc_warp: source plane %d is not aligned to its %d-byte elements", p, eb);
+      SC_REQUIRE(a->row_stride[p] >= 0 && a->col_stride[p] >= 0, "sc_warp: negative stride of plane %d", p);
+    }
+    d.src[p] = on ? a->src[p] : nullptr;
+    d.rs[p] = on ? a->row_stride[p] : 0;
+    d.cs[p] = on ? a->col_stride[p] : 0;
+    d.nod[p] = on ? a->nodata_bits[p] : 0;
+  }
+  const int V = eb == 8 ? 2 : 4;
+  const uintptr_t store = (uintptr_t)(V * eb < 16 ? V * eb : 16);
+  const bool vec = a->out_w % V == 0 && (uintptr_t)a->out % store == 0;
+  hipStream_t st = (hipStream_t)stream;
+  int rc;
+  if (bil) rc = launch<uint32_t, 4, true>(d, vec, st);
+  else if (eb == 1) rc = launch<uint8_t, 4, false>(d, vec, st);
+  else if (eb == 2) rc = launch<uint16_t, 4, false>(d, vec, st);
+  else if (eb == 4) rc = launch<uint32_t, 4, false>(d, vec, st);
+  else rc = launch<uint64_t, 2, false>(d, vec, st);
+  if (rc) return rc;
+  SC_LAUNCH_OK("sc_warp");
+  return SC_OK;
+}

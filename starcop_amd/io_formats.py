@@ -616,6 +616,45 @@ def envi_geo_tags(header: Dict[str, object]) -> Dict[int, tuple]:
     return tags
 
 
+def envi_geotransform(header: Dict[str, object]):
+    """The full 6-term GDAL geotransform of an ENVI ``map info``, ``rotation=`` included, with the sign convention of
+    :func:`envi_geo_tags` (degrees, counter-clockwise, applied to the pixel axes: the numbers its ModelTransformationTag holds), the
+    EPSG code of the header (326zz / 327zz for UTM, 4326 for ``Geographic Lat/Lon``, else None) and the rotation in degrees ->
+    ``(gt, epsg, rotation)``; ``(None, None, 0.0)`` when the header has no usable map info."""
+    tags = envi_geo_tags(header)
+    if not tags:
+        return None, None, 0.0
+    gt, epsg = geo_from_tags(tags)
+    rot = 0.0
+    for v in header["map info"][7:]:
+        if v.lower().replace(" ", "").startswith("rotation="):
+            rot = float(v.split("=")[1])
+    return gt, epsg, rot
+
+
+def geo_from_tags(info):
+    """``(geotransform, epsg)`` of a GeoTIFF from its tags (a ``TiffInfo`` or a {tag: (type, values)} dict): the 6-term GDAL
+    geotransform from ModelPixelScale (33550) + ModelTiepoint (33922) -- the tiepoint may sit at any pixel -- or from the
+    ModelTransformation (34264), and the EPSG code from the GeoKeyDirectory (34735) as :func:`envi_geo_tags`,
+    ``ortho.emit_geo_tags`` and ``warp.geo_tags`` write it: ProjectedCSTypeGeoKey (3072), else GeographicTypeGeoKey (2048).
+    Either is None when the tags do not carry it."""
+    tags = info.tags if isinstance(info, TiffInfo) else dict(info)
+    gt = None
+    if 33550 in tags and 33922 in tags:
+        sx, sy = (float(v) for v in tags[33550][1][:2])
+        i, j, _, x, y, _ = (float(v) for v in tags[33922][1][:6])
+        gt = (x - i * sx, sx, 0.0, y + j * sy, 0.0, -sy)
+    elif 34264 in tags:
+        m = [float(v) for v in tags[34264][1]]
+        gt = (m[3], m[0], m[1], m[7], m[4], m[5])
+    epsg = None
+    if 34735 in tags:
+        keys = [int(v) for v in tags[34735][1]]
+        found = {keys[k]: keys[k + 3] for k in range(4, min(len(keys), 4 + 4 * keys[3]) - 3, 4) if keys[k + 1] == 0}
+        epsg = found.get(3072, found.get(2048))
+    return gt, epsg
+
+
 def window_geo_tags(info, row_off: int, col_off: int) -> Dict[int, tuple]:
     """Georeferencing tags of a window of a raster: the source's, moved to the window's upper-left corner (what the transform
     of ``RasterioReader.read_from_window(window, boundless=True)`` is, sampling_dataset.py:266).  ``info``: a ``TiffInfo`` or a

@@ -233,7 +233,7 @@ def _emit_predict_parts(model, sub, rgb, ratio, template, fill_value, column_ste
 def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_lerp_alpha=1e-4, tile=None, halo=RECEPTIVE_HALO,
                          ratio_bands=None, distributed=None, group=None, rows=None, threads=8, strips=True, georeferenced=False,
                          out_folder=None, geotransform=None, overwrite=False, plumes=False, plume_outlines=False,
-                         label_polygons=None, cog=False):
+                         label_polygons=None, cog=False, crs=None, resolution=None, resampling="nearest", label_crs=None):
     """The notebook path of the reference end to end FROM THE FILE (notebooks/inference_on_raw_EMIT_nc_file.ipynb cells 8-19:
     ``EMITImage(path)`` -> ``mag1c_emit`` -> RGB bands -> rescale -> ``model`` -> threshold): opens the EMIT L1B radiance granule
     (NetCDF-4) with :mod:`starcop_amd.hdf5_reader`, reads ONLY what the pipeline touches -- the contiguous band slice inside
@@ -266,8 +266,22 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
 
     ``cog=True`` (or a dict of :func:`starcop_amd.cog.write_cog` keyword arguments) writes every raster as a Cloud-Optimized
     GeoTIFF -- tiled, with an overview pyramid, empty tiles left out -- straight from the device tensors; the default leaves the
-    files as they were."""
+    files as they were.
+
+    ``crs`` (with ``georeferenced=True``; ``"utm"`` = the WGS-84 UTM zone of the centre of the orthorectified grid, or an EPSG
+    code: 326zz / 327zz / 4326) warps the orthorectified products from the granule's longitude / latitude grid onto the north-up
+    :func:`starcop_amd.warp.suggest_grid` of that CRS at ``resolution`` (its units; default: the pixel count along the diagonal is
+    kept) through :func:`starcop_amd.products.regrid`: ``pred_binary`` by ``nearest``, the float32 products by ``resampling``
+    (``"nearest"`` / ``"bilinear"``, or {key: mode}), no-data = the fill value.  The files then carry the tags of that grid
+    (:func:`starcop_amd.warp.geo_tags`), ``plumes`` has ``x`` / ``y`` in its units and -- for a UTM zone -- ``ime_ppmm_m2`` with
+    the pixel area ``resolution ** 2``; ``geotransform`` and ``crs`` of the new grid are added to the dict.  ``label_polygons``
+    are taken in the output CRS unless ``label_crs`` names another, in which case they go through
+    :func:`starcop_amd.warp.transform_polygons`.  The default ``crs=None`` changes nothing."""
     from .hdf5_reader import H5File
+    if crs is not None and not georeferenced:
+        raise ValueError("emit_granule_predict: crs warps the orthorectified products; pass georeferenced=True")
+    if label_crs is not None and crs is None:
+        raise ValueError("emit_granule_predict: label_crs needs crs= (without it the polygons are taken in the granule's own coordinates)")
     if out_folder is not None:
         if str(out_folder).startswith("gs://"):
             raise NotImplementedError(f"{out_folder}: writing to Google Cloud Storage is not supported")
@@ -297,7 +311,7 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
         rgb_h = np.stack([plane(i) for i in nearest_bands(wl)])
         ratio_h = [plane(i) for i in nearest_bands(wl, ratio_bands)] if ratio_bands is not None else None
         glt = (f["location/glt_x"].read(), f["location/glt_y"].read()) if ("location/glt_x" in f and "location/glt_y" in f) else (None, None)
-        root = f.attrs("/") if out_folder is not None or ((plumes or label_polygons is not None) and georeferenced) else {}
+        root = f.attrs("/") if out_folder is not None or crs is not None or ((plumes or label_polygons is not None) and georeferenced) else {}
     if georeferenced and glt[0] is None:
         raise ValueError(f"{nc_path}: no location/glt_x, location/glt_y to orthorectify with")
     template = mag1c.generate_template_from_bands(wl[b0:b1], fwhm[b0:b1])
@@ -308,6 +322,27 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
         out = georeference_products(out, glt[0], glt[1], fill)
     out.update(wavelengths=wl[b0:b1], fwhm=fwhm[b0:b1], glt_x=glt[0], glt_y=glt[1], fill_value=fill)
     gt = geotransform if geotransform is not None else root.get("geotransform")
+    geo = area = None
+    if crs is not None:
+        import os
+        from . import warp
+        from .ortho import emit_geo_tags
+        if gt is None:
+            raise ValueError("emit_granule_predict: crs needs the grid of the orthorectified products: the granule has no geotransform "
+                             "attribute and none was passed")
+        emit_geo_tags(gt, root.get("spatial_ref"))                        # refuses a granule that is not on a WGS-84 lon / lat grid
+        gt = [float(v) for v in np.asarray(gt, dtype=np.float64).ravel()]
+        if crs == "utm":
+            h, w = out["mf"].shape
+            crs = warp.utm_crs_for(*(float(v) for v in warp.apply_geotransform(gt, w / 2.0, h / 2.0)))
+        gt, crs, area = products.regrid(out, gt, 4326, int(crs), resolution, resampling, fill)
+        geo = warp.geo_tags(gt, crs)
+        out.update(geotransform=gt, crs=crs)
+        if label_polygons is not None and label_crs is not None:
+            if isinstance(label_polygons, (str, os.PathLike)):
+                from .plumes import read_plumes
+                label_polygons = read_plumes(label_polygons)[1]
+            label_polygons = warp.transform_polygons(label_polygons, label_crs, crs)
     mf = prob = None
     if plumes:
         # pixels that carry the fill value become NaN, which the per-plume statistics leave out; in sensor geometry the network
@@ -316,10 +351,11 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
         h, w = out["pred_binary"].shape
         mf = out["mf"][:h, :w]
         mf, prob = torch.where(mf == fill, nan, mf), torch.where(out["prediction"] == fill, nan, out["prediction"])
-    products.annotate(out, out["pred_binary"], mf, prob, gt if georeferenced else None, None, plumes, plume_outlines, label_polygons)
+    products.annotate(out, out["pred_binary"], mf, prob, gt if georeferenced else None, area, plumes, plume_outlines, label_polygons)
     if out_folder is not None:
         from .ortho import emit_geo_tags
-        geo = emit_geo_tags(gt, root.get("spatial_ref")) if gt is not None else {}
+        if geo is None:
+            geo = emit_geo_tags(gt, root.get("spatial_ref")) if gt is not None else {}
         out["files"] = products.write_rasters(
             out, products.EMIT_RASTERS, str(out_folder), overwrite, geo, fill, {"wavelengths": out["wavelengths"], "mag1c": "acrwl1mf"}, cog,
             "emit_granule_predict: the granule has no geotransform attribute and none was passed: the GeoTIFFs are written without georeferencing")
@@ -405,7 +441,7 @@ def _envi_geotransform(header):
 @torch.no_grad()
 def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=None, toa_correction_factor=None, solar_altitude=None,
                          normalize_by_acquisition_date=True, tile=None, halo=None, batch=None, plumes=False, overwrite=False,
-                         device="cuda", plume_outlines=False, label_polygons=None, cog=False):
+                         device="cuda", plume_outlines=False, label_polygons=None, cog=False, north_up=False):
     """An orthorectified AVIRIS-NG flight line through the plume model, file to file: ``{folder}/{name}_img`` (ENVI radiance,
     float32) -> the network's input products -> ``model.predict_scene`` -> (with ``out_folder``) ``pred.tif`` / ``predbinary.tif``.
 
@@ -432,7 +468,14 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
     ``cog=True`` (or a dict of :func:`starcop_amd.cog.write_cog` keyword arguments) writes every raster of the call --
     ``pred.tif``, ``predbinary.tif``, ``label.tif`` and a ``mag1c.tif`` it computes -- as a Cloud-Optimized GeoTIFF straight from
     the device tensor: tiles, overviews (average for float32, mode for uint8) and the search for empty tiles run on the device.
-    The default leaves every byte of the files as it was."""
+    The default leaves every byte of the files as it was.
+
+    ``north_up=True``: a line whose ``map info`` carries a ``rotation=`` has no north-up geotransform, so by default its plume
+    table has no ``x`` / ``y``, its outlines are in pixels and ``label_polygons`` cannot be burnt.  With this flag ``prediction``,
+    ``pred_binary`` and ``mf`` of such a line are warped (same CRS, ``nearest``: :func:`starcop_amd.products.regrid`) onto the
+    north-up :func:`starcop_amd.warp.suggest_grid` at the line's own pixel size before the annotations are made; ``pred.tif``,
+    ``predbinary.tif`` and ``label.tif`` carry that grid (a ``mag1c.tif`` the call computes stays on the line's grid, where
+    the next run reads it) and ``geotransform`` / ``crs`` are added to the dict.  A line without rotation is left as it is."""
     import datetime
     import os
     import re
@@ -505,6 +548,18 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
     out = model.predict_scene(planes, fill_value=fills, scales=scales, clips=clips, tile=tile, halo=halo, batch=batch)
     out["mf"] = mf
     gt, area = _envi_geotransform(header)
+    full, epsg, rotation = io.envi_geotransform(header) if north_up else (None, None, 0.0)
+    if full is not None and rotation != 0.0:
+        from . import warp
+        px, py = float(header["map info"][5]), float(header["map info"][6])
+        if px != py:
+            raise NotImplementedError(f"aviris_scene_predict: north_up with pixels of {px} x {py}: one pixel size per grid")
+        gt, _, area = products.regrid(out, full, epsg, epsg, px, "nearest", {"prediction": mag1c.NODATA, "mf": mf_fill},
+                                      keys=("prediction", "pred_binary", "mf"))
+        mf = out["mf"]
+        out.update(geotransform=gt, crs=epsg)
+        if geo is not None:
+            geo = warp.geo_tags(gt, epsg)
     products.annotate(out, out["pred_binary"], mf, out["prediction"], gt, area, plumes, plume_outlines, label_polygons)
     if out_folder is not None:
         files += products.write_rasters(out, products.AVIRIS_RASTERS, str(out_folder), overwrite, geo, mag1c.NODATA, cog=cog)

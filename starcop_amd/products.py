@@ -84,6 +84,46 @@ def write_rasters(out, table, folder, overwrite=False, geo_tags=None, nodata=Non
     return [p[0] for p in plan]
 
 
+REGRID_KEYS = ("mf", "albedo", "prediction", "ratio", "rgb", "pred_binary", "label_mask")
+
+
+def regrid(out, src_gt, src_crs, dst_crs, resolution=None, resampling="nearest", nodata=None, keys=REGRID_KEYS):
+    """The raster keys of a prediction dict put on another grid, in place: every ``out[key]`` of ``keys`` that is there -- (H, W) or
+    (bands, H, W) device tensors on the grid ``(src_gt, src_crs)`` -- is warped (``warp.reproject``) onto the north-up
+    ``warp.suggest_grid`` of ``dst_crs`` at ``resolution``.  Integer images (masks) are always resampled ``nearest`` with no-data 0;
+    floating-point ones with ``resampling`` -- one mode, or {key: mode} with ``nearest`` for the keys it leaves out -- and ``nodata``
+    (a value, or {key: value}).  Images that share dtype, mode and no-data go through one launch, so the coordinates of a pixel are
+    computed once for all of them.  -> (geotransform of the new grid, its CRS, the area of a pixel in m2 -- None unless the CRS
+    is a UTM zone)"""
+    from . import warp
+    have = [k for k in keys if out.get(k) is not None]
+    if not have:
+        raise ValueError(f"regrid: none of {keys} in the prediction dict")
+    shape = tuple(out[have[0]].shape[-2:])
+    dst_shape, dst_gt = warp.suggest_grid(shape, src_gt, src_crs, dst_crs, resolution)
+    groups = {}
+    for k in have:
+        t = out[k]
+        if tuple(t.shape[-2:]) != shape:
+            raise ValueError(f"regrid: {k} is {tuple(t.shape)}, {have[0]} {tuple(out[have[0]].shape)}: one grid per call")
+        if t.dtype.is_floating_point:
+            mode = resampling.get(k, "nearest") if isinstance(resampling, dict) else resampling
+            fill = nodata.get(k) if isinstance(nodata, dict) else nodata
+        else:
+            mode, fill = "nearest", 0
+        groups.setdefault((t.dtype, mode, 0 if fill is None else fill), []).append(k)
+    for (_, mode, fill), ks in groups.items():
+        planes = [p for k in ks for p in ([out[k]] if out[k].dim() == 2 else out[k].unbind(0))]
+        res = warp.reproject(planes, src_gt, src_crs, dst_gt, dst_crs, dst_shape, mode, fill)
+        i = 0
+        for k in ks:
+            n = 1 if out[k].dim() == 2 else out[k].shape[0]
+            out[k] = res[i] if out[k].dim() == 2 else res[i:i + n]
+            i += n
+    metric = dst_crs is not None and warp.crs_kind(dst_crs)[0] == 2
+    return dst_gt, dst_crs, (abs(dst_gt[1] * dst_gt[5]) if metric else None)
+
+
 def annotate(out, mask, mf, prob, geotransform=None, pixel_area_m2=None, plumes=False, plume_outlines=False, label_polygons=None):
     """The plume annotations of a prediction dict, as asked for: ``plumes`` (``plumes.plume_table`` of ``mask`` with ``mf`` as mag1c
     and ``prob`` as probability), ``plume_outlines`` of the same mask in the same coordinates, and for ``label_polygons`` (a
