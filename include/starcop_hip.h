@@ -937,6 +937,71 @@ typedef struct sc_warp_args {
 } sc_warp_args;
 int sc_warp(const sc_warp_args* a, sc_stream stream);
 
+/* Mosaic: N rasters on grids of their own composed into ONE raster on a destination grid, in one launch.  Per destination pixel the
+ * world coordinates of the centre are computed once; when the destination is a UTM zone and a source of the pixel's tile has another
+ * CRS, longitude / latitude (the Krueger inverse) once per pixel and not once per source; per source nothing more (same CRS), the
+ * affine of longitude / latitude (4326) or the Krueger forward series (another zone; shared by consecutive sources of one code), then
+ * that source's inverse affine -> (u, v), inside as in sc_warp.  All of it is the arithmetic of sc_warp (one shared header).
+ *   Source s is VALID at a pixel when (u, v) is inside it and -- with key_plane >= 0 -- the NEAREST element of its plane key_plane
+ *   differs in bits from nodata_bits[key_plane] and, with SC_MOSAIC_KEY_FLOAT (4- or 8-byte IEEE elements), is not NaN.
+ *   FIRST / LAST : the valid source with the lowest / highest number wins; any element width.
+ *   MAX / MIN    : float32; the valid source whose NEAREST key element is largest / smallest wins (NaN never valid; equal values go
+ *                  to the lower number; the comparison is on the raw element whatever `resampling` is).  key_plane >= 0.
+ *   BY_INDEX     : the winner is select[r][c] when that source is inside at the pixel (validity is not consulted); values outside
+ *                  [0, N) mean none.  count must be NULL.
+ *   For these five: out[p] = what sc_warp writes for plane p of the winner at its (u, v) under `resampling` (nearest: a word copy;
+ *   bilinear: float32, the plane's no-data when the nearest element does not count), nodata_bits[p] without a winner; index = the
+ *   winner or -1.
+ *   MEAN         : float32, P <= SC_MOSAIC_MEAN_PLANES.  out[p] = the fp64 sum, in ascending source order, of the valid sources'
+ *                  samples of plane p that count (nearest: the element; bilinear: the value before rounding), divided by the number
+ *                  of terms and rounded once; no-data without a term.  index must be NULL.
+ *   count (any rule but BY_INDEX, may be NULL) = the number of valid sources.
+ * `sources` is a HOST array of N descriptors; it is checked here and copied once into `table`, device memory of at least
+ * N * sizeof(sc_mosaic_source) bytes (8-byte aligned) that the kernel reads.  box = {r0, r1, c0, c1}: a half-open box of destination
+ * pixels outside of which the source has no pixel (0 <= r0, r1 <= out_h, 0 <= c0, c1 <= out_w; empty allowed).  It only culls: a
+ * work-group runs the per-source work for the sources whose box meets its tile, and a tile that meets none writes no-data / -1 / 0
+ * before any projection; a box larger than needed changes no byte.  Planes are read in place as in sc_warp (strides in elements,
+ * >= 0); nodata_bits[p] is shared by all sources.  out [P][out_h][out_w], index / count int32 [out_h][out_w].
+ * CRS: every source code equals dst_crs (any code >= 0), or it and dst_crs are 4326 / WGS-84 UTM.  SC_ERR_ARG as sc_warp, and for
+ * N outside [1, 64], P outside [1, 32], key_plane outside [-1, P), a rule / width combination above, a box outside the grid.
+ * No LDS, no atomics: repeated calls give identical bits.                                                                       */
+#define SC_MOSAIC_MAX_SOURCES 64
+#define SC_MOSAIC_MEAN_PLANES 4
+#define SC_MOSAIC_FIRST 0
+#define SC_MOSAIC_LAST 1
+#define SC_MOSAIC_MAX 2
+#define SC_MOSAIC_MIN 3
+#define SC_MOSAIC_MEAN 4
+#define SC_MOSAIC_BY_INDEX 5
+#define SC_MOSAIC_KEY_FLOAT 1 /* flags: the key plane holds IEEE floating-point numbers of elem_bytes (4 or 8); a NaN is not valid */
+typedef struct sc_mosaic_source {
+  double src_inv[6];                             /* world -> source pixel coordinates, as in sc_warp_args        */
+  int32_t src_crs, src_h, src_w;
+  int32_t reserved;                              /* 0                                                            */
+  int32_t box[4];                                /* r0, r1, c0, c1 in destination pixels, half-open              */
+  const void* src[SC_WARP_MAX_PLANES];           /* element (0, 0) of every plane, device                        */
+  int64_t row_stride[SC_WARP_MAX_PLANES];        /* elements                                                     */
+  int64_t col_stride[SC_WARP_MAX_PLANES];
+} sc_mosaic_source;
+typedef struct sc_mosaic_args {
+  double dst_gt[6];                              /* geotransform of the destination grid, GDAL order             */
+  int32_t dst_crs, out_h, out_w;
+  int32_t N, P;                                  /* sources 1..64, planes per source 1..32                       */
+  int32_t elem_bytes;                            /* 1, 2, 4 or 8: one width per call                             */
+  int32_t rule;                                  /* SC_MOSAIC_FIRST ... SC_MOSAIC_BY_INDEX                       */
+  int32_t key_plane;                             /* -1: the footprint alone decides validity                     */
+  int32_t resampling;                            /* SC_WARP_NEAREST, SC_WARP_BILINEAR                            */
+  int32_t flags;                                 /* SC_MOSAIC_KEY_FLOAT                                          */
+  uint64_t nodata_bits[SC_WARP_MAX_PLANES];      /* raw bit pattern of every plane's no-data value               */
+  const sc_mosaic_source* sources;               /* HOST, N descriptors                                          */
+  void* table;                                   /* device, >= N * sizeof(sc_mosaic_source) bytes                */
+  void* out;                                     /* [P][out_h][out_w] device                                     */
+  int32_t* index;                                /* [out_h][out_w] device, or NULL                               */
+  int32_t* count;                                /* [out_h][out_w] device, or NULL                               */
+  const int32_t* select;                         /* [out_h][out_w] device: SC_MOSAIC_BY_INDEX                    */
+} sc_mosaic_args;
+int sc_mosaic(const sc_mosaic_args* a, sc_stream stream);
+
 /* Cutting the sampled windows of a flight line into dense sample tensors: the reads of WindowDataset.__getitem__,
  * starcop/data/sampling_dataset.py:259-303 -- RasterioReader.read_from_window(window, boundless=True).load(boundless=True) at :266,
  * nodata -> 0 at :269-271, the acquisition-date multiply at :285 / :289 and np.clip at :287 / :293 -- for every window of a chunk

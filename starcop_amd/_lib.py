@@ -161,6 +161,27 @@ class sc_warp_args(C.Structure):
                 ("out", C.c_void_p), ("coords", C.c_void_p), ("oob_count", C.c_void_p)]
 
 
+MOSAIC_MAX_SOURCES, MOSAIC_MEAN_PLANES = 64, 4
+MOSAIC_FIRST, MOSAIC_LAST, MOSAIC_MAX, MOSAIC_MIN, MOSAIC_MEAN, MOSAIC_BY_INDEX = range(6)
+MOSAIC_KEY_FLOAT = 1
+
+
+class sc_mosaic_source(C.Structure):
+    """one source of a mosaic (include/starcop_hip.h: sc_mosaic_source)"""
+    _fields_ = [("src_inv", C.c_double * 6), ("src_crs", C.c_int32), ("src_h", C.c_int32), ("src_w", C.c_int32),
+                ("reserved", C.c_int32), ("box", C.c_int32 * 4), ("src", C.c_void_p * WARP_MAX_PLANES),
+                ("row_stride", C.c_int64 * WARP_MAX_PLANES), ("col_stride", C.c_int64 * WARP_MAX_PLANES)]
+
+
+class sc_mosaic_args(C.Structure):
+    """mosaic operands (include/starcop_hip.h: sc_mosaic_args)"""
+    _fields_ = [("dst_gt", C.c_double * 6), ("dst_crs", C.c_int32), ("out_h", C.c_int32), ("out_w", C.c_int32), ("N", C.c_int32),
+                ("P", C.c_int32), ("elem_bytes", C.c_int32), ("rule", C.c_int32), ("key_plane", C.c_int32),
+                ("resampling", C.c_int32), ("flags", C.c_int32), ("nodata_bits", C.c_uint64 * WARP_MAX_PLANES),
+                ("sources", C.POINTER(sc_mosaic_source)), ("table", C.c_void_p), ("out", C.c_void_p), ("index", C.c_void_p),
+                ("count", C.c_void_p), ("select", C.c_void_p)]
+
+
 WCUT_MAX_PLANES = 64
 WCUT_FILL, WCUT_SCALE, WCUT_CLIP = 1, 2, 4
 
@@ -365,6 +386,7 @@ SIGNATURES = {
     "sc_window_stats": (_i, [C.POINTER(sc_winstats_args), _vp, _sz, _vp]),
     "sc_glt_ortho": (_i, [C.POINTER(sc_ortho_args), _vp]),
     "sc_warp": (_i, [C.POINTER(sc_warp_args), _vp]),
+    "sc_mosaic": (_i, [C.POINTER(sc_mosaic_args), _vp]),
     "sc_window_cut": (_i, [C.POINTER(sc_wcut_args), _vp]),
     "sc_scene_gather": (_i, [C.POINTER(sc_scene_args), _vp]),
     "sc_head_conv_fwd_k_mosaic": (_i, [C.POINTER(sc_src), _vp, _vp, _vp, _i, _i, C.c_int64, _vp, _vp, _i, _i, _i, _i, _i, _vp]),

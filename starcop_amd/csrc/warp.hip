@@ -24,19 +24,12 @@
 #include <cmath>
 
 #include "sc_common.h"
+#include "sc_warp.h"
 
 namespace {
 
 constexpr int WARP_PMAX = SC_WARP_MAX_PLANES;
 constexpr int WARP_WG = 256;
-constexpr double WARP_DEG = 0.017453292519943295769;      // radians per degree
-constexpr double WARP_MAX_DLON = 30.0;                    // degrees from the central meridian beyond which a point is outside
-constexpr int WARP_NEWTON = 3;                            // steps of the conformal-latitude inversion: 2 reach the last place for |lat| < 89.999, one spare
-
-struct Krueger {
-  double e, e2m, ka;                             // first eccentricity, 1 - e^2, k0 * rectifying radius
-  double alp[6], bet[6];
-};
 
 struct WarpD {
   double gt[6], inv[6];
@@ -53,73 +46,6 @@ struct WarpD {
   unsigned long long nod[WARP_PMAX];
 };
 
-template <class T, int V>
-struct alignas((V * sizeof(T) >= 16) ? 16 : V * sizeof(T)) Pack {
-  T v[V];
-};
-
-// sum_j c[j-1] sin(2 j (xi + i eta)), j = 1..6 -> (real, imaginary) part
-__device__ __forceinline__ void clenshaw_sin(const double* c, double xi, double eta, double& re, double& im) {
-  double s0, c0;
-  sincos(2.0 * xi, &s0, &c0);
-  const double sh0 = sinh(2.0 * eta), ch0 = cosh(2.0 * eta);
-  const double ar = 2.0 * c0 * ch0, ai = -2.0 * s0 * sh0;              // 2 cos(2 zeta)
-  double y1r = 0.0, y1i = 0.0, y2r = 0.0, y2i = 0.0;
-#pragma unroll
-  for (int j = 5; j >= 0; --j) {
-    const double yr = c[j] + ar * y1r - ai * y1i - y2r;
-    const double yi = ar * y1i + ai * y1r - y2i;
-    y2r = y1r; y2i = y1i; y1r = yr; y1i = yi;
-  }
-  const double zr = s0 * ch0, zi = c0 * sh0;                           // sin(2 zeta)
-  re = zr * y1r - zi * y1i;
-  im = zr * y1i + zi * y1r;
-}
-
-// tangent of the conformal latitude from the tangent of the geographic one (Karney 2011 eq. 7-9)
-__device__ __forceinline__ double taup_of(double tau, double e) {
-  const double t1 = sqrt(1.0 + tau * tau);
-  const double sig = sinh(e * atanh(e * tau / t1));
-  return tau * sqrt(1.0 + sig * sig) - sig * t1;
-}
-
-// longitude / latitude in degrees -> easting / northing; false outside 30 degrees of the central meridian or |lat| > 90
-__device__ __forceinline__ bool tm_forward(const Krueger& k, double lon0, double fn, double lon, double lat, double& E, double& N) {
-  const double dl = remainder(lon - lon0, 360.0);
-  if (!(fabs(dl) <= WARP_MAX_DLON) || !(fabs(lat) <= 90.0)) return false;
-  const double taup = taup_of(tan(lat * WARP_DEG), k.e);
-  double sl, cl;
-  sincos(dl * WARP_DEG, &sl, &cl);
-  const double xip = atan2(taup, cl), etap = asinh(sl / sqrt(taup * taup + cl * cl));
-  double dx, de;
-  clenshaw_sin(k.alp, xip, etap, dx, de);
-  E = 500000.0 + k.ka * (etap + de);
-  N = fn + k.ka * (xip + dx);
-  return true;
-}
-
-// easting / northing -> longitude / latitude in degrees; false outside 30 degrees of the central meridian
-__device__ __forceinline__ bool tm_inverse(const Krueger& k, double lon0, double fn, double E, double N, double& lon, double& lat) {
-  const double xi = (N - fn) / k.ka, eta = (E - 500000.0) / k.ka;
-  double dx, de;
-  clenshaw_sin(k.bet, xi, eta, dx, de);
-  const double xip = xi - dx, etap = eta - de;
-  double sx, cx;
-  sincos(xip, &sx, &cx);
-  const double shp = sinh(etap);
-  const double taup = sx / sqrt(shp * shp + cx * cx);
-  const double lam = atan2(shp, cx);
-  double tau = taup / k.e2m;
-#pragma unroll
-  for (int i = 0; i < WARP_NEWTON; ++i) {
-    const double ta = taup_of(tau, k.e);
-    tau += (taup - ta) * (1.0 + k.e2m * tau * tau) / (k.e2m * sqrt(1.0 + ta * ta) * sqrt(1.0 + tau * tau));
-  }
-  lat = atan(tau) / WARP_DEG;
-  lon = lon0 + lam / WARP_DEG;
-  return fabs(lam) <= WARP_MAX_DLON * WARP_DEG;
-}
-
 // source pixel coordinates of the centre of destination pixel (r, c); NaN when the point is outside the source
 __device__ __forceinline__ bool source_uv(const WarpD& a, int r, long long c, double& u, double& v) {
   const double px = (double)c + 0.5, py = (double)r + 0.5;
@@ -135,9 +61,6 @@ __device__ __forceinline__ bool source_uv(const WarpD& a, int r, long long c, do
   if (!ok) u = v = __builtin_nan("");
   return ok;
 }
-
-// a float32 sample takes part in an interpolation: not the plane's no-data pattern and not NaN
-__device__ __forceinline__ bool counts(uint32_t bits, uint32_t nod) { return bits != nod && (bits & 0x7FFFFFFFu) <= 0x7F800000u; }
 
 // grid.x = tiles_y * tiles_x tiles of TY rows x TX * V pixels.  BIL: bilinear (T = uint32_t, the bits of a float32)
 template <class T, int V, bool BIL>
@@ -167,12 +90,6 @@ __global__ __launch_bounds__(WARP_WG) void k_warp(WarpD a) {
     }
   }
   if (a.P == 0) return;
-  long long sx[V], sy[V];                         // the nearest source pixel (0 where there is none: never dereferenced)
-#pragma unroll
-  for (int e = 0; e < V; ++e) {
-    sx[e] = in[e] ? (long long)floor(u[e]) : 0;
-    sy[e] = in[e] ? (long long)floor(v[e]) : 0;
-  }
   T* o = static_cast<T*>(a.out) + pix;
   for (int p = 0; p < a.P; ++p) {                 // p is uniform: the plane's descriptor comes in scalar registers
     const T* s = static_cast<const T*>(a.src[p]);
@@ -180,35 +97,7 @@ __global__ __launch_bounds__(WARP_WG) void k_warp(WarpD a) {
     const T nod = (T)a.nod[p];
     Pack<T, V> r;
 #pragma unroll
-    for (int e = 0; e < V; ++e) {
-      T val = nod;
-      if (in[e]) val = s[sy[e] * rs + sx[e] * cs];
-      if constexpr (BIL) {
-        if (in[e] && counts(val, nod)) {
-          const double ub = u[e] - 0.5, vb = v[e] - 0.5;
-          const double fx0 = floor(ub), fy0 = floor(vb);
-          const double fx = ub - fx0, fy = vb - fy0;
-          const long long ix = (long long)fx0, iy = (long long)fy0;
-          double acc = 0.0, wsum = 0.0;
-#pragma unroll
-          for (int k = 0; k < 4; ++k) {           // (row, column) offsets (0, 0), (0, 1), (1, 0), (1, 1)
-            const long long xx = ix + (k & 1), yy = iy + (k >> 1);
-            const double w = ((k & 1) ? fx : 1.0 - fx) * ((k >> 1) ? fy : 1.0 - fy);
-            if (w > 0.0 && xx >= 0 && xx < a.sw && yy >= 0 && yy < a.sh) {
-              const uint32_t b = s[yy * rs + xx * cs];
-              if (counts(b, nod)) {
-                acc += w * (double)__uint_as_float(b);
-                wsum += w;
-              }
-            }
-          }
-          val = __float_as_uint((float)(acc / wsum));      // wsum >= 0.25: the nearest pixel counts and has at least that weight
-        } else {
-          val = nod;
-        }
-      }
-      r.v[e] = val;
-    }
+    for (int e = 0; e < V; ++e) r.v[e] = sample<T, BIL>(s, rs, cs, nod, a.sh, a.sw, u[e], v[e], in[e]);
     *reinterpret_cast<Pack<T, V>*>(o + (size_t)p * plane) = r;
   }
 }
@@ -223,37 +112,6 @@ int launch(const WarpD& d0, bool vec, hipStream_t st) {
   if (vec) hipLaunchKernelGGL((k_warp<T, V, BIL>), dim3((unsigned)tiles), dim3(WARP_WG), 0, st, d);
   else hipLaunchKernelGGL((k_warp<T, 1, BIL>), dim3((unsigned)tiles), dim3(WARP_WG), 0, st, d);
   return SC_OK;
-}
-
-// 0 = affine only, 1 = WGS-84 geographic, 2 = WGS-84 UTM (zone and hemisphere set), -1 = not a code this operator knows
-int crs_kind(int code, double& lon0, double& fn) {
-  lon0 = fn = 0.0;
-  if (code == 4326) return 1;
-  const bool north = code >= 32601 && code <= 32660, south = code >= 32701 && code <= 32760;
-  if (!north && !south) return -1;
-  lon0 = 6.0 * (code % 100) - 183.0;
-  fn = south ? 10000000.0 : 0.0;
-  return 2;
-}
-
-void krueger_wgs84(Krueger& k) {
-  const double a = 6378137.0, f = 1.0 / 298.257223563, k0 = 0.9996;
-  const double n = f / (2.0 - f), n2 = n * n, n3 = n2 * n, n4 = n3 * n, n5 = n4 * n, n6 = n5 * n;
-  k.e = sqrt(f * (2.0 - f));
-  k.e2m = (1.0 - f) * (1.0 - f);
-  k.ka = k0 * a / (1.0 + n) * (1.0 + n2 / 4.0 + n4 / 64.0 + n6 / 256.0);
-  k.alp[0] = n / 2 - 2 * n2 / 3 + 5 * n3 / 16 + 41 * n4 / 180 - 127 * n5 / 288 + 7891 * n6 / 37800;
-  k.alp[1] = 13 * n2 / 48 - 3 * n3 / 5 + 557 * n4 / 1440 + 281 * n5 / 630 - 1983433 * n6 / 1935360;
-  k.alp[2] = 61 * n3 / 240 - 103 * n4 / 140 + 15061 * n5 / 26880 + 167603 * n6 / 181440;
-  k.alp[3] = 49561 * n4 / 161280 - 179 * n5 / 168 + 6601661 * n6 / 7257600;
-  k.alp[4] = 34729 * n5 / 80640 - 3418889 * n6 / 1995840;
-  k.alp[5] = 212378941 * n6 / 319334400;
-  k.bet[0] = n / 2 - 2 * n2 / 3 + 37 * n3 / 96 - n4 / 360 - 81 * n5 / 512 + 96199 * n6 / 604800;
-  k.bet[1] = n2 / 48 + n3 / 15 - 437 * n4 / 1440 + 46 * n5 / 105 - 1118711 * n6 / 3870720;
-  k.bet[2] = 17 * n3 / 480 - 37 * n4 / 840 - 209 * n5 / 4480 + 5569 * n6 / 90720;
-  k.bet[3] = 4397 * n4 / 161280 - 11 * n5 / 504 - 830251 * n6 / 7257600;
-  k.bet[4] = 4583 * n5 / 161280 - 108847 * n6 / 3991680;
-  k.bet[5] = 20648693 * n6 / 638668800;
 }
 
 }  // namespace

@@ -567,6 +567,77 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
     return out
 
 
+@torch.no_grad()
+def mosaic_products(folders, out_folder, crs=None, resolution=None, rule="max", plumes=False, plume_outlines=False, label_polygons=None,
+                    cog=False, overwrite=False, device="cuda"):
+    """The product folders of N scenes -- what ``emit_granule_predict`` / ``aviris_scene_predict`` write -- composed into one:
+    ``pred.tif``, ``predbinary.tif`` and, where every folder has one, ``mag1c.tif`` are read (``io_formats.read_tiff``; grid and
+    CRS from the GeoTIFF tags, a file without them raises ValueError), put on the union grid of the scenes in ``crs`` (default:
+    that of the first folder) at ``resolution`` by :func:`starcop_amd.products.mosaic` with ``rule`` on the probability, and written
+    under the same names into ``out_folder``, with ``source.tif``: uint8, the number of the folder a pixel came from, 255 = none,
+    the folder names in the GDAL metadata (``source_0``, ...).  ``plumes`` / ``plume_outlines`` / ``label_polygons`` add the files
+    of ``products.write_annotations``, made on the mosaic: a plume in the overlap of two scenes is one row.  No-data of the float
+    rasters is each file's GDAL_NODATA of the first folder (default -9999).  -> the dict of ``products.mosaic`` with ``files``."""
+    import os
+    from . import io_formats as io
+    from . import warp
+    from .sampling import _nodata
+    if plume_outlines and not plumes:
+        raise ValueError("mosaic_products: plume_outlines=True needs plumes=True")
+    folders = [str(f).rstrip("/") for f in folders]
+    for path in folders + [out_folder]:
+        if str(path).startswith("gs://"):
+            raise NotImplementedError(f"{path}: Google Cloud Storage is not supported; pass a local path")
+    if not folders:
+        raise ValueError("mosaic_products: no folders")
+    table = [products.PRED, products.PREDBINARY]
+    if all(os.path.exists(os.path.join(f, products.MAG1C.name)) for f in folders):
+        table.insert(0, products.MAG1C)
+    dev = torch.device(device)
+    outs, fills = [], {}
+    for f in folders:
+        o = {}
+        for row in table:
+            path = os.path.join(f, row.name)
+            info = io.tiff_info(path)
+            gt, epsg = io.geo_from_tags(info)
+            if gt is None or epsg is None:
+                raise ValueError(f"{path}: the file carries no georeferencing (geotransform and CRS tags)")
+            if "geotransform" in o and (tuple(gt) != tuple(o["geotransform"]) or epsg != o["crs"]):
+                raise ValueError(f"{path}: another grid than the other rasters of {f}")
+            a = io.read_tiff(path, info=info)
+            a = a[0] if a.ndim == 3 else a
+            want = np.uint8 if row.uint8 else np.float32
+            if a.dtype != want:
+                raise ValueError(f"{path}: expected {np.dtype(want)}, got {a.dtype}")
+            if row.nodata and row.key not in fills:
+                nod = _nodata(info)
+                fills[row.key] = float(mag1c.NODATA) if nod is None else nod
+            o[row.key] = torch.from_numpy(np.ascontiguousarray(a)).to(dev)
+            o.update(geotransform=gt, crs=epsg)
+        outs.append(o)
+    out = products.mosaic(outs, crs, resolution, rule, "prediction", "nearest", fills, keys=[row.key for row in table])
+    gt, epsg = out["geotransform"], out["crs"]
+    area = abs(gt[1] * gt[5]) if warp.crs_kind(epsg)[0] == 2 else None
+    products.annotate(out, out["pred_binary"], out.get("mf"), out["prediction"], gt, area, plumes, plume_outlines, label_polygons)
+    geo = warp.geo_tags(gt, epsg)
+    out_folder = str(out_folder)
+    files = []
+    for row in table:                             # every float raster under its own no-data value
+        files += products.write_rasters(out, (row,), out_folder, overwrite, geo, fills.get(row.key), {}, cog)
+    src = out["source_index"]
+    out["source"] = torch.where(src < 0, products.SOURCE_NONE, src).to(torch.uint8)
+    path = os.path.join(out_folder, products.SOURCE.name)
+    if overwrite or not os.path.exists(path):
+        os.makedirs(out_folder, exist_ok=True)
+        names = {f"source_{i}": os.path.basename(f) for i, f in enumerate(folders)}
+        tags = {**geo, 42113: (2, (nodata_text(products.SOURCE_NONE),)), **io.gdal_metadata_tag(names, list(products.SOURCE.bands))}
+        products.write_raster(path, out["source"], tags, cog, products.SOURCE_NONE)
+        files.append(path)
+    out["files"] = files + products.write_annotations(out, out_folder, overwrite, geo, cog)
+    return out
+
+
 BANDS_S2 = ["B1", "B2", "B3", "B4", "B5", "B6", "B7", "B8", "B8A", "B9", "B10", "B11", "B12"]
 BANDS_WV3 = ["SWIR1", "SWIR2", "SWIR3", "SWIR4", "SWIR5", "SWIR6", "SWIR7", "SWIR8"]
 BANDS_SENSOR = {"S2A": BANDS_S2, "S2B": BANDS_S2, "WV3": BANDS_WV3}

@@ -124,6 +124,81 @@ def regrid(out, src_gt, src_crs, dst_crs, resolution=None, resampling="nearest",
     return dst_gt, dst_crs, (abs(dst_gt[1] * dst_gt[5]) if metric else None)
 
 
+SOURCE = Raster("source.tif", "source", ("Source scene",), True, False, True)
+SOURCE_NONE = 255           # in source.tif: no scene has a valid pixel here
+
+
+def mosaic(outs, dst_crs=None, resolution=None, rule="max", key="prediction", resampling="nearest", nodata=None, keys=REGRID_KEYS,
+           grids=None):
+    """N prediction dicts -- as ``pipeline.emit_granule_predict(..., georeferenced=True)`` / ``aviris_scene_predict`` return them,
+    each with ``geotransform`` and ``crs``, or with ``grids=[(gt, crs), ...]`` -- composed into ONE new dict on the
+    ``mosaic.union_grid`` of their grids in ``dst_crs`` (default: the CRS of the first) at ``resolution``; the inputs stay untouched.
+
+    The float32 raster keys of ``keys`` that every input carries go through one ``mosaic.mosaic`` launch with ``rule`` and the
+    plane ``key`` as key (None: the footprint alone), ``resampling`` and ``nodata`` (a value, or {key: value}; default 0); the
+    integer keys (``pred_binary``, ``label_mask``) follow by rule ``"index"`` with the index of that launch, so mask, probability
+    and mag1c of a pixel come from the same scene.  With ``rule="mean"`` there is no winner: the masks go by ``"first"`` over the
+    footprint.  Added: ``geotransform``, ``crs``, ``source_index`` (int32: the scene of every pixel, -1 for none) and
+    ``source_count`` (int32: scenes with a valid pixel).  ``annotate`` works on the result as it is, so plume tables, outlines and
+    label polygons over a mosaic count each plume once."""
+    from . import mosaic as mz
+    outs = list(outs)
+    if grids is None:
+        grids = [(o.get("geotransform"), o.get("crs")) for o in outs]
+    grids = list(grids)
+    if len(grids) != len(outs) or any(g[0] is None for g in grids):
+        raise ValueError("mosaic: every input needs a geotransform: `geotransform` / `crs` in the dict, or grids=[(gt, crs), ...]")
+    if not 1 <= len(outs) <= mz.MAX_SOURCES:
+        raise ValueError(f"mosaic: {len(outs)} inputs; one call takes 1 to {mz.MAX_SOURCES}")
+    dst_crs = grids[0][1] if dst_crs is None else dst_crs
+    have = [k for k in keys if all(o.get(k) is not None for o in outs)]
+    floats = [k for k in have if outs[0][k].dtype.is_floating_point]
+    ints = [k for k in have if k not in floats]
+    if not floats or (key is not None and key not in floats):
+        raise ValueError(f"mosaic: the key {key!r} must be a floating-point raster every input carries; common rasters: {have}")
+    shapes = [tuple(o[have[0]].shape[-2:]) for o in outs]
+    for o, shape in zip(outs, shapes):
+        if any(tuple(o[k].shape[-2:]) != shape for k in have):
+            raise ValueError("mosaic: the rasters of one input share one grid")
+    dst_shape, dst_gt = mz.union_grid([(s, g, c) for s, (g, c) in zip(shapes, grids)], dst_crs, resolution)
+
+    def planes(o, ks):
+        return [p for k in ks for p in ([o[k]] if o[k].dim() == 2 else o[k].unbind(0))]
+
+    def split(res, ks, new):
+        i = 0
+        for k in ks:
+            n = 1 if outs[0][k].dim() == 2 else outs[0][k].shape[0]
+            new[k] = res[i] if outs[0][k].dim() == 2 else res[i:i + n]
+            i += n
+
+    fills, kidx = [], -1
+    for k in floats:
+        n = 1 if outs[0][k].dim() == 2 else outs[0][k].shape[0]
+        kidx = len(fills) if k == key else kidx
+        v = nodata.get(k) if isinstance(nodata, dict) else nodata
+        fills += [0 if v is None else v] * n
+    srcs = [(planes(o, floats), g, c) for o, (g, c) in zip(outs, grids)]
+    new = {}
+    if rule == "mean":
+        res, count = mz.mosaic(srcs, dst_gt, dst_crs, dst_shape, rule, kidx, resampling, fills, return_count=True)
+        index = None
+    else:
+        res, index, count = mz.mosaic(srcs, dst_gt, dst_crs, dst_shape, rule, kidx, resampling, fills, return_index=True, return_count=True)
+    split(res, floats, new)
+    groups = {}
+    for k in ints:
+        groups.setdefault(outs[0][k].dtype, []).append(k)
+    if index is None:                             # mean: the first scene whose footprint holds the pixel
+        index = mz.mosaic([(o[floats[0]] if o[floats[0]].dim() == 2 else o[floats[0]][0], g, c) for o, (g, c) in zip(outs, grids)],
+                          dst_gt, dst_crs, dst_shape, "first", -1, return_index=True)[1]
+    for ks in groups.values():
+        split(mz.mosaic([(planes(o, ks), g, c) for o, (g, c) in zip(outs, grids)], dst_gt, dst_crs, dst_shape, "index", -1,
+                        nodata=0, select=index), ks, new)
+    new.update(geotransform=dst_gt, crs=dst_crs, source_index=index, source_count=count)
+    return new
+
+
 def annotate(out, mask, mf, prob, geotransform=None, pixel_area_m2=None, plumes=False, plume_outlines=False, label_polygons=None):
     """The plume annotations of a prediction dict, as asked for: ``plumes`` (``plumes.plume_table`` of ``mask`` with ``mf`` as mag1c
     and ``prob`` as probability), ``plume_outlines`` of the same mask in the same coordinates, and for ``label_polygons`` (a
