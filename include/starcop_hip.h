@@ -373,6 +373,22 @@ int sc_irt_wgrad_finalize(const sc_irt_args* a, const float* cst_bwd_expand, flo
 size_t sc_wgrad_bx3_workspace_floats(int N, int H, int W, int Cout, int Cin);
 int sc_conv3x3_wgrad_bx3(const sc_wgrad_args* a, sc_stream stream);
 
+/* HOST queries (no GPU work): which kernel instantiation the four 3x3 matrix-core entry points of conv_bx3.hip launch for these
+ * arguments, with the development knobs of the environment applied; -1 for arguments the entry point rejects (the reason is left in
+ * sc_last_error).  Pointers are only tested for NULL and alignment; the workspace size of the weight gradients is not looked at.
+ * The entry points dispatch on these values.  M = 1, 2, 3: that many bf16 terms per operand (terms 0 = 3), 4: two fp16 terms.
+ *   sc_conv3_variant (sc_conv3x3_bx3):  1000 * WS + 100 * Q + 10 * BNB + M -- WS: the wave-specialised k_conv3_ws<Q, BNB> (M = 4 only),
+ *     else k_conv3_bx3<Q, BNB, ..>; Q = co_t / 32; BNB: src[0] is SC_SRC_BNBWD
+ *   sc_thin16_variant (sc_conv3x3_thin16):  100 * (C / 16) + 10 * BNB + UPS for k_conv3_thin_h<C, BNB, UPS> (100, 110, 200, 201, 210),
+ *     1200 = k_conv3_thin_sp (an up-sampled 32-channel RAW / AFFINE source), 2110 = k_conv3_thin_spd (down0)
+ *   sc_wgrad3_variant (sc_conv3x3_wgrad_bx3):  10000 * PIPE + 1000 * M + 100 * WM + 10 * NCI + R for k_wgrad3_bx3<WM, .., NCI, .., PIPE>;
+ *     R = 1: the kernel sums its K parts itself (sc_wgrad_finish sees one row per slice)
+ *   sc_wgrad_thin16_variant (sc_conv3x3_wgrad_thin16):  100 * (Cin / 16) + 10 * (dy is SC_SRC_BNBWD) for k_wgrad_thin_h<Cin, BNB> */
+int sc_conv3_variant(const sc_conv_args* a);
+int sc_thin16_variant(const sc_conv_args* a);
+int sc_wgrad3_variant(const sc_wgrad_args* a);
+int sc_wgrad_thin16_variant(const sc_wgrad_args* a);
+
 /* ------------------------------------------------------------------------- */
 /* depthwise 3x3 (groups=C, pad 1, stride 1|2): forward, backward-data, backward-weight */
 int sc_dwconv3x3_fwd(const sc_src* in, const float* w /*[C][3][3]*/, float* out,

@@ -322,6 +322,10 @@ SIGNATURES = {
     "sc_pack_weights_bx3": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _vp]),
     "sc_packed_weight_floats_bx3": (_sz, [_i, _i, _i, _i, _i]),
     "sc_conv3x3_bx3": (_i, [C.POINTER(sc_conv_args), _vp]),
+    "sc_conv3_variant": (_i, [C.POINTER(sc_conv_args)]),
+    "sc_thin16_variant": (_i, [C.POINTER(sc_conv_args)]),
+    "sc_wgrad3_variant": (_i, [C.POINTER(sc_wgrad_args)]),
+    "sc_wgrad_thin16_variant": (_i, [C.POINTER(sc_wgrad_args)]),
     "sc_wgrad_workspace_floats": (_sz, [_i, _i, _i, _i, _i, _i]),
     "sc_conv2d_wgrad_mfma": (_i, [C.POINTER(sc_wgrad_args), _vp]),
     "sc_dwconv3x3_fwd": (_i, [C.POINTER(sc_src), _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp]),

@@ -2744,7 +2744,8 @@ extern "C" int sc_pack_weights_bx3(const float* w, float* wpk, int Cout, int Cin
   return SC_OK;
 }
 
-extern "C" int sc_conv3x3_bx3(const sc_conv_args* a, sc_stream stream) {
+// argument checks of sc_conv3x3_bx3, shared with its host query
+static int conv3_bx3_check(const sc_conv_args* a) {
   SC_REQUIRE(a != nullptr, "sc_conv3x3_bx3: null args");
   SC_REQUIRE(a->ks == 3, "sc_conv3x3_bx3: ks must be 3 (got %d)", a->ks);
   SC_REQUIRE(a->co_t == 32 || a->co_t == 64, "sc_conv3x3_bx3: co_t must be 32 or 64 (got %d)", a->co_t);
@@ -2764,6 +2765,38 @@ extern "C" int sc_conv3x3_bx3(const sc_conv_args* a, sc_stream stream) {
     SC_REQUIRE(a->src[s].mode != SC_SRC_BNBWD || a->src[s].aux != nullptr, "sc_conv3x3_bx3: BNBWD source needs aux");
     SC_REQUIRE(a->src[s].mode != SC_SRC_BNBWD || a->nsrc == 1, "sc_conv3x3_bx3: a BNBWD source cannot be part of a concat");
   }
+  SC_REQUIRE(!a->down0 || (a->H % 2 == 0 && a->W % 2 == 0 && a->stats == nullptr && a->add0 == nullptr && a->add1 == nullptr),
+             "sc_conv3x3_bx3: down0 (2x2-summed half-resolution out0) needs even H, W and no stats/add tensors");
+  SC_REQUIRE(a->terms >= 0 && a->terms <= 4, "sc_conv3x3_bx3: terms must be 0 (= 3), 1, 2, 3 or SC_TERMS_F16X2 (got %d)", a->terms);
+  if (a->bnr) {
+    SC_REQUIRE(a->src[0].mode == SC_SRC_BNBWD && a->bnr->y && a->bnr->cst && a->bnr->rows, "sc_conv3x3_bx3: bnr needs a BNBWD source and y / cst / rows");
+    SC_REQUIRE(!a->accum0 && !a->add0 && !a->add1 && !a->stats, "sc_conv3x3_bx3: bnr: out0 must receive the complete gradient (no accum0 / add / stats)");
+    SC_REQUIRE(a->csplit == a->Cout || a->csplit % a->co_t == 0, "sc_conv3x3_bx3: bnr: csplit must fall on a cout-tile boundary");
+  }
+  return SC_OK;
+}
+
+// Which kernel sc_conv3x3_bx3 launches for checked arguments: 1000 * (k_conv3_ws, else k_conv3_bx3) + 100 * Q (co_t / 32) +
+// 10 * (BNBWD source) + M, M = 1, 2, 3 bf16 terms or 4 = two fp16 terms.
+static int conv3_bx3_variant_of(const sc_conv_args* a) {
+  const int C0 = a->src[0].C, C1 = a->nsrc == 2 ? a->src[1].C : 0;
+  const int bnb = a->src[0].mode == SC_SRC_BNBWD ? 1 : 0;
+  const int m = a->terms == SC_TERMS_F16X2 ? 4 : (a->terms == 1 || a->terms == 2 ? a->terms : 3);
+  constexpr int ws_env = 1;
+  static const int ws_env_min = [] { const char* e = getenv("STARCOP_BX3_WS_MINCHUNKS"); return e ? atoi(e) : 16; }();
+  // the wave-specialised kernel pays for its 8-wave work-groups (prologue / epilogue of only two per CU) on short K loops:
+  // measured faster from 16 chunks of 16 input channels up (decoder.blocks.0), level at 8-10, slower below
+  const int ws = (m == 4 && ws_env && (C0 + C1 + 15) / 16 >= ws_env_min && (!bnb || a->src[0].C <= 256) && !a->bnr) ? 1 : 0;
+  return 1000 * ws + 100 * (a->co_t / 32) + 10 * bnb + m;
+}
+
+extern "C" int sc_conv3_variant(const sc_conv_args* a) {
+  return conv3_bx3_check(a) == SC_OK ? conv3_bx3_variant_of(a) : -1;
+}
+
+extern "C" int sc_conv3x3_bx3(const sc_conv_args* a, sc_stream stream) {
+  if (const int rc = conv3_bx3_check(a)) return rc;
+  const int C0 = a->src[0].C, C1 = a->nsrc == 2 ? a->src[1].C : 0;
   ConvXP p;
   p.s0 = to_srcd(a->src[0]);
   p.s1 = a->nsrc == 2 ? to_srcd(a->src[1]) : empty_srcd();
@@ -2771,8 +2804,6 @@ extern "C" int sc_conv3x3_bx3(const sc_conv_args* a, sc_stream stream) {
   p.out0 = a->out0; p.out1 = a->out1; p.csplit = a->csplit; p.accum0 = a->accum0; p.accum1 = a->accum1;
   p.add0 = a->add0; p.add1 = a->add1; p.stats = a->stats;
   p.down0 = a->down0 ? 1 : 0;
-  SC_REQUIRE(!p.down0 || (a->H % 2 == 0 && a->W % 2 == 0 && a->stats == nullptr && a->add0 == nullptr && a->add1 == nullptr),
-             "sc_conv3x3_bx3: down0 (2x2-summed half-resolution out0) needs even H, W and no stats/add tensors");
   const int co_tiles = (a->Cout + a->co_t - 1) / a->co_t;
   dim3 grid(((a->W + 31) / 32) * ((a->H + 7) / 8), co_tiles, a->N);
   constexpr int xcdmap_env = 2;   // XCD-aware 1-D numbering (0 = plain 3-D grid: 2.7x instead of 1.24x the algorithmic bytes)
@@ -2797,35 +2828,24 @@ extern "C" int sc_conv3x3_bx3(const sc_conv_args* a, sc_stream stream) {
     grid = dim3((unsigned)(pt8 * co_tiles));
   }
   hipStream_t st = (hipStream_t)stream;
-  const bool bnb = a->src[0].mode == SC_SRC_BNBWD;
-  SC_REQUIRE(a->terms >= 0 && a->terms <= 4, "sc_conv3x3_bx3: terms must be 0 (= 3), 1, 2, 3 or SC_TERMS_F16X2 (got %d)", a->terms);
   p.absmax = a->absmax; p.xb0 = a->xbound[0]; p.xb1 = a->xbound[1];
   set_bnr(p, a->bnr);
-  if (a->bnr) {
-    SC_REQUIRE(bnb && a->bnr->y && a->bnr->cst && a->bnr->rows, "sc_conv3x3_bx3: bnr needs a BNBWD source and y / cst / rows");
-    SC_REQUIRE(!a->accum0 && !a->add0 && !a->add1 && !a->stats, "sc_conv3x3_bx3: bnr: out0 must receive the complete gradient (no accum0 / add / stats)");
-    SC_REQUIRE(a->csplit == a->Cout || a->csplit % a->co_t == 0, "sc_conv3x3_bx3: bnr: csplit must fall on a cout-tile boundary");
+#define SC_BX3_CASE(Q, B, M, NT, HF) \
+  case 100 * Q + 10 * B + M: hipLaunchKernelGGL((k_conv3_bx3<Q, B != 0, NT, HF>), grid, dim3(256), 0, st, p); break;
+#define SC_BX3_CASES(M, NT, HF) SC_BX3_CASE(1, 0, M, NT, HF) SC_BX3_CASE(1, 1, M, NT, HF) SC_BX3_CASE(2, 0, M, NT, HF) SC_BX3_CASE(2, 1, M, NT, HF)
+#define SC_BX3_WS_CASE(Q, B) \
+  case 1000 + 100 * Q + 10 * B + 4: hipLaunchKernelGGL((k_conv3_ws<Q, B != 0>), grid, dim3(512), 0, st, p); break;
+  switch (conv3_bx3_variant_of(a)) {
+    SC_BX3_CASES(1, 1, false)
+    SC_BX3_CASES(2, 2, false)
+    SC_BX3_CASES(3, 3, false)
+    SC_BX3_CASES(4, 2, true)
+    SC_BX3_WS_CASE(1, 0) SC_BX3_WS_CASE(1, 1) SC_BX3_WS_CASE(2, 0) SC_BX3_WS_CASE(2, 1)
+    default: SC_REQUIRE(false, "sc_conv3x3_bx3: no kernel for variant %d", conv3_bx3_variant_of(a));
   }
-#define SC_LAUNCH_BX3(NT, HF)                                                                                  \
-  do {                                                                                                         \
-    if (a->co_t == 64 && bnb) hipLaunchKernelGGL((k_conv3_bx3<2, true, NT, HF>), grid, dim3(256), 0, st, p);   \
-    else if (a->co_t == 64) hipLaunchKernelGGL((k_conv3_bx3<2, false, NT, HF>), grid, dim3(256), 0, st, p);    \
-    else if (bnb) hipLaunchKernelGGL((k_conv3_bx3<1, true, NT, HF>), grid, dim3(256), 0, st, p);               \
-    else hipLaunchKernelGGL((k_conv3_bx3<1, false, NT, HF>), grid, dim3(256), 0, st, p);                       \
-  } while (0)
-  constexpr int ws_env = 1;
-  static const int ws_env_min = [] { const char* e = getenv("STARCOP_BX3_WS_MINCHUNKS"); return e ? atoi(e) : 16; }();
-  if (a->terms == 1) SC_LAUNCH_BX3(1, false); else if (a->terms == 2) SC_LAUNCH_BX3(2, false);
-  // the wave-specialised kernel pays for its 8-wave work-groups (prologue / epilogue of only two per CU) on short K loops:
-  // measured faster from 16 chunks of 16 input channels up (decoder.blocks.0), level at 8-10, slower below
-  else if (a->terms == SC_TERMS_F16X2 && ws_env && (C0 + C1 + 15) / 16 >= ws_env_min && (!bnb || a->src[0].C <= 256) && !a->bnr) {
-    if (a->co_t == 64 && bnb) hipLaunchKernelGGL((k_conv3_ws<2, true>), grid, dim3(512), 0, st, p);
-    else if (a->co_t == 64) hipLaunchKernelGGL((k_conv3_ws<2, false>), grid, dim3(512), 0, st, p);
-    else if (bnb) hipLaunchKernelGGL((k_conv3_ws<1, true>), grid, dim3(512), 0, st, p);
-    else hipLaunchKernelGGL((k_conv3_ws<1, false>), grid, dim3(512), 0, st, p);
-  }
-  else if (a->terms == SC_TERMS_F16X2) SC_LAUNCH_BX3(2, true); else SC_LAUNCH_BX3(3, false);
-#undef SC_LAUNCH_BX3
+#undef SC_BX3_WS_CASE
+#undef SC_BX3_CASES
+#undef SC_BX3_CASE
   SC_LAUNCH_OK("sc_conv3x3_bx3");
   return SC_OK;
 }
@@ -2847,7 +2867,8 @@ extern "C" size_t sc_wgrad_bx3_workspace_floats(int N, int H, int W, int Cout, i
   return a > b ? a : b;
 }
 
-extern "C" int sc_conv3x3_wgrad_bx3(const sc_wgrad_args* a, sc_stream stream) {
+// argument checks of sc_conv3x3_wgrad_bx3, shared with its host query (the workspace size is the launcher's own check)
+static int wgrad3_bx3_check(const sc_wgrad_args* a) {
   SC_REQUIRE(a != nullptr, "sc_conv3x3_wgrad_bx3: null args");
   SC_REQUIRE(a->ks == 3, "sc_conv3x3_wgrad_bx3: ks must be 3");
   SC_REQUIRE(a->nsrc == 1 || a->nsrc == 2, "sc_conv3x3_wgrad_bx3: nsrc must be 1 or 2");
@@ -2861,6 +2882,13 @@ extern "C" int sc_conv3x3_wgrad_bx3(const sc_wgrad_args* a, sc_stream stream) {
     SC_REQUIRE(a->src[s].mode == SC_SRC_RAW || a->src[s].mode == SC_SRC_AFFINE, "sc_conv3x3_wgrad_bx3: input sources must be RAW or AFFINE");
     SC_REQUIRE(a->src[s].up == 0 || (a->src[s].up == 1 && a->H % 2 == 0 && a->W % 2 == 0), "sc_conv3x3_wgrad_bx3: upsampled source needs even H,W");
   }
+  SC_REQUIRE(a->terms >= 0 && a->terms <= 4, "sc_conv3x3_wgrad_bx3: terms must be 0 (= 3), 1, 2, 3 or SC_TERMS_F16X2 (got %d)", a->terms);
+  return SC_OK;
+}
+
+// Which k_wgrad3_bx3 instantiation sc_conv3x3_wgrad_bx3 launches for checked arguments, and its plan: 10000 * PIPE + 1000 * M (1, 2, 3
+// bf16 terms or 4 = two fp16 terms) + 100 * WM + 10 * NCI + (the kernel sums its K parts itself, so that sc_wgrad_finish sees nsl rows).
+static int wgrad3_bx3_variant_of(const sc_wgrad_args* a, WgradXPlan* plan) {
   static const bool no96 = [] { const char* e = getenv("STARCOP_WGRAD96"); return e && atoi(e) == 0; }();      // (same-box A/B)
   constexpr int pipe_env = 1;      // one-barrier refill pipeline (0 = the two-barrier stages it replaced: 1.89 vs 1.63 ms per step)
   // the pipelined variant: BatchNorm-backward gradients, 8-byte gradient loads (even W), 32-bit byte offsets within a tensor
@@ -2868,6 +2896,19 @@ extern "C" int sc_conv3x3_wgrad_bx3(const sc_wgrad_args* a, sc_stream stream) {
               (size_t)a->Cout * a->H * a->W * 4 < (1ull << 32);
   for (int s = 0; s < a->nsrc; ++s) pipe = pipe && (size_t)a->N * a->src[s].C * (a->H >> a->src[s].up) * (a->W >> a->src[s].up) * 4 < (1ull << 32);
   const WgradXPlan pl = plan_wgrad_bx3(a->N, a->H, a->W, a->Cout, a->Cin, pipe && !no96);      // (the 96-wide tile: pipelined kernel only)
+  if (plan) *plan = pl;
+  const int m = a->terms == SC_TERMS_F16X2 ? 4 : (a->terms == 1 || a->terms == 2 ? a->terms : 3);
+  return 10000 * (pipe ? 1 : 0) + 1000 * m + 100 * pl.wm + 10 * pl.nci + (pipe && wgrad3_pipe_reduces(pl) ? 1 : 0);
+}
+
+extern "C" int sc_wgrad3_variant(const sc_wgrad_args* a) {
+  return wgrad3_bx3_check(a) == SC_OK ? wgrad3_bx3_variant_of(a, nullptr) : -1;
+}
+
+extern "C" int sc_conv3x3_wgrad_bx3(const sc_wgrad_args* a, sc_stream stream) {
+  if (const int rc = wgrad3_bx3_check(a)) return rc;
+  WgradXPlan pl;
+  const int variant = wgrad3_bx3_variant_of(a, &pl);
   const size_t need = sc_wgrad_bx3_workspace_floats(a->N, a->H, a->W, a->Cout, a->Cin);
   SC_REQUIRE(a->part_floats >= need, "sc_conv3x3_wgrad_bx3: workspace too small (%zu < %zu floats)", a->part_floats, need);
   WgradXP p;
@@ -2876,24 +2917,22 @@ extern "C" int sc_conv3x3_wgrad_bx3(const sc_wgrad_args* a, sc_stream stream) {
   p.nsl = pl.nsl; p.CoP = pl.CoP; p.CiP = pl.CiP;
   dim3 grid(pl.nsl, pl.ci_tiles, pl.co_tiles);
   hipStream_t st = (hipStream_t)stream;
-  SC_REQUIRE(a->terms >= 0 && a->terms <= 4, "sc_conv3x3_wgrad_bx3: terms must be 0 (= 3), 1, 2, 3 or SC_TERMS_F16X2 (got %d)", a->terms);
   p.absmax = a->absmax; p.xb0 = a->xbound[0]; p.xb1 = a->xbound[1];
-  int nparts = pl.nsl * pl.kp;          // (the pipelined variant sums its K parts in the kernel: pl.nsl)
-#define SC_WGX(WM_, NT_, NCI_, HF_, PIPE_) hipLaunchKernelGGL((k_wgrad3_bx3<WM_, NT_, NCI_, HF_, PIPE_>), grid, dim3(768), 0, st, p)
-#define SC_WGX_NT(NT_, HF_, PIPE_)                                   \
-  do {                                                               \
-    if constexpr (HF_ && PIPE_) { if (pl.nci == 3) { SC_WGX(1, NT_, 3, HF_, PIPE_); break; } }      \
-    if (pl.wm == 2 && pl.nci == 2) SC_WGX(2, NT_, 2, HF_, PIPE_);    \
-    else if (pl.wm == 2) SC_WGX(2, NT_, 1, HF_, PIPE_);              \
-    else if (pl.nci == 2) SC_WGX(1, NT_, 2, HF_, PIPE_);             \
-    else SC_WGX(1, NT_, 1, HF_, PIPE_);                              \
-  } while (0)
-  if (a->terms == 1) SC_WGX_NT(1, false, false); else if (a->terms == 2) SC_WGX_NT(2, false, false);
-  else if (a->terms == SC_TERMS_F16X2) {
-    if (pipe) { SC_WGX_NT(2, true, true); if (wgrad3_pipe_reduces(pl)) nparts = pl.nsl; } else SC_WGX_NT(2, true, false);
+  const int nparts = variant % 10 ? pl.nsl : pl.nsl * pl.kp;          // (last digit: the pipelined kernel summed its K parts itself)
+#define SC_WGX(PIPE_, M_, WM_, NCI_, NT_, HF_) \
+  case 1000 * PIPE_ + 100 * M_ + 10 * WM_ + NCI_: hipLaunchKernelGGL((k_wgrad3_bx3<WM_, NT_, NCI_, HF_, PIPE_ != 0>), grid, dim3(768), 0, st, p); break;
+#define SC_WGX_TILES(PIPE_, M_, NT_, HF_) \
+  SC_WGX(PIPE_, M_, 1, 1, NT_, HF_) SC_WGX(PIPE_, M_, 1, 2, NT_, HF_) SC_WGX(PIPE_, M_, 2, 1, NT_, HF_) SC_WGX(PIPE_, M_, 2, 2, NT_, HF_)
+  switch (variant / 10) {
+    SC_WGX_TILES(0, 1, 1, false)
+    SC_WGX_TILES(0, 2, 2, false)
+    SC_WGX_TILES(0, 3, 3, false)
+    SC_WGX_TILES(0, 4, 2, true)
+    SC_WGX_TILES(1, 4, 2, true)
+    SC_WGX(1, 4, 1, 3, 2, true)
+    default: SC_REQUIRE(false, "sc_conv3x3_wgrad_bx3: no kernel for variant %d", variant);
   }
-  else SC_WGX_NT(3, false, false);
-#undef SC_WGX_NT
+#undef SC_WGX_TILES
 #undef SC_WGX
   SC_LAUNCH_OK("sc_conv3x3_wgrad_bx3");
   return sc_wgrad_finish(a->part, nparts, 9, a->Cout, a->Cin, pl.CoP, pl.CiP, a->dw, st);
@@ -2912,7 +2951,8 @@ extern "C" size_t sc_wgrad_thin16_workspace_floats(int N, int H, int W, int Cout
   return (size_t)nparts * E + sc_reduce_scratch_floats(nparts, E);
 }
 
-extern "C" int sc_conv3x3_wgrad_thin16(const sc_wgrad_args* a, sc_stream stream) {
+// argument checks of sc_conv3x3_wgrad_thin16, shared with its host query (the workspace size is the launcher's own check)
+static int wgrad_thin16_check(const sc_wgrad_args* a) {
   SC_REQUIRE(a != nullptr && a->ks == 3 && a->nsrc == 1, "sc_conv3x3_wgrad_thin16: one source, ks = 3");
   SC_REQUIRE(a->Cout >= 1 && a->Cout <= 16 && (a->Cin == 16 || a->Cin == 32) && a->src[0].C == a->Cin && a->dy.C == a->Cout,
              "sc_conv3x3_wgrad_thin16: needs <= 16 output and 16 or 32 input channels (got %d, %d)", a->Cout, a->Cin);
@@ -2926,6 +2966,21 @@ extern "C" int sc_conv3x3_wgrad_thin16(const sc_wgrad_args* a, sc_stream stream)
   SC_REQUIRE((size_t)a->Cout * a->H * a->W * 4 < (1ull << 32) && (size_t)a->N * a->Cin * a->H * a->W * 4 < (1ull << 32),
              "sc_conv3x3_wgrad_thin16: tensors too large for 32-bit byte offsets");
   SC_REQUIRE(a->W % 2 == 0 && (((uintptr_t)a->dy.x | (uintptr_t)a->dy.aux) & 7) == 0, "sc_conv3x3_wgrad_thin16: needs an even width and 8-byte aligned gradient tensors");
+  return SC_OK;
+}
+
+// Which k_wgrad_thin_h instantiation sc_conv3x3_wgrad_thin16 launches for checked arguments: 100 * (Cin / 16) + 10 * (BNBWD dy)
+static int wgrad_thin16_variant_of(const sc_wgrad_args* a) {
+  return 100 * (a->Cin / 16) + 10 * (a->dy.mode == SC_SRC_BNBWD ? 1 : 0);
+}
+
+extern "C" int sc_wgrad_thin16_variant(const sc_wgrad_args* a) {
+  return wgrad_thin16_check(a) == SC_OK ? wgrad_thin16_variant_of(a) : -1;
+}
+
+extern "C" int sc_conv3x3_wgrad_thin16(const sc_wgrad_args* a, sc_stream stream) {
+  if (const int rc = wgrad_thin16_check(a)) return rc;
+  const sc_src& s = a->src[0];
   const size_t need = sc_wgrad_thin16_workspace_floats(a->N, a->H, a->W, a->Cout, a->Cin);
   SC_REQUIRE(a->part_floats >= need, "sc_conv3x3_wgrad_thin16: workspace too small (%zu < %zu floats)", a->part_floats, need);
   WgradXP p;
@@ -2934,10 +2989,14 @@ extern "C" int sc_conv3x3_wgrad_thin16(const sc_wgrad_args* a, sc_stream stream)
   p.N = a->N; p.H = a->H; p.W = a->W; p.Cout = a->Cout; p.Cin = a->Cin; p.part = a->part;
   p.nsl = wgrad_thin16_slices(a->N, a->H, a->W, a->Cin); p.CoP = 16; p.CiP = a->Cin;
   hipStream_t st = (hipStream_t)stream;
-  const bool bnb = a->dy.mode == SC_SRC_BNBWD;
   dim3 grid(p.nsl);
-  if (a->Cin == 16) { if (bnb) hipLaunchKernelGGL((k_wgrad_thin_h<16, true>), grid, dim3(256), 0, st, p); else hipLaunchKernelGGL((k_wgrad_thin_h<16, false>), grid, dim3(256), 0, st, p); }
-  else              { if (bnb) hipLaunchKernelGGL((k_wgrad_thin_h<32, true>), grid, dim3(256), 0, st, p); else hipLaunchKernelGGL((k_wgrad_thin_h<32, false>), grid, dim3(256), 0, st, p); }
+  switch (wgrad_thin16_variant_of(a)) {
+    case 100: hipLaunchKernelGGL((k_wgrad_thin_h<16, false>), grid, dim3(256), 0, st, p); break;
+    case 110: hipLaunchKernelGGL((k_wgrad_thin_h<16, true>), grid, dim3(256), 0, st, p); break;
+    case 200: hipLaunchKernelGGL((k_wgrad_thin_h<32, false>), grid, dim3(256), 0, st, p); break;
+    case 210: hipLaunchKernelGGL((k_wgrad_thin_h<32, true>), grid, dim3(256), 0, st, p); break;
+    default: SC_REQUIRE(false, "sc_conv3x3_wgrad_thin16: no kernel for variant %d", wgrad_thin16_variant_of(a));
+  }
   SC_LAUNCH_OK("sc_conv3x3_wgrad_thin16");
   return sc_wgrad_finish(a->part, p.nsl, 9, a->Cout, a->Cin, 16, a->Cin, a->dw, st);
 }
@@ -2970,19 +3029,61 @@ extern "C" int sc_pack_weights_thin16(const float* w, float* wpk, int Cout, int 
   return SC_OK;
 }
 
-extern "C" int sc_conv3x3_thin16(const sc_conv_args* a, sc_stream stream) {
+// argument checks of sc_conv3x3_thin16, shared with its host query
+static int thin16_check(const sc_conv_args* a) {
   SC_REQUIRE(a != nullptr && a->ks == 3 && a->nsrc == 1, "sc_conv3x3_thin16: one source, ks = 3");
   const int Cin = a->src[0].C;
+  const sc_src& s = a->src[0];
   if (a->down0) {
-    // the data gradient of a 32 -> 16 channel layer whose source was up-sampled: 32 rows from 16 gradient channels, stored 2x2-summed
-    // at half resolution (k_conv3_thin_spd; filters: sc_pack_weights_thin16(Cout = 16, Cin = 32, transpose_flip = 1))
-    const sc_src& s = a->src[0];
     SC_REQUIRE(Cin == 16 && a->Cout == 32 && a->csplit == 32 && s.mode == SC_SRC_BNBWD && s.aux && s.cst && s.up == 0,
                "sc_conv3x3_thin16(down0): needs a 16-channel BatchNorm-backward source and 32 output channels (got %d, %d)", Cin, a->Cout);
     SC_REQUIRE(a->H % 2 == 0 && a->W % 2 == 0 && a->N > 0 && a->N <= 65535 && a->out0 && !a->add0 && !a->add1 && !a->stats && !a->bnr && !a->out1,
                "sc_conv3x3_thin16(down0): even H, W; one output, no add / statistics / bnr epilogue");
     SC_REQUIRE(a->terms == SC_TERMS_F16X2 && ((uintptr_t)a->wpk & 15) == 0, "sc_conv3x3_thin16(down0): terms must be SC_TERMS_F16X2, filters 16-byte aligned");
     SC_REQUIRE((size_t)16 * a->H * a->W < ((size_t)1 << 30), "sc_conv3x3_thin16(down0): one image of the gradient must stay below 2^30 elements");
+    return SC_OK;
+  }
+  SC_REQUIRE(a->Cout >= 1 && a->Cout <= 16 && (Cin == 16 || Cin == 32), "sc_conv3x3_thin16: needs <= 16 output and 16 or 32 input channels (got %d, %d)",
+             a->Cout, Cin);
+  SC_REQUIRE(a->N > 0 && a->N <= 65535 && a->H > 0 && a->W > 0, "sc_conv3x3_thin16: bad shape");
+  SC_REQUIRE(a->csplit == a->Cout && !a->accum0 && !a->add0 && !a->add1 && !a->down0 && a->out0,
+             "sc_conv3x3_thin16: a single plain output only (no split / add / accumulate / down-sum epilogue)");
+  SC_REQUIRE(a->terms == SC_TERMS_F16X2, "sc_conv3x3_thin16: terms must be SC_TERMS_F16X2");
+  SC_REQUIRE(((uintptr_t)a->wpk & 15) == 0, "sc_conv3x3_thin16: packed filters must be 16-byte aligned");
+  SC_REQUIRE(s.up == 0 || (s.up == 1 && a->H % 2 == 0 && a->W % 2 == 0), "sc_conv3x3_thin16: upsampled source needs even H, W");
+  SC_REQUIRE(s.mode == SC_SRC_RAW || s.cst != nullptr, "sc_conv3x3_thin16: source needs constants");
+  SC_REQUIRE(s.mode != SC_SRC_NORM && (s.mode != SC_SRC_BNBWD || s.aux != nullptr), "sc_conv3x3_thin16: unsupported source");
+  SC_REQUIRE((size_t)a->Cout * a->H * a->W < ((size_t)1 << 30), "sc_conv3x3_thin16: one image of the output must stay below 2^30 elements");
+  SC_REQUIRE(!a->bnr || (s.mode == SC_SRC_BNBWD && a->bnr->y && a->bnr->cst && a->bnr->rows && !a->stats),
+             "sc_conv3x3_thin16: bnr needs a BNBWD source, y / cst / rows and no stats");
+  return SC_OK;
+}
+
+// Which kernel sc_conv3x3_thin16 launches for checked arguments: 1000 * K + 100 * (source channels / 16) + 10 * (BNBWD source) + UPS,
+// K = 0: k_conv3_thin_h<CIN, BNB, UPS>, 1: k_conv3_thin_sp (the sub-pixel form of an up-sampled 32-channel source), 2: k_conv3_thin_spd
+// (down0: the half-resolution data gradient)
+static int thin16_variant_of(const sc_conv_args* a) {
+  const sc_src& s = a->src[0];
+  if (a->down0) return 2110;
+  static const bool sp_off = [] { const char* e = getenv("STARCOP_THIN_SP"); return e && atoi(e) == 0; }();       // (same-box A/B)
+  static const bool ups_off = [] { const char* e = getenv("STARCOP_THIN_UPS"); return e && atoi(e) == 0; }();      // (same-box A/B)
+  const bool bnb = s.mode == SC_SRC_BNBWD;
+  if (s.C == 32 && s.up == 1 && !bnb && !sp_off) return 1200;      // the sub-pixel form (k_conv3_thin_sp)
+  return 100 * (s.C / 16) + 10 * (bnb ? 1 : 0) + (s.C == 32 && s.up == 1 && !bnb && !ups_off ? 1 : 0);
+}
+
+extern "C" int sc_thin16_variant(const sc_conv_args* a) {
+  return thin16_check(a) == SC_OK ? thin16_variant_of(a) : -1;
+}
+
+extern "C" int sc_conv3x3_thin16(const sc_conv_args* a, sc_stream stream) {
+  if (const int rc = thin16_check(a)) return rc;
+  const int Cin = a->src[0].C;
+  const sc_src& s = a->src[0];
+  const int variant = thin16_variant_of(a);
+  if (variant == 2110) {
+    // the data gradient of a 32 -> 16 channel layer whose source was up-sampled: 32 rows from 16 gradient channels, stored 2x2-summed
+    // at half resolution (k_conv3_thin_spd; filters: sc_pack_weights_thin16(Cout = 16, Cin = 32, transpose_flip = 1))
     ConvXP p{};
     p.s0 = to_srcd(s); p.s1 = empty_srcd();
     p.wpk = reinterpret_cast<const uintx4*>(a->wpk); p.N = a->N; p.H = a->H; p.W = a->W; p.Cout = a->Cout;
@@ -2994,28 +3095,12 @@ extern "C" int sc_conv3x3_thin16(const sc_conv_args* a, sc_stream stream) {
     SC_LAUNCH_OK("sc_conv3x3_thin16(down0)");
     return SC_OK;
   }
-  SC_REQUIRE(a->Cout >= 1 && a->Cout <= 16 && (Cin == 16 || Cin == 32), "sc_conv3x3_thin16: needs <= 16 output and 16 or 32 input channels (got %d, %d)",
-             a->Cout, Cin);
-  SC_REQUIRE(a->N > 0 && a->N <= 65535 && a->H > 0 && a->W > 0, "sc_conv3x3_thin16: bad shape");
-  SC_REQUIRE(a->csplit == a->Cout && !a->accum0 && !a->add0 && !a->add1 && !a->down0 && a->out0,
-             "sc_conv3x3_thin16: a single plain output only (no split / add / accumulate / down-sum epilogue)");
-  SC_REQUIRE(a->terms == SC_TERMS_F16X2, "sc_conv3x3_thin16: terms must be SC_TERMS_F16X2");
-  SC_REQUIRE(((uintptr_t)a->wpk & 15) == 0, "sc_conv3x3_thin16: packed filters must be 16-byte aligned");
-  const sc_src& s = a->src[0];
-  SC_REQUIRE(s.up == 0 || (s.up == 1 && a->H % 2 == 0 && a->W % 2 == 0), "sc_conv3x3_thin16: upsampled source needs even H, W");
-  SC_REQUIRE(s.mode == SC_SRC_RAW || s.cst != nullptr, "sc_conv3x3_thin16: source needs constants");
-  SC_REQUIRE(s.mode != SC_SRC_NORM && (s.mode != SC_SRC_BNBWD || s.aux != nullptr), "sc_conv3x3_thin16: unsupported source");
-  SC_REQUIRE((size_t)a->Cout * a->H * a->W < ((size_t)1 << 30), "sc_conv3x3_thin16: one image of the output must stay below 2^30 elements");
   ConvXP p{};
   p.s0 = to_srcd(s); p.s1 = empty_srcd();
   p.wpk = reinterpret_cast<const uintx4*>(a->wpk); p.N = a->N; p.H = a->H; p.W = a->W; p.Cout = a->Cout;
   p.out0 = a->out0; p.csplit = a->Cout; p.stats = a->stats; p.absmax = a->absmax; p.xb0 = a->xbound[0]; p.xb1 = a->xbound[1];
   set_bnr(p, a->bnr);
-  SC_REQUIRE(!a->bnr || (s.mode == SC_SRC_BNBWD && a->bnr->y && a->bnr->cst && a->bnr->rows && !a->stats),
-             "sc_conv3x3_thin16: bnr needs a BNBWD source, y / cst / rows and no stats");
-  static const bool sp_off = [] { const char* e = getenv("STARCOP_THIN_SP"); return e && atoi(e) == 0; }();       // (same-box A/B)
-  const bool thin_sp = Cin == 32 && s.up == 1 && s.mode != SC_SRC_BNBWD && !sp_off;      // the sub-pixel form (k_conv3_thin_sp)
-  const int tw = (Cin == 16 || thin_sp) ? 64 : 32;        // (k_conv3_thin_h: TW)
+  const int tw = (Cin == 16 || variant == 1200) ? 64 : 32;        // (k_conv3_thin_h: TW)
   dim3 grid(((a->W + tw - 1) / tw) * ((a->H + 7) / 8), 1, a->N);
   constexpr int xcdmap_env = 2;
   p.xcdmap = xcdmap_env ? 2 : 0;
@@ -3024,12 +3109,15 @@ extern "C" int sc_conv3x3_thin16(const sc_conv_args* a, sc_stream stream) {
     grid = dim3((unsigned)(per_xcd * 8));
   }
   hipStream_t st = (hipStream_t)stream;
-  const bool bnb = s.mode == SC_SRC_BNBWD;
-  static const bool ups_off = [] { const char* e = getenv("STARCOP_THIN_UPS"); return e && atoi(e) == 0; }();      // (same-box A/B)
-  if (thin_sp) hipLaunchKernelGGL(k_conv3_thin_sp, grid, dim3(256), 0, st, p);
-  else if (Cin == 16) { if (bnb) hipLaunchKernelGGL((k_conv3_thin_h<16, true>), grid, dim3(256), 0, st, p); else hipLaunchKernelGGL((k_conv3_thin_h<16, false>), grid, dim3(256), 0, st, p); }
-  else if (s.up == 1 && !bnb && !ups_off) hipLaunchKernelGGL((k_conv3_thin_h<32, false, true>), grid, dim3(256), 0, st, p);
-  else           { if (bnb) hipLaunchKernelGGL((k_conv3_thin_h<32, true>), grid, dim3(256), 0, st, p); else hipLaunchKernelGGL((k_conv3_thin_h<32, false>), grid, dim3(256), 0, st, p); }
+  switch (variant) {
+    case 1200: hipLaunchKernelGGL(k_conv3_thin_sp, grid, dim3(256), 0, st, p); break;
+    case 100: hipLaunchKernelGGL((k_conv3_thin_h<16, false>), grid, dim3(256), 0, st, p); break;
+    case 110: hipLaunchKernelGGL((k_conv3_thin_h<16, true>), grid, dim3(256), 0, st, p); break;
+    case 201: hipLaunchKernelGGL((k_conv3_thin_h<32, false, true>), grid, dim3(256), 0, st, p); break;
+    case 200: hipLaunchKernelGGL((k_conv3_thin_h<32, false>), grid, dim3(256), 0, st, p); break;
+    case 210: hipLaunchKernelGGL((k_conv3_thin_h<32, true>), grid, dim3(256), 0, st, p); break;
+    default: SC_REQUIRE(false, "sc_conv3x3_thin16: no kernel for variant %d", variant);
+  }
   SC_LAUNCH_OK("sc_conv3x3_thin16");
   return SC_OK;
 }
