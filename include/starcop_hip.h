@@ -268,6 +268,19 @@ int sc_conv3x3_sp_dgrad(const sc_conv_args* a, sc_stream stream);
 size_t sc_sp_wgrad_workspace_bytes(int N, int H, int W, int Cout, int Cup);
 int sc_conv3x3_sp_wgrad(const sc_wgrad_args* a, void* ws, size_t ws_bytes, sc_stream stream);
 int sc_wgrad_scatter_cols(const float* src, float* dw, int Cout, int Ccols, int CinTotal, int col_off, sc_stream stream);
+/* HOST queries (no GPU work): which kernel instantiation the three sub-pixel entry points launch for these arguments, with
+ * STARCOP_SP_NPP applied; -1 for arguments the entry point rejects (the reason is left in sc_last_error).  Pointers are only tested
+ * for NULL and alignment; the workspace of the weight gradient is not looked at.  The entry points dispatch on these values.
+ *   sc_sp_variant (sc_conv3x3_sp):  100 * (TW / 16) + 10 * NPP + M for k_conv3_sp<TW, M == 1, NPP> -- TW = 32 from 32 low-resolution
+ *     columns, else 16; NPP = 2 (256-pixel tiles) when N x the 256-pixel tiles x the 32-channel output tiles exceed 128 work-groups,
+ *     else 1 (sc_sp_stat_rows counts the tiles of the same NPP); M = 4: two fp16 terms, 1: one bf16 term.  8 codes.
+ *   sc_spd_variant (sc_conv3x3_sp_dgrad):  1000 * skip_mode + the same code for k_conv3_spd<TW, M == 1, NPP>, its channel tiles being
+ *     ntu + nts (128 up-sampled channels each + in mode 2 32 skip channels each); skip_mode 0: no out1, 1: virtual skip channels
+ *     (sc_spd_vskip_ok), 2: skip tiles -- a run-time branch with its own store path and pack layout.  24 codes.
+ *   sc_sp_wgrad_variant (sc_conv3x3_sp_wgrad):  CB of k_spw_gemm<CB>: 2 above 64 up-sampled channels, else 1. */
+int sc_sp_variant(const sc_conv_args* a);
+int sc_spd_variant(const sc_conv_args* a);
+int sc_sp_wgrad_variant(const sc_wgrad_args* a);
 
 /* weight gradient of the same thin layers (Cout <= 16, Cin = 16 | 32, one source which may be upsampled) with two fp16 terms on
  * v_mfma_f32_16x16x32_f16: same sc_wgrad_args as sc_conv2d_wgrad_mfma with terms = SC_TERMS_F16X2 (absmax = the dy range hint),

@@ -719,7 +719,8 @@ extern "C" int sc_sp_stat_rows(int N, int H, int W, int Cout) {
   return N * ((Wl + TW - 1) / TW) * ((Hl + TH - 1) / TH);
 }
 
-extern "C" int sc_conv3x3_sp(const sc_conv_args* a, sc_stream stream) {
+// argument checks of sc_conv3x3_sp, shared with its host query
+static int conv3_sp_check(const sc_conv_args* a) {
   SC_REQUIRE(a != nullptr, "sc_conv3x3_sp: null args");
   SC_REQUIRE(a->ks == 3 && (a->nsrc == 1 || a->nsrc == 2), "sc_conv3x3_sp: ks = 3, one (up-sampled) or two (up-sampled, skip) sources");
   SC_REQUIRE(a->src[0].up == 1, "sc_conv3x3_sp: src[0] must be the half-resolution tensor (up = 1)");
@@ -736,6 +737,28 @@ extern "C" int sc_conv3x3_sp(const sc_conv_args* a, sc_stream stream) {
              "sc_conv3x3_sp: a single plain output");
   SC_REQUIRE(((uintptr_t)a->wpk & 15) == 0 && ((uintptr_t)a->out0 & 7) == 0, "sc_conv3x3_sp: alignment");
   SC_REQUIRE((size_t)32 * a->H * a->W < (1ull << 32), "sc_conv3x3_sp: plane too large");
+  return SC_OK;
+}
+
+// Which kernel the sub-pixel launchers start for a low-resolution plane, `ctiles` channel tiles and `terms`:
+// 100 * (TW / 16) + 10 * NPP + M for k_conv3_sp / k_conv3_spd<TW, M == 1, NPP>, M = 4 two fp16 terms, 1 one bf16 term
+static int sp_variant_code(int N, int Hl, int Wl, int ctiles, int terms) {
+  return 100 * (Wl >= 32 ? 2 : 1) + 10 * sp_groups_per_wave(N, Hl, Wl, ctiles) + (terms == 1 ? 1 : 4);
+}
+static int conv3_sp_variant_of(const sc_conv_args* a) { return sp_variant_code(a->N, a->H / 2, a->W / 2, (a->Cout + 31) / 32, a->terms); }
+
+extern "C" int sc_sp_variant(const sc_conv_args* a) {
+  return conv3_sp_check(a) == SC_OK ? conv3_sp_variant_of(a) : -1;
+}
+
+#define SC_SP_CASE(K, TW, NPP, M) \
+  case 100 * (TW / 16) + 10 * NPP + M: kern = K<TW, M == 1, NPP>; break;
+#define SC_SP_CASES(K) \
+  SC_SP_CASE(K, 16, 1, 1) SC_SP_CASE(K, 16, 1, 4) SC_SP_CASE(K, 16, 2, 1) SC_SP_CASE(K, 16, 2, 4) \
+  SC_SP_CASE(K, 32, 1, 1) SC_SP_CASE(K, 32, 1, 4) SC_SP_CASE(K, 32, 2, 1) SC_SP_CASE(K, 32, 2, 4)
+
+extern "C" int sc_conv3x3_sp(const sc_conv_args* a, sc_stream stream) {
+  if (const int rc = conv3_sp_check(a)) return rc;
   ConvSPP p;
   p.s0 = to_srcd(a->src[0]);
   p.s1 = a->nsrc == 2 ? to_srcd(a->src[1]) : p.s0;          // (C = 0 below: never selected, but its pointers stay valid)
@@ -747,15 +770,17 @@ extern "C" int sc_conv3x3_sp(const sc_conv_args* a, sc_stream stream) {
   p.N = a->N; p.Hl = a->H / 2; p.Wl = a->W / 2; p.Cout = a->Cout;
   p.out = a->out0; p.stats = a->stats;
   p.xb0 = a->xbound[0]; p.xb1 = a->nsrc == 2 ? a->xbound[1] : nullptr;
-  const int npp = sp_groups_per_wave(a->N, p.Hl, p.Wl, (a->Cout + 31) / 32);
-  const int TW = p.Wl >= 32 ? 32 : 16, TH = 128 * npp / TW;
+  const int variant = conv3_sp_variant_of(a);
+  const int TW = 16 * (variant / 100), TH = 128 * ((variant / 10) % 10) / TW;
   const long tiles = (long)((p.Wl + TW - 1) / TW) * ((p.Hl + TH - 1) / TH) * a->N;
   const long ncot = (a->Cout + 31) / 32;
   const long grid = (tiles + 7) / 8 * 8 * ncot;
   SC_REQUIRE(grid < (1L << 31), "sc_conv3x3_sp: grid too large");
-  const bool bf = a->terms == 1;
-  void (*const kern)(ConvSPP) = npp == 2 ? (!bf ? (TW == 32 ? k_conv3_sp<32, false> : k_conv3_sp<16, false>) : (TW == 32 ? k_conv3_sp<32, true> : k_conv3_sp<16, true>))
-                                       : (TW == 16 ? (!bf ? k_conv3_sp<16, false, 1> : k_conv3_sp<16, true, 1>) : (!bf ? k_conv3_sp<32, false, 1> : k_conv3_sp<32, true, 1>));
+  void (*kern)(ConvSPP) = nullptr;
+  switch (variant) {
+    SC_SP_CASES(k_conv3_sp)
+    default: SC_REQUIRE(false, "sc_conv3x3_sp: no kernel for variant %d", variant);
+  }
   const int lds = TW == 32 ? sp_smem_bytes<32>() : sp_smem_bytes<16>();
   if (int rc = sc_lds_limit(kern, lds, "sc_conv3x3_sp")) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, (hipStream_t)stream, p);
@@ -783,7 +808,8 @@ extern "C" int sc_pack_weights_spd(const float* w, float* wpk, int Cout, int Cin
   return SC_OK;
 }
 
-extern "C" int sc_conv3x3_sp_dgrad(const sc_conv_args* a, sc_stream stream) {
+// argument checks of sc_conv3x3_sp_dgrad, shared with its host query
+static int conv3_spd_check(const sc_conv_args* a) {
   SC_REQUIRE(a != nullptr, "sc_conv3x3_sp_dgrad: null args");
   SC_REQUIRE(a->ks == 3 && a->nsrc == 1, "sc_conv3x3_sp_dgrad: ks = 3, one source (the layer's output gradient)");
   SC_REQUIRE(a->src[0].mode == SC_SRC_BNBWD && a->src[0].aux != nullptr && a->src[0].cst != nullptr && a->src[0].up == 0,
@@ -796,28 +822,52 @@ extern "C" int sc_conv3x3_sp_dgrad(const sc_conv_args* a, sc_stream stream) {
   SC_REQUIRE((a->csplit == a->Cout) == (a->out1 == nullptr), "sc_conv3x3_sp_dgrad: out1 exactly when csplit < Cout");
   SC_REQUIRE(((uintptr_t)a->wpk & 15) == 0, "sc_conv3x3_sp_dgrad: alignment");
   SC_REQUIRE((size_t)128 * (a->H / 2) * (a->W / 2) < (1ull << 32) && (size_t)a->H * a->W < (1ull << 31), "sc_conv3x3_sp_dgrad: plane too large");
+  return SC_OK;
+}
+
+// the skip channels' gradient in the same launch: in the idle half of the one channel tile (vskip, 1) where that fits, else as skip
+// tiles (2); 0: no out1
+static int spd_skip_mode(const sc_conv_args* a) {
+  return a->out1 == nullptr ? 0 : (sc_spd_vskip_ok(a->csplit, a->Cout - a->csplit) ? 1 : 2);
+}
+static int spd_skip_tiles(const sc_conv_args* a) { return spd_skip_mode(a) == 2 ? (a->Cout - a->csplit + 31) / 32 : 0; }
+
+// 1000 * skip_mode + the code of sp_variant_code for the ntu + nts channel tiles of the launch
+static int conv3_spd_variant_of(const sc_conv_args* a) {
+  return 1000 * spd_skip_mode(a) + sp_variant_code(a->N, a->H / 2, a->W / 2, (a->csplit + 127) / 128 + spd_skip_tiles(a), a->terms);
+}
+
+extern "C" int sc_spd_variant(const sc_conv_args* a) {
+  return conv3_spd_check(a) == SC_OK ? conv3_spd_variant_of(a) : -1;
+}
+
+extern "C" int sc_conv3x3_sp_dgrad(const sc_conv_args* a, sc_stream stream) {
+  if (const int rc = conv3_spd_check(a)) return rc;
   ConvSPD p;
   p.dy = to_srcd(a->src[0]);
   p.wpk = reinterpret_cast<const uintx4*>(a->wpk);
   p.N = a->N; p.Hl = a->H / 2; p.Wl = a->W / 2; p.Cup = a->csplit;
   p.out = a->out0; p.accum = a->accum0; p.absmax = a->absmax;
   p.out_skip = a->out1; p.Cskip = a->Cout - a->csplit; p.accum_skip = a->accum1;
-  // the skip channels' gradient in the same launch: in the idle half of the one channel tile (vskip) where that fits, else as skip tiles
-  p.skip_mode = a->out1 == nullptr ? 0 : (sc_spd_vskip_ok(a->csplit, a->Cout - a->csplit) ? 1 : 2);
+  const int variant = conv3_spd_variant_of(a);
+  p.skip_mode = variant / 1000;
   p.ntu = (a->csplit + 127) / 128;
-  p.nts = p.skip_mode == 2 ? (p.Cskip + 31) / 32 : 0;
-  const int npp = sp_groups_per_wave(a->N, p.Hl, p.Wl, p.ntu + p.nts);
-  const int TW = p.Wl >= 32 ? 32 : 16, TH = 128 * npp / TW;
+  p.nts = spd_skip_tiles(a);
+  const int TW = 16 * ((variant / 100) % 10), TH = 128 * ((variant / 10) % 10) / TW;
   const long tiles = (long)((p.Wl + TW - 1) / TW) * ((p.Hl + TH - 1) / TH) * a->N;
   const long ncot = p.ntu + p.nts;
   const long grid = (tiles + 7) / 8 * 8 * ncot;
   SC_REQUIRE(grid < (1L << 31), "sc_conv3x3_sp_dgrad: grid too large");
-  const bool bf = a->terms == 1;
-  void (*const kern)(ConvSPD) = npp == 2 ? (!bf ? (TW == 32 ? k_conv3_spd<32, false> : k_conv3_spd<16, false>) : (TW == 32 ? k_conv3_spd<32, true> : k_conv3_spd<16, true>))
-                                       : (TW == 16 ? (!bf ? k_conv3_spd<16, false, 1> : k_conv3_spd<16, true, 1>) : (!bf ? k_conv3_spd<32, false, 1> : k_conv3_spd<32, true, 1>));
+  void (*kern)(ConvSPD) = nullptr;
+  switch (variant % 1000) {
+    SC_SP_CASES(k_conv3_spd)
+    default: SC_REQUIRE(false, "sc_conv3x3_sp_dgrad: no kernel for variant %d", variant);
+  }
   const int lds = TW == 32 ? sp_smem_bytes<32>() : sp_smem_bytes<16>();
   if (int rc = sc_lds_limit(kern, lds, "sc_conv3x3_sp_dgrad")) return rc;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), lds, (hipStream_t)stream, p);
   SC_LAUNCH_OK("sc_conv3x3_sp_dgrad");
   return SC_OK;
 }
+#undef SC_SP_CASES
+#undef SC_SP_CASE

@@ -303,8 +303,9 @@ extern "C" size_t sc_sp_wgrad_workspace_bytes(int N, int H, int W, int Cout, int
   return spw_plan(N, H, W, Cout, Cup).bytes;
 }
 
-extern "C" int sc_conv3x3_sp_wgrad(const sc_wgrad_args* a, void* ws, size_t ws_bytes, sc_stream stream) {
-  SC_REQUIRE(a != nullptr && ws != nullptr, "sc_conv3x3_sp_wgrad: null argument");
+// argument checks of sc_conv3x3_sp_wgrad (all but the workspace), shared with its host query
+static int sp_wgrad_check(const sc_wgrad_args* a) {
+  SC_REQUIRE(a != nullptr, "sc_conv3x3_sp_wgrad: null argument");
   SC_REQUIRE(a->ks == 3 && a->nsrc == 1 && a->src[0].up == 1, "sc_conv3x3_sp_wgrad: ks = 3, one source: the half-resolution tensor (up = 1)");
   SC_REQUIRE(a->src[0].mode == SC_SRC_RAW || a->src[0].mode == SC_SRC_AFFINE, "sc_conv3x3_sp_wgrad: the input source must be RAW or AFFINE");
   SC_REQUIRE(a->src[0].mode == SC_SRC_RAW || a->src[0].cst != nullptr, "sc_conv3x3_sp_wgrad: the input source needs constants");
@@ -314,6 +315,18 @@ extern "C" int sc_conv3x3_sp_wgrad(const sc_wgrad_args* a, void* ws, size_t ws_b
   const int Cup = a->src[0].C;
   SC_REQUIRE(Cup > 0 && Cup <= a->Cin, "sc_conv3x3_sp_wgrad: Cin is the filter's total input channel count (>= the source's %d)", Cup);
   SC_REQUIRE(a->terms == SC_TERMS_F16X2, "sc_conv3x3_sp_wgrad: two-fp16-term arithmetic only (terms = SC_TERMS_F16X2)");
+  return SC_OK;
+}
+
+// Which GEMM sc_conv3x3_sp_wgrad launches: CB of k_spw_gemm<CB>, the 64-column blocks per wave column (1 or 2)
+extern "C" int sc_sp_wgrad_variant(const sc_wgrad_args* a) {
+  return sp_wgrad_check(a) == SC_OK ? spw_plan(a->N, a->H, a->W, a->Cout, a->src[0].C).cb : -1;
+}
+
+extern "C" int sc_conv3x3_sp_wgrad(const sc_wgrad_args* a, void* ws, size_t ws_bytes, sc_stream stream) {
+  SC_REQUIRE(a != nullptr && ws != nullptr, "sc_conv3x3_sp_wgrad: null argument");
+  if (const int rc = sp_wgrad_check(a)) return rc;
+  const int Cup = a->src[0].C;
   SC_REQUIRE(((uintptr_t)ws & 255) == 0, "sc_conv3x3_sp_wgrad: workspace must be 256-byte aligned");
   const SpwPlan pl = spw_plan(a->N, a->H, a->W, a->Cout, Cup);
   SC_REQUIRE(ws_bytes >= pl.bytes, "sc_conv3x3_sp_wgrad: workspace too small (%zu < %zu bytes)", ws_bytes, pl.bytes);
@@ -348,9 +361,17 @@ extern "C" int sc_conv3x3_sp_wgrad(const sc_wgrad_args* a, void* ws, size_t ws_b
     p.M = pl.M; p.Nc = Cup; p.Mp = pl.Mp; p.Np = pl.Np; p.Kp = pl.Kp; p.kstages = pl.kstages;
     dim3 grid(pl.nsl, pl.mtiles, pl.ntiles);
     constexpr int lds2 = 2 * 2 * (256 + 128) * 5 * 16, lds1 = 2 * 2 * (256 + 64) * 5 * 16;
-    if (int rc = pl.cb == 2 ? sc_lds_limit(&k_spw_gemm<2>, lds2, "sc_conv3x3_sp_wgrad") : sc_lds_limit(&k_spw_gemm<1>, lds1, "sc_conv3x3_sp_wgrad")) return rc;
-    if (pl.cb == 2) hipLaunchKernelGGL((k_spw_gemm<2>), grid, dim3(512), lds2, st, p);
-    else hipLaunchKernelGGL((k_spw_gemm<1>), grid, dim3(512), lds1, st, p);
+    switch (pl.cb) {
+      case 1:
+        if (int rc = sc_lds_limit(&k_spw_gemm<1>, lds1, "sc_conv3x3_sp_wgrad")) return rc;
+        hipLaunchKernelGGL((k_spw_gemm<1>), grid, dim3(512), lds1, st, p);
+        break;
+      case 2:
+        if (int rc = sc_lds_limit(&k_spw_gemm<2>, lds2, "sc_conv3x3_sp_wgrad")) return rc;
+        hipLaunchKernelGGL((k_spw_gemm<2>), grid, dim3(512), lds2, st, p);
+        break;
+      default: SC_REQUIRE(false, "sc_conv3x3_sp_wgrad: no kernel for variant %d", pl.cb);
+    }
     SC_LAUNCH_OK("sc_conv3x3_sp_wgrad(gemm)");
   }
   {
