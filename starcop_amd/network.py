@@ -27,7 +27,7 @@ import torch.nn as nn
 
 from . import _lib, scene
 from ._lib import (ACT_NONE, ACT_RELU, ACT_RELU6, SC_CST, sc_irb_args, sc_irt_args, SRC_AFFINE, SRC_BNBWD, SRC_NORM, SRC_RAW, STAT_BNBWD, sc_wgrad_pending,
-                   PACK_PW3, PACK_SP, PACK_SPD, PACK_THIN16, STAT_PW3, STAT_CONV1, STAT_CONV1K, STAT_CONV3, STAT_DW, STAT_STEM, TERMS_F16X2, check, make_src, ptr, sc_bn_tail, sc_bnr_args,
+                   PACK_PW3, PACK_SP, PACK_SPD, PACK_THIN16, STAT_PW3, STAT_CONV1, STAT_CONV1K, STAT_CONV3, STAT_DW, STAT_STEM, TERMS_F16X2, check, make_src, ptr,
                    sc_conv_args, sc_wgrad_args, stream)
 
 MBV2_SETTINGS = ((1, 16, 1, 1), (6, 24, 2, 2), (6, 32, 3, 2), (6, 64, 4, 2),
@@ -104,10 +104,8 @@ class _T:
         self.res_grad = None        # 'fin' tensor z = self + ...: z.grad must be added to self.grad
 
 
-_BN_PRE = True      # coalesced pre-reduction of many-row BatchNorm statistics (sc_bn_finalize scratch)
 _COT_RATIO = 1.15      # 64-wide cout tiles when they pad the channel count by less than this factor (measured per layer)
 _COT_RATIO3 = 1.15     # the same choice for the 3x3 layers
-_HEAD_FUSED_BWD = True     # gin, dW and dbias of the head in one sweep (False: the separate data / weight gradient launches)
 
 
 def _pick_cot(M, ks=1):
@@ -134,10 +132,6 @@ def _pick_cot(M, ks=1):
 #   backward-weight  planes up to 32^2 of at most 32768 batch pixels, small filters (K*M bounds as measured at batch 16)
 # "1" = these rules, "all" = every pointwise launch (the tests run both), "0" = off.
 _PW3 = os.environ.get("STARCOP_PW3", "1")
-# 64 x 64 planes with a short contraction on the streaming kernel of sc_conv2d_mfma (k_pw_stream) instead of sc_conv1x1_pw3: the
-# features.5-.7 expansions forward 25-27 -> 21-22 us, the features.4-.6 projections' data gradients 23-30 -> 19-25 us at batch 16
-# (tools/bench_layers.py, same box); step level to +0.6 % (four alternating pairs).  "0": the round-5 rule
-_PWS64 = os.environ.get("STARCOP_PWS64", "1") == "1"
 
 
 def _use_pw3(which, N, HW, Cin, Cout):
@@ -149,9 +143,10 @@ def _use_pw3(which, N, HW, Cin, Cout):
         return True
     NP = N * HW
     npb = -(-NP // 32)
-    if _PWS64 and HW == 4096 and which in (0, 1):
-        # 64 x 64 planes with a short contraction (the features.5-.7 expansions forward, the features.4-.6 projections' data gradients):
-        # the streaming kernel inside sc_conv2d_mfma (k_pw_stream)
+    if HW == 4096 and which in (0, 1):
+        # 64 x 64 planes with a short contraction on the streaming kernel inside sc_conv2d_mfma (k_pw_stream) instead of sc_conv1x1_pw3:
+        # the features.5-.7 expansions forward 25-27 -> 21-22 us, the features.4-.6 projections' data gradients 23-30 -> 19-25 us at
+        # batch 16 (tools/bench_layers.py, same box); step level to +0.6 % (four alternating pairs)
         K_, M_ = (Cin, Cout) if which == 0 else (Cout, Cin)
         if K_ in (16, 24, 32) and M_ <= 192 and (which == 1 or K_ in (24, 32)):
             return False
@@ -213,49 +208,6 @@ def _use_irb(N, Cin, hidden, Cout, H, W, stride):
 # (16 output channels: half-empty MFMA rows) 196-213, level with sc_conv3x3_thin16's 202, stays there.  "1" = that rule, "all" =
 # every decoder conv1 (tests), "0" = off.
 _SP = os.environ.get("STARCOP_SP", "1")
-# BatchNorm-backward sums of a decoder tensor from the data-gradient launch that writes its gradient (sc_bnr_args) instead of the separate
-# sc_bn_bwd_reduce pass over (gradient, y).  Built, parity-tested and measured in round 5 (tools/bench_layers.py, batch 16, us): the pass it
-# removes streams at 5.3 TB/s, the extra read of y in a convolution epilogue runs at that kernel's 2.3-3 TB/s -- decoder.blocks.4.conv2
-# data gradient 197 -> 302 for a 120 -> 10 BatchNorm pass, blocks.3.conv2 134 -> 193 for 60 -> 10, blocks.4.conv1 (2x2 down-summed store,
-# every other lane idle) 244 -> 392 for 59 -> 13: the step loses 1 % (1444 / 1436 vs 1460 / 1454 tiles/s, same box, alternating).  OFF by
-# default; "1" enables it (tests/test_gpu_unet.py runs the network both ways).
-_BNR = os.environ.get("STARCOP_BNR", "0") == "1"
-# ... for the thin layer alone (decoder.blocks.4.conv2's data gradient leaves conv1's sums; y requested ahead of the MFMA phase since round 6)
-_BNR_THIN = os.environ.get("STARCOP_BNR_THIN", "0") == "1"
-_THIN_SPD = os.environ.get("STARCOP_THIN_SPD", "1") == "1"      # (same-box A/B of decoder.blocks.4.conv1's sub-pixel data gradient)
-# training steps pack the decoder's / the backward filter layouts on the weight-gradient stream, beside the encoder's forward ("0": on
-# the main stream, ahead of the forward -- A/B)
-_PACK_SIDE = os.environ.get("STARCOP_PACK_SIDE", "1") == "1"
-# depthwise layers finalize their own BatchNorm in the launch's tail (sc_dwconv3x3_fwd_bn: last arrival per channel by ticket) when a
-# channel has at most this many statistics rows (15 of the 17 depthwise layers at batch 16 have 16-32).  Built, parity-tested and
-# measured in round 5: with a device-scope fence before the ticket the step went 1460 -> 1060 tiles/s (every arriving work-group
-# writes back its XCD's L2); with write-through stores + a relaxed ticket it is correct and LEVEL (1470.0 / 1469.2 vs 1473.7 / 1472.4
-# same-box): every work-group now waits ~2-3 us for its ticket to come back from memory, which is what the 15 removed ~6 us launches
-# had cost.  0 = off (default): the separate sc_bn_finalize launch.
-_DW_TAIL_ROWS = int(os.environ.get("STARCOP_DW_TAIL_ROWS", "0"))
-_SP_SKIPTILES = os.environ.get("STARCOP_SP_SKIPTILES", "1") == "1"      # (same-box A/B of decoder.blocks.0's one-launch data gradient)
-
-
-def _experiment(name, default=""):
-    """Elimination experiments (STARCOP_EXP_*: launches skipped or bytes halved -- results WRONG, timing valid) are measuring tools, not
-    product switches: a stray variable must not silently skip weight gradients.  They are honoured only together with
-    STARCOP_EXPERIMENT_OK=1 (tools/ab_*.sh set it); without it the import fails, with it every active one is announced once."""
-    v = os.environ.get(name, default)
-    if v not in ("", "0"):
-        if os.environ.get("STARCOP_EXPERIMENT_OK") != "1":
-            raise RuntimeError(f"{name}={v} is an elimination experiment (wrong results by design); set STARCOP_EXPERIMENT_OK=1 to run it")
-        import warnings
-        warnings.warn(f"starcop_amd: elimination experiment {name}={v} is ACTIVE -- results of this process are wrong by design")
-    return v
-
-
-_EXP_NO_WGRAD = _experiment("STARCOP_EXP_NO_WGRAD", "0") == "1"
-# elimination experiment (results WRONG after the first steps, timing valid): skip the BatchNorm finalize launches of the training forward
-# ("f"), of the backward ("b") or both ("fb") from the fourth step of a plan on -- what the ~93 dependent ~5 us launches cost the step
-_EXP_NO_BNFIN = _experiment("STARCOP_EXP_NO_BNFIN", "")
-_EXP_SIDE2 = _experiment("STARCOP_EXP_SIDE2", "0") == "1"      # tools/: elimination experiment only
-
-
 _SP_TERMS = (TERMS_F16X2, 1)      # arithmetic modes of the sub-pixel forward / data-gradient kernels (conv_sp.hip)
 
 
@@ -287,7 +239,7 @@ def _use_spd_skip_tiles(Cup, Csk):
     batch 16).  decoder.blocks.1 (2 + 1): level; blocks.2 (1 + 1: twice the launch for a 50 us one): no."""
     if _SP == "all":
         return True
-    return _SP != "0" and _SP_SKIPTILES and Cup >= 1024 and -(-Csk // 32) * 3 <= -(-Cup // 128)
+    return _SP != "0" and Cup >= 1024 and -(-Csk // 32) * 3 <= -(-Cup // 128)
 
 
 def _use_spw(N, Ho, Wo, Cout, Cup):
@@ -516,6 +468,18 @@ class HyperStarcopUNet(nn.Module):
             cur = o2
         logits = T("logits", self.classes, 0, "fin")
         ops.append(dict(type="head", conv=self.segmentation_head[0], ins=[cur], out=logits))
+        # tables of the backward walk (_backward_impl)
+        self._res_of = {op["ins"][0].name: op["out"].name for op in ops if op["type"] == "add"}      # tensor -> the residual sum z = t + ...
+        # consumers per tensor: a gradient is complete after ONE launch only for single-consumer tensors
+        self._n_cons = collections.Counter(t.name for op in ops for t in op["ins"])
+        self._prod_idx = {op["out"].name: k for k, op in enumerate(ops)}      # producer op of every tensor (its range-hint slot)
+        self._dw_offs, off = {}, 0      # depthwise op -> offset of its filter gradient in plan.dw_acc
+        for i, op in enumerate(ops):
+            if op["type"] == "dw":
+                self._dw_offs[i] = off
+                off += op["conv"].out_channels * 9
+        self._last_dw = min(self._dw_offs, default=-1)      # the depthwise op the backward walk reaches last
+        self._tail_lo = sum(p.numel() for p in self.encoder.parameters())      # flat offset of the decoder's / head's parameters
         return ops, tensors
 
     # ------------------------------------------------------------------------------------------
@@ -675,7 +639,7 @@ class HyperStarcopUNet(nn.Module):
                             self._pack_version = None
                             self._pack_tables = {}
             fins = [t.name for t in self._tensors.values() if t.kind == "fin" and t.name != "logits"]
-            plan.bn_scratch = torch.empty(64 * 2 * max(t.C for t in self._tensors.values()), dtype=torch.float64, device=dev)   # sc_bn_finalize
+            plan.bn_scratch = torch.empty(64 * 2 * max(t.C for t in self._tensors.values()), dtype=torch.float64, device=dev)   # sc_bn_finalize: coalesced pre-reduction of many-row statistics
             plan.fin_slot = {n: i for i, n in enumerate(fins)}
             plan.fin_amax = torch.zeros(len(fins), **f32)        # running max |value| of each residual sum (never lowered)
             raw_feed = self._split_feeders()[0]
@@ -744,15 +708,14 @@ class HyperStarcopUNet(nn.Module):
             # pointwise weight gradients keep their K-slice partials in buffers of their own until ONE batched reduction at the
             # end of the backward pass (sc_wgrad_reduce_batch) instead of 2-3 dependent few-microsecond launches per layer
             plan.pw_part, plan.pw_table = {}, None
-            if self.batch_pw_reduce:
-                for i, op in enumerate(self._ops):
-                    if op["type"] == "pw" and i not in plan.irt:
-                        conv, o = op["conv"], op["out"]
-                        Hq, Wq = H >> o.shift, W >> o.shift
-                        nfl = (lib.sc_wgrad_pw3_workspace_floats(N, Hq, Wq, conv.out_channels, conv.in_channels)
-                               if _use_pw3(2, N, Hq * Wq, conv.in_channels, conv.out_channels)
-                               else lib.sc_wgrad_workspace_floats(N, Hq, Wq, conv.out_channels, conv.in_channels, 1))
-                        plan.pw_part[i] = torch.empty(nfl, **f32)
+            for i, op in enumerate(self._ops):
+                if op["type"] == "pw" and i not in plan.irt:
+                    conv, o = op["conv"], op["out"]
+                    Hq, Wq = H >> o.shift, W >> o.shift
+                    nfl = (lib.sc_wgrad_pw3_workspace_floats(N, Hq, Wq, conv.out_channels, conv.in_channels)
+                           if _use_pw3(2, N, Hq * Wq, conv.in_channels, conv.out_channels)
+                           else lib.sc_wgrad_workspace_floats(N, Hq, Wq, conv.out_channels, conv.in_channels, 1))
+                    plan.pw_part[i] = torch.empty(nfl, **f32)
             plan.up_tmp = torch.empty(max(up, 1), **f32)
             plan.dw_acc = torch.zeros(n_dw, dtype=torch.float64, device=dev)
             # one float per BatchNorm'd tensor: max |gamma*invstd * g| of its gradient, the range hint of the fp16-split kernels
@@ -775,7 +738,7 @@ class HyperStarcopUNet(nn.Module):
     def _pack_all(self, need_bwd):
         """(Re)pack conv filters into the MFMA kernels' layouts when the parameters changed."""
         lib = _lib.load()
-        ver = (tuple(p._version for p in self.parameters()), self._terms, self.split_bf16, self.thin16)    # a precision switch repacks too
+        ver = (tuple(p._version for p in self.parameters()), self._terms, self.split_bf16)    # a precision switch repacks too
         pv = self._pack_version
         need_irb = (not need_bwd) and bool(getattr(self, "_irb_layers", None))      # the fused inference blocks' PW3 layouts
         if pv is not None and pv[0] == ver and (pv[1] or not need_bwd) and (pv[2] or not need_irb):
@@ -808,7 +771,7 @@ class HyperStarcopUNet(nn.Module):
                 # decoder.blocks.4 (<= 16 output channels at full resolution) under the two-fp16-term split: filters in registers
                 # (sc_conv3x3_thin16; 0.20-0.28 vs 0.31-0.51 ms per launch).  The backward-data kernel only takes the plain
                 # epilogue, so the regular pack is kept beside it.
-                if self.split_bf16 and self.thin16 and ks == 3 and len(op["ins"]) == 1:
+                if self.split_bf16 and ks == 3 and len(op["ins"]) == 1:
                     if tf_ == TERMS_F16X2 and co <= 16 and ci in (16, 32):
                         ent["tf"] = torch.empty(lib.sc_packed_weight_floats_thin16(co, ci, 0), dtype=torch.float32, device=dev)
                     if tb_ == TERMS_F16X2 and ci <= 16 and co in (16, 32):
@@ -823,7 +786,7 @@ class HyperStarcopUNet(nn.Module):
                 # 212 -> 197 us (5 -> 3 passes), decoder.blocks.3.conv1 293 -> 288 us (a 64-wide pass costs two 32-wide ones there: the
                 # operand reads and MFMAs, not the staging, are what its work-groups wait for); 288 = 256 + 32, which already runs on
                 # 64-wide tiles, loses 5 us to the second launch and stays as it was.  Step +0.6 % (same-box pairs).
-                if xb and cb == 32 and op.get("up") and len(op["ins"]) == 2 and self.split_dgrad_launch:
+                if xb and cb == 32 and op.get("up") and len(op["ins"]) == 2:
                     cu, cs_ = op["ins"][0].C, op["ins"][1].C
                     if cu % 64 == 0 and cs_ <= 32 and cu + cs_ == ci:
                         ent["bA"] = torch.empty(lib.sc_packed_weight_floats_bx3(co, ci, 64, 1, tb_), dtype=torch.float32, device=dev)
@@ -927,7 +890,7 @@ class HyperStarcopUNet(nn.Module):
             check(lib.sc_pack_weights_batch(ptr(tab[0][0]), ptr(tab[0][1]), tab[0][2], tab[0][3], st))
         if tab[1] is not None:
             side = None
-            if need_bwd and self.overlap_wgrad and self.light_stream_sync and _PACK_SIDE and not torch.cuda.is_current_stream_capturing():
+            if need_bwd and self.overlap_wgrad and not torch.cuda.is_current_stream_capturing():
                 main = torch.cuda.current_stream()
                 if self._side_stream is None or self._side_stream.device != main.device:
                     self._side_stream = torch.cuda.Stream(device=main.device)
@@ -1064,8 +1027,11 @@ class HyperStarcopUNet(nn.Module):
                 continue
             stats = ptr(plan.stats_v[o.name]) if (training and o.bn is not None) else None
             srows = plan.srows.get(o.name, 0)
-            bn_done = False        # the producer finalized its BatchNorm itself
             conv = op.get("conv")
+            ent = self._wpk[i] if ty in ("pw", "conv3") else None
+            # a decoder conv1 in its sub-pixel form (sc_conv3x3_sp)?
+            use_sp = bool(op.get("up") and ent.get("sp") is not None and ent["terms_f"] in _SP_TERMS and self.split_bf16
+                          and _use_sp(N, Ho, Wo, o.C))
             tok = None
             self._cur_op = o.name + ":fwd"
             if self.profile is not None:
@@ -1073,13 +1039,11 @@ class HyperStarcopUNet(nn.Module):
                     src_elems = sum(t.C * (H >> t.shift) * (W >> t.shift) for t in op["ins"])
                     fl = 2.0 * N * Ho * Wo * conv.out_channels * conv.in_channels * conv.kernel_size[0] ** 2
                     fle = None
-                    ent_ = self._wpk[i]
-                    if (op.get("up") and ent_.get("sp") is not None and ent_["terms_f"] in _SP_TERMS and self.split_bf16
-                            and ent_["tf"] is None and _use_sp(N, Ho, Wo, o.C)):
+                    if use_sp and ent["tf"] is None:
                         cu_ = op["ins"][0].C        # per low-resolution pixel: 16 slots per up-sampled channel, 16 per (skip channel, parity)
                         fle = 2.0 * N * (Ho // 2) * (Wo // 2) * 16 * (-(-conv.out_channels // 32) * 32) * (cu_ + 4 * (conv.in_channels - cu_))
-                    tok = self._pb("k_conv3_thin_h (fwd+dgrad)" if self._wpk[i]["tf"] is not None else
-                                   self._bx3_family("fwd") if self._wpk[i]["bx3_f"] else f"k_conv_mfma<{conv.kernel_size[0]}> (fwd+dgrad)",
+                    tok = self._pb("k_conv3_thin_h (fwd+dgrad)" if ent["tf"] is not None else
+                                   self._bx3_family("fwd") if ent["bx3_f"] else f"k_conv_mfma<{conv.kernel_size[0]}> (fwd+dgrad)",
                                    fl, 4.0 * (N * src_elems + N * o.C * Ho * Wo + conv.weight.numel()), fle)
                 else:
                     tok = self._pb({"stem": "k_stem_*", "dw": "k_dw_*", "head": "k_head_*", "add": "elementwise/bn"}[ty])
@@ -1090,28 +1054,8 @@ class HyperStarcopUNet(nn.Module):
             elif ty == "dw":
                 tin = op["ins"][0]
                 s = self._src_of(plan, tin)
-                if (training and o.bn is not None and stats is not None and 0 < srows <= _DW_TAIL_ROWS
-                        and not torch.cuda.is_current_stream_capturing()):
-                    # few statistics rows per channel: the launch finalizes the BatchNorm itself (last arrival per channel by ticket)
-                    # -- no dependent ~5 us sc_bn_finalize launch behind it
-                    if not hasattr(plan, "bn_tickets"):
-                        plan.bn_tickets = {}
-                    if o.name not in plan.bn_tickets:
-                        plan.bn_tickets[o.name] = torch.zeros(o.C, dtype=torch.int32, device=self._pflat.device)
-                    bn = o.bn
-                    bt = sc_bn_tail()
-                    bt.gamma, bt.beta = bn.weight.data_ptr(), bn.bias.data_ptr()
-                    bt.running_mean, bt.running_var = bn.running_mean.data_ptr(), bn.running_var.data_ptr()
-                    bt.momentum, bt.eps = float(bn.momentum), float(bn.eps)
-                    bt.cst, bt.tickets = plan.cst[o.name].data_ptr(), plan.bn_tickets[o.name].data_ptr()
-                    xb_ = self._xbound(plan, o)
-                    bt.act_bound = xb_.value if xb_ is not None else None
-                    check(lib.sc_dwconv3x3_fwd_bn(C.byref(s), ptr(conv.weight), ptr(plan.buf[o.name]), N, o.C,
-                                                  H >> tin.shift, W >> tin.shift, op["stride"], stats, C.byref(bt), st))
-                    bn_done = True
-                else:
-                    check(lib.sc_dwconv3x3_fwd(C.byref(s), ptr(conv.weight), ptr(plan.buf[o.name]), N, o.C,
-                                               H >> tin.shift, W >> tin.shift, op["stride"], stats, st))
+                check(lib.sc_dwconv3x3_fwd(C.byref(s), ptr(conv.weight), ptr(plan.buf[o.name]), N, o.C,
+                                           H >> tin.shift, W >> tin.shift, op["stride"], stats, st))
             elif ty in ("pw", "conv3"):
                 if ty == "conv3" and self._late_pack_stream is not None:      # the decoder's filter layouts were packed beside the encoder
                     check(lib.sc_stream_wait_stream(st, self._late_pack_stream))
@@ -1122,7 +1066,6 @@ class HyperStarcopUNet(nn.Module):
                 a.src[0] = self._src_of(plan, ins[0], up=1 if op.get("up") else 0)
                 if len(ins) == 2:
                     a.src[1] = self._src_of(plan, ins[1])
-                ent = self._wpk[i]
                 a.wpk = ent["f"].data_ptr()
                 a.N, a.H, a.W, a.Cout = N, Ho, Wo, o.C
                 a.ks, a.co_t = conv.kernel_size[0], ent["cot_f"]
@@ -1137,8 +1080,7 @@ class HyperStarcopUNet(nn.Module):
                 if ty == "pw" and _use_pw3(0, N, Ho * Wo, conv.in_channels, conv.out_channels):
                     fconv = lib.sc_conv1x1_pw3
                     a.wpk = ent["pf"].data_ptr()
-                elif (op.get("up") and ent.get("sp") is not None and ent["terms_f"] in _SP_TERMS and self.split_bf16
-                      and _use_sp(N, Ho, Wo, o.C)):
+                elif use_sp:
                     fconv = lib.sc_conv3x3_sp
                     a.wpk = ent["sp"].data_ptr()
                     srows = lib.sc_sp_stat_rows(N, Ho, Wo, o.C)       # one partial row per work-group tile (fewer than SC_STAT_CONV3's)
@@ -1184,11 +1126,11 @@ class HyperStarcopUNet(nn.Module):
                                                  ptr(plan.classes) if head == "classes" else None,
                                                  N, conv.in_channels, self.classes, Ho, Wo, st))
             self._pe(tok)
-            if o.bn is not None and training and not bn_done and not ("f" in _EXP_NO_BNFIN and plan.generation > 3):
+            if o.bn is not None and training:
                 bn = o.bn
                 check(lib.sc_bn_finalize(stats, srows, float(N * Ho * Wo), ptr(bn.weight), ptr(bn.bias),
                                          ptr(bn.running_mean), ptr(bn.running_var), float(bn.momentum), float(bn.eps),
-                                         1 if training else 0, ptr(plan.cst[o.name]), o.C, ptr(plan.bn_scratch) if _BN_PRE else None,
+                                         1 if training else 0, ptr(plan.cst[o.name]), o.C, ptr(plan.bn_scratch),
                                          self._xbound(plan, o), st))
         if self._late_pack_stream is not None:      # (no 3x3 layer ran: still order the main stream after the pack)
             check(lib.sc_stream_wait_stream(st, self._late_pack_stream))
@@ -1257,7 +1199,7 @@ class HyperStarcopUNet(nn.Module):
         bn = te.bn
         check(lib.sc_bn_finalize(ptr(plan.stats_v[te.name]), plan.irt_rows[te.name], cnt_e, ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
                                  ptr(bn.running_var), float(bn.momentum), float(bn.eps), 1, ptr(plan.cst[te.name]), te.C,
-                                 ptr(plan.bn_scratch) if _BN_PRE else None, None, st))
+                                 ptr(plan.bn_scratch), None, st))
         self._cur_op = td.name + ":fwd"
         tok = self._pb("k_irt_* (fused expand+dw)")
         check(lib.sc_irt_fwd(C.byref(a), ptr(plan.buf[td.name]), ptr(plan.stats_v[td.name]), st))
@@ -1265,7 +1207,7 @@ class HyperStarcopUNet(nn.Module):
         bn = td.bn
         check(lib.sc_bn_finalize(ptr(plan.stats_v[td.name]), plan.irt_rows[td.name], float(plan.N * Hd_ * Wd_), ptr(bn.weight), ptr(bn.bias),
                                  ptr(bn.running_mean), ptr(bn.running_var), float(bn.momentum), float(bn.eps), 1, ptr(plan.cst[td.name]), td.C,
-                                 ptr(plan.bn_scratch) if _BN_PRE else None, None, st))
+                                 ptr(plan.bn_scratch), None, st))
 
     def _nbt_list(self):
         nbt = getattr(self, "_nbt", None)
@@ -1278,18 +1220,7 @@ class HyperStarcopUNet(nn.Module):
     # HIP stream, forked after each layer's BatchNorm-backward constants and joined before the optimiser, so they fill
     # the CUs the small dgrad / reduce kernels of the dependency chain leave idle.
     overlap_wgrad = True
-    batch_pw_reduce = True      # one reduction launch for all pointwise weight gradients (False: per-layer reductions; test switch)
-    fuse_dw_bwd = True          # depthwise dgrad + wgrad + the input's BatchNorm-backward sums in one kernel (False: the three separate kernels)
     fuse_irt = _IRT != "0"      # training: expansion + depthwise of the stride-2 blocks the rule picks without the 6x tensor (conv_irt.hip)
-    fuse_head_bn = True         # BatchNorm-backward sums of the decoder's last tensor in the head backward
-    # ... and of the <= 32 x 32 depthwise outputs in the projections' data-gradient epilogues (sc_conv1x1_pw3 + sc_bnr_args; VERDICT r5 #1b).
-    # Built and parity-tested in round 6, measured LEVEL on the step (1481.8 / 1482.0 vs 1481.5 / 1481.1 tiles/s, tools/ab_switch.sh pw_bnr:
-    # the pointwise data gradients get 0.06 ms slower, the BatchNorm launches 0.04 ms faster) -- off
-    pw_bnr = False
-    batch_dw_cast = True        # the depthwise filter gradients' fp64 -> fp32 rounding in one launch per walk (17 forks fewer)
-    light_stream_sync = True    # fork points of the weight-gradient stream: events without the system-scope fence (sc_stream_wait_stream)
-    split_dgrad_launch = True   # decoder conv1 data gradient: up-sampled and skip channels as two launches with their own cout tiles
-    thin16 = True               # decoder.blocks.4 on sc_conv3x3_thin16 (0: the fp32-MFMA thin kernels)
     split_bf16 = True        # 3x3 convs with >= 32 output channels on the 16-bit matrix cores (False: everything on the fp32 MFMA)
     bn_small_max = 16384     # BatchNorm backward in one launch (block per channel) when a channel has at most this many elements
     # Arithmetic of the 3x3 convolutions with >= 32 channels (conv_bx3.hip): every fp32 operand is split exactly into a few
@@ -1336,39 +1267,22 @@ class HyperStarcopUNet(nn.Module):
         lib = _lib.load()
         st = stream()
         main = torch.cuda.current_stream()
-        side = None
+        side = sd = None
         if self.overlap_wgrad:
             if self._side_stream is None or self._side_stream.device != main.device:
                 self._side_stream = torch.cuda.Stream(device=main.device)
             side = self._side_stream
+            sd = C.c_void_p(side.cuda_stream)      # raw handle, looked up once per walk
 
-        # experiment (STARCOP_EXP_SIDE2=1): the pointwise weight gradients (own partial buffers) on a SECOND weight-gradient stream
-        side2 = None
-        if side is not None and _EXP_SIDE2:
-            if getattr(self, "_side_stream2", None) is None or self._side_stream2.device != main.device:
-                self._side_stream2 = torch.cuda.Stream(device=main.device)
-            side2 = self._side_stream2
-        hnd = {id(s_): C.c_void_p(s_.cuda_stream) for s_ in (main, side, side2) if s_ is not None}      # raw handles, looked up once per walk
-
-        def wait_stream(waiter, signaller):
-            # same-device ordering without the system-scope fence of a default event (sc_stream_wait_stream)
-            if self.light_stream_sync:
-                check(lib.sc_stream_wait_stream(hnd[id(waiter)], hnd[id(signaller)]))
-            else:
-                waiter.wait_stream(signaller)
-
-        def wgrad_launch(fn, second=False):
+        def wgrad_launch(fn):
             """run fn(stream_handle) on the weight-gradient stream, ordered after everything queued on the main stream.  (One fork per
             launch: serving two to eight launches with one fork -- fewer markers in the main queue -- measured 0.5-2.5 % SLOWER, the
             weight gradients then start too late to fill the gaps of the data-gradient chain.)"""
-            if _EXP_NO_WGRAD:
-                return           # elimination experiment (results wrong): what the step costs without any weight-gradient launch
             if side is None:
                 fn(st)
             else:
-                sd = side2 if (second and side2 is not None) else side
-                wait_stream(sd, main)
-                fn(hnd[id(sd)])       # (every fn launches through the C ABI with the handle it is given: no stream context switch needed)
+                check(lib.sc_stream_wait_stream(sd, st))      # same-device ordering without the system-scope fence of a default event
+                fn(sd)       # (every fn launches through the C ABI with the handle it is given: no stream context switch needed)
 
         N, H, W = plan.N, plan.H, plan.W
         if not getattr(plan, "training", False):
@@ -1381,25 +1295,9 @@ class HyperStarcopUNet(nn.Module):
         if half_bwd:
             plan.gmax.zero_()
         written = set()
-        res_of = {}       # tensor name -> name of the residual sum z (z = t + ...)
-        for op in self._ops:
-            if op["type"] == "add":
-                res_of[op["ins"][0].name] = op["out"].name
+        res_of, n_cons, prod_idx, dw_offs, last_dw = self._res_of, self._n_cons, self._prod_idx, self._dw_offs, self._last_dw
         gv = self._grad_view
-        dw_off = 0
-        dw_offs = {}
-        for i, op in enumerate(self._ops):
-            if op["type"] == "dw":
-                dw_offs[i] = dw_off
-                dw_off += op["conv"].out_channels * 9
-
         reduced = set()      # tensors whose BatchNorm-backward sums were produced by the launch that wrote their gradient
-        reduced32 = {}       # ... by a convolution data-gradient launch (sc_bnr_args): name -> (float rows, number of rows)
-        n_cons = {}          # consumers per tensor: a gradient is complete after ONE launch only for single-consumer tensors
-        for op in self._ops:
-            for t in op["ins"]:
-                n_cons[t.name] = n_cons.get(t.name, 0) + 1
-        prod_idx = {op["out"].name: k for k, op in enumerate(self._ops)}      # producer op of every tensor (its range-hint slot)
         pw_pending = []      # pointwise weight gradients whose K-slice partials await the batched reduction
 
         def bn_backward(t, slot=None):
@@ -1408,15 +1306,7 @@ class HyperStarcopUNet(nn.Module):
             if slot is not None:
                 amax = plan.gmax.data_ptr() + 4 * slot
                 gmax_slot[t.name] = amax
-            if t.name in reduced32:        # the data-gradient launch that wrote this gradient left float rows (sc_bnr_args)
-                rows_t, nrows = reduced32[t.name]
-                check(lib.sc_bn_bwd_finalize_rows32(ptr(rows_t), nrows, float(N * Ho * Wo), ptr(plan.cst[t.name]),
-                                                    ptr(gv(t.bn.weight)), ptr(gv(t.bn.bias)), ptr(plan.cstb[t.name]), t.C,
-                                                    ptr(plan.bn_scratch) if _BN_PRE else None, st))
-                return
             if t.name in reduced:          # the launch that wrote this gradient left the sums (and raised the range-hint slot)
-                if "b" in _EXP_NO_BNFIN and plan.generation > 3:
-                    return
                 check(lib.sc_bn_bwd_finalize(ptr(plan.dwsums[t.name]), plan.dwrows[t.name], float(N * Ho * Wo), ptr(plan.cst[t.name]),
                                              ptr(gv(t.bn.weight)), ptr(gv(t.bn.bias)), ptr(plan.cstb[t.name]), t.C, st))
                 return
@@ -1428,29 +1318,8 @@ class HyperStarcopUNet(nn.Module):
                 return
             check(lib.sc_bn_bwd_reduce(ptr(plan.grad[t.name]), ptr(plan.buf[t.name]), ptr(plan.cst[t.name]), t.act,
                                        ptr(plan.bsums_v[t.name]), N, t.C, Ho * Wo, amax, aact, st))
-            if "b" in _EXP_NO_BNFIN and plan.generation > 3:
-                return
             check(lib.sc_bn_bwd_finalize(ptr(plan.bsums_v[t.name]), plan.brows[t.name], float(N * Ho * Wo), ptr(plan.cst[t.name]),
                                          ptr(gv(t.bn.weight)), ptr(gv(t.bn.bias)), ptr(plan.cstb[t.name]), t.C, st))
-
-        def bnr_for(t, nrows, enabled=_BNR):
-            """sc_bnr_args for the data-gradient launch that is about to write the COMPLETE gradient of tensor t (a single-consumer,
-            BatchNorm'd tensor that nothing wrote or will add to): the launch leaves t's BatchNorm-backward sums (nrows partial rows) and
-            range hint, instead of sc_bn_bwd_reduce streaming (gradient, y) again -- 0.41 ms of such passes per batch-16 step in the decoder"""
-            if (not enabled or t.bn is None or t.kind != "raw" or n_cons.get(t.name, 0) != 1 or t.name in written
-                    or res_of.get(t.name) is not None):
-                return None
-            if not hasattr(plan, "bnr_rows"):
-                plan.bnr_rows = {}
-            key = (t.name, nrows)
-            if key not in plan.bnr_rows:
-                plan.bnr_rows[key] = torch.empty(nrows * t.C * 2, dtype=torch.float32, device=self._pflat.device)
-            b = sc_bnr_args()
-            b.y, b.cst, b.act = plan.buf[t.name].data_ptr(), plan.cst[t.name].data_ptr(), t.act
-            b.rows = plan.bnr_rows[key].data_ptr()
-            b.absmax = (plan.gmax.data_ptr() + 4 * prod_idx[t.name]) if (half_bwd and self._ops[prod_idx[t.name]]["type"] == "conv3") else None
-            reduced32[t.name] = (plan.bnr_rows[key], nrows)
-            return b
 
         def reduce_pointwise_batch():
             """ONE launch (weight-gradient stream) sums the K-slice partials of every pointwise weight gradient queued so far"""
@@ -1472,12 +1341,11 @@ class HyperStarcopUNet(nn.Module):
                                       torch.tensor(starts, dtype=torch.int32).to(self._pflat.device), len(pw_pending), nblk)
             tab = plan.pw_table[raw]
             tok = self._pb("k_wgrad_mfma<1> (+reduce)")
-            wgrad_launch(lambda sx: check(lib.sc_wgrad_reduce_batch(ptr(tab[0]), ptr(tab[1]), tab[2], tab[3], sx)), second=True)
+            wgrad_launch(lambda sx: check(lib.sc_wgrad_reduce_batch(ptr(tab[0]), ptr(tab[1]), tab[2], tab[3], sx)))
             self._pe(tok)
             pw_pending.clear()
 
         dw_casts = []        # (fp64 accumulator, flat fp32 gradient view, n) of the fused depthwise backward launches walked so far
-        last_dw = min((k for k, op_ in enumerate(self._ops) if op_["type"] == "dw"), default=-1)
 
         def cast_dw_gradients():
             """ONE launch (weight-gradient stream) rounds every depthwise filter gradient accumulated so far to fp32 -- per layer it was
@@ -1496,7 +1364,7 @@ class HyperStarcopUNet(nn.Module):
             dw_casts.clear()
 
         last_pw = min((k for k, op_ in enumerate(self._ops) if op_["type"] == "pw" and k in plan.pw_part), default=-1)
-        tail_lo = sum(p.numel() for p in self.encoder.parameters())
+        tail_lo = self._tail_lo
         tail_pending = on_tail_ready is not None
         irt_done = set()
         for i in (range(len(self._ops) - 1, -1, -1) if only_ops is None else only_ops):
@@ -1519,28 +1387,21 @@ class HyperStarcopUNet(nn.Module):
                 tin = op["ins"][0]
                 s = self._src_of(plan, tin)
                 tok = self._pb("k_head_*")
-                if conv.in_channels == 16 and _HEAD_FUSED_BWD:
-                    # one sweep over (dlogits, x) for gin, dW and dbias (sc_head_conv_bwd) -- and, the head being the only consumer
-                    # of the decoder's last tensor, that tensor's BatchNorm-backward sums and range hint (its raw values stream
-                    # through the kernel anyway): saves sc_bn_bwd_reduce's pass over 2 x 268 MB at 16 x 512^2
-                    bns = bna = None
-                    if self.fuse_head_bn and tin.bn is not None and tin.kind == "raw" and n_cons.get(tin.name, 0) == 1:
-                        if tin.name not in plan.dwsums:
-                            plan.dwrows[tin.name] = lib.sc_head_bwd_bn_rows(N, Ho, Wo)
-                            plan.dwsums[tin.name] = torch.empty(plan.dwrows[tin.name] * tin.C * 2, dtype=torch.float64, device=self._pflat.device)
-                        bns = ptr(plan.dwsums[tin.name])
-                        if half_bwd:
-                            bna = plan.gmax.data_ptr() + 4 * prod_idx[tin.name]
-                        reduced.add(tin.name)
-                    check(lib.sc_head_conv_bwd(ptr(dlogits), C.byref(s), ptr(conv.weight), ptr(plan.grad[tin.name]), ptr(plan.ws),
-                                               plan.ws_floats, ptr(gv(conv.weight)), ptr(gv(conv.bias)), N, conv.in_channels, Ho, Wo,
-                                               bns, bna, st))
-                else:
-                    wgrad_launch(lambda sx, s=s, conv=conv, Ho=Ho, Wo=Wo: check(lib.sc_head_conv_wgrad(
-                        ptr(dlogits), C.byref(s), ptr(plan.ws), plan.ws_floats, ptr(gv(conv.weight)), ptr(gv(conv.bias)), N,
-                        conv.in_channels, Ho, Wo, sx)))
-                    check(lib.sc_head_conv_dgrad(ptr(dlogits), ptr(conv.weight), ptr(plan.grad[tin.name]), N,
-                                                 conv.in_channels, Ho, Wo, st))
+                # one sweep over (dlogits, x) for gin, dW and dbias (sc_head_conv_bwd) -- and, the head being the only consumer
+                # of the decoder's last tensor, that tensor's BatchNorm-backward sums and range hint (its raw values stream
+                # through the kernel anyway): saves sc_bn_bwd_reduce's pass over 2 x 268 MB at 16 x 512^2
+                bns = bna = None
+                if tin.bn is not None and tin.kind == "raw" and n_cons.get(tin.name, 0) == 1:
+                    if tin.name not in plan.dwsums:
+                        plan.dwrows[tin.name] = lib.sc_head_bwd_bn_rows(N, Ho, Wo)
+                        plan.dwsums[tin.name] = torch.empty(plan.dwrows[tin.name] * tin.C * 2, dtype=torch.float64, device=self._pflat.device)
+                    bns = ptr(plan.dwsums[tin.name])
+                    if half_bwd:
+                        bna = plan.gmax.data_ptr() + 4 * prod_idx[tin.name]
+                    reduced.add(tin.name)
+                check(lib.sc_head_conv_bwd(ptr(dlogits), C.byref(s), ptr(conv.weight), ptr(plan.grad[tin.name]), ptr(plan.ws),
+                                           plan.ws_floats, ptr(gv(conv.weight)), ptr(gv(conv.bias)), N, conv.in_channels, Ho, Wo,
+                                           bns, bna, st))
                 self._pe(tok)
                 written.add(tin.name)
                 continue
@@ -1575,10 +1436,7 @@ class HyperStarcopUNet(nn.Module):
                 tok = self._pb("k_irt_* (fused expand+dw)")
                 wgrad_launch(lambda sx, a_irt=a_irt, work=work: check(lib.sc_irt_xmoments(C.byref(a_irt), ptr(work), sx)))
                 check(lib.sc_irt_bwd(C.byref(a_irt), C.byref(dy), ptr(esums), ptr(acc), ptr(work), st))
-                if self.batch_dw_cast:
-                    dw_casts.append((acc.data_ptr(), gv(conv.weight).data_ptr(), o.C * 9))
-                else:
-                    wgrad_launch(lambda sx, acc=acc, conv=conv, o=o: check(lib.sc_cast_f64_f32(ptr(acc), ptr(gv(conv.weight)), o.C * 9, sx)))
+                dw_casts.append((acc.data_ptr(), gv(conv.weight).data_ptr(), o.C * 9))
                 check(lib.sc_bn_bwd_finalize(ptr(esums), lib.sc_irt_bwd_rows(N, te.C, a_irt.H, a_irt.W), float(N * a_irt.H * a_irt.W),
                                              ptr(plan.cst[te.name]), ptr(gv(te.bn.weight)), ptr(gv(te.bn.bias)), ptr(plan.cstb[te.name]), te.C, st))
                 z = res_of.get(tin.name)
@@ -1597,15 +1455,12 @@ class HyperStarcopUNet(nn.Module):
                 s = self._src_of(plan, tin)
                 acc = plan.dw_acc[dw_offs[i]:dw_offs[i] + o.C * 9]
                 tok = self._pb("k_dw_*")
-                if (self.fuse_dw_bwd and tin.name not in written and tin.bn is not None and tin.name in plan.dwsums
+                if (tin.name not in written and tin.bn is not None and tin.name in plan.dwsums
                         and n_cons.get(tin.name, 0) == 1):      # the fused sums are complete only for a single-consumer input
                     # one pass: dx, dW and the BatchNorm-backward sums of the (6x expanded) input tensor
                     check(lib.sc_dwconv3x3_bwd_fused(C.byref(dy), C.byref(s), ptr(conv.weight), ptr(plan.grad[tin.name]), ptr(acc),
                                                      ptr(plan.dwsums[tin.name]), N, o.C, Hi, Wi, op["stride"], st))
-                    if self.batch_dw_cast:
-                        dw_casts.append((acc.data_ptr(), gv(conv.weight).data_ptr(), o.C * 9))
-                    else:
-                        wgrad_launch(lambda sx, acc=acc, conv=conv, o=o: check(lib.sc_cast_f64_f32(ptr(acc), ptr(gv(conv.weight)), o.C * 9, sx)))
+                    dw_casts.append((acc.data_ptr(), gv(conv.weight).data_ptr(), o.C * 9))
                     self._pe(tok)
                     written.add(tin.name)
                     reduced.add(tin.name)
@@ -1679,7 +1534,7 @@ class HyperStarcopUNet(nn.Module):
             else:
                 wfn = (lib.sc_conv3x3_wgrad_bx3 if (self.split_bf16 and ks == 3 and conv.out_channels >= 32 and conv.in_channels >= 32)
                        else lib.sc_conv2d_wgrad_mfma)     # 16-channel layers outside the cases below stay on the fp32 MFMA
-            if (wfn is not None and self.split_bf16 and self.thin16 and ks == 3 and self._terms[1] == TERMS_F16X2 and len(ins) == 1
+            if (wfn is not None and self.split_bf16 and ks == 3 and self._terms[1] == TERMS_F16X2 and len(ins) == 1
                     and conv.out_channels <= 16 and conv.in_channels in (16, 32) and Wo % 2 == 0):
                 wfn = lib.sc_conv3x3_wgrad_thin16     # decoder.blocks.4: two fp16 terms on the 16x16x32 MFMA (was MFMA-bound in fp32)
             tok = None if wfn is None else self._pb(
@@ -1692,7 +1547,7 @@ class HyperStarcopUNet(nn.Module):
                 pend = sc_wgrad_pending()
                 wdef = (lib.sc_conv1x1_wgrad_pw3 if _use_pw3(2, N, Ho * Wo, conv.in_channels, conv.out_channels)
                         else lib.sc_conv2d_wgrad_mfma_deferred)
-                wgrad_launch(lambda sx, wa=wa, pend=pend, wdef=wdef: check(wdef(C.byref(wa), C.byref(pend), sx)), second=True)
+                wgrad_launch(lambda sx, wa=wa, pend=pend, wdef=wdef: check(wdef(C.byref(wa), C.byref(pend), sx)))
                 pw_pending.append(pend)
                 if i == last_pw:
                     # every pointwise layer has been walked: queue the batched reduction NOW, behind this layer's weight gradient, where it
@@ -1725,28 +1580,27 @@ class HyperStarcopUNet(nn.Module):
                 conv_dgrad = lib.sc_conv2d_mfma
             a.add0 = None; a.add1 = None; a.stats = None
             a.accum0 = a.accum1 = 0
-            # (sc_bnr_args are taken by k_conv3_bx3, not by its wave-specialised variant, which sc_conv3x3_bx3 picks from 16 K chunks up)
-            bx3_plain = ent["bx3_b"] and not (a.terms == TERMS_F16X2 and (conv.out_channels + 15) // 16 >= 16 and conv.out_channels <= 256)
             # algorithmic bytes of the data gradient: g and y of the output once each, the input gradient once, the filter
             gin_elems = N * conv.in_channels * Ho * Wo
             if op.get("up") and ent["bx3_b"]:      # the upsampled source's gradient is stored 2x2-summed (quarter size)
                 gin_elems -= N * ins[0].C * Ho * Wo * 3 // 4
             thin_b = (ent["tb"] is not None and not op.get("up") and ins[0].name not in written and res_of.get(ins[0].name) is None)
             # decoder.blocks.4.conv1: 16 gradient channels -> 32 channels at half resolution, the sub-pixel form on the thin layer's MFMA
-            # (sc_conv3x3_thin16 with down0: 251 -> see DESIGN 16; STARCOP_THIN_SPD=0: sc_conv3x3_bx3 with its summing store)
-            thin_sd = (ent.get("tsd") is not None and op.get("up") and len(ins) == 1 and a.terms == TERMS_F16X2 and _THIN_SPD and not _BNR
+            # (sc_conv3x3_thin16 with down0: 251 -> see DESIGN 16; otherwise sc_conv3x3_bx3 with its summing store)
+            thin_sd = (ent.get("tsd") is not None and op.get("up") and len(ins) == 1 and a.terms == TERMS_F16X2
                        and Ho % 2 == 0 and Wo % 2 == 0)
+            # a decoder conv1's data gradient in its sub-pixel form (sc_conv3x3_sp_dgrad)?
+            use_spd = bool(op.get("up") and ent.get("spd") is not None and ent["terms_b"] in _SP_TERMS and self.split_bf16
+                           and _use_spd(N, Ho, Wo, ins[0].C, conv.in_channels - ins[0].C))
             fle = None
-            if (op.get("up") and ent.get("spd") is not None and ent["terms_b"] in _SP_TERMS and self.split_bf16
-                    and _use_spd(N, Ho, Wo, ins[0].C, conv.in_channels - ins[0].C)):
+            if use_spd:
                 cu_ = ins[0].C          # up-sampled channels: 4 parity planes x 4 taps per low-resolution pixel; skip channels: the 3x3 form
                 fle = (2.0 * N * (Ho // 2) * (Wo // 2) * 16 * conv.out_channels * (-(-cu_ // 128) * 128 + (128 * -(-(conv.in_channels - cu_) // 32) if ent["spd_stiles"] else 0))
                        + (0.0 if (ent["spd_vskip"] or ent["spd_stiles"]) else 2.0 * N * Ho * Wo * 9 * conv.out_channels * (conv.in_channels - cu_)))
             tok = self._pb("k_conv3_thin_h (fwd+dgrad)" if (thin_b or thin_sd) else
                            self._bx3_family("dgrad") if ent["bx3_b"] else f"k_conv_mfma<{ks}> (fwd+dgrad)", flop,
                            4.0 * (2 * N * o.C * Ho * Wo + gin_elems + conv.weight.numel()), fle)
-            if (op.get("up") and ent.get("spd") is not None and ent["terms_b"] in _SP_TERMS and self.split_bf16
-                    and _use_spd(N, Ho, Wo, ins[0].C, conv.in_channels - ins[0].C)):
+            if use_spd:
                 if ent["spd_vskip"] or ent["spd_stiles"]:
                     # <= 64 up-sampled + <= 16 skip channels (decoder.blocks.3): the skip channels' gradient as virtual channels of the
                     # 128-channel tile's second half -- dy (g, y) is staged ONCE for both gradients (289 us in two 3x3 launches before);
@@ -1784,7 +1638,7 @@ class HyperStarcopUNet(nn.Module):
                 a.Cout = a.csplit = t_up.C
                 a.wpk, a.co_t = ent["tsd"].data_ptr(), 16
                 a.out0, a.out1 = plan.grad[t_up.name].data_ptr(), None
-                a.accum0, a.down0, a.bnr = (1 if t_up.name in written else 0), 1, None
+                a.accum0, a.down0 = (1 if t_up.name in written else 0), 1
                 check(lib.sc_conv3x3_thin16(C.byref(a), st))
                 self._pe(tok)
                 written.add(t_up.name)
@@ -1792,16 +1646,13 @@ class HyperStarcopUNet(nn.Module):
             if op.get("up"):
                 t_up = ins[0]
                 fused_down = conv_dgrad is lib.sc_conv3x3_bx3      # the split-bf16 kernel stores the 2x2 sums itself
-                if fused_down and ent.get("bA") is not None and self.split_dgrad_launch:
+                if fused_down and ent.get("bA") is not None:
                     t_sk = ins[1]
                     a.Cout = a.csplit = t_up.C
                     a.wpk, a.co_t = ent["bA"].data_ptr(), 64
                     a.out0, a.out1 = plan.grad[t_up.name].data_ptr(), None
                     a.accum0, a.down0 = (1 if t_up.name in written else 0), 1
-                    b_ = bnr_for(t_up, lib.sc_stat_rows(STAT_CONV3, N, Ho, Wo)) if bx3_plain else None
-                    a.bnr = C.addressof(b_) if b_ is not None else None
                     check(conv_dgrad(C.byref(a), st))
-                    a.bnr = None
                     a.Cout = a.csplit = t_sk.C
                     a.wpk, a.co_t = ent["bB"].data_ptr() + 4 * ent["bB_off"], 32
                     a.out0 = plan.grad[t_sk.name].data_ptr()
@@ -1824,10 +1675,6 @@ class HyperStarcopUNet(nn.Module):
                     written.add(t_sk.name)
                 else:
                     a.out1 = None
-                b_ = None
-                if fused_down and bx3_plain and (a.csplit == a.Cout or a.csplit % a.co_t == 0):
-                    b_ = bnr_for(t_up, lib.sc_stat_rows(STAT_CONV3, N, Ho, Wo))
-                a.bnr = C.addressof(b_) if b_ is not None else None
                 check(conv_dgrad(C.byref(a), st))
                 self._pe(tok)
                 if not fused_down:
@@ -1845,16 +1692,6 @@ class HyperStarcopUNet(nn.Module):
                 if thin_b:
                     conv_dgrad = lib.sc_conv3x3_thin16
                     a.wpk = ent["tb"].data_ptr()
-                b_ = None
-                if ks == 3 and (thin_b or (conv_dgrad is lib.sc_conv3x3_bx3 and bx3_plain)):
-                    b_ = bnr_for(tin, lib.sc_stat_rows(STAT_CONV3, N, Ho, Wo), enabled=_BNR or (thin_b and _BNR_THIN))
-                elif (conv_dgrad is lib.sc_conv1x1_pw3 and self.pw_bnr and z is None and not a.accum0
-                      and N * Ho * Wo <= self.bn_small_max and tin.C >= 64):
-                    # a projection's data gradient at <= 32 x 32 (the register-only pointwise kernel): it writes the COMPLETE gradient of the
-                    # depthwise output d, so its epilogue leaves d's BatchNorm-backward sums (one row per 32-pixel block) and the dependent
-                    # sc_bn_bwd_small launch over (gradient, d) -- 8 us alone, ~21 us under the weight-gradient stream -- becomes a finalize
-                    b_ = bnr_for(tin, -(-(N * Ho * Wo) // 32), enabled=True)
-                a.bnr = C.addressof(b_) if b_ is not None else None
                 check(conv_dgrad(C.byref(a), st))
                 self._pe(tok)
                 written.add(tin.name)
@@ -1865,12 +1702,8 @@ class HyperStarcopUNet(nn.Module):
             # (on_tail_ready: the data-parallel path) a default event, otherwise the device-scope one
             if exchange_follows if exchange_follows is not None else on_tail_ready is not None:
                 main.wait_stream(side)
-                if side2 is not None:
-                    main.wait_stream(side2)
             else:
-                wait_stream(main, side)
-                if side2 is not None:
-                    wait_stream(main, side2)
+                check(lib.sc_stream_wait_stream(st, sd))
 
     # ------------------------------------------------------------------------------------------
     def forward(self, x, normalizer_consts=None):

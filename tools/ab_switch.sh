@@ -1,5 +1,6 @@
 #!/bin/bash
-# same-box A/B of a class switch of network.HyperStarcopUNet: bash tools/ab_switch.sh <attribute> [bench args]
+# same-box A/B of a boolean class attribute of network.HyperStarcopUNet (fuse_irt, overlap_wgrad, split_bf16):
+# bash tools/ab_switch.sh <attribute> [bench args]
 # prints tiles/s, ms/step and the families of the serial pass that moved, switch on / off / on / off
 ATTR=$1; shift
 for f in True False True False; do

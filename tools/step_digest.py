@@ -1,5 +1,7 @@
-"""sha256 of the logits and of every gradient of one training step on a fixed batch: run it under two builds of the library
-(STARCOP_HIP_LIB=...) to show that a kernel change is bit-neutral.  python tools/step_digest.py [--size 256] [--batch 4]"""
+"""sha256 of the logits and of every gradient of one training step on a fixed batch, and of the logits of the eval-mode forward that
+follows it (the inference path, on the running statistics that step left): run it under two builds of the library
+(STARCOP_HIP_LIB=...) or two versions of the package to show that a change is bit-neutral.
+python tools/step_digest.py [--size 256] [--batch 4] [--precision fp32]"""
 import sys, os, argparse, hashlib
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import torch
@@ -23,3 +25,7 @@ g = hashlib.sha256()
 for k, p in sorted(net.named_parameters()):
     g.update(p.grad.detach().cpu().numpy().tobytes())
 print("grads ", g.hexdigest()[:16])
+model.eval()
+with torch.no_grad():
+    ev = model(batch["input"])
+print("eval  ", hashlib.sha256(ev.cpu().numpy().tobytes()).hexdigest()[:16])
