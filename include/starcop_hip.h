@@ -966,6 +966,67 @@ typedef struct sc_warp_args {
 } sc_warp_args;
 int sc_warp(const sc_warp_args* a, sc_stream stream);
 
+/* Footprint resampling for the warp: where sc_warp looks at the destination pixel's CENTRE, this operator reduces every source pixel
+ * under the destination pixel's FOOTPRINT -- what a coarser destination grid needs.  For destination pixel (r, c), in fp64:
+ *   corners : (c, r), (c+1, r), (c, r+1), (c+1, r+1) go through the arithmetic of sc_warp's centre (dst_gt, the CRS route, src_inv),
+ *             unclipped.  A corner without a finite result or outside the 30-degree band makes the pixel no-data.
+ *   box     : u0 = min u_k, u1 = max u_k, v0, v1 likewise: the axis-aligned BOUNDING BOX of the footprint in source pixel
+ *             coordinates (for a rotated pair larger than the true quadrilateral, as in GDAL).  A = (u1 - u0)(v1 - v0) is its
+ *             unclipped area; it is clipped to [0, src_w] x [0, src_h] -> [cu0, cu1] x [cv0, cv1]; empty = no-data.
+ *   weights : source column j in [floor(cu0), ceil(cu1)) has wx = min(j+1, cu1) - max(j, cu0), row i likewise wy.  A source pixel
+ *             TAKES PART when wx > 2^-20 and wy > 2^-20 (the sliver rule: on a shared lattice with an integer ratio the corners land
+ *             on integers +- 1e-11, and max / min / mode must not depend on that noise); its weight is w = wx * wy.
+ *   counting: a taking-part sample COUNTS when it differs in bits from nodata_bits[p] and (float32) is not NaN.
+ *   coverage: per plane, sum of w over counting samples / A.  The pixel is data when a sample counts and coverage >= min_coverage
+ *             (all modes); otherwise nodata_bits[p] is written.
+ *   SC_WARP_AREA_AVERAGE : float32.  sum w x / sum w over counting samples, rounded once.
+ *   SC_WARP_AREA_MAX/MIN : float32 or uint8.  The extreme counting sample, exact bits (float32 in the total order -0 < +0; NaN
+ *                          never counts, infinities do).
+ *   SC_WARP_AREA_MODE    : uint8.  The value with the most counting samples (unweighted, integer tally), ties to the smallest.
+ * coverage (device, may be NULL): float32 [P][out_h][out_w], the coverage where the pixel is data and 0 where it is no-data, so
+ * that sum average * coverage * pixel area conserves an integral.  boxes (device, may be NULL): float64 [4][out_h][out_w] =
+ * u0, u1, v0, v1 unclipped, NaN where a corner has no coordinates; a call with P = 0 writes only this.
+ * A work-group projects the 17 x 17 (17 x 65 with 16-byte stores in the thread mapping) corners of its tile once into LDS -- about
+ * 1.1 projections per pixel, not 4 -- and box, clip and weights are computed once per pixel for all planes.  Two mappings:
+ *   variant 1 (thread)    : one thread per destination pixel loops over its box; for boxes of a few source pixels.
+ *   variant 2 (lane group): 16 lanes own one destination pixel and run along source columns, the 4 groups of a wave own 4
+ *                           adjacent pixels of a row, so a wave reads one contiguous segment per source row; the partial results
+ *                           are combined by a fixed xor-butterfly (8, 4, 2, 1).  The mode tally is a 256-bin LDS histogram per group.
+ *   variant 0             : chosen from the box width (source columns) of the destination grid's four corner pixels, estimated on
+ *                           the host; sc_warp_area_variant returns that choice (1 or 2) or SC_ERR_ARG.
+ * max / min / mode are bit-equal between the variants, average to the last place or two (another fp64 summation order).  Loops over
+ * the box have no cap.  No floating-point atomics, a fixed reduction order: repeated calls give identical bits.  Planes are read in
+ * place as in sc_warp; 16-byte stores (4-byte for uint8) when out_w is a multiple of 4 and out / coverage are aligned to them.
+ * SC_ERR_ARG ("sc_warp_area: ...") as sc_warp, and for a mode / elem_bytes pair not listed above, min_coverage outside [0, 1] or
+ * NaN, variant outside 0..2, P = 0 without boxes.                                                                                 */
+#define SC_WARP_AREA_AVERAGE 2
+#define SC_WARP_AREA_MAX 3
+#define SC_WARP_AREA_MIN 4
+#define SC_WARP_AREA_MODE 5
+#define SC_WARP_AREA_THREAD 1
+#define SC_WARP_AREA_LANES 2
+typedef struct sc_warp_area_args {
+  double dst_gt[6];                              /* geotransform of the destination grid, GDAL order           */
+  double src_inv[6];                             /* world -> source pixel coordinates, as in sc_warp_args       */
+  int32_t dst_crs, src_crs;                      /* 0, 4326, 326zz, 327zz                                      */
+  int32_t out_h, out_w;
+  int32_t src_h, src_w;
+  int32_t P;                                     /* planes, 0..32 (0: boxes only)                              */
+  int32_t elem_bytes;                            /* 4 = float32, 1 = uint8 (ignored with P = 0)                */
+  int32_t mode;                                  /* SC_WARP_AREA_AVERAGE ... SC_WARP_AREA_MODE                 */
+  int32_t variant;                               /* 0 = chosen by the library, SC_WARP_AREA_THREAD / _LANES    */
+  double min_coverage;                           /* [0, 1]                                                     */
+  const void* src[SC_WARP_MAX_PLANES];           /* element (0, 0) of every plane, device                      */
+  int64_t row_stride[SC_WARP_MAX_PLANES];        /* elements                                                   */
+  int64_t col_stride[SC_WARP_MAX_PLANES];
+  uint64_t nodata_bits[SC_WARP_MAX_PLANES];      /* raw bit pattern of every plane's no-data value             */
+  void* out;                                     /* [P][out_h][out_w] device (NULL with P = 0)                 */
+  float* coverage;                               /* [P][out_h][out_w] device, or NULL                          */
+  double* boxes;                                 /* [4][out_h][out_w] device, or NULL                          */
+} sc_warp_area_args;
+int sc_warp_area(const sc_warp_area_args* a, sc_stream stream);
+int sc_warp_area_variant(const sc_warp_area_args* a);
+
 /* Mosaic: N rasters on grids of their own composed into ONE raster on a destination grid, in one launch.  Per destination pixel the
  * world coordinates of the centre are computed once; when the destination is a UTM zone and a source of the pixel's tile has another
  * CRS, longitude / latitude (the Krueger inverse) once per pixel and not once per source; per source nothing more (same CRS), the

@@ -161,6 +161,20 @@ class sc_warp_args(C.Structure):
                 ("out", C.c_void_p), ("coords", C.c_void_p), ("oob_count", C.c_void_p)]
 
 
+WARP_AREA_AVERAGE, WARP_AREA_MAX, WARP_AREA_MIN, WARP_AREA_MODE = 2, 3, 4, 5
+WARP_AREA_THREAD, WARP_AREA_LANES = 1, 2
+
+
+class sc_warp_area_args(C.Structure):
+    """footprint resampling operands (include/starcop_hip.h: sc_warp_area_args)"""
+    _fields_ = [("dst_gt", C.c_double * 6), ("src_inv", C.c_double * 6), ("dst_crs", C.c_int32), ("src_crs", C.c_int32),
+                ("out_h", C.c_int32), ("out_w", C.c_int32), ("src_h", C.c_int32), ("src_w", C.c_int32), ("P", C.c_int32),
+                ("elem_bytes", C.c_int32), ("mode", C.c_int32), ("variant", C.c_int32), ("min_coverage", C.c_double),
+                ("src", C.c_void_p * WARP_MAX_PLANES), ("row_stride", C.c_int64 * WARP_MAX_PLANES),
+                ("col_stride", C.c_int64 * WARP_MAX_PLANES), ("nodata_bits", C.c_uint64 * WARP_MAX_PLANES),
+                ("out", C.c_void_p), ("coverage", C.c_void_p), ("boxes", C.c_void_p)]
+
+
 MOSAIC_MAX_SOURCES, MOSAIC_MEAN_PLANES = 64, 4
 MOSAIC_FIRST, MOSAIC_LAST, MOSAIC_MAX, MOSAIC_MIN, MOSAIC_MEAN, MOSAIC_BY_INDEX = range(6)
 MOSAIC_KEY_FLOAT = 1
@@ -390,6 +404,8 @@ SIGNATURES = {
     "sc_window_stats": (_i, [C.POINTER(sc_winstats_args), _vp, _sz, _vp]),
     "sc_glt_ortho": (_i, [C.POINTER(sc_ortho_args), _vp]),
     "sc_warp": (_i, [C.POINTER(sc_warp_args), _vp]),
+    "sc_warp_area": (_i, [C.POINTER(sc_warp_area_args), _vp]),
+    "sc_warp_area_variant": (_i, [C.POINTER(sc_warp_area_args)]),
     "sc_mosaic": (_i, [C.POINTER(sc_mosaic_args), _vp]),
     "sc_window_cut": (_i, [C.POINTER(sc_wcut_args), _vp]),
     "sc_scene_gather": (_i, [C.POINTER(sc_scene_args), _vp]),

@@ -4,7 +4,8 @@
 // recurrence, the conformal latitude inverted with a FIXED number of Newton steps; and the sampling of one plane at (u, v): `nearest`
 // copies element (floor(v), floor(u)) as a word, `bilinear` (float32) weighs the four pixels around (u - 0.5, v - 0.5) in fp64, leaves
 // out samples that lie outside the raster, are NaN or carry the plane's no-data bit pattern, divides by the weight of those that
-// count and rounds once.  Both operators include this file, so a pixel of one source gets the same arithmetic from either.
+// count and rounds once.  Both operators include this file, so a pixel of one source gets the same arithmetic from either.  The
+// footprint resampling (warp_area.hip) shares the projection and calls it on the host too, to estimate the size of a footprint.
 #pragma once
 #include <math.h>
 
@@ -22,7 +23,7 @@ struct Krueger {
 };
 
 // sum_j c[j-1] sin(2 j (xi + i eta)), j = 1..6 -> (real, imaginary) part
-__device__ __forceinline__ void clenshaw_sin(const double* c, double xi, double eta, double& re, double& im) {
+__host__ __device__ __forceinline__ void clenshaw_sin(const double* c, double xi, double eta, double& re, double& im) {
   double s0, c0;
   sincos(2.0 * xi, &s0, &c0);
   const double sh0 = sinh(2.0 * eta), ch0 = cosh(2.0 * eta);
@@ -40,14 +41,14 @@ __device__ __forceinline__ void clenshaw_sin(const double* c, double xi, double 
 }
 
 // tangent of the conformal latitude from the tangent of the geographic one (Karney 2011 eq. 7-9)
-__device__ __forceinline__ double taup_of(double tau, double e) {
+__host__ __device__ __forceinline__ double taup_of(double tau, double e) {
   const double t1 = sqrt(1.0 + tau * tau);
   const double sig = sinh(e * atanh(e * tau / t1));
   return tau * sqrt(1.0 + sig * sig) - sig * t1;
 }
 
 // longitude / latitude in degrees -> easting / northing; false outside 30 degrees of the central meridian or |lat| > 90
-__device__ __forceinline__ bool tm_forward(const Krueger& k, double lon0, double fn, double lon, double lat, double& E, double& N) {
+__host__ __device__ __forceinline__ bool tm_forward(const Krueger& k, double lon0, double fn, double lon, double lat, double& E, double& N) {
   const double dl = remainder(lon - lon0, 360.0);
   if (!(fabs(dl) <= WARP_MAX_DLON) || !(fabs(lat) <= 90.0)) return false;
   const double taup = taup_of(tan(lat * WARP_DEG), k.e);
@@ -62,7 +63,7 @@ __device__ __forceinline__ bool tm_forward(const Krueger& k, double lon0, double
 }
 
 // easting / northing -> longitude / latitude in degrees; false outside 30 degrees of the central meridian
-__device__ __forceinline__ bool tm_inverse(const Krueger& k, double lon0, double fn, double E, double N, double& lon, double& lat) {
+__host__ __device__ __forceinline__ bool tm_inverse(const Krueger& k, double lon0, double fn, double E, double N, double& lon, double& lat) {
   const double xi = (N - fn) / k.ka, eta = (E - 500000.0) / k.ka;
   double dx, de;
   clenshaw_sin(k.bet, xi, eta, dx, de);

@@ -156,8 +156,8 @@ def mosaic(sources, dst_gt, dst_crs, dst_shape, rule="first", key=0, resampling=
     who = "mosaic"
     if rule not in RULES:
         raise ValueError(f"{who}: rule {rule!r}; expected one of {sorted(RULES)}")
-    if resampling not in warp.RESAMPLING:
-        raise ValueError(f"{who}: resampling {resampling!r}; expected one of {sorted(warp.RESAMPLING)}")
+    if resampling not in warp.POINT_RESAMPLING:         # the footprint modes of warp.reproject are not part of the mosaic
+        raise ValueError(f"{who}: resampling {resampling!r}; expected one of {sorted(warp.POINT_RESAMPLING)}")
     sources = list(sources)
     N = len(sources)
     if N < 1 or N > MAX_SOURCES:

@@ -233,7 +233,8 @@ def _emit_predict_parts(model, sub, rgb, ratio, template, fill_value, column_ste
 def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_lerp_alpha=1e-4, tile=None, halo=RECEPTIVE_HALO,
                          ratio_bands=None, distributed=None, group=None, rows=None, threads=8, strips=True, georeferenced=False,
                          out_folder=None, geotransform=None, overwrite=False, plumes=False, plume_outlines=False,
-                         label_polygons=None, cog=False, crs=None, resolution=None, resampling="nearest", label_crs=None):
+                         label_polygons=None, cog=False, crs=None, resolution=None, resampling="nearest", label_crs=None,
+                         mask_resampling="nearest"):
     """The notebook path of the reference end to end FROM THE FILE (notebooks/inference_on_raw_EMIT_nc_file.ipynb cells 8-19:
     ``EMITImage(path)`` -> ``mag1c_emit`` -> RGB bands -> rescale -> ``model`` -> threshold): opens the EMIT L1B radiance granule
     (NetCDF-4) with :mod:`starcop_amd.hdf5_reader`, reads ONLY what the pipeline touches -- the contiguous band slice inside
@@ -271,8 +272,10 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
     ``crs`` (with ``georeferenced=True``; ``"utm"`` = the WGS-84 UTM zone of the centre of the orthorectified grid, or an EPSG
     code: 326zz / 327zz / 4326) warps the orthorectified products from the granule's longitude / latitude grid onto the north-up
     :func:`starcop_amd.warp.suggest_grid` of that CRS at ``resolution`` (its units; default: the pixel count along the diagonal is
-    kept) through :func:`starcop_amd.products.regrid`: ``pred_binary`` by ``nearest``, the float32 products by ``resampling``
-    (``"nearest"`` / ``"bilinear"``, or {key: mode}), no-data = the fill value.  The files then carry the tags of that grid
+    kept) through :func:`starcop_amd.products.regrid`: ``pred_binary`` by ``mask_resampling`` (``"nearest"``, or ``"mode"`` / ``"max"``
+    / ``"min"`` over the pixel's footprint), the float32 products by ``resampling`` (``"nearest"`` / ``"bilinear"``, for a
+    ``resolution`` coarser than the granule's ``"average"`` / ``"max"`` / ``"min"`` over the footprint, or {key: mode}), no-data =
+    the fill value.  The files then carry the tags of that grid
     (:func:`starcop_amd.warp.geo_tags`), ``plumes`` has ``x`` / ``y`` in its units and -- for a UTM zone -- ``ime_ppmm_m2`` with
     the pixel area ``resolution ** 2``; ``geotransform`` and ``crs`` of the new grid are added to the dict.  ``label_polygons``
     are taken in the output CRS unless ``label_crs`` names another, in which case they go through
@@ -335,7 +338,7 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
         if crs == "utm":
             h, w = out["mf"].shape
             crs = warp.utm_crs_for(*(float(v) for v in warp.apply_geotransform(gt, w / 2.0, h / 2.0)))
-        gt, crs, area = products.regrid(out, gt, 4326, int(crs), resolution, resampling, fill)
+        gt, crs, area = products.regrid(out, gt, 4326, int(crs), resolution, resampling, fill, mask_resampling=mask_resampling)
         geo = warp.geo_tags(gt, crs)
         out.update(geotransform=gt, crs=crs)
         if label_polygons is not None and label_crs is not None:
@@ -441,7 +444,8 @@ def _envi_geotransform(header):
 @torch.no_grad()
 def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=None, toa_correction_factor=None, solar_altitude=None,
                          normalize_by_acquisition_date=True, tile=None, halo=None, batch=None, plumes=False, overwrite=False,
-                         device="cuda", plume_outlines=False, label_polygons=None, cog=False, north_up=False):
+                         device="cuda", plume_outlines=False, label_polygons=None, cog=False, north_up=False, resolution=None,
+                         resampling="nearest", mask_resampling="nearest"):
     """An orthorectified AVIRIS-NG flight line through the plume model, file to file: ``{folder}/{name}_img`` (ENVI radiance,
     float32) -> the network's input products -> ``model.predict_scene`` -> (with ``out_folder``) ``pred.tif`` / ``predbinary.tif``.
 
@@ -475,7 +479,13 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
     ``pred_binary`` and ``mf`` of such a line are warped (same CRS, ``nearest``: :func:`starcop_amd.products.regrid`) onto the
     north-up :func:`starcop_amd.warp.suggest_grid` at the line's own pixel size before the annotations are made; ``pred.tif``,
     ``predbinary.tif`` and ``label.tif`` carry that grid (a ``mag1c.tif`` the call computes stays on the line's grid, where
-    the next run reads it) and ``geotransform`` / ``crs`` are added to the dict.  A line without rotation is left as it is."""
+    the next run reads it) and ``geotransform`` / ``crs`` are added to the dict.  A line without rotation is left as it is.
+
+    ``resolution`` (with ``north_up=True``; the units of the ``map info``): the three products are put on the north-up grid at THAT
+    pixel size, whether or not the line is rotated -- a 5 m line on a 60 m grid, say -- the float32 ones by ``resampling`` and
+    ``pred_binary`` by ``mask_resampling`` (:func:`starcop_amd.products.regrid`; on a coarser grid the footprint modes
+    ``"average"`` / ``"max"`` / ``"min"`` and ``"mode"`` / ``"max"`` / ``"min"``).  The plume table then has its areas and
+    ``ime_ppmm_m2`` with the new pixel area.  ``resolution=None`` with the default modes is the behaviour described above."""
     import datetime
     import os
     import re
@@ -484,6 +494,8 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
     from .sampling import _nodata
     if plume_outlines and not plumes:
         raise ValueError("aviris_scene_predict: plume_outlines=True needs plumes=True")
+    if not north_up and (resolution is not None or resampling != "nearest" or mask_resampling != "nearest"):
+        raise ValueError("aviris_scene_predict: resolution, resampling and mask_resampling regrid the products; pass north_up=True")
     inputs = aviris_scene_products(model.input_products, normalize_by_acquisition_date)
     for path in (out_folder, mag1c_path, aviris_img_folder):
         if path is not None and str(path).startswith("gs://"):
@@ -549,13 +561,16 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
     out["mf"] = mf
     gt, area = _envi_geotransform(header)
     full, epsg, rotation = io.envi_geotransform(header) if north_up else (None, None, 0.0)
-    if full is not None and rotation != 0.0:
+    if resolution is not None and full is None:
+        raise ValueError("aviris_scene_predict: resolution needs the grid of the flight line: the header has no usable map info")
+    if full is not None and (rotation != 0.0 or resolution is not None):
         from . import warp
         px, py = float(header["map info"][5]), float(header["map info"][6])
-        if px != py:
+        if resolution is None and px != py:
             raise NotImplementedError(f"aviris_scene_predict: north_up with pixels of {px} x {py}: one pixel size per grid")
-        gt, _, area = products.regrid(out, full, epsg, epsg, px, "nearest", {"prediction": mag1c.NODATA, "mf": mf_fill},
-                                      keys=("prediction", "pred_binary", "mf"))
+        gt, _, area = products.regrid(out, full, epsg, epsg, px if resolution is None else float(resolution), resampling,
+                                      {"prediction": mag1c.NODATA, "mf": mf_fill}, keys=("prediction", "pred_binary", "mf"),
+                                      mask_resampling=mask_resampling)
         mf = out["mf"]
         out.update(geotransform=gt, crs=epsg)
         if geo is not None:

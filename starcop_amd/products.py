@@ -87,15 +87,28 @@ def write_rasters(out, table, folder, overwrite=False, geo_tags=None, nodata=Non
 REGRID_KEYS = ("mf", "albedo", "prediction", "ratio", "rgb", "pred_binary", "label_mask")
 
 
-def regrid(out, src_gt, src_crs, dst_crs, resolution=None, resampling="nearest", nodata=None, keys=REGRID_KEYS):
+MASK_RESAMPLING = ("nearest", "mode", "max", "min")
+
+
+def regrid(out, src_gt, src_crs, dst_crs, resolution=None, resampling="nearest", nodata=None, keys=REGRID_KEYS,
+           mask_resampling="nearest", min_coverage=0.5):
     """The raster keys of a prediction dict put on another grid, in place: every ``out[key]`` of ``keys`` that is there -- (H, W) or
     (bands, H, W) device tensors on the grid ``(src_gt, src_crs)`` -- is warped (``warp.reproject``) onto the north-up
-    ``warp.suggest_grid`` of ``dst_crs`` at ``resolution``.  Integer images (masks) are always resampled ``nearest`` with no-data 0;
-    floating-point ones with ``resampling`` -- one mode, or {key: mode} with ``nearest`` for the keys it leaves out -- and ``nodata``
-    (a value, or {key: value}).  Images that share dtype, mode and no-data go through one launch, so the coordinates of a pixel are
-    computed once for all of them.  -> (geotransform of the new grid, its CRS, the area of a pixel in m2 -- None unless the CRS
+    ``warp.suggest_grid`` of ``dst_crs`` at ``resolution``.  Integer images (masks) are resampled with ``mask_resampling``
+    (``nearest``, or on a coarser grid the footprint modes ``mode`` / ``max`` / ``min``) and no-data 0; floating-point ones with
+    ``resampling`` -- one mode of ``warp.reproject`` but ``mode``, or {key: mode} with ``nearest`` for the keys it leaves out -- and
+    ``nodata`` (a value, or {key: value}).  ``min_coverage`` is the footprint rule of the footprint modes (``warp.reproject``).
+    Images that share dtype, mode and no-data go through one launch, so the coordinates of a pixel are computed once for all of
+    them.  -> (geotransform of the new grid, its CRS, the area of a pixel in m2 -- None unless the CRS
     is a UTM zone)"""
     from . import warp
+    if mask_resampling not in MASK_RESAMPLING:
+        raise ValueError(f"regrid: mask_resampling {mask_resampling!r}; expected one of {MASK_RESAMPLING}")
+    for m in (resampling.values() if isinstance(resampling, dict) else [resampling]):
+        if m not in warp.RESAMPLING or m == "mode":
+            raise ValueError(f"regrid: resampling {m!r} for floating-point images; expected one of {sorted(set(warp.RESAMPLING) - {'mode'})}")
+    if not 0.0 <= float(min_coverage) <= 1.0:
+        raise ValueError(f"regrid: min_coverage {min_coverage!r} outside [0, 1]")
     have = [k for k in keys if out.get(k) is not None]
     if not have:
         raise ValueError(f"regrid: none of {keys} in the prediction dict")
@@ -110,11 +123,11 @@ def regrid(out, src_gt, src_crs, dst_crs, resolution=None, resampling="nearest",
             mode = resampling.get(k, "nearest") if isinstance(resampling, dict) else resampling
             fill = nodata.get(k) if isinstance(nodata, dict) else nodata
         else:
-            mode, fill = "nearest", 0
+            mode, fill = mask_resampling, 0
         groups.setdefault((t.dtype, mode, 0 if fill is None else fill), []).append(k)
     for (_, mode, fill), ks in groups.items():
         planes = [p for k in ks for p in ([out[k]] if out[k].dim() == 2 else out[k].unbind(0))]
-        res = warp.reproject(planes, src_gt, src_crs, dst_gt, dst_crs, dst_shape, mode, fill)
+        res = warp.reproject(planes, src_gt, src_crs, dst_gt, dst_crs, dst_shape, mode, fill, min_coverage)
         i = 0
         for k in ks:
             n = 1 if out[k].dim() == 2 else out[k].shape[0]

@@ -7,7 +7,8 @@ Mercator by the Krueger series to order n^6 (Karney 2011) where the CRS differ, 
 planes of a call there, ``nearest`` (a word copy: bit-equal to a numpy gather for every dtype) or ``bilinear`` (float32; fp64
 weights renormalised over the samples that are inside, not NaN and not no-data; one rounding).  Both modes give a pixel the plane's
 no-data when it lies outside the source; ``bilinear`` also when its nearest source pixel does not count, so the two have the same
-valid pixels.  There is no CPU fallback for the rasters.
+valid pixels.  ``average``, ``max``, ``min`` and ``mode`` (``sc_warp_area``) reduce the source pixels under the destination pixel's
+footprint instead -- what a coarser destination needs; :func:`reproject` states the rule.  There is no CPU fallback for the rasters.
 
 :func:`transform_points` is the host restatement of the projection step, the same series in numpy; bounds (:func:`suggest_grid`),
 polygons (:func:`transform_polygons`) and the tests use it.  Datums other than WGS-84, polar stereographic and the Norway / Svalbard
@@ -20,11 +21,15 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import check as _check, sc_warp_args, stream
+from ._lib import check as _check, sc_warp_area_args, sc_warp_args, stream
 from .ortho import _fill_bits, _numpy_dtype
 
 MAX_PLANES = _lib.WARP_MAX_PLANES
-RESAMPLING = {"nearest": _lib.WARP_NEAREST, "bilinear": _lib.WARP_BILINEAR}
+RESAMPLING = {"nearest": _lib.WARP_NEAREST, "bilinear": _lib.WARP_BILINEAR, "average": _lib.WARP_AREA_AVERAGE,
+              "max": _lib.WARP_AREA_MAX, "min": _lib.WARP_AREA_MIN, "mode": _lib.WARP_AREA_MODE}
+POINT_RESAMPLING = ("nearest", "bilinear")        # look at the destination pixel's centre (sc_warp)
+AREA_RESAMPLING = ("average", "max", "min", "mode")      # reduce the source pixels under its footprint (sc_warp_area)
+AREA_VARIANTS = {None: 0, "thread": _lib.WARP_AREA_THREAD, "lanes": _lib.WARP_AREA_LANES}
 MAX_DLON = 30.0            # degrees from a zone's central meridian beyond which a point is outside (NaN)
 NEWTON_STEPS = 3            # of the conformal-latitude inversion, as in the kernel: 2 reach the last place for |lat| < 89.999, one spare
 
@@ -281,6 +286,45 @@ def _launch(planes, nd, bits, src_shape, inv, s_code, d_code, dst_gt, dst_shape,
         _check(lib.sc_warp(a, stream()))
 
 
+def _area_args(src_shape, inv, s_code, d_code, dst_gt, dst_shape, variant):
+    a = sc_warp_area_args()
+    for i in range(6):
+        a.dst_gt[i], a.src_inv[i] = dst_gt[i], inv[i]
+    a.dst_crs, a.src_crs = d_code, s_code
+    a.out_h, a.out_w = dst_shape
+    a.src_h, a.src_w = src_shape
+    if variant not in AREA_VARIANTS:
+        raise ValueError(f"variant {variant!r}; expected None (chosen by the library), 'thread' or 'lanes'")
+    a.variant = AREA_VARIANTS[variant]
+    return a
+
+
+def _launch_area(planes, nd, bits, src_shape, inv, s_code, d_code, dst_gt, dst_shape, mode, min_coverage, out, cov, boxes, variant):
+    lib = _lib.load()
+    P = len(planes)
+    for p0 in range(0, max(P, 1), MAX_PLANES):
+        n = min(MAX_PLANES, P - p0)
+        a = _area_args(src_shape, inv, s_code, d_code, dst_gt, dst_shape, variant)
+        a.P, a.elem_bytes, a.mode, a.min_coverage = n, nd.itemsize if nd is not None else 0, mode, min_coverage
+        for k in range(n):
+            t = planes[p0 + k]
+            a.src[k] = t.data_ptr()
+            a.row_stride[k], a.col_stride[k] = t.stride()
+            a.nodata_bits[k] = bits[p0 + k]
+        a.out = out[p0].data_ptr() if n else None
+        a.coverage = cov[p0].data_ptr() if cov is not None and n else None
+        a.boxes = boxes.data_ptr() if boxes is not None and p0 == 0 else None        # the boxes are the same for every chunk
+        _check(lib.sc_warp_area(a, stream()))
+
+
+def _area_dtype_check(resampling, dt):
+    """the dtype refusals of the footprint modes (``dt``: a numpy or torch dtype); before any device use"""
+    name = str(dt).replace("torch.", "")
+    ok = {"average": ("float32",), "mode": ("uint8",), "max": ("float32", "uint8"), "min": ("float32", "uint8")}[resampling]
+    if name not in ok:
+        raise ValueError(f"reproject: {resampling} resampling is defined for {' and '.join(ok)}, not {name}")
+
+
 def _dst_shape(shape, who):
     H, W = (int(v) for v in shape)
     if H < 1 or W < 1 or H * W >= 2 ** 31:
@@ -288,7 +332,8 @@ def _dst_shape(shape, who):
     return H, W
 
 
-def reproject(data, src_gt, src_crs, dst_gt, dst_crs, dst_shape, resampling="nearest", nodata=None):
+def reproject(data, src_gt, src_crs, dst_gt, dst_crs, dst_shape, resampling="nearest", nodata=None, min_coverage=0.5,
+              return_coverage=False, variant=None):
     """``data`` on the grid ``(src_gt, src_crs)`` resampled onto ``(dst_shape, dst_gt, dst_crs)`` on the GPU.
 
     ``data``: a device tensor (H, W) or (P, H, W) with any non-negative strides (a permuted pixel-interleaved cube is read in
@@ -297,9 +342,29 @@ def reproject(data, src_gt, src_crs, dst_gt, dst_crs, dst_shape, resampling="nea
     interpolation.  ``resampling``: ``"nearest"`` for any 1-, 2-, 4- or 8-byte dtype, ``"bilinear"`` for float32 (an integer dtype
     raises ValueError).  Geotransforms are 6 numbers in GDAL order and may be rotated.  Equal CRS codes, or None on both sides,
     take the affine-only path (any integer is allowed there); otherwise both must be 4326 or WGS-84 UTM (NotImplementedError names
-    the pair).  Returns (H_d, W_d) for 2-D input, else (P, H_d, W_d): contiguous, in the dtype of the input.  No CPU fallback."""
+    the pair).  Returns (H_d, W_d) for 2-D input, else (P, H_d, W_d): contiguous, in the dtype of the input.  No CPU fallback.
+
+    The footprint modes, for a destination coarser than the source: ``"average"`` (float32), ``"max"`` / ``"min"`` (float32 and
+    uint8) and ``"mode"`` (uint8; ties to the smallest value).  The four corners of the destination pixel are projected like its
+    centre; their axis-aligned BOUNDING BOX in source pixel coordinates is the footprint (for a rotated pair it is larger than the
+    true quadrilateral, as in GDAL).  A source pixel takes part when it overlaps the box by more than 2^-20 px along both axes
+    (the sliver rule: on a shared lattice the corners land on integers +- 1e-11, and the result must not depend on that noise)
+    and counts when it is not ``nodata`` and not NaN.  ``average`` weighs by overlap area; ``coverage`` is the overlap area of
+    the counting samples over the area of the whole box, the part outside the raster included.  The pixel is data when a sample
+    counts and ``coverage >= min_coverage`` (in [0, 1]; 0: any counting sample suffices), else ``nodata``.
+    ``return_coverage=True`` returns ``(out, coverage)``, coverage float32 in the shape of ``out`` and 0 where the pixel is
+    no-data: ``sum(average * coverage) * pixel area`` conserves an integral.  ``variant`` forces one of the kernel's two mappings
+    (``"thread"`` / ``"lanes"``; tests and measurements)."""
     if resampling not in RESAMPLING:
         raise ValueError(f"reproject: resampling {resampling!r}; expected one of {sorted(RESAMPLING)}")
+    area = resampling in AREA_RESAMPLING
+    if return_coverage and not area:
+        raise ValueError(f"reproject: return_coverage goes with the footprint resampling modes {AREA_RESAMPLING}, not {resampling!r}")
+    if variant is not None and not area:
+        raise ValueError(f"reproject: variant goes with the footprint resampling modes {AREA_RESAMPLING}, not {resampling!r}")
+    min_coverage = float(min_coverage)
+    if not 0.0 <= min_coverage <= 1.0:
+        raise ValueError(f"reproject: min_coverage {min_coverage!r} outside [0, 1]")
     s_code, d_code = _crs_pair(src_crs, dst_crs, "reproject")
     inv, dgt = invert_geotransform(src_gt), _gt6(dst_gt, "reproject")
     Hd, Wd = _dst_shape(dst_shape, "reproject")
@@ -307,6 +372,8 @@ def reproject(data, src_gt, src_crs, dst_gt, dst_crs, dst_shape, resampling="nea
     if host:
         if resampling == "bilinear" and data.dtype != np.float32:
             raise ValueError(f"reproject: bilinear resampling is defined for float32, not {data.dtype}")
+        if area:
+            _area_dtype_check(resampling, data.dtype)
         _lib.require_device()
         data = torch.from_numpy(data if all(s >= 0 for s in data.strides) else np.ascontiguousarray(data)).cuda()
     single = False
@@ -326,6 +393,8 @@ def reproject(data, src_gt, src_crs, dst_gt, dst_crs, dst_shape, resampling="nea
         raise ValueError("reproject: all planes of a call share one dtype, device and shape")
     if resampling == "bilinear" and dt != torch.float32:
         raise ValueError(f"reproject: bilinear resampling is defined for float32, not {dt}")
+    if area:
+        _area_dtype_check(resampling, dt)
     nd = _numpy_dtype(dt)
     if shape[0] < 1 or shape[1] < 1:
         raise ValueError(f"reproject: empty source {shape}")
@@ -341,9 +410,15 @@ def reproject(data, src_gt, src_crs, dst_gt, dst_crs, dst_shape, resampling="nea
     bits = [_fill_bits(v, nd) for v in fills]
     _lib.require_device(planes[0])
     out = torch.empty((P, Hd, Wd), dtype=dt, device=dev)
-    _launch(planes, nd, bits, shape, inv, s_code, d_code, dgt, (Hd, Wd), RESAMPLING[resampling], out, None)
-    res = out[0] if single else out
-    return res.cpu().numpy() if host else res
+    cov = torch.empty((P, Hd, Wd), dtype=torch.float32, device=dev) if return_coverage else None
+    if area:
+        _launch_area(planes, nd, bits, shape, inv, s_code, d_code, dgt, (Hd, Wd), RESAMPLING[resampling], min_coverage, out, cov, None,
+                     variant)
+    else:
+        _launch(planes, nd, bits, shape, inv, s_code, d_code, dgt, (Hd, Wd), RESAMPLING[resampling], out, None)
+    res = [t[0] if single else t for t in ((out, cov) if return_coverage else (out,))]
+    res = [t.cpu().numpy() if host else t for t in res]
+    return tuple(res) if return_coverage else res[0]
 
 
 def source_coords(dst_shape, dst_gt, dst_crs, src_gt, src_crs, src_shape=None, device="cuda"):
@@ -361,7 +436,31 @@ def source_coords(dst_shape, dst_gt, dst_crs, src_gt, src_crs, src_shape=None, d
     return coords
 
 
-def reproject_like(data, src_gt, src_crs, like, resampling="nearest", nodata=None):
+def source_boxes(dst_shape, dst_gt, dst_crs, src_gt, src_crs, device="cuda", variant=None):
+    """The footprint of every destination pixel in source pixel coordinates, as the kernel of the footprint modes computes it: device
+    float64 (4, H, W) = u0, u1, v0, v1, the axis-aligned bounding box of the pixel's four projected corners, NOT clipped to the
+    source; NaN where a corner has no coordinates.  The counterpart of :func:`source_coords`."""
+    s_code, d_code = _crs_pair(src_crs, dst_crs, "source_boxes")
+    inv, dgt = invert_geotransform(src_gt), _gt6(dst_gt, "source_boxes")
+    Hd, Wd = _dst_shape(dst_shape, "source_boxes")
+    _lib.require_device()
+    boxes = torch.empty((4, Hd, Wd), dtype=torch.float64, device=device)
+    _launch_area([], None, [], (1, 1), inv, s_code, d_code, dgt, (Hd, Wd), 0, 0.0, None, None, boxes, variant)
+    return boxes
+
+
+def area_variant(dst_shape, dst_gt, dst_crs, src_gt, src_crs) -> str:
+    """the mapping the library chooses for the footprint modes on a grid pair: ``"thread"`` (one thread per destination pixel; boxes of
+    a few source pixels) or ``"lanes"`` (16 lanes along the source columns of one pixel's box).  Host only."""
+    s_code, d_code = _crs_pair(src_crs, dst_crs, "area_variant")
+    a = _area_args((1, 1), invert_geotransform(src_gt), s_code, d_code, _gt6(dst_gt, "area_variant"), _dst_shape(dst_shape, "area_variant"), None)
+    rc = _lib.load().sc_warp_area_variant(a)
+    if rc < 0:
+        _check(rc)
+    return {v: k for k, v in AREA_VARIANTS.items()}[rc]
+
+
+def reproject_like(data, src_gt, src_crs, like, resampling="nearest", nodata=None, min_coverage=0.5, return_coverage=False):
     """:func:`reproject` onto the grid of another raster: ``like`` is an ``io_formats.TiffInfo`` or the path of a GeoTIFF; its shape
     comes from the image, its geotransform from ModelPixelScale + ModelTiepoint or the ModelTransformation tag, its CRS from the
     GeoKeyDirectory (``io_formats.geo_from_tags``).  A file without georeferencing: ValueError."""
@@ -370,4 +469,4 @@ def reproject_like(data, src_gt, src_crs, like, resampling="nearest", nodata=Non
     gt, epsg = io.geo_from_tags(info)
     if gt is None:
         raise ValueError("reproject_like: the target raster carries no georeferencing tags")
-    return reproject(data, src_gt, src_crs, gt, epsg, (info.height, info.width), resampling, nodata)
+    return reproject(data, src_gt, src_crs, gt, epsg, (info.height, info.width), resampling, nodata, min_coverage, return_coverage)
