@@ -372,6 +372,19 @@ int sc_irt_supported(int Cin, int hidden, int H, int W, int stride);
 int sc_irt_rows(int stage, int N, int H, int W, int stride);        /* stage 0: sc_irt_expand_stats, 1: sc_irt_fwd */
 int sc_irt_bwd_rows(int N, int hidden, int H, int W);
 size_t sc_irt_bwd_workspace_floats(int N, int Cin, int hidden, int H, int W);
+/* HOST only (no GPU touched): the launch geometry of the sweeps above for a block, as the launchers themselves derive it (they read
+ * the same function).  SC_ERR_ARG for a block sc_irt_supported rejects, N <= 0 or N H W hidden >= 2^31.  out[SC_IRT_GEO_FIELDS]:
+ *   [0] NKS          K steps of 16 input channels (template argument of the kernels)
+ *   [1] nch          chunks of 32 hidden channels            [2] ngroups     chunk groups of <= 3 chunks = grid.y of k_irt_bwd
+ *   [3] stats grid   work-groups of k_irt_stats (<= 512)     [4] pixel blocks  flat 32-pixel blocks of N H W (4 per work-group and trip)
+ *   [5] fwd tiles    tiles of 4 x 16 outputs                 [6] fwd per_cu  work-groups per CU at the kernel's LDS size (1..4)
+ *   [7] fwd grid     min(tiles, 256 per_cu) persistent work-groups of k_irt_fwd
+ *   [8] bwd tiles    tiles of 4 x 32 e pixels                [9] tiles_per_wg  consecutive tiles one k_irt_bwd work-group walks
+ *   [10] bwd rows    grid.x of k_irt_bwd = sc_irt_bwd_rows   [11] moments grid  work-groups of k_irt_xmom (<= 256)
+ *   [12] moments K steps  16-pixel steps per k_irt_xmom work-group (4 waves x 4 steps per trip)
+ *   [13] fix grid    work-groups of k_irt_fix (<= 1024) over the pixel blocks of [4]                                            */
+#define SC_IRT_GEO_FIELDS 14
+int sc_irt_geometry(int N, int Cin, int hidden, int H, int W, int stride, int* out);
 int sc_irt_expand_stats(const sc_irt_args* a, float* stats /*[rows][hidden][2]*/, sc_stream stream);
 int sc_irt_fwd(const sc_irt_args* a, float* d_out /*[N,hidden,Ho,Wo] raw*/, float* stats_d /*[rows][hidden][2] or NULL (inference)*/, sc_stream stream);
 int sc_irt_bwd(const sc_irt_args* a, const sc_src* dy_d, double* e_sums /*[rows][hidden][2]*/, double* dw_acc /*[hidden][9]*/,

@@ -456,6 +456,7 @@ SIGNATURES = {
     "sc_irt_rows": (_i, [_i, _i, _i, _i, _i]),
     "sc_irt_bwd_rows": (_i, [_i, _i, _i, _i]),
     "sc_irt_bwd_workspace_floats": (_sz, [_i, _i, _i, _i, _i]),
+    "sc_irt_geometry": (_i, [_i, _i, _i, _i, _i, _i, C.POINTER(_i)]),
     "sc_irt_expand_stats": (_i, [C.POINTER(sc_irt_args), _vp, _vp]),
     "sc_irt_fwd": (_i, [C.POINTER(sc_irt_args), _vp, _vp, _vp]),
     "sc_irt_bwd": (_i, [C.POINTER(sc_irt_args), C.POINTER(sc_src), _vp, _vp, _vp, _vp]),
@@ -582,6 +583,19 @@ def ptr(t):
     if t is None:
         return None
     return C.c_void_p(t.data_ptr())
+
+
+# out[] of sc_irt_geometry, in order (include/starcop_hip.h SC_IRT_GEO_FIELDS)
+IRT_GEO_FIELDS = ("nks", "nch", "ngroups", "stats_grid", "pixel_blocks", "fwd_tiles", "fwd_per_cu", "fwd_grid", "bwd_tiles", "tiles_per_wg",
+                  "bwd_rows", "mom_grid", "mom_ksteps", "fix_grid")
+
+
+def irt_geometry(N, Cin, hidden, H, W, stride=2):
+    """host: the launch geometry of the fused training block (sc_irt_geometry) as a dict; None for a block the library rejects"""
+    out = (C.c_int * len(IRT_GEO_FIELDS))()
+    if load().sc_irt_geometry(N, Cin, hidden, H, W, stride, out) != 0:
+        return None
+    return dict(zip(IRT_GEO_FIELDS, out))
 
 
 def make_src(x, C_, mode=SRC_RAW, act=ACT_NONE, up=0, cst=None, aux=None):

@@ -875,6 +875,8 @@ bool irt_ok(int Cin, int Hd, int H, int W, int S) {
   // the recomputation (tile halos, staging of an equally large d) measured slower than the separate kernels
   return S == 2 && Cin >= 8 && Cin <= 32 && Cin % 8 == 0 && Hd >= 8 && Hd <= 32 * IRT_MAXCH && H >= 4 && W >= 8 && H % 4 == 0 && W % 8 == 0;
 }
+// ---- launch geometry: every grid size, trip count and LDS size below is derived HERE and nowhere else; the launchers, the row
+// queries, the workspace layout and sc_irt_geometry all read this struct
 int irt_stat_wgs(long npb) { const long w = (npb + 3) / 4; return (int)(w < 512 ? w : 512); }
 int irt_fwd_tiles(int N, int H, int W, int S, int* tx, int* ty) {
   const int Ho = (H - 1) / S + 1, Wo = (W - 1) / S + 1;
@@ -882,30 +884,51 @@ int irt_fwd_tiles(int N, int H, int W, int S, int* tx, int* ty) {
   *tx = (Wo + TW - 1) / TW; *ty = (Ho + TH - 1) / TH;
   return N * *tx * *ty;
 }
-int irt_bwd_tiles(int N, int H, int W, int* tx, int* ty) {        // tiles of 4 x 32 e pixels
-  *tx = (W + 31) / 32; *ty = (H + 3) / 4;
-  return N * *tx * *ty;
-}
-// rows (= work-groups along x) of the backward sweep: two 256-thread work-groups per CU over both grid dimensions
-int irt_bwd_rows(int N, int hidden, int H, int W, int* per_out) {
-  int tx, ty;
-  const int nt = irt_bwd_tiles(N, H, W, &tx, &ty);
-  const int ngroups = ((hidden + 31) / 32 + IRT_CG - 1) / IRT_CG;
-  int want = 512 / ngroups;
+struct IrtGeo {
+  int nks, nch, ngroups;                                       // K steps of 16 input channels, chunks of 32 hidden channels, groups of IRT_CG chunks
+  int npb, stat_wgs; size_t stat_lds;                          // k_irt_stats: flat 32-pixel blocks, work-groups (4 blocks per trip)
+  int fwd_tiles, fwd_tx, fwd_ty, fwd_per_cu, fwd_wgs; size_t fwd_lds;      // k_irt_fwd: persistent work-groups over tiles of 4 x 16 outputs
+  int bwd_tiles, bwd_tx, bwd_ty, bwd_per, bwd_rows;            // k_irt_bwd: tiles of 4 x 32 e pixels, tiles per work-group, work-groups along x
+  int mom_wgs, mom_per;                                        // k_irt_xmom: work-groups, 16-pixel K steps per work-group
+  int fix_wgs;                                                 // k_irt_fix: work-groups over the same 32-pixel blocks
+};
+// N > 0 and a block irt_ok accepts; NP = N H W fits 32-bit element counts (irt_fill / sc_irt_geometry check both)
+IrtGeo irt_geo(int N, int Cin, int hidden, int H, int W, int S) {
+  IrtGeo g;
+  g.nks = (Cin + 15) / 16;
+  g.nch = (hidden + 31) / 32;
+  g.ngroups = (g.nch + IRT_CG - 1) / IRT_CG;
+  const long NP = (long)N * H * W;
+  g.npb = (int)((NP + 31) / 32);
+  g.stat_wgs = irt_stat_wgs(g.npb);
+  g.stat_lds = (size_t)g.nch * g.nks * 3 * 64 * 16 + 64 * 4 + (size_t)4 * g.nch * 32 * 2 * 4;
+  g.fwd_tiles = irt_fwd_tiles(N, H, W, S, &g.fwd_tx, &g.fwd_ty);
+  g.fwd_lds = (size_t)(32 * IrtFwdGeo<2>::EPAD + 64 + g.nch * 32 * 12) * 4 + (size_t)g.nch * g.nks * 3 * 64 * 16;
+  // persistent work-groups: as many as fit the chip at this LDS size (160 KB per CU), at most one per tile
+  g.fwd_per_cu = (int)((160 * 1024) / g.fwd_lds);
+  if (g.fwd_per_cu < 1) g.fwd_per_cu = 1;
+  if (g.fwd_per_cu > 4) g.fwd_per_cu = 4;
+  g.fwd_wgs = g.fwd_tiles < 256 * g.fwd_per_cu ? g.fwd_tiles : 256 * g.fwd_per_cu;
+  // rows (= work-groups along x) of the backward sweep: two 256-thread work-groups per CU over both grid dimensions
+  g.bwd_tx = (W + 31) / 32; g.bwd_ty = (H + 3) / 4;
+  g.bwd_tiles = N * g.bwd_tx * g.bwd_ty;
+  int want = 512 / g.ngroups;
   if (want < 1) want = 1;
-  int per = (nt + want - 1) / want;
-  if (per < 1) per = 1;
-  if (per_out) *per_out = per;
-  return (nt + per - 1) / per;
+  g.bwd_per = (g.bwd_tiles + want - 1) / want;
+  if (g.bwd_per < 1) g.bwd_per = 1;
+  g.bwd_rows = (g.bwd_tiles + g.bwd_per - 1) / g.bwd_per;
+  const long k = (NP + 15) / 16, w = (k + 15) / 16;
+  g.mom_wgs = (int)(w < 256 ? (w < 1 ? 1 : w) : 256);
+  g.mom_per = (int)((k + g.mom_wgs - 1) / g.mom_wgs);        // what k_irt_xmom derives from its grid size
+  const int fw = (g.npb + 3) / 4;
+  g.fix_wgs = g.stat_wgs * 2 > fw ? fw : g.stat_wgs * 2;
+  return g;
 }
-int irt_mom_wgs(long NP) { const long k = (NP + 15) / 16; const long w = (k + 15) / 16; return (int)(w < 256 ? (w < 1 ? 1 : w) : 256); }
 
 struct IrtWork { float* gpart; float* mpart; double* mfin; float* qr; float* wpk; float* dxp; size_t total; };
-IrtWork irt_work(float* work, int N, int Cin, int hidden, int H, int W) {
+IrtWork irt_work(float* work, const IrtGeo& g, int N, int Cin, int H, int W) {
   IrtWork w;
-  const size_t rows = (size_t)irt_bwd_rows(N, hidden, H, W, nullptr), nch = (size_t)(hidden + 31) / 32;
-  const size_t ngroups = (nch + IRT_CG - 1) / IRT_CG;
-  const size_t mrows = (size_t)irt_mom_wgs((long)N * H * W);
+  const size_t rows = (size_t)g.bwd_rows, nch = (size_t)g.nch, ngroups = (size_t)g.ngroups, mrows = (size_t)g.mom_wgs;
   size_t o = 0;
   w.gpart = work + o; o += rows * nch * 32 * 32;
   w.mpart = work + o; o += mrows * 33 * 32;
@@ -919,7 +942,7 @@ IrtWork irt_work(float* work, int N, int Cin, int hidden, int H, int W) {
   return w;
 }
 
-int irt_fill(IrtP& p, const sc_irt_args* a, const char* who) {
+int irt_fill(IrtP& p, IrtGeo& g, const sc_irt_args* a, const char* who) {
   SC_REQUIRE(a && a->x.x && a->w_expand && a->w_dw && a->cst_expand, "%s: null argument", who);
   SC_REQUIRE(irt_ok(a->Cin, a->hidden, a->H, a->W, a->stride), "%s: unsupported block (Cin %d, hidden %d, %dx%d, stride %d)", who, a->Cin,
              a->hidden, a->H, a->W, a->stride);
@@ -937,11 +960,12 @@ int irt_fill(IrtP& p, const sc_irt_args* a, const char* who) {
   p.dx = nullptr; p.add0 = nullptr; p.accum = 0; p.wpk = nullptr;
   p.N = a->N; p.Cin = a->Cin; p.Hd = a->hidden; p.H = a->H; p.W = a->W; p.S = a->stride;
   p.Ho = (a->H - 1) / a->stride + 1; p.Wo = (a->W - 1) / a->stride + 1;
-  p.nch = (a->hidden + 31) / 32;
   p.tiles_x = p.tiles_y = p.ntiles = p.tiles_per_wg = 0;
   const long NP = (long)a->N * a->H * a->W;
   SC_REQUIRE(NP * a->hidden < (1L << 31), "%s: tensor too large for 32-bit element counts", who);
-  p.npb = (int)((NP + 31) / 32);
+  g = irt_geo(a->N, a->Cin, a->hidden, a->H, a->W, a->stride);
+  p.nch = g.nch;
+  p.npb = g.npb;
   return SC_OK;
 }
 }  // namespace
@@ -950,25 +974,35 @@ int irt_fill(IrtP& p, const sc_irt_args* a, const char* who) {
 extern "C" int sc_irt_supported(int Cin, int hidden, int H, int W, int stride) { return irt_ok(Cin, hidden, H, W, stride) ? 1 : 0; }
 
 extern "C" int sc_irt_rows(int stage, int N, int H, int W, int stride) {
-  int tx, ty;
-  if (stage == 0) return irt_stat_wgs(((long)N * H * W + 31) / 32);
-  if (stage == 1) return irt_fwd_tiles(N, H, W, stride, &tx, &ty);
+  const IrtGeo g = irt_geo(N, 8, 8, H, W, stride);          // neither row count depends on the channel counts
+  if (stage == 0) return g.stat_wgs;
+  if (stage == 1) return g.fwd_tiles;
   return -1;
 }
-extern "C" int sc_irt_bwd_rows(int N, int hidden, int H, int W) { return irt_bwd_rows(N, hidden, H, W, nullptr); }
+extern "C" int sc_irt_bwd_rows(int N, int hidden, int H, int W) { return irt_geo(N, 8, hidden, H, W, 2).bwd_rows; }
 
 extern "C" size_t sc_irt_bwd_workspace_floats(int N, int Cin, int hidden, int H, int W) {
-  return irt_work(nullptr, N, Cin, hidden, H, W).total + 16;
+  return irt_work(nullptr, irt_geo(N, Cin, hidden, H, W, 2), N, Cin, H, W).total + 16;
+}
+
+extern "C" int sc_irt_geometry(int N, int Cin, int hidden, int H, int W, int stride, int* out) {
+  SC_REQUIRE(out, "sc_irt_geometry: null output");
+  SC_REQUIRE(irt_ok(Cin, hidden, H, W, stride), "sc_irt_geometry: unsupported block (Cin %d, hidden %d, %dx%d, stride %d)", Cin, hidden, H, W, stride);
+  SC_REQUIRE(N > 0 && (long)N * H * W * hidden < (1L << 31), "sc_irt_geometry: N %d: empty or too large for 32-bit element counts", N);
+  const IrtGeo g = irt_geo(N, Cin, hidden, H, W, stride);
+  const int v[SC_IRT_GEO_FIELDS] = {g.nks, g.nch, g.ngroups, g.stat_wgs, g.npb, g.fwd_tiles, g.fwd_per_cu, g.fwd_wgs,
+                                    g.bwd_tiles, g.bwd_per, g.bwd_rows, g.mom_wgs, g.mom_per, g.fix_wgs};
+  for (int i = 0; i < SC_IRT_GEO_FIELDS; ++i) out[i] = v[i];
+  return SC_OK;
 }
 
 extern "C" int sc_irt_expand_stats(const sc_irt_args* a, float* stats, sc_stream stream) {
-  IrtP p;
-  if (int rc = irt_fill(p, a, "sc_irt_expand_stats")) return rc;
+  IrtP p; IrtGeo g;
+  if (int rc = irt_fill(p, g, a, "sc_irt_expand_stats")) return rc;
   SC_REQUIRE(stats, "sc_irt_expand_stats: null stats");
   p.stats = stats;
-  const int nks = (p.Cin + 15) / 16;
-  const int wgs = irt_stat_wgs(p.npb);
-  const size_t lds = (size_t)p.nch * nks * 3 * 64 * 16 + 64 * 4 + (size_t)4 * p.nch * 32 * 2 * 4;
+  const int nks = g.nks, wgs = g.stat_wgs;
+  const size_t lds = g.stat_lds;
   hipStream_t st = (hipStream_t)stream;
   if (nks == 1) { if (int rc = sc_lds_limit(&k_irt_stats<1>, lds, "sc_irt_expand_stats")) return rc; hipLaunchKernelGGL((k_irt_stats<1>), dim3(wgs), dim3(256), lds, st, p); }
   else { if (int rc = sc_lds_limit(&k_irt_stats<2>, lds, "sc_irt_expand_stats")) return rc; hipLaunchKernelGGL((k_irt_stats<2>), dim3(wgs), dim3(256), lds, st, p); }
@@ -977,19 +1011,14 @@ extern "C" int sc_irt_expand_stats(const sc_irt_args* a, float* stats, sc_stream
 }
 
 extern "C" int sc_irt_fwd(const sc_irt_args* a, float* d_out, float* stats_d, sc_stream stream) {
-  IrtP p;
-  if (int rc = irt_fill(p, a, "sc_irt_fwd")) return rc;
+  IrtP p; IrtGeo g;
+  if (int rc = irt_fill(p, g, a, "sc_irt_fwd")) return rc;
   SC_REQUIRE(d_out, "sc_irt_fwd: null output");            // stats_d == NULL: inference (eval-mode constants in cst_expand)
   p.dout = d_out; p.stats = stats_d;
-  p.ntiles = irt_fwd_tiles(p.N, p.H, p.W, p.S, &p.tiles_x, &p.tiles_y);
-  const int nks = (p.Cin + 15) / 16;
+  p.ntiles = g.fwd_tiles; p.tiles_x = g.fwd_tx; p.tiles_y = g.fwd_ty;
+  const int nks = g.nks, wgs = g.fwd_wgs;
   hipStream_t st = (hipStream_t)stream;
-  const size_t lds = (size_t)(32 * IrtFwdGeo<2>::EPAD + 64 + p.nch * 32 * 12) * 4 + (size_t)p.nch * nks * 3 * 64 * 16;
-  // persistent work-groups: as many as fit the chip at this LDS size (160 KB per CU), at most one per tile
-  int per_cu = (int)((160 * 1024) / lds);
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > 4) per_cu = 4;
-  const int wgs = p.ntiles < 256 * per_cu ? p.ntiles : 256 * per_cu;
+  const size_t lds = g.fwd_lds;
   if (nks == 1) { if (int rc = sc_lds_limit(&k_irt_fwd<1, 2>, lds, "sc_irt_fwd")) return rc; hipLaunchKernelGGL((k_irt_fwd<1, 2>), dim3(wgs), dim3(256), lds, st, p); }
   else { if (int rc = sc_lds_limit(&k_irt_fwd<2, 2>, lds, "sc_irt_fwd")) return rc; hipLaunchKernelGGL((k_irt_fwd<2, 2>), dim3(wgs), dim3(256), lds, st, p); }
   SC_LAUNCH_OK("sc_irt_fwd");
@@ -997,18 +1026,17 @@ extern "C" int sc_irt_fwd(const sc_irt_args* a, float* d_out, float* stats_d, sc
 }
 
 extern "C" int sc_irt_bwd(const sc_irt_args* a, const sc_src* dy_d, double* e_sums, double* dw_acc, float* work, sc_stream stream) {
-  IrtP p;
-  if (int rc = irt_fill(p, a, "sc_irt_bwd")) return rc;
+  IrtP p; IrtGeo g;
+  if (int rc = irt_fill(p, g, a, "sc_irt_bwd")) return rc;
   SC_REQUIRE(dy_d && dy_d->x && dy_d->C == p.Hd && dy_d->up == 0, "sc_irt_bwd: dy must be a source of `hidden` channels at the depthwise output's size");
   SC_REQUIRE(dy_d->mode == SC_SRC_RAW || (dy_d->mode == SC_SRC_BNBWD && dy_d->aux && dy_d->cst), "sc_irt_bwd: dy must be a RAW or BNBWD source");
   SC_REQUIRE(e_sums && dw_acc && work && ((uintptr_t)work & 15) == 0, "sc_irt_bwd: null / misaligned output");
   p.dy = to_srcd(*dy_d);
-  p.ntiles = irt_bwd_tiles(p.N, p.H, p.W, &p.tiles_x, &p.tiles_y);
-  const int rows = irt_bwd_rows(p.N, p.Hd, p.H, p.W, &p.tiles_per_wg);
-  const IrtWork w = irt_work(work, p.N, p.Cin, p.Hd, p.H, p.W);
+  p.ntiles = g.bwd_tiles; p.tiles_x = g.bwd_tx; p.tiles_y = g.bwd_ty; p.tiles_per_wg = g.bwd_per;
+  const int rows = g.bwd_rows;
+  const IrtWork w = irt_work(work, g, p.N, p.Cin, p.H, p.W);
   p.esums = e_sums; p.dwacc = dw_acc; p.gpart = w.gpart; p.dx = w.dxp;
-  const int nks = (p.Cin + 15) / 16;
-  const int ngroups = (p.nch + IRT_CG - 1) / IRT_CG;
+  const int nks = g.nks, ngroups = g.ngroups;
   hipStream_t st = (hipStream_t)stream;
   const size_t lds = (size_t)irt_bwd_lds().total;      // (measured with a padded request: the second work-group per CU is lost between 80.0 and 82 KB)
   const dim3 grid(rows, ngroups);
@@ -1026,12 +1054,12 @@ extern "C" int sc_irt_bwd(const sc_irt_args* a, const sc_src* dy_d, double* e_su
 }
 
 extern "C" int sc_irt_xmoments(const sc_irt_args* a, float* work, sc_stream stream) {
-  IrtP p;
-  if (int rc = irt_fill(p, a, "sc_irt_xmoments")) return rc;
+  IrtP p; IrtGeo g;
+  if (int rc = irt_fill(p, g, a, "sc_irt_xmoments")) return rc;
   SC_REQUIRE(work && ((uintptr_t)work & 15) == 0, "sc_irt_xmoments: null / misaligned workspace");
-  const IrtWork w = irt_work(work, p.N, p.Cin, p.Hd, p.H, p.W);
+  const IrtWork w = irt_work(work, g, p.N, p.Cin, p.H, p.W);
   p.mpart = w.mpart;
-  const int wgs = irt_mom_wgs((long)p.N * p.H * p.W);
+  const int wgs = g.mom_wgs;
   hipLaunchKernelGGL(k_irt_xmom, dim3(wgs), dim3(256), (3 * 16 * 64 + 4 * 32) * sizeof(float), (hipStream_t)stream, p);
   SC_LAUNCH_OK("sc_irt_xmoments");
   return SC_OK;
@@ -1039,16 +1067,14 @@ extern "C" int sc_irt_xmoments(const sc_irt_args* a, float* work, sc_stream stre
 
 extern "C" int sc_irt_bwd_fix(const sc_irt_args* a, const float* cst_bwd_expand, float* work, float* dx, const float* add0, int accum,
                               sc_stream stream) {
-  IrtP p;
-  if (int rc = irt_fill(p, a, "sc_irt_bwd_fix")) return rc;
+  IrtP p; IrtGeo g;
+  if (int rc = irt_fill(p, g, a, "sc_irt_bwd_fix")) return rc;
   SC_REQUIRE(cst_bwd_expand && work && dx && ((uintptr_t)work & 15) == 0, "sc_irt_bwd_fix: null / misaligned argument");
-  const IrtWork w = irt_work(work, p.N, p.Cin, p.Hd, p.H, p.W);
+  const IrtWork w = irt_work(work, g, p.N, p.Cin, p.H, p.W);
   p.dx = dx; p.add0 = add0; p.accum = accum;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_irt_qr, dim3(p.Cin), dim3(256), 0, st, p.we, cst_bwd_expand, p.Hd, p.Cin, w.qr);
-  const int nks = (p.Cin + 15) / 16;
-  const int ngroups = (p.nch + IRT_CG - 1) / IRT_CG;
-  const int wgs = irt_stat_wgs(p.npb) * 2 > (p.npb + 3) / 4 ? (p.npb + 3) / 4 : irt_stat_wgs(p.npb) * 2;
+  const int nks = g.nks, ngroups = g.ngroups, wgs = g.fix_wgs;
   if (nks == 1) hipLaunchKernelGGL((k_irt_fix<1>), dim3(wgs), dim3(256), 0, st, p, w.dxp, ngroups, w.qr);
   else hipLaunchKernelGGL((k_irt_fix<2>), dim3(wgs), dim3(256), 0, st, p, w.dxp, ngroups, w.qr);
   SC_LAUNCH_OK("sc_irt_bwd_fix");
@@ -1058,10 +1084,9 @@ extern "C" int sc_irt_bwd_fix(const sc_irt_args* a, const float* cst_bwd_expand,
 extern "C" int sc_irt_wgrad_finalize(const sc_irt_args* a, const float* cst_bwd_expand, float* work, float* dw_expand, sc_stream stream) {
   SC_REQUIRE(a && cst_bwd_expand && work && dw_expand && a->w_expand, "sc_irt_wgrad_finalize: null argument");
   SC_REQUIRE(irt_ok(a->Cin, a->hidden, a->H, a->W, a->stride), "sc_irt_wgrad_finalize: unsupported block");
-  const IrtWork w = irt_work(work, a->N, a->Cin, a->hidden, a->H, a->W);
-  const int rows = irt_bwd_rows(a->N, a->hidden, a->H, a->W, nullptr);
-  const int mrows = irt_mom_wgs((long)a->N * a->H * a->W);
-  const int nch = (a->hidden + 31) / 32;
+  const IrtGeo g = irt_geo(a->N, a->Cin, a->hidden, a->H, a->W, a->stride);
+  const IrtWork w = irt_work(work, g, a->N, a->Cin, a->H, a->W);
+  const int rows = g.bwd_rows, mrows = g.mom_wgs, nch = g.nch;
   hipStream_t st = (hipStream_t)stream;
   hipLaunchKernelGGL(k_irt_msum, dim3(33), dim3(256), 0, st, w.mpart, mrows, w.mfin);
   hipLaunchKernelGGL(k_irt_dwe, dim3(a->hidden), dim3(256), 0, st, w.gpart, rows, nch * 32, w.mfin, a->w_expand, cst_bwd_expand, dw_expand, a->hidden,
