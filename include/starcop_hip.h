@@ -1586,6 +1586,54 @@ int sc_overview_reduce(const sc_overview_args* a, sc_stream stream);
 int sc_tiff_tile_flags(const sc_cog_image* src, int bs, uint8_t* flags /*[tiles] device*/, sc_stream stream);
 int sc_tiff_pack_tiles(const sc_tiff_pack_args* a, sc_stream stream);
 
+/* Exact Euclidean distance transform of binary images, and disc morphology as a threshold on it (starcop_amd/morphology.py).
+ * For a batch (N, H, W) the TARGETS are the pixels with mask != 0 (invert = 0) or mask == 0 (invert = 1); for every pixel p
+ *     d2(p) = min over the targets t of the same image of (row_p - row_t)^2 + (col_p - col_t)^2
+ * an int32, exact, 0 on targets; SC_EDT_FAR everywhere in an image without a target.  Pixels outside the image do not exist.
+ * The mask is uint8, read in place through non-negative element strides: one band of an (H, W, 4) interleaved image has
+ * stride_w = 4.  H, W <= 32767 (H^2 + W^2 fits an int32), H*W < 2^31, N <= 65535.  Outputs, dense [N][H][W], any non-empty subset:
+ *   dist2   int32; with max_dist2 > 0 every value above it is written as SC_EDT_FAR
+ *   dist    float32 (float)(sqrt((double)d2) * pixel_size), one rounding of the fp64 product; +inf where dist2 is SC_EDT_FAR
+ *   within  uint8 d2 <= thresh2: the dilation by the disc {dy^2 + dx^2 <= thresh2} when the targets are the set pixels, the
+ *           complement of the erosion (outside counted as set) when they are the unset ones; with `negate` d2 > thresh2, that
+ *           erosion itself
+ * Two row passes behind the entry point, bit-equal wherever both apply; sc_edt_variant is the rule (a pure host function):
+ *   SC_EDT_WINDOW    when a cap is known -- max_dist2 (the larger of it and thresh2 when `within` is asked for too), or thresh2
+ *                    when `within` is the only output -- and R = floor(sqrt(cap)) <= SC_EDT_WINDOW_MAX_R: minimum over the
+ *                    2 R + 1 columns around the pixel, staged in LDS
+ *   SC_EDT_ENVELOPE  otherwise: the lower envelope of parabolas per row, work independent of the distances
+ * `variant` / `forced`: 0 the rule, or one of the two; SC_ERR_ARG for the window beyond its limit or without a cap.
+ * work: 16-byte aligned device memory of sc_edt_call_workspace_bytes(a) bytes, the size THAT call needs (0 where sc_edt would
+ * refuse its arguments): about 2.3 bytes per pixel of the batch for the window pass, about 10.3 for the envelope.
+ * sc_edt_workspace_bytes(N, H, W) (0 for bad dims) is the larger of the two and serves any call.  thresh2 < SC_EDT_FAR, so that
+ * an image without a target is within nothing.  4 launches (window) or 5 (envelope).  SC_ERR_ARG, before any launch, for bad dims, a null mask, no output, negative strides or caps, a
+ * pixel_size <= 0 with `dist`, or a workspace that is too small.  No atomics: two calls give identical bytes.
+ * sc_label_keep: out[n][i] = keep[n][labels[n][i]] for label values in [0, M], 0 outside -- the sieve's gather; keep is a
+ * device table [N][M + 1] (entry 0 the background).                                                                          */
+#define SC_EDT_FAR 0x7FFFFFFF
+#define SC_EDT_WINDOW_MAX_R 64
+enum sc_edt_row_pass { SC_EDT_WINDOW = 1, SC_EDT_ENVELOPE = 2 };
+typedef struct sc_edt_args {
+  const uint8_t* mask;                            /* element (0, 0) of image 0, device                             */
+  int64_t stride_n, stride_h, stride_w;           /* elements (bytes) between images, rows, columns                */
+  int32_t N, H, W;
+  int32_t invert;                                 /* 0: targets are mask != 0; 1: mask == 0                        */
+  int32_t max_dist2;                              /* 0: no cap                                                     */
+  int32_t thresh2;                                /* for `within`                                                  */
+  int32_t variant;                                /* 0, SC_EDT_WINDOW or SC_EDT_ENVELOPE                           */
+  int32_t negate;                                 /* 1: `within` receives d2 > thresh2 instead                     */
+  double pixel_size;                              /* for `dist`                                                    */
+  int32_t* dist2;                                 /* [N][H][W] device outputs, each may be NULL                    */
+  float* dist;
+  uint8_t* within;
+} sc_edt_args;
+size_t sc_edt_workspace_bytes(int N, int H, int W);
+size_t sc_edt_call_workspace_bytes(const sc_edt_args* a);
+int sc_edt(const sc_edt_args* a, void* work, size_t work_bytes, sc_stream stream);
+int sc_edt_variant(int H, int W, int max_dist2, int forced);
+int sc_label_keep(const int32_t* labels, const uint8_t* keep /*[N][M+1]*/, uint8_t* out, int N, int M, int H, int W,
+                  sc_stream stream);
+
 /* ------------------------------------------------------------------------- */
 /* HOST functions (no device involved): decoders of the on-disk sample format -- one tiled GeoTIFF per product per sample,
  * read by rasterio in the reference (starcop/data/dataset.py:66-76, written by save_cog at sampling_dataset.py:332-355).

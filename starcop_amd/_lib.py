@@ -317,6 +317,18 @@ class sc_tiff_pack_args(C.Structure):
                 ("slots", C.c_void_p), ("slots_host", C.c_void_p), ("out", C.c_void_p), ("out_bytes", C.c_size_t)]
 
 
+EDT_FAR, EDT_WINDOW_MAX_R = 0x7FFFFFFF, 64               # SC_EDT_FAR, SC_EDT_WINDOW_MAX_R
+EDT_WINDOW, EDT_ENVELOPE = 1, 2                          # enum sc_edt_row_pass
+
+
+class sc_edt_args(C.Structure):
+    """distance-transform operands (include/starcop_hip.h: sc_edt_args)"""
+    _fields_ = [("mask", C.c_void_p), ("stride_n", C.c_int64), ("stride_h", C.c_int64), ("stride_w", C.c_int64),
+                ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("invert", C.c_int32),
+                ("max_dist2", C.c_int32), ("thresh2", C.c_int32), ("variant", C.c_int32), ("negate", C.c_int32),
+                ("pixel_size", C.c_double), ("dist2", C.c_void_p), ("dist", C.c_void_p), ("within", C.c_void_p)]
+
+
 _vp, _i, _f, _d, _sz =C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/starcop_hip.h declares
@@ -484,6 +496,11 @@ SIGNATURES = {
     "sc_overview_reduce": (_i, [C.POINTER(sc_overview_args), _vp]),
     "sc_tiff_tile_flags": (_i, [C.POINTER(sc_cog_image), _i, _vp, _vp]),
     "sc_tiff_pack_tiles": (_i, [C.POINTER(sc_tiff_pack_args), _vp]),
+    "sc_edt_workspace_bytes": (_sz, [_i, _i, _i]),
+    "sc_edt": (_i, [C.POINTER(sc_edt_args), _vp, _sz, _vp]),
+    "sc_edt_call_workspace_bytes": (_sz, [C.POINTER(sc_edt_args)]),
+    "sc_edt_variant": (_i, [_i, _i, _i, _i]),
+    "sc_label_keep": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "sc_tiff_lzw_decode": (_i, [_vp, _sz, _vp, _sz, C.POINTER(C.c_size_t)]),
     "sc_tiff_unpredict": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp]),
 }

@@ -1,0 +1,189 @@
+"""Mask morphology on the GPU: the exact Euclidean distance transform of binary images and what is a threshold on it.
+
+``distance_transform`` is ``sc_edt`` (include/starcop_hip.h): int32 squared distances or float32 distances to the nearest set (or
+unset) pixel.  ``dilate`` / ``erode`` by a disc of any radius are one ``sc_edt`` call each that stores only the thresholded
+mask; ``opening`` / ``closing`` are their compositions.  ``remove_small_objects`` is the sieve: ``connected_components``, a device
+bincount of the labels and one gather (``sc_label_keep``).
+
+Every function takes an (H, W) or (N, H, W) mask, numpy or a device tensor of any dtype; anything but uint8 / bool becomes
+``x != 0``, uint8 device tensors are read in place through their strides (a band of an (H, W, 4) image, a ``[:, ::2]`` view).
+numpy in, numpy out; device in, device out.  There is no CPU fallback.
+
+Conventions.  The disc of radius r is {(dy, dx): dy^2 + dx^2 <= floor(r * r)}; r = 1 is the 3 x 3 cross (skimage's ``disk(1)``).
+Dilation sees no pixels outside the image.  Erosion treats the outside as set (skimage's border convention): a pixel survives
+when it is set and no UNSET pixel inside the image lies within r of it."""
+import math
+
+import numpy as np
+import torch
+
+from . import _lib
+from ._lib import check, ptr, stream
+from .mask_creation import connected_components
+
+FAR = _lib.EDT_FAR
+WINDOW_MAX_R = _lib.EDT_WINDOW_MAX_R
+VARIANTS = {None: 0, "window": _lib.EDT_WINDOW, "envelope": _lib.EDT_ENVELOPE}
+_D2_MAX = FAR - 1
+
+
+def _check_mask(mask, who):
+    if not isinstance(mask, (np.ndarray, torch.Tensor)):
+        raise ValueError(f"{who}: expected a numpy array or a tensor, got {type(mask).__name__}")
+    if mask.ndim not in (2, 3):
+        raise ValueError(f"{who}: expected an (H, W) or (N, H, W) mask, got {tuple(mask.shape)}")
+    H, W = mask.shape[-2:]
+    if not (0 < H <= 32767 and 0 < W <= 32767) or mask.shape[0] == 0:
+        raise ValueError(f"{who}: bad shape {tuple(mask.shape)} (H, W in 1..32767, no empty batch)")
+
+
+def _cap(v, who, what):
+    """floor(v * v) of a radius / distance in pixels, in float64 with no epsilon, kept inside the int32 range of d2"""
+    v = float(v)
+    if not v >= 0.0:
+        raise ValueError(f"{who}: {what} {v!r} must be >= 0")
+    sq = v * v
+    return _D2_MAX if sq >= _D2_MAX else int(math.floor(sq))
+
+
+def _device_u8(mask):
+    """-> ((N, H, W) device uint8 view -- in place for uint8 / bool device tensors --, was (H, W), was numpy)"""
+    host = isinstance(mask, np.ndarray)
+    if host:
+        m = np.ascontiguousarray(mask if mask.dtype == np.uint8 else (mask != 0).astype(np.uint8))
+        _lib.require_device()
+        m = torch.from_numpy(m).cuda()
+    else:
+        _lib.require_device(mask)
+        m = mask
+        if m.dtype == torch.bool:
+            m = m.view(torch.uint8)
+        elif m.dtype != torch.uint8:
+            m = (m != 0).to(torch.uint8)
+    single = m.dim() == 2
+    return (m[None] if single else m), single, host
+
+
+def _edt(m3, invert, want, max_dist2=0, thresh2=0, negate=False, pixel_size=1.0, variant=0):
+    """one ``sc_edt`` call on a device uint8 (N, H, W) view -> the output tensor ``want`` (``dist2``, ``dist`` or ``within``)"""
+    lib = _lib.load()
+    N, H, W = m3.shape
+    dtype = {"dist2": torch.int32, "dist": torch.float32, "within": torch.uint8}[want]
+    out = torch.empty((N, H, W), dtype=dtype, device=m3.device)
+    a = _lib.sc_edt_args()
+    a.mask, a.stride_n, a.stride_h, a.stride_w = m3.data_ptr(), m3.stride(0), m3.stride(1), m3.stride(2)
+    a.N, a.H, a.W, a.invert = N, H, W, int(bool(invert))
+    a.max_dist2, a.thresh2, a.variant, a.negate = int(max_dist2), int(thresh2), int(variant), int(bool(negate))
+    a.pixel_size = float(pixel_size)
+    setattr(a, want, out.data_ptr())
+    wb = lib.sc_edt_call_workspace_bytes(a)                  # what this call's row pass needs; 0 where the call itself will refuse
+    work = torch.empty(max(wb, 1), dtype=torch.uint8, device=m3.device)
+    check(lib.sc_edt(a, ptr(work), wb, stream()))
+    return out
+
+
+def _finish(out, single, host):
+    out = out[0] if single else out
+    return out.cpu().numpy() if host else out
+
+
+def edt_variant(H, W, max_dist2=0, forced=None):
+    """host: which row pass ``sc_edt`` takes for an (H, W) image and a cap on the squared distance (0: none) -> ``"window"`` or
+    ``"envelope"``; ``forced`` one of the two names.  ValueError where the library refuses (the window beyond its limit)."""
+    if forced not in VARIANTS:
+        raise ValueError(f"edt_variant: variant {forced!r}; expected one of None, 'window', 'envelope'")
+    v = _lib.load().sc_edt_variant(int(H), int(W), int(max_dist2), VARIANTS[forced])
+    check(v if v < 0 else 0)
+    return "window" if v == _lib.EDT_WINDOW else "envelope"
+
+
+def distance_transform(mask, to="set", max_distance=None, squared=False, pixel_size=1.0, variant=None):
+    """Exact Euclidean distance of every pixel to the nearest set pixel (``to="set"``) or, scipy's ``distance_transform_edt(mask)``
+    convention, to the nearest unset one (``to="unset"``): float32 ``sqrt(d2) * pixel_size`` rounded once from float64, or with
+    ``squared=True`` the int32 squared distance in pixels.  An image without a target gives ``inf`` / ``INT32_MAX`` everywhere.
+    ``max_distance`` (pixels) caps the result: pixels whose squared distance exceeds ``floor(max_distance * max_distance)`` are
+    ``inf`` / ``INT32_MAX``, and a small cap takes the windowed row pass.  ``variant``: None for the library's rule, ``"window"`` or
+    ``"envelope"`` to force a row pass (tests, benchmark)."""
+    who = "distance_transform"
+    _check_mask(mask, who)
+    if to not in ("set", "unset"):
+        raise ValueError(f"{who}: to={to!r}; expected 'set' or 'unset'")
+    if variant not in VARIANTS:
+        raise ValueError(f"{who}: variant {variant!r}; expected one of None, 'window', 'envelope'")
+    if not float(pixel_size) > 0.0:
+        raise ValueError(f"{who}: pixel_size {pixel_size!r} must be positive")
+    cap = None if max_distance is None else _cap(max_distance, who, "max_distance")
+    if cap == _D2_MAX:
+        cap = None                                           # no distance in an image reaches it
+    if variant == "window" and (cap is None or math.isqrt(cap) > WINDOW_MAX_R):
+        raise ValueError(f"{who}: variant='window' needs a max_distance of at most {WINDOW_MAX_R} pixels")
+    m3, single, host = _device_u8(mask)
+    invert = to == "unset"
+    if cap == 0:                                             # only the targets themselves lie within the cap
+        on = _edt(m3, invert, "within", thresh2=0, variant=VARIANTS[variant])
+        out = torch.where(on != 0, 0, FAR).to(torch.int32) if squared else torch.where(on != 0, 0.0, math.inf).to(torch.float32)
+        return _finish(out, single, host)
+    out = _edt(m3, invert, "dist2" if squared else "dist", max_dist2=cap or 0, pixel_size=pixel_size, variant=VARIANTS[variant])
+    return _finish(out, single, host)
+
+
+def _binary(mask, single, host):
+    return _finish((mask != 0).to(torch.uint8), single, host)
+
+
+def _disc_op(m3, t, erosion):
+    """dilation or erosion of a device uint8 (N, H, W) view by the disc d2 <= t, one ``sc_edt`` call -> device uint8 0 / 1"""
+    if t == 0:
+        return (m3 != 0).to(torch.uint8)
+    return _edt(m3, erosion, "within", thresh2=t, negate=erosion)
+
+
+def _disc_ops(mask, radius, who, steps):
+    """the arguments checked once, then ``steps`` (True: erosion, False: dilation) in order"""
+    _check_mask(mask, who)
+    t = _cap(radius, who, "radius")
+    m3, single, host = _device_u8(mask)
+    for erosion in steps:
+        m3 = _disc_op(m3, t, erosion)
+    return _finish(m3, single, host)
+
+
+def dilate(mask, radius):
+    """Binary dilation of ``mask != 0`` by the disc of ``radius`` pixels -> uint8 0 / 1.  Pixels outside the image are unset."""
+    return _disc_ops(mask, radius, "dilate", (False,))
+
+
+def erode(mask, radius):
+    """Binary erosion of ``mask != 0`` by the disc of ``radius`` pixels -> uint8 0 / 1.  Pixels outside the image count as set."""
+    return _disc_ops(mask, radius, "erode", (True,))
+
+
+def opening(mask, radius):
+    """``dilate(erode(mask, radius), radius)``: removes what the disc does not fit into"""
+    return _disc_ops(mask, radius, "opening", (True, False))
+
+
+def closing(mask, radius):
+    """``erode(dilate(mask, radius), radius)``: fills what the disc does not fit into"""
+    return _disc_ops(mask, radius, "closing", (False, True))
+
+
+def remove_small_objects(mask, min_area, connectivity=2):
+    """The sieve: the components of ``connected_components(mask, connectivity)`` with at least ``min_area`` pixels -> uint8 0 / 1.
+    ``min_area <= 1`` returns the mask as 0 / 1 without labelling.  One read-back (the largest component count sizes the table)."""
+    _check_mask(mask, "remove_small_objects")
+    if connectivity not in (1, 2):
+        raise ValueError(f"remove_small_objects: connectivity {connectivity!r} (1 or 2)")
+    min_area = int(min_area)
+    m3, single, host = _device_u8(mask)
+    if min_area <= 1:
+        return _binary(m3, single, host)
+    labels, counts = connected_components(m3, connectivity=connectivity)
+    N, H, W = labels.shape
+    M = max(int(counts.max().item()), 0)                     # the one read-back: sizes the table
+    area = torch.stack([torch.bincount(labels[n].reshape(-1), minlength=M + 1) for n in range(N)])     # on the int32 labels as they are
+    keep = (area >= min_area).to(torch.uint8)
+    keep[:, 0] = 0
+    out = torch.empty((N, H, W), dtype=torch.uint8, device=labels.device)
+    check(_lib.load().sc_label_keep(ptr(labels), ptr(keep.contiguous()), ptr(out), N, M, H, W, stream()))
+    return _finish(out, single, host)

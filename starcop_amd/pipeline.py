@@ -234,7 +234,7 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
                          ratio_bands=None, distributed=None, group=None, rows=None, threads=8, strips=True, georeferenced=False,
                          out_folder=None, geotransform=None, overwrite=False, plumes=False, plume_outlines=False,
                          label_polygons=None, cog=False, crs=None, resolution=None, resampling="nearest", label_crs=None,
-                         mask_resampling="nearest"):
+                         mask_resampling="nearest", clean=None, match_tolerance_px=0.0):
     """The notebook path of the reference end to end FROM THE FILE (notebooks/inference_on_raw_EMIT_nc_file.ipynb cells 8-19:
     ``EMITImage(path)`` -> ``mag1c_emit`` -> RGB bands -> rescale -> ``model`` -> threshold): opens the EMIT L1B radiance granule
     (NetCDF-4) with :mod:`starcop_amd.hdf5_reader`, reads ONLY what the pipeline touches -- the contiguous band slice inside
@@ -279,8 +279,16 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
     (:func:`starcop_amd.warp.geo_tags`), ``plumes`` has ``x`` / ``y`` in its units and -- for a UTM zone -- ``ime_ppmm_m2`` with
     the pixel area ``resolution ** 2``; ``geotransform`` and ``crs`` of the new grid are added to the dict.  ``label_polygons``
     are taken in the output CRS unless ``label_crs`` names another, in which case they go through
-    :func:`starcop_amd.warp.transform_polygons`.  The default ``crs=None`` changes nothing."""
+    :func:`starcop_amd.warp.transform_polygons`.  The default ``crs=None`` changes nothing.
+
+    ``clean`` (with ``georeferenced=True``): a dict of :func:`starcop_amd.products.clean` keyword arguments -- ``open_radius``,
+    ``min_area``, ``exclude``, ``exclude_buffer_px``, ``connectivity`` -- applied to ``pred_binary`` on the product grid (after the
+    regrid) and before the annotations and the files, which then all describe the cleaned mask; ``out["clean"]`` has the pixel
+    counts.  ``match_tolerance_px``: the ``tolerance_px`` of the match against ``label_polygons``.  The defaults add nothing."""
     from .hdf5_reader import H5File
+    products.check_clean(clean, "emit_granule_predict")
+    if clean is not None and not georeferenced:
+        raise ValueError("emit_granule_predict: clean works on the orthorectified products; pass georeferenced=True")
     if crs is not None and not georeferenced:
         raise ValueError("emit_granule_predict: crs warps the orthorectified products; pass georeferenced=True")
     if label_crs is not None and crs is None:
@@ -354,7 +362,10 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
         h, w = out["pred_binary"].shape
         mf = out["mf"][:h, :w]
         mf, prob = torch.where(mf == fill, nan, mf), torch.where(out["prediction"] == fill, nan, out["prediction"])
-    products.annotate(out, out["pred_binary"], mf, prob, gt if georeferenced else None, area, plumes, plume_outlines, label_polygons)
+    if clean is not None:
+        products.clean(out, **clean)
+    products.annotate(out, out["pred_binary"], mf, prob, gt if georeferenced else None, area, plumes, plume_outlines, label_polygons,
+                      match_tolerance_px)
     if out_folder is not None:
         from .ortho import emit_geo_tags
         if geo is None:
@@ -445,7 +456,7 @@ def _envi_geotransform(header):
 def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=None, toa_correction_factor=None, solar_altitude=None,
                          normalize_by_acquisition_date=True, tile=None, halo=None, batch=None, plumes=False, overwrite=False,
                          device="cuda", plume_outlines=False, label_polygons=None, cog=False, north_up=False, resolution=None,
-                         resampling="nearest", mask_resampling="nearest"):
+                         resampling="nearest", mask_resampling="nearest", clean=None, match_tolerance_px=0.0):
     """An orthorectified AVIRIS-NG flight line through the plume model, file to file: ``{folder}/{name}_img`` (ENVI radiance,
     float32) -> the network's input products -> ``model.predict_scene`` -> (with ``out_folder``) ``pred.tif`` / ``predbinary.tif``.
 
@@ -485,7 +496,13 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
     pixel size, whether or not the line is rotated -- a 5 m line on a 60 m grid, say -- the float32 ones by ``resampling`` and
     ``pred_binary`` by ``mask_resampling`` (:func:`starcop_amd.products.regrid`; on a coarser grid the footprint modes
     ``"average"`` / ``"max"`` / ``"min"`` and ``"mode"`` / ``"max"`` / ``"min"``).  The plume table then has its areas and
-    ``ime_ppmm_m2`` with the new pixel area.  ``resolution=None`` with the default modes is the behaviour described above."""
+    ``ime_ppmm_m2`` with the new pixel area.  ``resolution=None`` with the default modes is the behaviour described above.
+
+    ``clean``: a dict of :func:`starcop_amd.products.clean` keyword arguments (``open_radius``, ``min_area``, ``exclude``,
+    ``exclude_buffer_px``, ``connectivity``), applied to ``pred_binary`` after the regrid and before the annotations and the
+    files: ``predbinary.tif``, ``plumes.csv``, ``plumes.geojson`` and ``plume_match`` describe the cleaned mask, ``pred.tif`` is
+    untouched, ``out["clean"]`` has the pixel counts.  ``match_tolerance_px``: the ``tolerance_px`` of the match against
+    ``label_polygons``.  The defaults add nothing and change no byte."""
     import datetime
     import os
     import re
@@ -494,6 +511,7 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
     from .sampling import _nodata
     if plume_outlines and not plumes:
         raise ValueError("aviris_scene_predict: plume_outlines=True needs plumes=True")
+    products.check_clean(clean, "aviris_scene_predict")
     if not north_up and (resolution is not None or resampling != "nearest" or mask_resampling != "nearest"):
         raise ValueError("aviris_scene_predict: resolution, resampling and mask_resampling regrid the products; pass north_up=True")
     inputs = aviris_scene_products(model.input_products, normalize_by_acquisition_date)
@@ -575,7 +593,9 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
         out.update(geotransform=gt, crs=epsg)
         if geo is not None:
             geo = warp.geo_tags(gt, epsg)
-    products.annotate(out, out["pred_binary"], mf, out["prediction"], gt, area, plumes, plume_outlines, label_polygons)
+    if clean is not None:
+        products.clean(out, **clean)
+    products.annotate(out, out["pred_binary"], mf, out["prediction"], gt, area, plumes, plume_outlines, label_polygons, match_tolerance_px)
     if out_folder is not None:
         files += products.write_rasters(out, products.AVIRIS_RASTERS, str(out_folder), overwrite, geo, mag1c.NODATA, cog=cog)
         out["files"] = files + products.write_annotations(out, str(out_folder), overwrite, geo, cog)
@@ -584,7 +604,7 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
 
 @torch.no_grad()
 def mosaic_products(folders, out_folder, crs=None, resolution=None, rule="max", plumes=False, plume_outlines=False, label_polygons=None,
-                    cog=False, overwrite=False, device="cuda"):
+                    cog=False, overwrite=False, device="cuda", clean=None, match_tolerance_px=0.0):
     """The product folders of N scenes -- what ``emit_granule_predict`` / ``aviris_scene_predict`` write -- composed into one:
     ``pred.tif``, ``predbinary.tif`` and, where every folder has one, ``mag1c.tif`` are read (``io_formats.read_tiff``; grid and
     CRS from the GeoTIFF tags, a file without them raises ValueError), put on the union grid of the scenes in ``crs`` (default:
@@ -592,13 +612,16 @@ def mosaic_products(folders, out_folder, crs=None, resolution=None, rule="max", 
     under the same names into ``out_folder``, with ``source.tif``: uint8, the number of the folder a pixel came from, 255 = none,
     the folder names in the GDAL metadata (``source_0``, ...).  ``plumes`` / ``plume_outlines`` / ``label_polygons`` add the files
     of ``products.write_annotations``, made on the mosaic: a plume in the overlap of two scenes is one row.  No-data of the float
-    rasters is each file's GDAL_NODATA of the first folder (default -9999).  -> the dict of ``products.mosaic`` with ``files``."""
+    rasters is each file's GDAL_NODATA of the first folder (default -9999).  ``clean`` (a dict of :func:`starcop_amd.products.clean`
+    keyword arguments) cleans the mosaicked mask before the annotations and the files; ``match_tolerance_px`` is the
+    ``tolerance_px`` of the match against ``label_polygons``.  -> the dict of ``products.mosaic`` with ``files``."""
     import os
     from . import io_formats as io
     from . import warp
     from .sampling import _nodata
     if plume_outlines and not plumes:
         raise ValueError("mosaic_products: plume_outlines=True needs plumes=True")
+    products.check_clean(clean, "mosaic_products")
     folders = [str(f).rstrip("/") for f in folders]
     for path in folders + [out_folder]:
         if str(path).startswith("gs://"):
@@ -634,7 +657,10 @@ def mosaic_products(folders, out_folder, crs=None, resolution=None, rule="max", 
     out = products.mosaic(outs, crs, resolution, rule, "prediction", "nearest", fills, keys=[row.key for row in table])
     gt, epsg = out["geotransform"], out["crs"]
     area = abs(gt[1] * gt[5]) if warp.crs_kind(epsg)[0] == 2 else None
-    products.annotate(out, out["pred_binary"], out.get("mf"), out["prediction"], gt, area, plumes, plume_outlines, label_polygons)
+    if clean is not None:
+        products.clean(out, **clean)
+    products.annotate(out, out["pred_binary"], out.get("mf"), out["prediction"], gt, area, plumes, plume_outlines, label_polygons,
+                      match_tolerance_px)
     geo = warp.geo_tags(gt, epsg)
     out_folder = str(out_folder)
     files = []

@@ -215,20 +215,36 @@ def _read_back(st):
     return out
 
 
-def match_plumes(pred_mask, label_mask, connectivity=2, min_overlap_px=1, min_area=1):
+def match_plumes(pred_mask, label_mask, connectivity=2, min_overlap_px=1, min_area=1, tolerance_px=0.0):
     """Object-level detection score of a predicted against a labelled plume mask (same shape, numpy or device).  Both masks are
     labelled and each is reduced against the other: a predicted plume is a true positive when at least ``min_overlap_px`` of its
     pixels are labelled, a false positive otherwise; a labelled plume with fewer than ``min_overlap_px`` predicted pixels is a
     false negative.  Returns ``{"pred": table, "label": table, "tp", "fp", "fn", "precision", "recall"}``, the tables as
-    ``plume_table`` gives them (with ``overlap_px``), the ratios from ``starcop_amd.metrics`` on [[0, fp], [fn, tp]]."""
-    pred = plume_table(pred_mask, label_mask=label_mask, connectivity=connectivity, min_area=min_area)
-    lab = plume_table(label_mask, label_mask=pred_mask, connectivity=connectivity, min_area=min_area)
+    ``plume_table`` gives them (with ``overlap_px``), the ratios from ``starcop_amd.metrics`` on [[0, fp], [fn, tp]].
+
+    ``tolerance_px`` > 0 matches with a tolerance: each side is reduced against the OTHER mask dilated by the disc of that radius
+    (``morphology.dilate``), so ``overlap_px`` counts the pixels of a plume that lie within ``tolerance_px`` of a pixel of the other
+    mask.  0 is the plain overlap, with no extra launch."""
+    near_label, near_pred = _dilated_others(pred_mask, label_mask, tolerance_px, "match_plumes")
+    pred = plume_table(pred_mask, label_mask=near_label, connectivity=connectivity, min_area=min_area)
+    lab = plume_table(label_mask, label_mask=near_pred, connectivity=connectivity, min_area=min_area)
     tp = int((pred["overlap_px"] >= min_overlap_px).sum())
     fp = len(pred) - tp
     fn = int((lab["overlap_px"] < min_overlap_px).sum())
     cm = torch.tensor([[0, fp], [fn, tp]], dtype=torch.float64)
     return {"pred": pred, "label": lab, "tp": tp, "fp": fp, "fn": fn,
             "precision": float(metrics.precision(cm)), "recall": float(metrics.recall(cm))}
+
+
+def _dilated_others(pred_mask, label_mask, tolerance_px, who):
+    """(label mask, predicted mask) as the other side of a match sees them: dilated by ``tolerance_px``, or as they are at 0"""
+    tol = float(tolerance_px)
+    if not tol >= 0.0:
+        raise ValueError(f"{who}: tolerance_px {tolerance_px!r} must be >= 0")
+    if tol == 0.0:
+        return label_mask, pred_mask
+    from .morphology import dilate
+    return dilate(label_mask, tol), dilate(pred_mask, tol)
 
 
 OUTLINE_FIELDS = ("vertices", "ring_offsets", "ring_label", "ring_area2")
@@ -630,14 +646,16 @@ def rasterize_polygons(polygons, shape, geotransform=None, values=None, item=0):
     return rasterize_launch(rasterize_upload(edges, table, None if identity else vals.astype(np.int32)), (H, W))
 
 
-def burn_and_match(pred_mask, polygons, geotransform=None, connectivity=2, min_overlap_px=1, min_area=1):
+def burn_and_match(pred_mask, polygons, geotransform=None, connectivity=2, min_overlap_px=1, min_area=1, tolerance_px=0.0):
     """The polygons burnt with values 1..P on the grid of ``pred_mask`` and that image scored against the mask -> (burnt, device
-    int32 (H, W); the dict ``match_plumes_polygons`` returns) -- for callers that keep the burnt image as a label mask."""
+    int32 (H, W); the dict ``match_plumes_polygons`` returns) -- for callers that keep the burnt image as a label mask.
+    ``tolerance_px`` as in ``match_plumes``."""
     polys, _ = _polygon_list(polygons)
     P = len(polys)
     burnt = rasterize_polygons(polys, tuple(pred_mask.shape), geotransform=geotransform)
-    pred = plume_table(pred_mask, label_mask=(burnt != 0).to(torch.uint8), connectivity=connectivity, min_area=min_area)
     other = _to_device(pred_mask, burnt.device)
+    near_label, other = _dilated_others(other, (burnt != 0).to(torch.uint8), tolerance_px, "burn_and_match")
+    pred = plume_table(pred_mask, label_mask=near_label, connectivity=connectivity, min_area=min_area)
     st = component_stats(burnt, P, other=other, M=P)
     lab = table_from_stats(_read_back(st), [P], burnt.shape[-1], with_other=True, min_area=min_area)
     tp = int((pred["overlap_px"] >= min_overlap_px).sum())
@@ -648,13 +666,14 @@ def burn_and_match(pred_mask, polygons, geotransform=None, connectivity=2, min_o
                    "precision": float(metrics.precision(cm)), "recall": float(metrics.recall(cm))}
 
 
-def match_plumes_polygons(pred_mask, polygons, geotransform=None, connectivity=2, min_overlap_px=1, min_area=1):
+def match_plumes_polygons(pred_mask, polygons, geotransform=None, connectivity=2, min_overlap_px=1, min_area=1, tolerance_px=0.0):
     """``match_plumes`` against labelled POLYGONS (a sequence of ring lists or the dict of ``plume_outlines``, as
     ``rasterize_polygons`` takes them; with ``geotransform`` in its coordinates): the polygons are burnt with values 1..P on the
     grid of ``pred_mask`` ((H, W), numpy or device) and the labelled objects are the polygons themselves, not the connected
     components of their union -- two polygons that share an edge stay two.  The ``label`` table is ``component_stats`` of the burnt
     image against ``pred_mask``, one row per polygon that burnt at least ``min_area`` pixels (``plume_id`` = its position + 1);
-    the ``pred`` table is ``plume_table(pred_mask, label_mask=burnt != 0)``.  Returns the dict ``match_plumes`` returns."""
+    the ``pred`` table is ``plume_table(pred_mask, label_mask=burnt != 0)``.  ``tolerance_px`` as in ``match_plumes``: each side is
+    reduced against the other dilated by that radius.  Returns the dict ``match_plumes`` returns."""
     if len(pred_mask.shape) != 2:
         raise ValueError(f"match_plumes_polygons: expected an (H, W) mask, got {tuple(pred_mask.shape)}")
-    return burn_and_match(pred_mask, polygons, geotransform, connectivity, min_overlap_px, min_area)[1]
+    return burn_and_match(pred_mask, polygons, geotransform, connectivity, min_overlap_px, min_area, tolerance_px)[1]

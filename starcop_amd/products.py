@@ -212,11 +212,62 @@ def mosaic(outs, dst_crs=None, resolution=None, rule="max", key="prediction", re
     return new
 
 
-def annotate(out, mask, mf, prob, geotransform=None, pixel_area_m2=None, plumes=False, plume_outlines=False, label_polygons=None):
+CLEAN_KEYS = ("open_radius", "min_area", "exclude", "exclude_buffer_px", "connectivity")
+
+
+def check_clean(clean, who):
+    """the ``clean=`` argument of the pipeline calls: None or a dict of ``clean`` keyword arguments (no device involved)"""
+    if clean is None:
+        return
+    if not isinstance(clean, dict) or set(clean) - set(CLEAN_KEYS):
+        raise ValueError(f"{who}: clean must be a dict with keys from {CLEAN_KEYS}, got {clean!r}")
+
+
+def clean(out, open_radius=0.0, min_area=1, exclude=None, exclude_buffer_px=0.0, connectivity=2):
+    """Clean the mask of a prediction dict in place, before ``annotate`` and the writers, so that ``predbinary.tif``, the plume
+    table, the outlines and the match all describe the same plumes.  ``out["pred_binary"]`` ((H, W), device) is rewritten, in
+    this order: ``morphology.opening`` by the disc of ``open_radius`` pixels; ``morphology.remove_small_objects`` below ``min_area``
+    pixels (``connectivity`` as ``connected_components``); cleared wherever ``exclude != 0`` dilated by ``exclude_buffer_px`` is set.
+    ``exclude``: an (H, W) array or device tensor on the grid of the mask (clouds, water, flares), or the path of a single-band
+    GeoTIFF of exactly that shape -- a mask on another grid goes through ``warp.reproject_like`` first.  The defaults do nothing.
+    ``prediction`` and ``mf`` are left alone.  ``out["clean"]`` records the pixels each step removed, ``{"opened_px", "sieved_px",
+    "excluded_px"}``: the four pixel counts come back in one copy (the sieve, when it runs, reads the number of components back on
+    its own to size its table).  -> ``out``"""
+    from . import morphology as mo
+    mask = out["pred_binary"]
+    if mask.dim() != 2:
+        raise ValueError(f"clean: pred_binary must be (H, W), got {tuple(mask.shape)}")
+    if not float(open_radius) >= 0.0 or not float(exclude_buffer_px) >= 0.0:
+        raise ValueError(f"clean: open_radius {open_radius!r} and exclude_buffer_px {exclude_buffer_px!r} must be >= 0")
+    if connectivity not in (1, 2):
+        raise ValueError(f"clean: connectivity {connectivity!r} (1 or 2)")
+    if isinstance(exclude, (str, os.PathLike)):
+        exclude = io.read_tiff(str(exclude))
+        if exclude.ndim == 3 and exclude.shape[0] == 1:
+            exclude = exclude[0]
+    if exclude is not None and tuple(exclude.shape) != tuple(mask.shape):
+        raise ValueError(f"clean: exclude has shape {tuple(exclude.shape)}, the mask {tuple(mask.shape)}: put it on the product grid "
+                         "first (warp.reproject_like)")
+    m0 = mo.dilate(mask, 0)                                  # the mask as 0 / 1
+    m1 = mo.opening(m0, open_radius) if float(open_radius) > 0.0 else m0
+    m2 = mo.remove_small_objects(m1, min_area, connectivity) if int(min_area) > 1 else m1
+    m3 = m2
+    if exclude is not None:
+        if isinstance(exclude, np.ndarray):
+            exclude = torch.from_numpy(np.ascontiguousarray(exclude != 0).view(np.uint8)).to(mask.device)
+        m3 = m2 & (mo.dilate(exclude, exclude_buffer_px) ^ 1)
+    n = torch.stack([m.sum(dtype=torch.int64) for m in (m0, m1, m2, m3)]).cpu().tolist()      # the one read-back
+    out["pred_binary"] = m3.to(mask.dtype)
+    out["clean"] = {"opened_px": n[0] - n[1], "sieved_px": n[1] - n[2], "excluded_px": n[2] - n[3]}
+    return out
+
+
+def annotate(out, mask, mf, prob, geotransform=None, pixel_area_m2=None, plumes=False, plume_outlines=False, label_polygons=None,
+             match_tolerance_px=0.0):
     """The plume annotations of a prediction dict, as asked for: ``plumes`` (``plumes.plume_table`` of ``mask`` with ``mf`` as mag1c
     and ``prob`` as probability), ``plume_outlines`` of the same mask in the same coordinates, and for ``label_polygons`` (a
     ``.geojson`` path or polygons) ``label_mask``, the polygons burnt into the grid of ``mask`` (device uint8), and ``plume_match``,
-    the same burnt image scored against the mask."""
+    the same burnt image scored against the mask, with ``match_tolerance_px`` as the ``tolerance_px`` of ``plumes.burn_and_match``."""
     from . import plumes as pl
     if plumes:
         out["plumes"] = pl.plume_table(mask, mag1c=mf, prob=prob, geotransform=geotransform, pixel_area_m2=pixel_area_m2)
@@ -225,7 +276,7 @@ def annotate(out, mask, mf, prob, geotransform=None, pixel_area_m2=None, plumes=
     if label_polygons is not None:
         if isinstance(label_polygons, (str, os.PathLike)):
             label_polygons = pl.read_plumes(label_polygons)[1]
-        burnt, match = pl.burn_and_match(mask, label_polygons, geotransform)
+        burnt, match = pl.burn_and_match(mask, label_polygons, geotransform, tolerance_px=match_tolerance_px)
         out["label_mask"], out["plume_match"] = (burnt != 0).to(torch.uint8), match
 
 
