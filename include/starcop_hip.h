@@ -473,13 +473,26 @@ int sc_stem_conv_fwd(const sc_src* in, const float* w /*[32][Cin][3][3]*/, float
 /* the kernel sc_stem_conv_fwd launches for (Cin, input width, 16-byte alignment of out); SC_ERR_ARG for Cin outside [1,16] */
 enum sc_stem_kernel { SC_STEM_K_MFMA4 = 0, SC_STEM_K_VALU4 = 1, SC_STEM_K_VALU8 = 2, SC_STEM_K_VALU16 = 3 };
 int sc_stem_fwd_kernel(int Cin, int Win, int out_aligned16);
+/* HOST: the instantiation sc_stem_conv_wgrad launches, k_stem_wgrad<NJB>: NJB = the 16-column blocks of the (ci, tap) axis a wave
+ * carries -- 3 for Cin <= 5 (9 Cin <= 48), 5 for Cin 6..8; SC_ERR_ARG for Cin outside [1,8].  The entry point dispatches on this value. */
+int sc_stem_wgrad_njb(int Cin);
+/* HOST: the work-groups of that launch = the partial rows [32][Cin][9] it leaves: min(N x tiles of 4 x 32 output pixels, 1024); with
+ * more tiles than that a work-group walks several (tile += rows).  The rows are summed 16 at a time: no intermediate level up to 16
+ * rows, one up to 256, two above.  SC_ERR_ARG for a non-positive size. */
+int sc_stem_wgrad_rows(int N, int Hin, int Win);
 size_t sc_stem_wgrad_workspace_floats(int N, int Cin, int Hin, int Win);
 int sc_stem_conv_wgrad(const sc_src* dy, const sc_src* in, float* part, size_t part_floats,
                        float* dw, int N, int Cin, int Hin, int Win, sc_stream stream);
 
-/* segmentation head: conv 3x3 pad 1, Cin -> 1, bias (fwd/dgrad: Cin <= 32; wgrad: Cin in {8, 16}) */
+/* segmentation head: conv 3x3 pad 1, Cin -> 1, bias (fwd/dgrad/wgrad: Cin <= 32; the one-sweep backward: Cin = 16) */
 int sc_head_conv_fwd(const sc_src* in, const float* w /*[1][Cin][3][3]*/, const float* bias,
                      float* out, int N, int Cin, int H, int W, sc_stream stream);
+/* HOST: the kernel sc_head_conv_fwd launches for (Cin, width, 16-byte alignment of in->x, of out): the generic kernel (8 x 32 tiles,
+ * any Cin) unless Cin == 16; for Cin == 16 the register-blocked 16 x 64 tile with 16-byte staging and stores when W % 4 == 0 and both
+ * pointers are aligned (k_head_fwd16v), else with 4-byte staging (k_head_fwd16).  SC_ERR_ARG for Cin outside [1,32] or W < 1.  The
+ * entry point dispatches on this value. */
+enum sc_head_kernel { SC_HEAD_K_GENERIC = 0, SC_HEAD_K_FWD16 = 1, SC_HEAD_K_FWD16V = 2 };
+int sc_head_fwd_kernel(int Cin, int W, int in_aligned16, int out_aligned16);
 /* K-class head, 1 <= K <= 8, Cin <= 32, same source modes (RAW / AFFINE, no upsample): smp.Unet(classes=K) followed by
  * torch.argmax(dim=1).type(uint8) (starcop/sentinel2/models.py:63-78; classes = settings.model.num_classes,
  * models/model_module.py:244-251).  At least one of logits / classes is non-NULL; with logits == NULL no logit is stored.  classes

@@ -362,6 +362,9 @@ SIGNATURES = {
     "sc_cast_f64_f32_batch": (_i, [_vp, _i, _vp]),
     "sc_stem_conv_fwd": (_i, [C.POINTER(sc_src), _vp, _vp, _i, _i, _i, _i, _vp, _vp]),
     "sc_stem_fwd_kernel": (_i, [_i, _i, _i]),
+    "sc_stem_wgrad_njb": (_i, [_i]),
+    "sc_stem_wgrad_rows": (_i, [_i, _i, _i]),
+    "sc_head_fwd_kernel": (_i, [_i, _i, _i, _i]),
     "sc_stem_wgrad_workspace_floats": (_sz, [_i, _i, _i, _i]),
     "sc_stem_conv_wgrad": (_i, [C.POINTER(sc_src), C.POINTER(sc_src), _vp, _sz, _vp, _i, _i, _i, _i, _vp]),
     "sc_head_conv_fwd": (_i, [C.POINTER(sc_src), _vp, _vp, _vp, _i, _i, _i, _i, _vp]),

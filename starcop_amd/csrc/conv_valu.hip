@@ -1448,7 +1448,7 @@ __global__ __launch_bounds__(256, 4) void k_head_fwd16(const SrcD in, const floa
   const int y = y0 + py, x = x0 + 4 * pxg;
   if (y >= H) return;
   float* op = out + (size_t)n * H * W + (size_t)y * W + x;
-  if (x + 3 < W && ((W & 3) == 0)) {
+  if (x + 3 < W && ((W & 3) == 0) && ((uintptr_t)op & 15) == 0) {      // (this kernel also takes outputs that are not 16-byte aligned)
     *reinterpret_cast<float4*>(op) = make_float4(acc[0], acc[1], acc[2], acc[3]);
   } else {
 #pragma unroll
@@ -2375,9 +2375,21 @@ extern "C" int sc_stem_fwd_kernel(int Cin, int Win, int out_aligned16) {
   return Cin <= STEM_MAXCI ? SC_STEM_K_VALU8 : SC_STEM_K_VALU16;
 }
 
+// which instantiation sc_stem_conv_wgrad launches: the 16-column blocks of the (ci, tap) axis a wave carries
+extern "C" int sc_stem_wgrad_njb(int Cin) {
+  if (Cin < 1 || Cin > STEM_MAXCI) return SC_ERR_ARG;
+  return (Cin * 9 + 15) / 16 <= 3 ? 3 : 5;
+}
+
+// the work-groups of that launch = the partial rows it leaves for sc_reduce_rows
+extern "C" int sc_stem_wgrad_rows(int N, int Hin, int Win) {
+  if (N < 1 || Hin < 1 || Win < 1) return SC_ERR_ARG;
+  return stem_blocks(N, (Hin - 1) / 2 + 1, (Win - 1) / 2 + 1);
+}
+
 extern "C" size_t sc_stem_wgrad_workspace_floats(int N, int Cin, int Hin, int Win) {
-  const int Hout = (Hin - 1) / 2 + 1, Wout = (Win - 1) / 2 + 1;
-  const int nb = stem_blocks(N, Hout, Wout);          // one partial row per work-group
+  const int nb = sc_stem_wgrad_rows(N, Hin, Win);     // one partial row per work-group
+  if (nb < 0) return 0;
   const size_t E = (size_t)STEM_CO * Cin * 9;
   return (size_t)nb * E + sc_reduce_scratch_floats(nb, E);
 }
@@ -2386,16 +2398,23 @@ extern "C" int sc_stem_conv_wgrad(const sc_src* dy, const sc_src* in, float* par
                                   int Cin, int Hin, int Win, sc_stream stream) {
   SC_REQUIRE(dy && in && in->C == Cin && dy->C == STEM_CO, "sc_stem_conv_wgrad: bad source channels");
   SC_REQUIRE(Cin >= 1 && Cin <= STEM_MAXCI, "sc_stem_conv_wgrad: Cin must be in [1,%d]", STEM_MAXCI);
+  SC_REQUIRE(N > 0 && Hin > 0 && Win > 0, "sc_stem_conv_wgrad: bad shape");
   SC_REQUIRE(part_floats >= sc_stem_wgrad_workspace_floats(N, Cin, Hin, Win), "sc_stem_conv_wgrad: workspace too small");
   const int Hout = (Hin - 1) / 2 + 1, Wout = (Win - 1) / 2 + 1;
-  const int nb = stem_blocks(N, Hout, Wout);
+  const int nb = sc_stem_wgrad_rows(N, Hin, Win);
   const size_t E = (size_t)STEM_CO * Cin * 9;
   hipStream_t st = (hipStream_t)stream;
-  const int njb = (Cin * 9 + 15) / 16;
-  if (njb <= 3) hipLaunchKernelGGL((k_stem_wgrad<3>), dim3(nb), dim3(256), 0, st, to_srcd(*dy), to_srcd(*in), part, N, Cin, Hin, Win, Hout, Wout);
+  if (sc_stem_wgrad_njb(Cin) == 3) hipLaunchKernelGGL((k_stem_wgrad<3>), dim3(nb), dim3(256), 0, st, to_srcd(*dy), to_srcd(*in), part, N, Cin, Hin, Win, Hout, Wout);
   else hipLaunchKernelGGL((k_stem_wgrad<5>), dim3(nb), dim3(256), 0, st, to_srcd(*dy), to_srcd(*in), part, N, Cin, Hin, Win, Hout, Wout);
   SC_LAUNCH_OK("sc_stem_conv_wgrad");
   return sc_reduce_rows(part, nb, E, part + (size_t)nb * E, dw, st);
+}
+
+// which kernel sc_head_conv_fwd launches (its own dispatch rule)
+extern "C" int sc_head_fwd_kernel(int Cin, int W, int in_aligned16, int out_aligned16) {
+  if (Cin < 1 || Cin > HEAD_MAXCI || W < 1) return SC_ERR_ARG;
+  if (Cin != 16) return SC_HEAD_K_GENERIC;
+  return (W % 4 == 0 && in_aligned16 && out_aligned16) ? SC_HEAD_K_FWD16V : SC_HEAD_K_FWD16;
 }
 
 extern "C" int sc_head_conv_fwd(const sc_src* in, const float* w, const float* bias, float* out, int N, int Cin,
@@ -2404,13 +2423,11 @@ extern "C" int sc_head_conv_fwd(const sc_src* in, const float* w, const float* b
   SC_REQUIRE(Cin >= 1 && Cin <= HEAD_MAXCI, "sc_head_conv_fwd: Cin must be in [1,%d]", HEAD_MAXCI);
   SC_REQUIRE((in->mode == SC_SRC_RAW || in->mode == SC_SRC_AFFINE) && in->up == 0, "sc_head_conv_fwd: unsupported source mode");
   dim3 grid(((W + HT_C - 1) / HT_C) * ((H + HT_R - 1) / HT_R), 1, N);
-  if (Cin == 16) {
-    dim3 g16(((W + 63) / 64) * ((H + 15) / 16), 1, N);
-    const bool vec = (W % 4 == 0) && (((uintptr_t)in->x | (uintptr_t)out) & 15) == 0;
-    if (vec) hipLaunchKernelGGL(k_head_fwd16v, g16, dim3(256), 0, (hipStream_t)stream, to_srcd(*in), w, bias, out, H, W);
-    else hipLaunchKernelGGL(k_head_fwd16, g16, dim3(256), 0, (hipStream_t)stream, to_srcd(*in), w, bias, out, H, W);
-  } else {
-    hipLaunchKernelGGL((k_head_fwd<0>), grid, dim3(256), 0, (hipStream_t)stream, to_srcd(*in), w, bias, out, Cin, H, W);
+  dim3 g16(((W + 63) / 64) * ((H + 15) / 16), 1, N);
+  switch (sc_head_fwd_kernel(Cin, W, ((uintptr_t)in->x & 15) == 0, ((uintptr_t)out & 15) == 0)) {
+    case SC_HEAD_K_FWD16V: hipLaunchKernelGGL(k_head_fwd16v, g16, dim3(256), 0, (hipStream_t)stream, to_srcd(*in), w, bias, out, H, W); break;
+    case SC_HEAD_K_FWD16: hipLaunchKernelGGL(k_head_fwd16, g16, dim3(256), 0, (hipStream_t)stream, to_srcd(*in), w, bias, out, H, W); break;
+    default: hipLaunchKernelGGL((k_head_fwd<0>), grid, dim3(256), 0, (hipStream_t)stream, to_srcd(*in), w, bias, out, Cin, H, W); break;
   }
   SC_LAUNCH_OK("sc_head_conv_fwd");
   return SC_OK;
