@@ -659,6 +659,26 @@ typedef struct sc_mag1c_args {
 } sc_mag1c_args;
 size_t sc_mag1c_workspace_doubles(int G, int S, int64_t npix);
 int sc_mag1c_groups(const sc_mag1c_args* a, sc_stream stream);
+/* The launch or pair of launches sc_mag1c_groups takes, a pure host function and the ONE place the rule is written (the entry point
+ * switches on it).  Arguments: what the dispatch depends on -- the band count, the element type of x, alpha == 0, compute_energy
+ * (energy != NULL), DIRECT mode (cube != NULL).  Codes: 1000 + 100 * (JB / 4) + 10 * form + shrink for k_mag1c_tile<JB, RES, SHRINK,
+ * ENERGY> on fp32 radiances (form 0: the streaming kernel alone, 1: the streaming energy kernel, 2: the resident + streaming pair,
+ * 3: the resident kernel alone; shrink = alpha != 0), 2000 + 100 * (NT / 512) + 10 * energy for k_mag1c<double, NT, ENERGY> (fp64,
+ * alpha != 0), 2000 for k_mag1c_fast<double, 1024> (fp64, alpha == 0).  JB = 4 / NT = 512 up to 64 bands, JB = 8 / NT = 1024 above.
+ * k_mag1c_fast is ONE instantiation with and without compute_energy (a run-time branch on energy != NULL inside it), so both give
+ * SC_MAG1C_F64_FAST.  SC_ERR_ARG with sc_last_error set for what sc_mag1c_groups refuses: S outside [1, 128]; DIRECT mode with fp64
+ * radiances, with S <= 64 or with compute_energy. */
+enum sc_mag1c_launch {
+  SC_MAG1C_TILE4 = 1100, SC_MAG1C_TILE4_SHRINK = 1101,                 /* k_mag1c_tile<4, false, SHRINK>                             */
+  SC_MAG1C_TILE4_ENERGY = 1110, SC_MAG1C_TILE4_ENERGY_SHRINK = 1111,   /* k_mag1c_tile<4, false, SHRINK, true>                       */
+  SC_MAG1C_TILE8_ENERGY = 1210, SC_MAG1C_TILE8_ENERGY_SHRINK = 1211,   /* k_mag1c_tile<8, false, SHRINK, true>                       */
+  SC_MAG1C_TILE8_PAIR = 1220, SC_MAG1C_TILE8_PAIR_SHRINK = 1221,       /* k_mag1c_tile<8, true, SHRINK> then <8, false, SHRINK>      */
+  SC_MAG1C_TILE8_DIRECT = 1230, SC_MAG1C_TILE8_DIRECT_SHRINK = 1231,   /* k_mag1c_tile<8, true, SHRINK> alone, DIRECT mode           */
+  SC_MAG1C_F64_FAST = 2000,                                            /* k_mag1c_fast<double, 1024>                                 */
+  SC_MAG1C_F64_512 = 2100, SC_MAG1C_F64_512_ENERGY = 2110,             /* k_mag1c<double, 512, ENERGY>                               */
+  SC_MAG1C_F64_1024 = 2200, SC_MAG1C_F64_1024_ENERGY = 2210            /* k_mag1c<double, 1024, ENERGY>                              */
+};
+int sc_mag1c_variant(int S, int x_is_f64, int alpha_is_zero, int energy, int direct);
 /* gather the pixels of a (H,W,S_total) band-interleaved cube into the packed band-major layout:
  * x[xoff[g] + s*Ppad[g] + p] = cube[pix_index[poff[g]+p]*S_total + band0 + s] */
 int sc_mag1c_pack(const void* cube, int cube_is_f64, int S_total, int band0, int S,

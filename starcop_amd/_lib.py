@@ -90,6 +90,20 @@ class sc_mag1c_args(C.Structure):
                 ("scatter_mf", C.c_void_p), ("scatter_alb", C.c_void_p), ("scatter_is_f64", C.c_int32)]
 
 
+# enum sc_mag1c_launch (include/starcop_hip.h): what sc_mag1c_variant answers
+MAG1C_TILE4, MAG1C_TILE4_SHRINK, MAG1C_TILE4_ENERGY, MAG1C_TILE4_ENERGY_SHRINK = 1100, 1101, 1110, 1111
+MAG1C_TILE8_ENERGY, MAG1C_TILE8_ENERGY_SHRINK, MAG1C_TILE8_PAIR, MAG1C_TILE8_PAIR_SHRINK = 1210, 1211, 1220, 1221
+MAG1C_TILE8_DIRECT, MAG1C_TILE8_DIRECT_SHRINK = 1230, 1231
+MAG1C_F64_FAST, MAG1C_F64_512, MAG1C_F64_512_ENERGY, MAG1C_F64_1024, MAG1C_F64_1024_ENERGY = 2000, 2100, 2110, 2200, 2210
+MAG1C_LAUNCHES = {          # the enumerators by name (without the SC_MAG1C_ prefix)
+    "TILE4": MAG1C_TILE4, "TILE4_SHRINK": MAG1C_TILE4_SHRINK, "TILE4_ENERGY": MAG1C_TILE4_ENERGY,
+    "TILE4_ENERGY_SHRINK": MAG1C_TILE4_ENERGY_SHRINK, "TILE8_ENERGY": MAG1C_TILE8_ENERGY,
+    "TILE8_ENERGY_SHRINK": MAG1C_TILE8_ENERGY_SHRINK, "TILE8_PAIR": MAG1C_TILE8_PAIR, "TILE8_PAIR_SHRINK": MAG1C_TILE8_PAIR_SHRINK,
+    "TILE8_DIRECT": MAG1C_TILE8_DIRECT, "TILE8_DIRECT_SHRINK": MAG1C_TILE8_DIRECT_SHRINK, "F64_FAST": MAG1C_F64_FAST,
+    "F64_512": MAG1C_F64_512, "F64_512_ENERGY": MAG1C_F64_512_ENERGY, "F64_1024": MAG1C_F64_1024,
+    "F64_1024_ENERGY": MAG1C_F64_1024_ENERGY}
+
+
 class sc_mlr_args(C.Structure):
     """multiple-linear-regression ratio operands (include/starcop_hip.h: sc_mlr_args)"""
     _fields_ = [("base", C.c_void_p), ("band_off", C.c_longlong * 16), ("k", C.c_int32), ("tile_stride", C.c_longlong),
@@ -393,6 +407,7 @@ SIGNATURES = {
     "sc_pred_classification": (_i, [_vp, _vp, _i, _i, _i, _vp]),
     "sc_mag1c_workspace_doubles": (_sz, [_i, _i, C.c_int64]),
     "sc_mag1c_groups": (_i, [C.POINTER(sc_mag1c_args), _vp]),
+    "sc_mag1c_variant": (_i, [_i, _i, _i, _i, _i]),
     "sc_mag1c_pack": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _i, _vp, _i, _vp]),
     "sc_valid_mask": (_i, [_vp, _i, _i, _i, _i, _d, C.c_int64, _vp, _vp]),
     "sc_scatter": (_i, [_vp, _i, _vp, _sz, _vp, _i, _vp]),

@@ -274,8 +274,9 @@ __global__ __launch_bounds__(NT, NT == 512 ? 6 : 4) void k_mag1c(const Mag1cP p)
       if constexpr (ENERGY) {
         // s^T C_k^{-1} s with s = P (d + wbar tau): the same two substitutions for a second right-hand side; first iteration: the
         // log-determinant term P/2 log(1 / prod diag L)
-        const double r0 = lane < S ? dvec[lane] + wbar * tau[lane] : 0.0;
-        const double r1 = lane + 64 < S ? dvec[lane + 64] + wbar * tau[lane + 64] : 0.0;
+        // (tau is first written at the end of iteration 0: until then it is whatever the LDS held, and 0 * NaN is NaN)
+        const double r0 = lane < S ? dvec[lane] + (it > 0 ? wbar * tau[lane] : 0.0) : 0.0;
+        const double r1 = lane + 64 < S ? dvec[lane + 64] + (it > 0 ? wbar * tau[lane + 64] : 0.0) : 0.0;
         double c0 = r0, c1 = r1;
         for (int j = 0; j < S; ++j) {
           const double bj = __shfl(j < 64 ? c0 : c1, j & 63, 64);
@@ -1832,15 +1833,38 @@ extern "C" size_t sc_mag1c_workspace_doubles(int G, int S, int64_t npix) {
   return (size_t)G * S * S + 3 * (size_t)npix;
 }
 
+extern "C" int sc_mag1c_variant(int S, int x_is_f64, int alpha_is_zero, int energy, int direct) {
+  SC_REQUIRE(S >= 1 && S <= MAXS, "sc_mag1c_groups: number of bands must be in [1,%d] (got %d)", MAXS, S);
+  SC_REQUIRE(!direct || (!x_is_f64 && S > 64 && !energy),
+             "sc_mag1c_groups: DIRECT mode takes fp32 cubes, 65..128 bands inside the cube's bands, no compute_energy");
+  const int wide = S > 64 ? 1 : 0, shrink = alpha_is_zero ? 0 : 1;
+  if (!x_is_f64) {
+    // fp32 radiances (both drivers of the reference): the register-tile kernel, one group per CU.  Up to 64 bands: chunks streamed;
+    // more: a pair of launches (groups of <= 512 pixels stay in registers, larger ones stream), see k_mag1c_tile.
+    // compute_energy: the streaming instantiations take every group.  DIRECT mode: every group is resident by the caller's promise --
+    // a larger one gets status 2 -- so the streaming launch is dropped
+    if (energy) return (wide ? SC_MAG1C_TILE8_ENERGY : SC_MAG1C_TILE4_ENERGY) + shrink;
+    if (!wide) return SC_MAG1C_TILE4 + shrink;
+    return (direct ? SC_MAG1C_TILE8_DIRECT : SC_MAG1C_TILE8_PAIR) + shrink;
+  }
+  // fp64 radiances.  alpha == 0: one factorisation per group + Woodbury updates, with compute_energy too (k_mag1c_fast branches on
+  // energy != NULL at run time).  alpha != 0: refactorisation every iteration; few bands: 512 threads (3 groups per CU); many bands:
+  // the matrix fills the LDS, one group of 1024 threads per CU
+  if (!shrink) return SC_MAG1C_F64_FAST;
+  if (energy) return wide ? SC_MAG1C_F64_1024_ENERGY : SC_MAG1C_F64_512_ENERGY;
+  return wide ? SC_MAG1C_F64_1024 : SC_MAG1C_F64_512;
+}
+
 extern "C" int sc_mag1c_groups(const sc_mag1c_args* a, sc_stream stream) {
   SC_REQUIRE(a != nullptr, "sc_mag1c_groups: null args");
-  SC_REQUIRE(a->S >= 1 && a->S <= MAXS, "sc_mag1c_groups: number of bands must be in [1,%d] (got %d)", MAXS, a->S);
-  SC_REQUIRE(a->G >= 0 && a->npix >= 0, "sc_mag1c_groups: bad group / pixel count");
   const bool direct = a->cube != nullptr;
+  const int variant = sc_mag1c_variant(a->S, a->x_is_f64, a->alpha == 0.0, a->energy != nullptr, direct);
+  if (variant < 0) return variant;
+  SC_REQUIRE(a->G >= 0 && a->npix >= 0, "sc_mag1c_groups: bad group / pixel count");
   if (direct) {
     SC_REQUIRE(a->P && a->poff && a->templ && a->work && a->status && a->pix_index && a->scatter_mf && a->scatter_alb,
                "sc_mag1c_groups: DIRECT mode: null pointer argument");
-    SC_REQUIRE(!a->x_is_f64 && a->S > 64 && a->energy == nullptr && a->band0 >= 0 && a->band0 + a->S <= a->S_total,
+    SC_REQUIRE(a->band0 >= 0 && a->band0 + a->S <= a->S_total,
                "sc_mag1c_groups: DIRECT mode takes fp32 cubes, 65..128 bands inside the cube's bands, no compute_energy");
   } else
   SC_REQUIRE(a->x && a->xoff && a->P && a->Ppad && a->poff && a->templ && a->work && a->mf_out && a->albedo_out && a->status,
@@ -1859,46 +1883,41 @@ extern "C" int sc_mag1c_groups(const sc_mag1c_args* a, sc_stream stream) {
   p.mf_out = a->mf_out; p.alb_out = a->albedo_out; p.status = a->status;
   p.energy = a->energy; p.logdet = a->logdet;
   SC_REQUIRE((a->energy == nullptr) == (a->logdet == nullptr), "sc_mag1c_groups: energy and logdet go together");
-  size_t lds = mag1c_lds_bytes(a->S);
+  size_t lds = 0;
   hipStream_t st = (hipStream_t)stream;
   int rc = SC_OK;
-  const bool fast = a->alpha == 0.0;     // no shrinkage: one factorisation per group + Woodbury updates
-  if (!a->x_is_f64) {
-    // fp32 radiances (both drivers of the reference): the register-tile kernel, one group per CU.  Up to 64 bands: chunks streamed;
-    // more: a pair of launches (groups of <= 512 pixels stay in registers, larger ones stream), see k_mag1c_tile
-#define SC_TILE_GO(...)                                                                                                        \
+#define SC_TILE_GO(JB_, ...)                                                                                                   \
     do {                                                                                                                       \
-      if (rc == SC_OK) rc = sc_lds_limit(&k_mag1c_tile<__VA_ARGS__>, lds, "sc_mag1c_groups");                                    \
-      if (rc == SC_OK) hipLaunchKernelGGL((k_mag1c_tile<__VA_ARGS__>), dim3(a->G), dim3(RNT), lds, st, p);                  \
+      lds = mag1c_tile_lds_bytes<JB_>(a->S);                                                                                   \
+      if (rc == SC_OK) rc = sc_lds_limit(&k_mag1c_tile<JB_, __VA_ARGS__>, lds, "sc_mag1c_groups");                             \
+      if (rc == SC_OK) hipLaunchKernelGGL((k_mag1c_tile<JB_, __VA_ARGS__>), dim3(a->G), dim3(RNT), lds, st, p);                \
     } while (0)
-    if (a->energy) {                 // compute_energy: the streaming instantiations take every group
-      if (a->S <= 64) { lds = mag1c_tile_lds_bytes<4>(a->S); if (fast) SC_TILE_GO(4, false, false, true); else SC_TILE_GO(4, false, true, true); }
-      else { lds = mag1c_tile_lds_bytes<8>(a->S); if (fast) SC_TILE_GO(8, false, false, true); else SC_TILE_GO(8, false, true, true); }
-    } else if (a->S <= 64) {
-      lds = mag1c_tile_lds_bytes<4>(a->S);
-      if (fast) SC_TILE_GO(4, false, false); else SC_TILE_GO(4, false, true);
-    } else {
-      lds = mag1c_tile_lds_bytes<8>(a->S);
-      // (DIRECT mode: every group is resident by the caller's promise -- a larger one gets status 2 -- so the streaming launch is dropped)
-      if (fast) { SC_TILE_GO(8, true, false); if (!direct) SC_TILE_GO(8, false, false); }
-      else { SC_TILE_GO(8, true, true); if (!direct) SC_TILE_GO(8, false, true); }
-    }
-#undef SC_TILE_GO
-  } else if (fast) {
-    rc = sc_lds_limit(&k_mag1c_fast<double, 1024>, lds, "sc_mag1c_groups");
-    if (rc == SC_OK) hipLaunchKernelGGL((k_mag1c_fast<double, 1024>), dim3(a->G), dim3(1024), lds, st, p);
-  } else {
-    // fp64 radiances, alpha != 0: refactorisation every iteration.  Few bands: 512 threads (3 groups per CU);
-    // many bands: the matrix fills the LDS, one group of 1024 threads per CU
-#define SC_MAG1C_GO(T_, NT_, EN_)                                                                                                 \
+#define SC_MAG1C_GO(NT_, ...)                                                                                                  \
     do {                                                                                                                       \
-      rc = sc_lds_limit(&k_mag1c<T_, NT_, EN_>, lds, "sc_mag1c_groups");                                                        \
-      if (rc == SC_OK) hipLaunchKernelGGL((k_mag1c<T_, NT_, EN_>), dim3(a->G), dim3(NT_), lds, st, p);                     \
+      lds = mag1c_lds_bytes(a->S);                                                                                             \
+      rc = sc_lds_limit(&__VA_ARGS__, lds, "sc_mag1c_groups");                                                                 \
+      if (rc == SC_OK) hipLaunchKernelGGL((__VA_ARGS__), dim3(a->G), dim3(NT_), lds, st, p);                                   \
     } while (0)
-    if (a->energy) { if (a->S <= 64) SC_MAG1C_GO(double, 512, true); else SC_MAG1C_GO(double, 1024, true); }
-    else { if (a->S <= 64) SC_MAG1C_GO(double, 512, false); else SC_MAG1C_GO(double, 1024, false); }
-#undef SC_MAG1C_GO
+  switch (variant) {      // the rule: sc_mag1c_variant
+    case SC_MAG1C_TILE4: SC_TILE_GO(4, false, false); break;
+    case SC_MAG1C_TILE4_SHRINK: SC_TILE_GO(4, false, true); break;
+    case SC_MAG1C_TILE4_ENERGY: SC_TILE_GO(4, false, false, true); break;
+    case SC_MAG1C_TILE4_ENERGY_SHRINK: SC_TILE_GO(4, false, true, true); break;
+    case SC_MAG1C_TILE8_ENERGY: SC_TILE_GO(8, false, false, true); break;
+    case SC_MAG1C_TILE8_ENERGY_SHRINK: SC_TILE_GO(8, false, true, true); break;
+    case SC_MAG1C_TILE8_PAIR: SC_TILE_GO(8, true, false); SC_TILE_GO(8, false, false); break;
+    case SC_MAG1C_TILE8_PAIR_SHRINK: SC_TILE_GO(8, true, true); SC_TILE_GO(8, false, true); break;
+    case SC_MAG1C_TILE8_DIRECT: SC_TILE_GO(8, true, false); break;
+    case SC_MAG1C_TILE8_DIRECT_SHRINK: SC_TILE_GO(8, true, true); break;
+    case SC_MAG1C_F64_FAST: SC_MAG1C_GO(1024, k_mag1c_fast<double, 1024>); break;
+    case SC_MAG1C_F64_512: SC_MAG1C_GO(512, k_mag1c<double, 512, false>); break;
+    case SC_MAG1C_F64_512_ENERGY: SC_MAG1C_GO(512, k_mag1c<double, 512, true>); break;
+    case SC_MAG1C_F64_1024: SC_MAG1C_GO(1024, k_mag1c<double, 1024, false>); break;
+    case SC_MAG1C_F64_1024_ENERGY: SC_MAG1C_GO(1024, k_mag1c<double, 1024, true>); break;
+    default: sc_set_error("sc_mag1c_groups: internal dispatch error (variant %d)", variant); return SC_ERR_ARG;
   }
+#undef SC_TILE_GO
+#undef SC_MAG1C_GO
   if (rc != SC_OK) return rc;
   SC_LAUNCH_OK("sc_mag1c_groups");
   return SC_OK;
