@@ -529,10 +529,27 @@ int sc_stat_rows(int kind, int N, int H, int W);
 #define SC_BN_FINALIZE_SCRATCH_DOUBLES(C) (64 * 2 * (size_t)(C))
 /* act_bound (optional, training=1): device float raised (order-independent atomic max; never lowered) to
  * max_c |gamma_c| sqrt(count - 1) + |beta_c| -- no normalised sample of `count` can exceed sqrt(count - 1), so this bounds every
- * |BatchNorm output| of the tensor BY CONSTRUCTION; the SC_TERMS_F16X2 kernels derive their activation scale from it (xbound). */
+ * |BatchNorm output| of the tensor BY CONSTRUCTION; the SC_TERMS_F16X2 kernels derive their activation scale from it (xbound).
+ * The value written lies in [b, b (1 + 2^-22)] for that b (count = 1: sqrt(0), the bound is max |beta_c|). */
 int sc_bn_finalize(const float* stats, int nrows, double count, const float* gamma, const float* beta,
                    float* running_mean, float* running_var, float momentum, float eps,
                    int training, float* cst_fwd, int C, double* scratch, float* act_bound, sc_stream stream);
+/* HOST: the launch form of sc_bn_finalize for (rows, channels, scratch given, training): EVAL = constants from the running statistics
+ * (k_bn_finalize<4>, no row is read); ROWS4 = below 4096 rows, 256 threads per channel; from 4096 rows up PRE64 = the coalesced
+ * pre-reduction into 64 fp64 rows (scratch given and 2 C <= 1024) and else ROWS16 = 1024 threads per channel.  SC_ERR_ARG for C < 1,
+ * or nrows < 1 in training.  The entry point dispatches on this value. */
+enum sc_bn_finalize_form { SC_BN_FIN_EVAL = 0, SC_BN_FIN_ROWS4 = 1, SC_BN_FIN_ROWS16 = 2, SC_BN_FIN_PRE64 = 3 };
+int sc_bn_finalize_form(int nrows, int C, int has_scratch, int training);
+/* HOST: the launch form of sc_bn_bwd_finalize_rows32: PRE64 = the same pre-reduction (from 4096 rows, scratch given, 2 C <= 1024), else
+ * ROWS_F32 = the float rows summed per channel.  SC_ERR_ARG for a non-positive size.  The entry point dispatches on this value. */
+enum sc_bn_bwd_rows32_form { SC_BN_ROWS_F32 = 0, SC_BN_ROWS_PRE64 = 1 };
+int sc_bn_bwd_rows32_form(int nrows, int C, int has_scratch);
+/* HOST: the loop form of the streaming kernels over [N][C][HW] planes -- sc_add_srcs_absmax, sc_bn_bwd_reduce, sc_bn_bwd_small: VEC4 =
+ * 16-byte loads (HW % 4 == 0 and every tensor the launch touches 16-byte aligned: aligned16 is that test, made by the entry point on
+ * the OR of its pointers), else SCALAR = 4-byte loads.  SC_ERR_ARG for HW < 1.  The form changes how the elements are loaded, not what
+ * is computed from them nor, within a form, the order of the sums. */
+enum sc_ew_vec_form { SC_EW_SCALAR = 0, SC_EW_VEC4 = 1 };
+int sc_ew_vec_form(int HW, int aligned16);
 /* sums[row][C][2] = { sum g_bn, sum g_bn * xhat } over the row's pixels, g_bn = g * act'(BN(y));
  * rows = sc_stat_rows(SC_STAT_BNBWD, N, H, W).
  * absmax (optional, device float, zeroed by the caller before the first launch of a step): raised to

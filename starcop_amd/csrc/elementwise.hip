@@ -166,7 +166,7 @@ __device__ __forceinline__ void block_absmax_to(float m, float factor, float* sl
 
 __global__ __launch_bounds__(256) void k_bn_bwd_reduce(const float* __restrict__ g, const float* __restrict__ y,
                                                        const float* __restrict__ cst, int act, double* __restrict__ sums, int C, int HW,
-                                                       float* __restrict__ absmax, float* __restrict__ act_absmax) {
+                                                       int vec4, float* __restrict__ absmax, float* __restrict__ act_absmax) {
   __shared__ double s_tmp[8];
   __shared__ float s_m[4];
   const int c = blockIdx.y, n = blockIdx.z;
@@ -179,7 +179,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_reduce(const float* __restrict__
   // ax: largest |BatchNorm output| seen (the activation clamps only towards zero, so this bounds |act(BN(y))|): the device-side
   // range record of the tensors that feed the two-fp16-term kernels -- one v_max per element in a pass that reads y anyway
   float s1 = 0.f, s2 = 0.f, mx = 0.f, ax = 0.f;
-  if ((HW & 3) == 0) {
+  if (vec4) {      // sc_ew_vec_form: HW % 4 == 0 and 16-byte aligned g, y (the host decides)
     for (int i = start + threadIdx.x * 4; i < end; i += 1024) {
       const float4 yv = *reinterpret_cast<const float4*>(y + base + i);
       const float4 gv = *reinterpret_cast<const float4*>(g + base + i);
@@ -219,7 +219,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_reduce(const float* __restrict__
 // (no partial rows, no second kernel: the two-kernel form costs two ~7 us dependent launches per BatchNorm and, at 16x16 or
 // 32x32, 10^4 work-groups of a few hundred elements each).
 __global__ __launch_bounds__(256) void k_bn_bwd_small(const float* __restrict__ g, const float* __restrict__ y,
-                                                      const float* __restrict__ cst, int act, int N, int C, int HW, double count,
+                                                      const float* __restrict__ cst, int act, int N, int C, int HW, int vec4, double count,
                                                       float* __restrict__ dgamma, float* __restrict__ dbeta, float* __restrict__ cst_bwd,
                                                       float* __restrict__ absmax, float* __restrict__ act_absmax) {
   __shared__ double s_tmp[8];
@@ -242,7 +242,7 @@ __global__ __launch_bounds__(256) void k_bn_bwd_small(const float* __restrict__ 
       ax = fmaxf(ax, fabsf(yh));
     }
   };
-  if ((HW & 3) == 0) {
+  if (vec4) {      // sc_ew_vec_form, as in k_bn_bwd_reduce
     // the channel's N planes as ONE list of float4 items, four items (eight 16-byte loads) in flight per thread: with one plane
     // per loop iteration a 32x32 layer was 16 dependent memory round trips (11 us per launch, 25 launches per step)
     const int q = HW >> 2, total = N * q;
@@ -648,21 +648,48 @@ extern "C" int sc_stat_rows(int kind, int N, int H, int W) {
   }
 }
 
+// The launch forms of this file's dispatching entry points: pure host functions, and the only copy of each rule.
+extern "C" int sc_bn_finalize_form(int nrows, int C, int has_scratch, int training) {
+  if (C <= 0 || (training && nrows <= 0)) return SC_ERR_ARG;
+  if (!training) return SC_BN_FIN_EVAL;
+  if (nrows < 4096) return SC_BN_FIN_ROWS4;
+  return (has_scratch && 2 * C <= 1024) ? SC_BN_FIN_PRE64 : SC_BN_FIN_ROWS16;
+}
+
+extern "C" int sc_bn_bwd_rows32_form(int nrows, int C, int has_scratch) {
+  if (C <= 0 || nrows <= 0) return SC_ERR_ARG;
+  return (nrows >= 4096 && has_scratch && 2 * C <= 1024) ? SC_BN_ROWS_PRE64 : SC_BN_ROWS_F32;
+}
+
+extern "C" int sc_ew_vec_form(int HW, int aligned16) {
+  if (HW <= 0) return SC_ERR_ARG;
+  return (HW % 4 == 0 && aligned16) ? SC_EW_VEC4 : SC_EW_SCALAR;
+}
+
 extern "C" int sc_bn_finalize(const float* stats, int nrows, double count, const float* gamma, const float* beta,
                               float* running_mean, float* running_var, float momentum, float eps, int training,
                               float* cst_fwd, int C, double* scratch, float* act_bound, sc_stream stream) {
   SC_REQUIRE(C > 0 && cst_fwd && gamma && beta && running_mean && running_var, "sc_bn_finalize: null argument");
   SC_REQUIRE(!training || (stats && count > 0 && nrows > 0), "sc_bn_finalize: training needs stats rows and count");
-  if (training && nrows >= 4096 && scratch && 2 * C <= 1024) {
-    hipLaunchKernelGGL(k_bn_rows_prereduce, dim3(BN_PRE_S), dim3(1024), 0, (hipStream_t)stream, stats, nrows, C, scratch);
-    hipLaunchKernelGGL((k_bn_finalize<4, double>), dim3(C), dim3(256), 0, (hipStream_t)stream, (const double*)scratch, BN_PRE_S, count, gamma,
-                       beta, running_mean, running_var, momentum, eps, training, cst_fwd, C, act_bound);
-  } else if (training && nrows >= 4096)
-    hipLaunchKernelGGL((k_bn_finalize<16>), dim3(C), dim3(1024), 0, (hipStream_t)stream, stats, nrows, count, gamma, beta,
-                       running_mean, running_var, momentum, eps, training, cst_fwd, C, act_bound);
-  else
-    hipLaunchKernelGGL((k_bn_finalize<4>), dim3(C), dim3(256), 0, (hipStream_t)stream, stats, nrows, count, gamma, beta,
-                       running_mean, running_var, momentum, eps, training, cst_fwd, C, act_bound);
+  switch (sc_bn_finalize_form(nrows, C, scratch != nullptr, training)) {
+    case SC_BN_FIN_PRE64:
+      hipLaunchKernelGGL(k_bn_rows_prereduce, dim3(BN_PRE_S), dim3(1024), 0, (hipStream_t)stream, stats, nrows, C, scratch);
+      hipLaunchKernelGGL((k_bn_finalize<4, double>), dim3(C), dim3(256), 0, (hipStream_t)stream, (const double*)scratch, BN_PRE_S, count, gamma,
+                         beta, running_mean, running_var, momentum, eps, training, cst_fwd, C, act_bound);
+      break;
+    case SC_BN_FIN_ROWS16:
+      hipLaunchKernelGGL((k_bn_finalize<16>), dim3(C), dim3(1024), 0, (hipStream_t)stream, stats, nrows, count, gamma, beta,
+                         running_mean, running_var, momentum, eps, training, cst_fwd, C, act_bound);
+      break;
+    case SC_BN_FIN_ROWS4:
+    case SC_BN_FIN_EVAL:
+      hipLaunchKernelGGL((k_bn_finalize<4>), dim3(C), dim3(256), 0, (hipStream_t)stream, stats, nrows, count, gamma, beta,
+                         running_mean, running_var, momentum, eps, training, cst_fwd, C, act_bound);
+      break;
+    default:
+      sc_set_error("sc_bn_finalize: no launch form for %d rows, %d channels", nrows, C);
+      return SC_ERR_ARG;
+  }
   SC_LAUNCH_OK("sc_bn_finalize");
   return SC_OK;
 }
@@ -671,7 +698,8 @@ extern "C" int sc_bn_bwd_reduce(const float* g, const float* y, const float* cst
                                 int HW, float* absmax, float* act_absmax, sc_stream stream) {
   SC_REQUIRE(g && y && cst_fwd && sums && N > 0 && C > 0 && HW > 0, "sc_bn_bwd_reduce: bad argument");
   dim3 grid((HW + 4095) / 4096, C, N);
-  hipLaunchKernelGGL(k_bn_bwd_reduce, grid, dim3(256), 0, (hipStream_t)stream, g, y, cst_fwd, act, sums, C, HW, absmax, act_absmax);
+  const int vec4 = sc_ew_vec_form(HW, (((uintptr_t)g | (uintptr_t)y) & 15) == 0) == SC_EW_VEC4;
+  hipLaunchKernelGGL(k_bn_bwd_reduce, grid, dim3(256), 0, (hipStream_t)stream, g, y, cst_fwd, act, sums, C, HW, vec4, absmax, act_absmax);
   SC_LAUNCH_OK("sc_bn_bwd_reduce");
   return SC_OK;
 }
@@ -679,7 +707,8 @@ extern "C" int sc_bn_bwd_reduce(const float* g, const float* y, const float* cst
 extern "C" int sc_bn_bwd_small(const float* g, const float* y, const float* cst_fwd, int act, int N, int C, int HW,
                                float* dgamma, float* dbeta, float* cst_bwd, float* absmax, float* act_absmax, sc_stream stream) {
   SC_REQUIRE(g && y && cst_fwd && cst_bwd && N > 0 && C > 0 && HW > 0, "sc_bn_bwd_small: bad argument");
-  hipLaunchKernelGGL(k_bn_bwd_small, dim3(C), dim3(256), 0, (hipStream_t)stream, g, y, cst_fwd, act, N, C, HW,
+  const int vec4 = sc_ew_vec_form(HW, (((uintptr_t)g | (uintptr_t)y) & 15) == 0) == SC_EW_VEC4;
+  hipLaunchKernelGGL(k_bn_bwd_small, dim3(C), dim3(256), 0, (hipStream_t)stream, g, y, cst_fwd, act, N, C, HW, vec4,
                      (double)N * HW, dgamma, dbeta, cst_bwd, absmax, act_absmax);
   SC_LAUNCH_OK("sc_bn_bwd_small");
   return SC_OK;
@@ -697,13 +726,20 @@ extern "C" int sc_bn_bwd_finalize(const double* sums, int nrows, double count, c
 extern "C" int sc_bn_bwd_finalize_rows32(const float* rows, int nrows, double count, const float* cst_fwd, float* dgamma,
                                          float* dbeta, float* cst_bwd, int C, double* scratch, sc_stream stream) {
   SC_REQUIRE(rows && cst_fwd && cst_bwd && C > 0 && count > 0 && nrows > 0, "sc_bn_bwd_finalize_rows32: bad argument");
-  if (nrows >= 4096 && scratch && 2 * C <= 1024) {       // many rows: the coalesced pre-reduction of sc_bn_finalize first
-    hipLaunchKernelGGL(k_bn_rows_prereduce, dim3(BN_PRE_S), dim3(1024), 0, (hipStream_t)stream, rows, nrows, C, scratch);
-    hipLaunchKernelGGL(k_bn_bwd_finalize<double>, dim3(C), dim3(256), 0, (hipStream_t)stream, (const double*)scratch, BN_PRE_S, count, cst_fwd,
-                       dgamma, dbeta, cst_bwd, C);
-  } else
-  hipLaunchKernelGGL(k_bn_bwd_finalize<float>, dim3(C), dim3(256), 0, (hipStream_t)stream, rows, nrows, count, cst_fwd,
-                     dgamma, dbeta, cst_bwd, C);
+  switch (sc_bn_bwd_rows32_form(nrows, C, scratch != nullptr)) {
+    case SC_BN_ROWS_PRE64:       // many rows: the coalesced pre-reduction of sc_bn_finalize first
+      hipLaunchKernelGGL(k_bn_rows_prereduce, dim3(BN_PRE_S), dim3(1024), 0, (hipStream_t)stream, rows, nrows, C, scratch);
+      hipLaunchKernelGGL(k_bn_bwd_finalize<double>, dim3(C), dim3(256), 0, (hipStream_t)stream, (const double*)scratch, BN_PRE_S, count, cst_fwd,
+                         dgamma, dbeta, cst_bwd, C);
+      break;
+    case SC_BN_ROWS_F32:
+      hipLaunchKernelGGL(k_bn_bwd_finalize<float>, dim3(C), dim3(256), 0, (hipStream_t)stream, rows, nrows, count, cst_fwd,
+                         dgamma, dbeta, cst_bwd, C);
+      break;
+    default:
+      sc_set_error("sc_bn_bwd_finalize_rows32: no launch form for %d rows, %d channels", nrows, C);
+      return SC_ERR_ARG;
+  }
   SC_LAUNCH_OK("sc_bn_bwd_finalize_rows32");
   return SC_OK;
 }
@@ -753,7 +789,7 @@ extern "C" int sc_add_srcs_absmax(const sc_src* a, const sc_src* b, float* out, 
   uintptr_t al = (uintptr_t)a->x | (uintptr_t)out;
   if (a->mode == SC_SRC_BNBWD) al |= (uintptr_t)a->aux;
   if (b) { al |= (uintptr_t)b->x; if (b->mode == SC_SRC_BNBWD) al |= (uintptr_t)b->aux; }
-  if (HW % 4 == 0 && (al & 15) == 0)
+  if (sc_ew_vec_form(HW, (al & 15) == 0) == SC_EW_VEC4)
     hipLaunchKernelGGL(k_add_srcs<true>, grid, dim3(256), 0, (hipStream_t)stream, to_srcd(*a), b ? to_srcd(*b) : empty_srcd(),
                        b ? 1 : 0, out, C, HW, absmax);
   else

@@ -122,7 +122,12 @@ __device__ __forceinline__ void bn_write_channel(double mean, double var, double
     // |BN(y)| = |gamma x_hat + beta| <= |gamma| sqrt(count - 1) + |beta| for batch statistics (Samuelson): the tensor's bound is the
     // maximum over its channels; unsigned atomicMax on the bit pattern of a non-negative float is order-independent (reproducible),
     // and a channel that cannot raise the slot skips the atomic (after the first step almost all do)
-    const float b = fabsf(gamma[c]) * (float)sqrt(count > 1.0 ? count - 1.0 : 1.0) * 1.0000002f + fabsf(beta[c]);
+    // (a single sample is its own mean: x_hat = 0 and the bound is |beta|, as the formula says).  Formed in float64 with a margin of
+    // 1.5 x 2^-24 for the fp32 roundings of the consumers' scale and shift, and rounded UP to the next float: in (1 + 1.5 x 2^-24,
+    // 1 + 3.5 x 2^-24] times the formula.  (In fp32 with a factor 1 + 2^-22 and three roundings it reached 1 + 4.4 x 2^-24.)
+    const double bd = (fabs((double)gamma[c]) * sqrt(count > 1.0 ? count - 1.0 : 0.0) + fabs((double)beta[c])) * (1.0 + 0x1.8p-24);
+    float b = (float)bd;
+    if (bd > 0.0 && !((double)b > bd) && b < 3.0e38f) b = __uint_as_float(__float_as_uint(b) + 1u);      // b >= 0: the next float up
     if (b < 3.0e38f && b > *(volatile float*)act_bound) atomicMax(reinterpret_cast<unsigned*>(act_bound), __float_as_uint(b));
   }
 }
