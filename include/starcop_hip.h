@@ -1684,6 +1684,45 @@ int sc_edt_variant(int H, int W, int max_dist2, int forced);
 int sc_label_keep(const int32_t* labels, const uint8_t* keep /*[N][M+1]*/, uint8_t* out, int N, int M, int H, int W,
                   sc_stream stream);
 
+/* Exact feature transform: WHICH target is the nearest one (starcop_amd/morphology.py: nearest_index, expand_labels,
+ * fill_nearest; starcop_amd/plumes.py: background_rings).  Targets, dims, strides and the two row passes are sc_edt's; for every
+ * pixel p, nearest(p) is the target minimising (row_p - row_t)^2 + (col_p - col_t)^2, AMONG EQUALLY NEAR TARGETS THE ONE WITH THE
+ * SMALLEST COLUMN, THEN THE ONE WITH THE SMALLEST ROW.  That is what the separable scheme gives when the column pass prefers the
+ * target above on a tie, the window scans left to right replacing on < only, and the envelope keeps the earlier parabola on
+ * equality.  Outputs, dense [N][H][W], any non-empty subset:
+ *   index   int32 row_t * W + col_t; a target's own index is itself; -1 wherever dist2 is SC_EDT_FAR (an image without a
+ *           target, or with max_dist2 > 0 every pixel with d2 > max_dist2)
+ *   dist2   int32, bit-equal to what sc_edt writes for the same mask, invert, max_dist2 and variant
+ *   dst[i]  for i < n_planes <= SC_EDT_NEAREST_MAX_PLANES: dst[i][n][p] = src[i][n][nearest(p)], and the pixel's own word
+ *           src[i][n][p] where index is -1.  A plane is 4-byte words (int32 labels, float32 values: copied as bits), dense H x W
+ *           per image, src_stride[i] >= 0 words between images; dst[i] dense and not overlapping any source.
+ * The row pass is sc_edt_variant(H, W, max_dist2, variant): the window when 0 < floor(sqrt(max_dist2)) <= SC_EDT_WINDOW_MAX_R.
+ * max_dist2 = 0 means no cap (a cap of 0 pixels is the caller's: the targets themselves).  work: 16-byte aligned device memory
+ * of sc_edt_nearest_call_workspace_bytes(a) bytes (0 where the call would refuse): sc_edt's layout for that row pass, and for
+ * the envelope 2 more bytes per padded pixel (the winning columns, uint16, transposed beside the distances);
+ * sc_edt_nearest_workspace_bytes(N, H, W) (0 for bad dims) serves any call.  Launches as sc_edt: 4 (window) or 5 (envelope); the
+ * gathers are scattered 4-byte loads.  SC_ERR_ARG, before any launch, for everything sc_edt refuses and for n_planes outside
+ * 0..8, a null or aliased plane pointer, a negative source stride.  No atomics: two calls give identical bytes.              */
+#define SC_EDT_NEAREST_MAX_PLANES 8
+typedef struct sc_edt_nearest_args {
+  const uint8_t* mask;                            /* element (0, 0) of image 0, device                             */
+  int64_t stride_n, stride_h, stride_w;           /* elements (bytes) between images, rows, columns                */
+  int32_t N, H, W;
+  int32_t invert;                                 /* 0: targets are mask != 0; 1: mask == 0                        */
+  int32_t max_dist2;                              /* 0: no cap                                                     */
+  int32_t variant;                                /* 0, SC_EDT_WINDOW or SC_EDT_ENVELOPE                           */
+  int32_t n_planes;                               /* gathered planes, 0..SC_EDT_NEAREST_MAX_PLANES                 */
+  int32_t reserved;
+  int32_t* index;                                 /* [N][H][W] device outputs, each may be NULL                    */
+  int32_t* dist2;
+  const void* src[SC_EDT_NEAREST_MAX_PLANES];     /* [H][W] words per image, device                                */
+  int64_t src_stride[SC_EDT_NEAREST_MAX_PLANES];  /* words between images                                          */
+  void* dst[SC_EDT_NEAREST_MAX_PLANES];           /* [N][H][W] words, device                                       */
+} sc_edt_nearest_args;
+size_t sc_edt_nearest_workspace_bytes(int N, int H, int W);
+size_t sc_edt_nearest_call_workspace_bytes(const sc_edt_nearest_args* a);
+int sc_edt_nearest(const sc_edt_nearest_args* a, void* work, size_t work_bytes, sc_stream stream);
+
 /* ------------------------------------------------------------------------- */
 /* HOST functions (no device involved): decoders of the on-disk sample format -- one tiled GeoTIFF per product per sample,
  * read by rasterio in the reference (starcop/data/dataset.py:66-76, written by save_cog at sampling_dataset.py:332-355).

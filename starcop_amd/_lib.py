@@ -343,6 +343,18 @@ class sc_edt_args(C.Structure):
                 ("pixel_size", C.c_double), ("dist2", C.c_void_p), ("dist", C.c_void_p), ("within", C.c_void_p)]
 
 
+EDT_NEAREST_MAX_PLANES = 8                               # SC_EDT_NEAREST_MAX_PLANES
+
+
+class sc_edt_nearest_args(C.Structure):
+    """feature-transform operands (include/starcop_hip.h: sc_edt_nearest_args)"""
+    _fields_ = [("mask", C.c_void_p), ("stride_n", C.c_int64), ("stride_h", C.c_int64), ("stride_w", C.c_int64),
+                ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("invert", C.c_int32),
+                ("max_dist2", C.c_int32), ("variant", C.c_int32), ("n_planes", C.c_int32), ("reserved", C.c_int32),
+                ("index", C.c_void_p), ("dist2", C.c_void_p), ("src", C.c_void_p * EDT_NEAREST_MAX_PLANES),
+                ("src_stride", C.c_int64 * EDT_NEAREST_MAX_PLANES), ("dst", C.c_void_p * EDT_NEAREST_MAX_PLANES)]
+
+
 _vp, _i, _f, _d, _sz =C.c_void_p, C.c_int, C.c_float, C.c_double, C.c_size_t
 
 # name -> (restype, argtypes); every symbol include/starcop_hip.h declares
@@ -521,6 +533,9 @@ SIGNATURES = {
     "sc_edt": (_i, [C.POINTER(sc_edt_args), _vp, _sz, _vp]),
     "sc_edt_call_workspace_bytes": (_sz, [C.POINTER(sc_edt_args)]),
     "sc_edt_variant": (_i, [_i, _i, _i, _i]),
+    "sc_edt_nearest_workspace_bytes": (_sz, [_i, _i, _i]),
+    "sc_edt_nearest_call_workspace_bytes": (_sz, [C.POINTER(sc_edt_nearest_args)]),
+    "sc_edt_nearest": (_i, [C.POINTER(sc_edt_nearest_args), _vp, _sz, _vp]),
     "sc_label_keep": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _vp]),
     "sc_tiff_lzw_decode": (_i, [_vp, _sz, _vp, _sz, C.POINTER(C.c_size_t)]),
     "sc_tiff_unpredict": (_i, [_vp, _i, _i, _i, _i, _i, _i, _vp]),

@@ -15,6 +15,16 @@
 //                whatever the distances.  A transposing kernel writes the outputs.
 // The epilogue of the last pass writes any of dist2 / dist / within.  No floating-point atomics, no atomics at all; every value
 // is a function of the image alone: two calls give identical bytes.
+//
+// sc_edt_nearest is the same two passes keeping the arg-min beside the minimum (the feature transform): the row passes are
+// templated on their parameter block, EdtP for sc_edt (the instantiations sc_edt launches do no more than before) and NearP,
+// which makes the window remember the column that won (left to right, replaced on < only: the smallest column among equals) and
+// the envelope write the column of the parabola it evaluates (its intersection abscissa is the first column where the LATER
+// parabola is strictly lower and its pop test keeps the earlier one on equality: the smallest column again).  The epilogue
+// recomputes the row of the target from the band word and carries of (band(h), winning column), the upper target on a tie, and
+// gathers up to SC_EDT_NEAREST_MAX_PLANES planes of 4-byte words there.
+#include <type_traits>
+
 #include "sc_common.h"
 
 namespace {
@@ -36,6 +46,16 @@ struct EdtP {
   int R, max_dist2, thresh2, negate;
   double pixel_size;
   int* dist2; float* dist; unsigned char* within;
+};
+
+// sc_edt_nearest: the same passes, and what the arg-min needs on top
+struct NearP : EdtP {
+  unsigned short* colt;                      // [N][W][Hp] envelope: column of the winning parabola, transposed beside d2t
+  int* index;                                // [N][H][W] row_t * W + col_t, -1 where dist2 is FAR
+  int np;
+  const unsigned* src[SC_EDT_NEAREST_MAX_PLANES];
+  long long ss[SC_EDT_NEAREST_MAX_PLANES];   // words between the images of a source plane
+  unsigned* dst[SC_EDT_NEAREST_MAX_PLANES];
 };
 
 __device__ __forceinline__ void edt_store(const EdtP& p, size_t o, int d2) {
@@ -88,6 +108,27 @@ __device__ __forceinline__ unsigned g_of(unsigned long long bits, int r, int h0,
   return g;
 }
 
+// pixel (h, x) of image n, its squared distance and the column c the row pass found it in: the row of the target is the nearest
+// set bit of column c at or above h, or the nearest below where that one is strictly nearer
+__device__ __forceinline__ void near_store(const NearP& p, int n, int h, int x, int d2, int c) {
+  const size_t pix = (size_t)h * p.W + x, o = (size_t)n * p.H * p.W + pix;
+  if (p.max_dist2 > 0 && d2 > p.max_dist2) d2 = FAR_;
+  int idx = -1;
+  if (d2 != FAR_) {
+    const int b = h / BH, h0 = b * BH, r = h - h0;
+    const size_t t = ((size_t)n * p.nb + b) * p.W + c;
+    const unsigned long long bits = p.bits[t];
+    const unsigned long long lo = bits & ((2ull << r) - 1ull), hi = bits >> r;
+    const int up = lo ? h0 + 63 - __clzll((long long)lo) : p.above[t];
+    const int dn = hi ? h + __ffsll(hi) - 1 : p.below[t];
+    idx = (up >= 0 && (dn < 0 || h - up <= dn - h) ? up : dn) * p.W + c;
+  }
+  if (p.dist2) p.dist2[o] = d2;
+  if (p.index) p.index[o] = idx;
+  const size_t s = idx >= 0 ? (size_t)idx : pix;                 // no target within the cap: the pixel's own word
+  for (int i = 0; i < p.np; ++i) p.dst[i][o] = p.src[i][(size_t)n * p.ss[i] + s];
+}
+
 template <bool TRANSPOSED>
 __global__ __launch_bounds__(256) void k_edt_cols(const EdtP p) {
   const int w = blockIdx.x * 256 + threadIdx.x, b = blockIdx.y, n = blockIdx.z;
@@ -112,7 +153,9 @@ __global__ __launch_bounds__(256) void k_edt_cols(const EdtP p) {
   }
 }
 
-__global__ __launch_bounds__(SEG) void k_edt_window(const EdtP p) {
+template <class P>
+__global__ __launch_bounds__(SEG) void k_edt_window(const P p) {
+  constexpr bool IDX = std::is_same<P, NearP>::value;
   extern __shared__ int s2[];                  // [SEG + 2 R]
   const int tid = threadIdx.x, x0 = blockIdx.x * SEG, h = blockIdx.y, n = blockIdx.z, R = p.R;
   const unsigned short* g = p.g + ((size_t)n * p.H + h) * p.W;
@@ -128,11 +171,19 @@ __global__ __launch_bounds__(SEG) void k_edt_window(const EdtP p) {
   __syncthreads();
   const int x = x0 + tid;
   if (x >= p.W) return;
-  int m = BIG2;
-  for (int j = -R; j <= R; ++j) m = min(m, j * j + s2[tid + R + j]);
+  int m = BIG2, jb = 0;
+  for (int j = -R; j <= R; ++j) {
+    const int v = j * j + s2[tid + R + j];
+    if constexpr (IDX) {
+      if (v < m) { m = v; jb = j; }              // left to right, replaced on < only: the smallest column among equals
+    } else {
+      m = min(m, v);
+    }
+  }
   // a candidate beyond the window contributes (R + 1)^2 or more: m is exact below that, and otherwise only known to lie above
   // the cap (< (R + 1)^2), where the distances are FAR and `within` is false anyway
-  edt_store(p, ((size_t)n * p.H + h) * p.W + x, m > R * R + 2 * R ? FAR_ : m);
+  if constexpr (IDX) near_store(p, n, h, x, m > R * R + 2 * R ? FAR_ : m, x + jb);
+  else edt_store(p, ((size_t)n * p.H + h) * p.W + x, m > R * R + 2 * R ? FAR_ : m);
 }
 
 __device__ __forceinline__ long long floordiv(long long a, long long b) {      // b > 0
@@ -141,7 +192,9 @@ __device__ __forceinline__ long long floordiv(long long a, long long b) {      /
   return q;
 }
 
-__global__ __launch_bounds__(64) void k_edt_envelope(const EdtP p) {
+template <class P>
+__global__ __launch_bounds__(64) void k_edt_envelope(const P p) {
+  constexpr bool IDX = std::is_same<P, NearP>::value;
   const int h = blockIdx.x * 64 + threadIdx.x, n = blockIdx.y;
   if (h >= p.H) return;
   const int W = p.W;
@@ -183,6 +236,7 @@ __global__ __launch_bounds__(64) void k_edt_envelope(const EdtP p) {
   for (int u = W - 1; u >= 0; --u) {
     const long long d = u - sq;
     out[u * Hp] = (int)(d * d + gq2);
+    if constexpr (IDX) p.colt[base + u * Hp] = (unsigned short)sq;
     if (u == tq && q > 0) {
       --q;
       const unsigned e = stk[q * Hp];
@@ -194,19 +248,28 @@ __global__ __launch_bounds__(64) void k_edt_envelope(const EdtP p) {
 }
 
 // d2t [W][Hp] -> the outputs [H][W] through a 64 x 65 LDS tile (64 x 64 values, a column of padding)
-__global__ __launch_bounds__(256) void k_edt_transpose_out(const EdtP p) {
+template <class P>
+__global__ __launch_bounds__(256) void k_edt_transpose_out(const P p) {
+  constexpr bool IDX = std::is_same<P, NearP>::value;
   __shared__ int tile[64][65];
+  __shared__ unsigned short ctile[IDX ? 64 : 1][IDX ? 66 : 1];
   const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6, n = blockIdx.z;
   const int x0 = blockIdx.x * 64, y0 = blockIdx.y * 64;
   const int* src = p.d2t + (size_t)n * p.W * p.Hp;
   for (int c = ty; c < 64; c += 4) {
     const int x = x0 + c, y = y0 + tx;
-    if (x < p.W && y < p.H) tile[c][tx] = src[(size_t)x * p.Hp + y];
+    if (x < p.W && y < p.H) {
+      tile[c][tx] = src[(size_t)x * p.Hp + y];
+      if constexpr (IDX) ctile[c][tx] = p.colt[((size_t)n * p.W + x) * p.Hp + y];
+    }
   }
   __syncthreads();
   for (int r = ty; r < 64; r += 4) {
     const int y = y0 + r, x = x0 + tx;
-    if (x < p.W && y < p.H) edt_store(p, ((size_t)n * p.H + y) * p.W + x, tile[tx][r]);
+    if (x < p.W && y < p.H) {
+      if constexpr (IDX) near_store(p, n, y, x, tile[tx][r], ctile[tx][r]);
+      else edt_store(p, ((size_t)n * p.H + y) * p.W + x, tile[tx][r]);
+    }
   }
 }
 
@@ -328,15 +391,102 @@ extern "C" int sc_edt(const sc_edt_args* a, void* work, size_t work_bytes, sc_st
     p.R = isqrt_floor(cap);
     hipLaunchKernelGGL(k_edt_cols<false>, cols, dim3(256), 0, st, p);
     SC_LAUNCH_OK("k_edt_cols");
-    hipLaunchKernelGGL(k_edt_window, dim3((W + SEG - 1) / SEG, H, N), dim3(SEG), (size_t)(SEG + 2 * p.R) * sizeof(int), st, p);
+    hipLaunchKernelGGL(k_edt_window<EdtP>, dim3((W + SEG - 1) / SEG, H, N), dim3(SEG), (size_t)(SEG + 2 * p.R) * sizeof(int), st, p);
     SC_LAUNCH_OK("k_edt_window");
     return SC_OK;
   }
   hipLaunchKernelGGL(k_edt_cols<true>, cols, dim3(256), 0, st, p);
   SC_LAUNCH_OK("k_edt_cols");
-  hipLaunchKernelGGL(k_edt_envelope, dim3((H + 63) / 64, N), dim3(64), 0, st, p);
+  hipLaunchKernelGGL(k_edt_envelope<EdtP>, dim3((H + 63) / 64, N), dim3(64), 0, st, p);
   SC_LAUNCH_OK("k_edt_envelope");
-  hipLaunchKernelGGL(k_edt_transpose_out, dim3((W + 63) / 64, (H + 63) / 64, N), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(k_edt_transpose_out<EdtP>, dim3((W + 63) / 64, (H + 63) / 64, N), dim3(256), 0, st, p);
+  SC_LAUNCH_OK("k_edt_transpose_out");
+  return SC_OK;
+}
+
+// sc_edt_nearest: the layout of sc_edt's row pass, then the envelope's transposed winning columns
+static size_t near_total(const EdtLayout& l, int N, int W, bool window) {
+  return l.total + (window ? 0 : align256((size_t)N * W * l.Hp * 2));
+}
+
+extern "C" size_t sc_edt_nearest_workspace_bytes(int N, int H, int W) {
+  if (!edt_dims_ok(N, H, W)) return 0;
+  return near_total(edt_layout(N, H, W, false), N, W, false);
+}
+
+static int near_plan(const sc_edt_nearest_args* a, int* variant_out) {
+  SC_REQUIRE(a && a->mask, "sc_edt_nearest: null pointer");
+  const int N = a->N, H = a->H, W = a->W;
+  SC_REQUIRE(edt_dims_ok(N, H, W), "sc_edt_nearest: bad dims N=%d H=%d W=%d (N <= 65535, H, W <= 32767, H*W < 2^31)", N, H, W);
+  SC_REQUIRE(a->n_planes >= 0 && a->n_planes <= SC_EDT_NEAREST_MAX_PLANES, "sc_edt_nearest: n_planes=%d (0..%d)", a->n_planes,
+             SC_EDT_NEAREST_MAX_PLANES);
+  SC_REQUIRE(a->index || a->dist2 || a->n_planes > 0, "sc_edt_nearest: no output requested");
+  SC_REQUIRE(a->stride_n >= 0 && a->stride_h >= 0 && a->stride_w >= 0, "sc_edt_nearest: negative mask stride");
+  SC_REQUIRE(a->max_dist2 >= 0, "sc_edt_nearest: negative max_dist2");
+  SC_REQUIRE(a->variant >= 0 && a->variant <= 2, "sc_edt_nearest: variant=%d (0 the rule, 1 window, 2 envelope)", a->variant);
+  for (int i = 0; i < a->n_planes; ++i) {
+    SC_REQUIRE(a->src[i] && a->dst[i], "sc_edt_nearest: plane %d: null pointer", i);
+    SC_REQUIRE(a->src[i] != a->dst[i], "sc_edt_nearest: plane %d: the destination must not be the source", i);
+    SC_REQUIRE(a->src_stride[i] >= 0, "sc_edt_nearest: plane %d: negative source stride", i);
+  }
+  const int variant = sc_edt_variant(H, W, a->max_dist2, a->variant);
+  if (variant < 0) return variant;
+  *variant_out = variant;
+  return SC_OK;
+}
+
+extern "C" size_t sc_edt_nearest_call_workspace_bytes(const sc_edt_nearest_args* a) {
+  int variant;
+  if (near_plan(a, &variant) != SC_OK) return 0;
+  const bool window = variant == SC_EDT_WINDOW;
+  return near_total(edt_layout(a->N, a->H, a->W, window), a->N, a->W, window);
+}
+
+extern "C" int sc_edt_nearest(const sc_edt_nearest_args* a, void* work, size_t work_bytes, sc_stream stream) {
+  int variant;
+  const int rc = near_plan(a, &variant);
+  if (rc != SC_OK) return rc;
+  SC_REQUIRE(work, "sc_edt_nearest: null pointer");
+  SC_REQUIRE((reinterpret_cast<uintptr_t>(work) & 15) == 0, "sc_edt_nearest: the workspace must be 16-byte aligned");
+  const int N = a->N, H = a->H, W = a->W;
+  const bool window = variant == SC_EDT_WINDOW;
+  const EdtLayout l = edt_layout(N, H, W, window);
+  const size_t total = near_total(l, N, W, window);
+  SC_REQUIRE(work_bytes >= total, "sc_edt_nearest: workspace %zu < %zu bytes", work_bytes, total);
+  hipStream_t st = (hipStream_t)stream;
+  char* wk = static_cast<char*>(work);
+  NearP p{};
+  p.mask = a->mask; p.sn = a->stride_n; p.sh = a->stride_h; p.sw = a->stride_w;
+  p.N = N; p.H = H; p.W = W; p.invert = a->invert; p.nb = l.nb; p.Hp = l.Hp;
+  p.bits = reinterpret_cast<unsigned long long*>(wk + l.bits);
+  p.above = reinterpret_cast<int*>(wk + l.above); p.below = reinterpret_cast<int*>(wk + l.below);
+  p.g = reinterpret_cast<unsigned short*>(wk + l.g);
+  p.stk = reinterpret_cast<unsigned*>(wk + l.stk); p.d2t = reinterpret_cast<int*>(wk + l.d2t);
+  p.colt = reinterpret_cast<unsigned short*>(wk + l.total);
+  p.max_dist2 = a->max_dist2; p.pixel_size = 1.0;
+  p.dist2 = a->dist2; p.index = a->index; p.np = a->n_planes;
+  for (int i = 0; i < a->n_planes; ++i) {
+    p.src[i] = static_cast<const unsigned*>(a->src[i]); p.ss[i] = a->src_stride[i]; p.dst[i] = static_cast<unsigned*>(a->dst[i]);
+  }
+  const EdtP& e = p;                                               // the column pass is sc_edt's own
+  const dim3 cols((W + 255) / 256, l.nb, N);
+  hipLaunchKernelGGL(k_edt_bits, cols, dim3(256), 0, st, e);
+  SC_LAUNCH_OK("k_edt_bits");
+  hipLaunchKernelGGL(k_edt_carry, dim3((W + 255) / 256, N), dim3(256), 0, st, e);
+  SC_LAUNCH_OK("k_edt_carry");
+  if (window) {
+    p.R = isqrt_floor(a->max_dist2);
+    hipLaunchKernelGGL(k_edt_cols<false>, cols, dim3(256), 0, st, e);
+    SC_LAUNCH_OK("k_edt_cols");
+    hipLaunchKernelGGL(k_edt_window<NearP>, dim3((W + SEG - 1) / SEG, H, N), dim3(SEG), (size_t)(SEG + 2 * p.R) * sizeof(int), st, p);
+    SC_LAUNCH_OK("k_edt_window");
+    return SC_OK;
+  }
+  hipLaunchKernelGGL(k_edt_cols<true>, cols, dim3(256), 0, st, e);
+  SC_LAUNCH_OK("k_edt_cols");
+  hipLaunchKernelGGL(k_edt_envelope<NearP>, dim3((H + 63) / 64, N), dim3(64), 0, st, p);
+  SC_LAUNCH_OK("k_edt_envelope");
+  hipLaunchKernelGGL(k_edt_transpose_out<NearP>, dim3((W + 63) / 64, (H + 63) / 64, N), dim3(256), 0, st, p);
   SC_LAUNCH_OK("k_edt_transpose_out");
   return SC_OK;
 }

@@ -5,6 +5,12 @@ unset) pixel.  ``dilate`` / ``erode`` by a disc of any radius are one ``sc_edt``
 mask; ``opening`` / ``closing`` are their compositions.  ``remove_small_objects`` is the sieve: ``connected_components``, a device
 bincount of the labels and one gather (``sc_label_keep``).
 
+``nearest_index`` is ``sc_edt_nearest``, the feature transform: WHICH target is the nearest one, as the int32 raster index
+``row * W + col``.  Among equally near targets the one with the smallest column wins, then the one with the smallest row (scipy's
+``distance_transform_edt(return_indices=True)`` breaks ties by another, undocumented rule; the two agree wherever the nearest
+target is unique).  ``expand_labels`` (skimage's, away from ties) and ``fill_nearest`` (the scipy idiom ``data[tuple(indices)]``)
+are the same call gathering a label or value plane at that index.
+
 Every function takes an (H, W) or (N, H, W) mask, numpy or a device tensor of any dtype; anything but uint8 / bool becomes
 ``x != 0``, uint8 device tensors are read in place through their strides (a band of an (H, W, 4) image, a ``[:, ::2]`` view).
 numpy in, numpy out; device in, device out.  There is no CPU fallback.
@@ -19,7 +25,7 @@ import torch
 
 from . import _lib
 from ._lib import check, ptr, stream
-from .mask_creation import connected_components
+from .mask_creation import _planes, connected_components
 
 FAR = _lib.EDT_FAR
 WINDOW_MAX_R = _lib.EDT_WINDOW_MAX_R
@@ -125,6 +131,130 @@ def distance_transform(mask, to="set", max_distance=None, squared=False, pixel_s
         return _finish(out, single, host)
     out = _edt(m3, invert, "dist2" if squared else "dist", max_dist2=cap or 0, pixel_size=pixel_size, variant=VARIANTS[variant])
     return _finish(out, single, host)
+
+
+def _nearest(m3, invert, max_dist2=0, variant=0, index=False, dist2=False, planes=()):
+    """one ``sc_edt_nearest`` call on a device uint8 (N, H, W) view -> (index or None, dist2 or None, [gathered planes]);
+    ``planes``: (N, H, W) device tensors of a 4-byte dtype, read in place where their H x W planes are dense"""
+    lib = _lib.load()
+    N, H, W = m3.shape
+    a = _lib.sc_edt_nearest_args()
+    a.mask, a.stride_n, a.stride_h, a.stride_w = m3.data_ptr(), m3.stride(0), m3.stride(1), m3.stride(2)
+    a.N, a.H, a.W, a.invert = N, H, W, int(bool(invert))
+    a.max_dist2, a.variant, a.n_planes = int(max_dist2), int(variant), len(planes)
+    idx = torch.empty((N, H, W), dtype=torch.int32, device=m3.device) if index else None
+    d2 = torch.empty((N, H, W), dtype=torch.int32, device=m3.device) if dist2 else None
+    a.index, a.dist2 = (idx.data_ptr() if index else None), (d2.data_ptr() if dist2 else None)
+    srcs, outs = [_planes(p) for p in planes], []            # holds the tensors the pointers belong to until the call is enqueued
+    for i, (t, stride) in enumerate(srcs):
+        outs.append(torch.empty((N, H, W), dtype=t.dtype, device=m3.device))
+        a.src[i], a.src_stride[i], a.dst[i] = t.data_ptr(), stride, outs[i].data_ptr()
+    wb = lib.sc_edt_nearest_call_workspace_bytes(a)          # 0 where the call itself will refuse
+    work = torch.empty(max(wb, 1), dtype=torch.uint8, device=m3.device)
+    check(lib.sc_edt_nearest(a, ptr(work), wb, stream()))
+    return idx, d2, outs
+
+
+def _distance_cap(max_distance, who, what="max_distance"):
+    """None (no cap) or floor(max_distance^2); a cap no distance in an image reaches is none"""
+    cap = None if max_distance is None else _cap(max_distance, who, what)
+    return None if cap == _D2_MAX else cap
+
+
+def nearest_index(mask, to="set", max_distance=None, return_distance=False, variant=None):
+    """The feature transform: for every pixel the int32 raster index ``row * W + col`` of the nearest set pixel (``to="set"``) or
+    unset pixel (``to="unset"``) of its image; among equally near targets the smallest column, then the smallest row.  A target's
+    index is its own.  -1 everywhere in an image without a target and, with ``max_distance`` (pixels), wherever the squared
+    distance exceeds ``floor(max_distance * max_distance)``: a cap of 0 leaves the targets alone.  ``return_distance``: also the
+    int32 squared distance (``INT32_MAX`` where the index is -1), bit-equal to ``distance_transform(..., squared=True)``.
+    ``variant`` as in ``distance_transform``."""
+    who = "nearest_index"
+    _check_mask(mask, who)
+    if to not in ("set", "unset"):
+        raise ValueError(f"{who}: to={to!r}; expected 'set' or 'unset'")
+    if variant not in VARIANTS:
+        raise ValueError(f"{who}: variant {variant!r}; expected one of None, 'window', 'envelope'")
+    cap = _distance_cap(max_distance, who)
+    if variant == "window" and (cap is None or math.isqrt(cap) > WINDOW_MAX_R):
+        raise ValueError(f"{who}: variant='window' needs a max_distance of at most {WINDOW_MAX_R} pixels")
+    m3, single, host = _device_u8(mask)
+    invert = to == "unset"
+    if cap == 0:                                             # only the targets themselves lie within the cap
+        N, H, W = m3.shape
+        on = (m3 != 0) != invert
+        idx = torch.where(on, torch.arange(H * W, dtype=torch.int32, device=m3.device).view(1, H, W), -1).to(torch.int32)
+        d2 = torch.where(on, 0, FAR).to(torch.int32)
+    else:
+        idx, d2, _ = _nearest(m3, invert, cap or 0, VARIANTS[variant], index=True, dist2=bool(return_distance))
+    if return_distance:
+        return _finish(idx, single, host), _finish(d2, single, host)
+    return _finish(idx, single, host)
+
+
+def expand_labels(labels, distance=1.0):
+    """skimage's ``expand_labels``: an integer label image, 0 the background -> int32, every background pixel within ``distance``
+    pixels (squared distance <= ``floor(distance * distance)``) of a labelled one takes the label of its nearest labelled pixel,
+    labelled pixels keep theirs.  Where two labels are equally near, the tie rule of ``nearest_index`` decides (skimage inherits
+    scipy's; the results agree away from ties).  ``distance=0`` returns the labels as int32.  One ``sc_edt_nearest`` call."""
+    who = "expand_labels"
+    _check_mask(labels, who)
+    host = isinstance(labels, np.ndarray)
+    if (labels.dtype.kind not in "iub") if host else (labels.dtype.is_floating_point or labels.dtype.is_complex):
+        raise ValueError(f"{who}: labels must be integers, got {labels.dtype}")
+    t = _cap(distance, who, "distance")
+    if host:
+        _lib.require_device()
+        lab = torch.from_numpy(np.ascontiguousarray(labels).astype(np.int32)).cuda()
+    else:
+        _lib.require_device(labels)
+        lab = labels.to(torch.int32)
+    single = lab.dim() == 2
+    lab = (lab[None] if single else lab).contiguous()
+    if t == 0:
+        return _finish(lab if host or labels.dtype != torch.int32 else lab.clone(), single, host)
+    m3 = (lab != 0).to(torch.uint8)
+    out = _nearest(m3, False, 0 if t == _D2_MAX else t, planes=[lab])[2][0]
+    return _finish(out, single, host)
+
+
+MAX_FILL_PLANES = _lib.EDT_NEAREST_MAX_PLANES
+
+
+def fill_nearest(data, invalid, max_distance=None):
+    """Nearest-value fill of no-data pixels: ``data`` a float32 (H, W) / (N, H, W) plane, or a list of up to 8 such planes that
+    share ``invalid``, a mask of that shape.  Every pixel with ``invalid != 0`` takes the value (the bits: NaN payloads survive) of
+    the nearest pixel with ``invalid == 0`` of its image, by the tie rule of ``nearest_index``; valid pixels keep theirs, and so
+    do invalid pixels farther than ``max_distance`` (pixels) or in an image without a valid pixel.  The mask is read in place
+    (uint8 / bool device tensors through their strides), all planes are gathered in one ``sc_edt_nearest`` call.  A plane in, a
+    plane out; a list in, a list out."""
+    who = "fill_nearest"
+    many = isinstance(data, (list, tuple))
+    planes = list(data) if many else [data]
+    if not 1 <= len(planes) <= MAX_FILL_PLANES:
+        raise ValueError(f"{who}: {len(planes)} planes, 1 to {MAX_FILL_PLANES} per call")
+    _check_mask(invalid, who)
+    host = isinstance(invalid, np.ndarray)
+    for i, p in enumerate(planes):
+        if isinstance(p, np.ndarray) != host or not isinstance(p, (np.ndarray, torch.Tensor)):
+            raise ValueError(f"{who}: plane {i} and the mask must both be numpy arrays or both tensors")
+        if tuple(p.shape) != tuple(invalid.shape):
+            raise ValueError(f"{who}: plane {i} has shape {tuple(p.shape)}, the mask {tuple(invalid.shape)}")
+        if p.dtype not in (np.float32, torch.float32):
+            raise ValueError(f"{who}: plane {i} must be float32, got {p.dtype}")
+    cap = _distance_cap(max_distance, who)
+    m3, single, _ = _device_u8(invalid)
+    if host:
+        planes = [torch.from_numpy(np.ascontiguousarray(p)).to(m3.device) for p in planes]
+    else:
+        for p in planes:
+            _lib.require_device(p)
+    planes = [p[None] if single else p for p in planes]
+    if cap == 0:
+        outs = [p.clone() for p in planes]
+    else:
+        outs = _nearest(m3, True, cap or 0, planes=planes)[2]
+    outs = [_finish(o, single, host) for o in outs]
+    return outs if many else outs[0]
 
 
 def _binary(mask, single, host):

@@ -104,11 +104,15 @@ def _operands(planes, other):
     return ops, oth
 
 
-def table_from_stats(stats, counts, width, plane_names=(), with_other=False, min_area=1, geotransform=None, pixel_area_m2=None):
+def table_from_stats(stats, counts, width, plane_names=(), with_other=False, min_area=1, geotransform=None, pixel_area_m2=None,
+                     ring_stats=None):
     """The DataFrame of ``plume_table`` from host copies of the ``component_stats`` columns (numpy, (N, M) and (N, M, P)),
     ``counts`` (N,) and the image width (for the row / column of ``argmax``).  ``plane_names``: which of ``"mag1c"``, ``"prob"``
-    the P planes are, in order.  No device involved."""
+    the P planes are, in order.  ``ring_stats``: the same columns reduced over the background-ring labels (``background_rings``)
+    with mag1c as plane 0, for the ring columns of ``plume_table``; it needs ``"mag1c"`` among the planes.  No device involved."""
     import pandas as pd
+    if ring_stats is not None and "mag1c" not in plane_names:
+        raise ValueError("table_from_stats: ring_stats needs the mag1c plane")
     counts = np.asarray(counts).reshape(-1)
     area = np.asarray(stats["area"])
     N, M = area.shape
@@ -132,6 +136,14 @@ def table_from_stats(stats, counts, width, plane_names=(), with_other=False, min
                         mag1c_max_col=np.where(am >= 0, am % width, -1))
             if pixel_area_m2 is not None:
                 cols["ime_ppmm_m2"] = s * float(pixel_area_m2)
+            if ring_stats is not None:
+                bg_n = np.asarray(ring_stats["n_finite"])[item, k, 0].astype(np.int64)
+                bg_s = np.asarray(ring_stats["sum"])[item, k, 0].astype(np.float64)
+                with np.errstate(invalid="ignore", divide="ignore"):
+                    bg_mean = np.where(bg_n > 0, bg_s / np.maximum(bg_n, 1), np.nan)
+                cols.update(bg_px=bg_n, mag1c_bg_mean=bg_mean, mag1c_sum_bgsub=s - bg_mean * nf.astype(np.float64))
+                if pixel_area_m2 is not None:
+                    cols["ime_bgsub_ppmm_m2"] = cols["mag1c_sum_bgsub"] * float(pixel_area_m2)
         elif name == "prob":
             cols.update(prob_mean=mean, prob_max=mx)
         else:
@@ -156,7 +168,44 @@ def _to_device(a, dev=None):
     return a
 
 
-def plume_table(mask, mag1c=None, prob=None, label_mask=None, connectivity=2, min_area=1, geotransform=None, pixel_area_m2=None):
+def _ring_caps(ring_px, gap_px, who):
+    """(floor(ring_px^2), floor(gap_px^2)), both radii >= 0, the ring at least a pixel wide and within the int32 range of d2"""
+    ring, gap = float(ring_px), float(gap_px)
+    if not ring >= 1.0 or not gap >= 0.0 or not gap < ring or not ring * ring < _lib.EDT_FAR - 1:
+        raise ValueError(f"{who}: ring_px {ring_px!r} and gap_px {gap_px!r}: need 0 <= gap_px < ring_px, 1 <= ring_px < 2^15.5")
+    return int(np.floor(ring * ring)), int(np.floor(gap * gap))
+
+
+def _rings(lab, ring2, gap2):
+    """``background_rings`` of a contiguous device int32 (N, H, W) label image and the two squared radii"""
+    from . import morphology as mo
+    _, d2, (near,) = mo._nearest((lab != 0).to(torch.uint8), False, ring2, dist2=True, planes=[lab])
+    return torch.where((lab == 0) & (d2 > gap2) & (d2 <= ring2), near, 0)
+
+
+def background_rings(labels, ring_px, gap_px=0.0):
+    """The local-background ring of every plume of an integer label image (0 the background; (H, W) or (N, H, W), numpy or
+    device) -> int32 ring labels: pixel p gets k when ``labels[p] == 0``, its squared distance d2 to the nearest labelled pixel
+    has ``floor(gap_px^2) < d2 <= floor(ring_px^2)``, and that nearest pixel (``morphology.nearest_index``'s tie rule) carries k;
+    every other pixel 0.  With several plumes each ring pixel belongs to the nearest one, so rings never overlap.  One
+    ``sc_edt_nearest`` call (squared distance and the gathered label plane) and one select."""
+    who = "background_rings"
+    if not isinstance(labels, (np.ndarray, torch.Tensor)) or labels.ndim not in (2, 3):
+        raise ValueError(f"{who}: expected an (H, W) or (N, H, W) label image")
+    host = isinstance(labels, np.ndarray)
+    if (labels.dtype.kind not in "iub") if host else (labels.dtype.is_floating_point or labels.dtype.is_complex):
+        raise ValueError(f"{who}: labels must be integers, got {labels.dtype}")
+    ring2, gap2 = _ring_caps(ring_px, gap_px, who)
+    lab = _to_device(labels.astype(np.int32) if host else labels)
+    _lib.require_device(lab)
+    lab = _as_batch(lab.to(torch.int32), who).contiguous()
+    out = _rings(lab, ring2, gap2)
+    out = out[0] if labels.ndim == 2 else out
+    return out.cpu().numpy() if host else out
+
+
+def plume_table(mask, mag1c=None, prob=None, label_mask=None, connectivity=2, min_area=1, geotransform=None, pixel_area_m2=None,
+                background_ring_px=None, background_gap_px=0.0):
     """One row per plume of ``mask != 0``: an (H, W) or (N, H, W) mask, numpy or device.  Labels the mask on the device
     (``connectivity`` 1 or 2 as ``connected_components``), reduces every component in one ``sc_component_stats`` call and reads
     the rows back once.  Components of fewer than ``min_area`` pixels are dropped.  Columns:
@@ -167,8 +216,16 @@ def plume_table(mask, mag1c=None, prob=None, label_mask=None, connectivity=2, mi
     ``mag1c_max_col`` of the first maximum in raster order, and with ``pixel_area_m2`` the integrated enhancement
     ``ime_ppmm_m2 = mag1c_sum * pixel_area_m2`` (ppm m x m2; turning it into a mass needs a constant the caller supplies);
     with ``prob``: ``prob_mean``, ``prob_max``;  with ``label_mask``: ``overlap_px``, the component's pixels inside it;
-    with ``geotransform`` (GDAL 6-tuple, north up): ``x``, ``y`` of the centroid, pixel centres at +0.5."""
+    with ``geotransform`` (GDAL 6-tuple, north up): ``x``, ``y`` of the centroid, pixel centres at +0.5;
+    with ``background_ring_px`` (needs ``mag1c``): the local background of every plume, taken over its ring of
+    ``background_rings(labels, background_ring_px, background_gap_px)`` in one more ``component_stats`` call: ``bg_px`` (ring pixels
+    with finite mag1c), ``mag1c_bg_mean`` (NaN when ``bg_px`` is 0), ``mag1c_sum_bgsub = mag1c_sum - mag1c_bg_mean * n`` with n the
+    plume's finite pixels, and with ``pixel_area_m2`` ``ime_bgsub_ppmm_m2``.  None leaves the table as it is without."""
     shape = tuple(mask.shape)
+    if background_ring_px is not None:
+        if mag1c is None:
+            raise ValueError("plume_table: background_ring_px needs mag1c")
+        ring2, gap2 = _ring_caps(background_ring_px, background_gap_px, "plume_table")
     for name, p in (("mag1c", mag1c), ("prob", prob), ("label_mask", label_mask)):
         if p is not None and tuple(p.shape) != shape:
             raise ValueError(f"plume_table: {name} has shape {tuple(p.shape)}, the mask {shape}")
@@ -180,10 +237,15 @@ def plume_table(mask, mag1c=None, prob=None, label_mask=None, connectivity=2, mi
     planes = [_to_device(p, m.device) for p in (mag1c, prob) if p is not None]
     other = _to_device(label_mask, m.device) if label_mask is not None else None
     counts_h = np.array([counts]) if isinstance(counts, int) else counts.cpu().numpy()      # the one read-back of the counts
-    st = component_stats(labels, counts, planes, other, M=max(int(counts_h.max()), 0))
+    M = max(int(counts_h.max()), 0)
+    st = component_stats(labels, counts, planes, other, M=M)
+    ring_host = None
+    if background_ring_px is not None:
+        lab3 = _as_batch(labels, "plume_table").contiguous()
+        ring_host = _read_back(component_stats(_rings(lab3, ring2, gap2), counts, planes[:1], M=M))
     counts = counts_h
     host = _read_back(st)
-    return table_from_stats(host, counts, shape[-1], names, other is not None, min_area, geotransform, pixel_area_m2)
+    return table_from_stats(host, counts, shape[-1], names, other is not None, min_area, geotransform, pixel_area_m2, ring_host)
 
 
 def _read_back(st):

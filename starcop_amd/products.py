@@ -262,15 +262,31 @@ def clean(out, open_radius=0.0, min_area=1, exclude=None, exclude_buffer_px=0.0,
     return out
 
 
+BACKGROUND_KEYS = ("ring_px", "gap_px")
+
+
+def check_plume_background(plume_background, who):
+    """the ``plume_background=`` argument of ``annotate`` and the pipeline calls: None, or a dict with ``ring_px`` and optionally
+    ``gap_px`` (no device involved) -> the keyword arguments of ``plumes.plume_table``"""
+    if plume_background is None:
+        return {}
+    if not isinstance(plume_background, dict) or set(plume_background) - set(BACKGROUND_KEYS) or "ring_px" not in plume_background:
+        raise ValueError(f"{who}: plume_background must be a dict with ring_px and keys from {BACKGROUND_KEYS}, got {plume_background!r}")
+    return {"background_ring_px": plume_background["ring_px"], "background_gap_px": plume_background.get("gap_px", 0.0)}
+
+
 def annotate(out, mask, mf, prob, geotransform=None, pixel_area_m2=None, plumes=False, plume_outlines=False, label_polygons=None,
-             match_tolerance_px=0.0):
+             match_tolerance_px=0.0, plume_background=None):
     """The plume annotations of a prediction dict, as asked for: ``plumes`` (``plumes.plume_table`` of ``mask`` with ``mf`` as mag1c
     and ``prob`` as probability), ``plume_outlines`` of the same mask in the same coordinates, and for ``label_polygons`` (a
     ``.geojson`` path or polygons) ``label_mask``, the polygons burnt into the grid of ``mask`` (device uint8), and ``plume_match``,
-    the same burnt image scored against the mask, with ``match_tolerance_px`` as the ``tolerance_px`` of ``plumes.burn_and_match``."""
+    the same burnt image scored against the mask, with ``match_tolerance_px`` as the ``tolerance_px`` of ``plumes.burn_and_match``.
+    ``plume_background``: ``{"ring_px": .., "gap_px": ..}`` adds the background-ring columns of ``plumes.plume_table`` to the table
+    (and so to ``plumes.csv`` and the GeoJSON properties); it needs ``mf``."""
     from . import plumes as pl
+    ring = check_plume_background(plume_background, "annotate")
     if plumes:
-        out["plumes"] = pl.plume_table(mask, mag1c=mf, prob=prob, geotransform=geotransform, pixel_area_m2=pixel_area_m2)
+        out["plumes"] = pl.plume_table(mask, mag1c=mf, prob=prob, geotransform=geotransform, pixel_area_m2=pixel_area_m2, **ring)
         if plume_outlines:
             out["plume_outlines"] = pl.plume_outlines(mask, geotransform=geotransform)
     if label_polygons is not None:
