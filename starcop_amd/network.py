@@ -91,17 +91,8 @@ class _Decoder(nn.Module):
 
 
 # ----------------------------------------------------------------------------------------------
-class _T:
-    """An activation of the plan.  kind: 'input' | 'raw' (conv output, BN+act applied by readers) | 'fin'."""
-    __slots__ = ("name", "C", "shift", "kind", "bn", "act", "buf", "grad", "cst", "cstb", "stats", "bsums",
-                 "grad_written", "alias_grad_of", "res_grad")
-
-    def __init__(self, name, Cn, shift, kind, bn=None, act=ACT_NONE):
-        self.name, self.C, self.shift, self.kind, self.bn, self.act = name, Cn, shift, kind, bn, act
-        self.buf = self.grad = self.cst = self.cstb = self.stats = self.bsums = None
-        self.grad_written = False
-        self.alias_grad_of = None   # raw-linear tensor whose grad is the grad of the residual sum
-        self.res_grad = None        # 'fin' tensor z = self + ...: z.grad must be added to self.grad
+# An activation of the plan.  kind: 'input' | 'raw' (conv output, BN+act applied by readers) | 'fin'.
+_T = collections.namedtuple("_T", "name C shift kind bn act")
 
 
 _COT_RATIO = 1.15      # 64-wide cout tiles when they pad the channel count by less than this factor (measured per layer, DESIGN.md 10)
@@ -262,6 +253,208 @@ def _use_ksplit(N, HW, K, M, ks=1):
     return wgs <= 512 and (K >= 384 or (K >= 192 and wgs <= 256))
 
 
+# ----------------------------------------------------------------------------------------------
+# Which kernel runs a pass of a pointwise / 3x3 layer at a shape and precision: ONE answer per pass (_fwd_route, _dgrad_route,
+# _wgrad_route) and one for the filter layouts a layer can be sent to (_layouts), built from the measured rules above.  Everything
+# else reads these: the statistics rows and workspaces of a plan (_get_plan), the packed layouts (_pack_all), both walks, the profile
+# families and kernel_table().  They need no device.
+# static facts of a layer; Cup / Csk: the up-sampled / skip channels of a decoder conv1 (0 elsewhere)
+_Layer = collections.namedtuple("_Layer", "type Cout Cin ks up Cup Csk nsrc")
+# A route names everything its launch needs: the entry point, the filter layout, the cout tile, the profile family.
+# _Fwd.rows: per-work-group partial rows of the BatchNorm statistics.  _Dgrad.launches: (entry, layout, cout tile, down0, sources whose
+# gradient the launch writes), down0 = 1: the kernel stores the 2x2 sums itself, 2: full resolution into up_tmp, then sc_downsum2x2;
+# _Dgrad.fallback: the route the walk takes where the preferred kernel's plain epilogue does not do.  _Wgrad.skip: the route of the skip
+# channels' columns beside the box-sum GEMM.
+_Fwd = collections.namedtuple("_Fwd", "kernel entry layout cot rows family")
+_Dgrad = collections.namedtuple("_Dgrad", "kernel launches family fallback", defaults=(None,))
+_Wgrad = collections.namedtuple("_Wgrad", "kernel entry family skip", defaults=(None,))
+_Routes = collections.namedtuple("_Routes", "fwd dgrad wgrad")
+_PACK_ORDER = ("f", "b", "bA", "bB", "spd", "sp", "tf", "tb", "tsd", "pf", "pb", "pfi")      # rows of the pack table, per layer
+_BWD_LAYOUTS = frozenset(("b", "bA", "bB", "spd", "tb", "tsd", "pb"))                        # ... of which a forward-only pack leaves out
+
+
+def _tiles(L, split):
+    """(forward, backward) cout-tile widths of a layer's packed filters, and whether each direction runs split (bx3): 3x3 layers with
+    >= 32 output channels run on the 16-bit matrix cores with exactly-split operands (fp32-level accuracy, conv_bx3.hip; `precision`
+    picks the split); thin ones stay on the fp32 MFMA kernels"""
+    cf, cb = _pick_cot(L.Cout, L.ks), _pick_cot(L.Cin, L.ks)
+    if L.ks == 3 and L.Cout <= 16 and L.Cin >= 32 and split:
+        cf = 32       # decoder.blocks.4.conv1 (32 -> 16): the split kernel with half-empty cout blocks still beats
+                      # the fp32-MFMA thin kernel (0.36 vs 0.50 ms); 16 -> 16 layers do not (tools/bench_thin_bx3.py)
+    return cf, cb, bool(split and L.ks == 3 and cf >= 32), bool(split and L.ks == 3 and cb >= 32)
+
+
+def _family(kind, ks, terms, which):
+    """profile family of a forward (which = "fwd") or data-gradient ("dgrad") launch.  The split-bf16 3x3 kernel: forward and dgrad
+    launches are one family unless they run with a different number of terms (then their MFMA ceilings differ)"""
+    if kind == "bx3":
+        return "k_conv3_bx3 (fwd+dgrad)" if terms[0] == terms[1] else f"k_conv3_bx3 ({which})"
+    return "k_conv3_thin_h (fwd+dgrad)" if kind == "thin" else f"k_conv_mfma<{ks}> (fwd+dgrad)"
+
+
+def _spd_skip(L):
+    """how the skip channels' gradient of a decoder conv1 rides with its sub-pixel data gradient: "vskip" (decoder.blocks.3: in the
+    same launch), "stiles" (additional channel tiles of that launch, where measured faster than a 3x3 launch of its own), "bx3" (a
+    3x3 launch on a 32-wide pack) or None (no skip source)"""
+    if not L.Csk:
+        return None
+    if _lib.load().sc_spd_vskip_ok(L.Cup, L.Csk):
+        return "vskip"
+    return "stiles" if _use_spd_skip_tiles(L.Cup, L.Csk) else "bx3"
+
+
+def _layouts(L, split, terms):
+    """{layout: (floats, co_t, tflip, bx3 code of its sc_pack_desc)}: the filter layouts a layer's routes can name at this precision
+    (split: split_bf16; terms: (forward, backward)).  Which of a pointwise layer's two families are packed follows the shapes in use
+    (HyperStarcopUNet._pw_need)."""
+    lib = _lib.load()
+    co, ci, ks, (tf_, tb_) = L.Cout, L.Cin, L.ks, terms
+    cf, cb, xf, xb = _tiles(L, split)
+    lay = {"f": (lib.sc_packed_weight_floats_bx3(co, ci, cf, 0, tf_) if xf else lib.sc_packed_weight_floats(co, ci, ks, cf, 0), cf, 0, tf_ if xf else 0),
+           "b": (lib.sc_packed_weight_floats_bx3(co, ci, cb, 1, tb_) if xb else lib.sc_packed_weight_floats(co, ci, ks, cb, 1), cb, 1, tb_ if xb else 0)}
+    if L.type == "pw":
+        for flip, name in enumerate(("pf", "pb")):
+            lay[name] = (lib.sc_packed_weight_floats_pw3(co, ci, flip), 0, flip, PACK_PW3)
+        lay["pfi"] = lay["pf"]      # a fused inference block's own copy of "pf" (HyperStarcopUNet._wanted_layouts)
+        return lay
+    # decoder.blocks.4 (<= 16 output channels at full resolution) under the two-fp16-term split: filters in registers
+    # (sc_conv3x3_thin16; 0.20-0.28 vs 0.31-0.51 ms per launch).  The backward-data kernel only takes the plain
+    # epilogue, so the regular pack is kept beside it.
+    thin = {"tf": split and tf_ == TERMS_F16X2 and co <= 16 and ci in (16, 32), "tb": split and tb_ == TERMS_F16X2 and ci <= 16 and co in (16, 32),
+            # decoder.blocks.4.conv1: the half-resolution data gradient in its sub-pixel form (sc_conv3x3_thin16 with down0)
+            "tsd": split and tb_ == TERMS_F16X2 and L.up and co == 16 and ci == 32}
+    for flip, name in ((0, "tf"), (1, "tb"), (1, "tsd")):
+        if ks == 3 and L.nsrc == 1 and thin[name]:
+            lay[name] = (lib.sc_packed_weight_floats_thin16(co, ci, flip), 16, flip, PACK_THIN16)
+    sk = _spd_skip(L)
+    spd = L.up and xb and tb_ in _SP_TERMS and _SP != "0" and L.Cup % 32 == 0
+    # decoder conv1 data gradient (up-sampled channels + skip channels): the two outputs as TWO launches with their own
+    # cout tiles -- 64-wide for the up-sampled part (a multiple of 64), one 32-wide tile for the <= 32 skip channels --
+    # instead of one launch of 32-wide tiles (80 = 64 + 16: 3 x 32; 152 = 128 + 24: 5 x 32): every cout tile stages (loads,
+    # BatchNorm-backward prologue, split) the whole gradient patch again.  Measured at 16 x 512^2: decoder.blocks.2.conv1
+    # 212 -> 197 us (5 -> 3 passes), decoder.blocks.3.conv1 293 -> 288 us (a 64-wide pass costs two 32-wide ones there: the
+    # operand reads and MFMAs, not the staging, are what its work-groups wait for); 288 = 256 + 32, which already runs on
+    # 64-wide tiles, loses 5 us to the second launch and stays as it was.  Step +0.6 % (same-box pairs).
+    split2 = xb and cb == 32 and L.up and L.nsrc == 2 and L.Cup % 64 == 0 and L.Csk <= 32
+    for cot, name in ((64, "bA"), (32, "bB")):
+        if split2 or (name == "bB" and spd and sk == "bx3"):
+            lay[name] = (lib.sc_packed_weight_floats_bx3(co, ci, cot, 1, tb_), cot, 1, tb_)
+    # decoder conv1 forward as a sub-pixel convolution (the two-fp16-term arithmetic or, "bf16", one bf16 term): phase /
+    # parity filters (tflip | 4: the one-bf16-term layout)
+    if L.up and xf and tf_ in _SP_TERMS and _SP != "0":
+        lay["sp"] = (lib.sc_packed_weight_floats_sp(co, L.Cup, L.Csk), L.Cup, 4 if tf_ == 1 else 0, PACK_SP)
+    # ... and the data gradient of its up-sampled channels (the skip channels' gradient: see _spd_skip)
+    if spd:
+        lay["spd"] = (lib.sc_packed_weight_floats_spd(co, L.Cup, L.Csk if sk == "stiles" else 0), L.Cup,
+                      {"stiles": 3, "vskip": 2}.get(sk, 1) | (4 if tb_ == 1 else 0), PACK_SPD)
+    return lay
+
+
+def _fwd_route(L, N, Ho, Wo, split, terms):
+    """forward kernel of a pointwise / 3x3 layer with an Ho x Wo output plane"""
+    lib = _lib.load()
+    cf, _, xf, _ = _tiles(L, split)
+    mfma = _family("mfma", L.ks, terms, "fwd")
+    if L.type == "pw":
+        if _use_pw3(0, N, Ho * Wo, L.Cin, L.Cout):
+            return _Fwd("pw3", "sc_conv1x1_pw3", "pf", cf, lib.sc_stat_rows(STAT_PW3, N, Ho, Wo), mfma)
+        if _use_ksplit(N, Ho * Wo, L.Cin, L.Cout):
+            return _Fwd("ksplit", "sc_conv1x1_ksplit", "f", cf, lib.sc_stat_rows(STAT_CONV1K, N, Ho, Wo), mfma)
+        return _Fwd("mfma", "sc_conv2d_mfma", "f", cf, lib.sc_stat_rows(STAT_CONV1, N, Ho, Wo), mfma)
+    lay, bx3 = _layouts(L, split, terms), _family("bx3", 3, terms, "fwd")
+    if "sp" in lay and _use_sp(N, Ho, Wo, L.Cout):       # one partial row per work-group tile
+        return _Fwd("sp", "sc_conv3x3_sp", "sp", cf, lib.sc_sp_stat_rows(N, Ho, Wo, L.Cout), bx3)
+    rows = lib.sc_stat_rows(STAT_CONV3, N, Ho, Wo)
+    if "tf" in lay:
+        return _Fwd("thin16", "sc_conv3x3_thin16", "tf", cf, rows, _family("thin", 3, terms, "fwd"))
+    # (a 3x3 layer never takes the K-split kernel: _use_ksplit)
+    return _Fwd("bx3", "sc_conv3x3_bx3", "f", cf, rows, bx3) if xf else _Fwd("mfma", "sc_conv2d_mfma", "f", cf, rows, mfma)
+
+
+def _dgrad_route(L, N, Ho, Wo, split, terms):
+    """data-gradient kernel(s) of a layer"""
+    cb, xb = _tiles(L, split)[1::2]
+    lay, every = _layouts(L, split, terms), tuple(range(L.nsrc))
+    bx3, thin = _family("bx3", 3, terms, "dgrad"), _family("thin", 3, terms, "dgrad")
+    if "spd" in lay and _use_spd(N, Ho, Wo, L.Cup, L.Csk):
+        # sub-pixel form: the up-sampled channels' gradient at half resolution from the four parity planes of dy (2.25x fewer MFMAs,
+        # 128 output channels per staged patch), the skip channels' by the 3x3 kernel on their own 32-wide tiles ("bx3") -- or in the SAME
+        # launch, dy (g, y) staged ONCE for both gradients: <= 64 up-sampled + <= 16 skip channels (decoder.blocks.3, "vskip") as virtual
+        # channels of the 128-channel tile's second half (289 us in two 3x3 launches before); "stiles": as additional channel tiles of
+        # the launch (32 skip channels x 4 output parities each)
+        sk = _spd_skip(L)
+        if sk == "bx3":
+            return _Dgrad("spd+bx3", (("sc_conv3x3_sp_dgrad", "spd", cb, 0, (0,)), ("sc_conv3x3_bx3", "bB", 32, 0, (1,))), bx3)
+        return _Dgrad("spd+" + sk if sk else "spd", (("sc_conv3x3_sp_dgrad", "spd", cb, 0, every),), bx3)
+    # decoder.blocks.4.conv1: 16 gradient channels -> 32 channels at half resolution, the sub-pixel form on the thin layer's MFMA
+    # (sc_conv3x3_thin16 with down0: 251 -> see DESIGN 16; otherwise sc_conv3x3_bx3 with its summing store)
+    if "tsd" in lay and Ho % 2 == 0 and Wo % 2 == 0:
+        return _Dgrad("thin16_down", (("sc_conv3x3_thin16", "tsd", 16, 1, (0,)),), thin)
+    if L.up and xb and "bA" in lay:
+        return _Dgrad("bx3_split", (("sc_conv3x3_bx3", "bA", 64, 1, (0,)), ("sc_conv3x3_bx3", "bB", 32, 0, (1,))), bx3)
+    # ONE ordinary convolution with the flipped filter; a decoder conv1's up-sampled source gets the 2x2 sums (down0)
+    down = (1 if xb else 2) if L.up else 0
+    if xb:
+        plain = _Dgrad("bx3", (("sc_conv3x3_bx3", "b", cb, down, every),), bx3)
+    elif L.type == "pw" and _use_pw3(1, N, Ho * Wo, L.Cin, L.Cout):
+        plain = _Dgrad("pw3", (("sc_conv1x1_pw3", "pb", cb, 0, every),), _family("mfma", 1, terms, "dgrad"))
+    else:
+        ksplit = _use_ksplit(N, Ho * Wo, L.Cout, L.Cin, L.ks)
+        plain = _Dgrad(("ksplit" if ksplit else "mfma") + ("+downsum" if L.up else ""),
+                       (("sc_conv1x1_ksplit" if ksplit else "sc_conv2d_mfma", "b", cb, down, every),), _family("mfma", L.ks, terms, "dgrad"))
+    if "tb" in lay and not L.up:      # (the thin kernel only takes the plain epilogue: no accumulation, no residual target)
+        return _Dgrad("thin16", (("sc_conv3x3_thin16", "tb", cb, 0, every),), thin, plain)
+    return plain
+
+
+def _wgrad_route(L, N, Ho, Wo, split, terms):
+    """weight-gradient kernel of a layer"""
+    f16 = split and terms[1] == TERMS_F16X2
+    mfma = _Wgrad("mfma", "sc_conv2d_wgrad_mfma", f"k_wgrad_mfma<{L.ks}> (+reduce)")
+    bx3 = _Wgrad("bx3", "sc_conv3x3_wgrad_bx3", "k_wgrad3_bx3 (+reduce)")
+    if L.up and f16 and _use_spw(N, Ho, Wo, L.Cout, L.Cup):
+        # decoder conv1 with many up-sampled channels: their filter gradient as nine plain GEMMs between the low-resolution source
+        # and tap-aligned 2x2 box sums of dy (conv_spw.hip); the skip channels' columns from the 3x3 kernel on the skip source alone
+        return _Wgrad("spw", "sc_conv3x3_sp_wgrad", bx3.family, None if L.nsrc == 1 else bx3 if (L.Cout >= 32 and L.Csk >= 32) else mfma)
+    if L.type == "pw":      # K-slice partials kept until the batched reduction (HyperStarcopUNet._size_backward)
+        return (_Wgrad("pw3", "sc_conv1x1_wgrad_pw3", mfma.family) if _use_pw3(2, N, Ho * Wo, L.Cin, L.Cout)
+                else mfma._replace(entry="sc_conv2d_wgrad_mfma_deferred"))
+    if f16 and L.ks == 3 and L.nsrc == 1 and L.Cout <= 16 and L.Cin in (16, 32) and Wo % 2 == 0:
+        # decoder.blocks.4: two fp16 terms on the 16x16x32 MFMA (was MFMA-bound in fp32)
+        return _Wgrad("thin16", "sc_conv3x3_wgrad_thin16", "k_wgrad_thin_h (+reduce)")
+    # 16-channel layers outside the cases above stay on the fp32 MFMA
+    return bx3 if (split and L.ks == 3 and L.Cout >= 32 and L.Cin >= 32) else mfma
+
+
+def _wgrad_floats(kernel, N, Ho, Wo, Cout, Cin, ks):
+    """K-slice partials (floats) a weight-gradient kernel needs"""
+    if kernel == "mfma":
+        return _lib.load().sc_wgrad_workspace_floats(N, Ho, Wo, Cout, Cin, ks)
+    return getattr(_lib.load(), f"sc_wgrad_{kernel}_workspace_floats")(N, Ho, Wo, Cout, Cin)
+
+
+def _block_table(raw, totals, dev):
+    """device table of a batched launch whose descriptors share 256-item blocks: (descriptor bytes, first block of each, count, blocks)"""
+    import numpy as np
+    starts = np.cumsum([0] + [-(-int(t) // 256) for t in totals]).tolist()
+    return (torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(dev), torch.tensor(starts[:-1], dtype=torch.int32).to(dev),
+            len(totals), starts[-1])
+
+
+class _BwdWalk:
+    """state of one backward walk (HyperStarcopUNet._backward_impl)"""
+    def __init__(self, plan, st, dlogits, half_bwd):
+        self.plan, self.st, self.dlogits, self.half_bwd = plan, st, dlogits, half_bwd      # st: handle of the main stream
+        self.side = self.sd = None         # the weight-gradient stream and its handle (overlap_wgrad)
+        self.last_pw = min(plan.pw_part, default=-1)      # the pointwise layer the walk reaches last
+        self.written = set()       # tensors whose gradient buffer holds a contribution (the next writer accumulates)
+        self.reduced = set()       # tensors whose BatchNorm-backward sums were produced by the launch that wrote their gradient
+        self.pw_pending = []       # pointwise weight gradients whose K-slice partials await the batched reduction
+        self.dw_casts = []         # (fp64 accumulator, flat fp32 gradient view, n) of the fused depthwise backward launches walked so far
+        self.gmax_slot = {}        # tensor -> its slot of plan.gmax (the range hint of the fp16-split kernels)
+        self.irt_done = set()      # expand ops a fused block's backward has covered
+
+
 class HyperStarcopUNet(nn.Module):
     """Drop-in for ``ModelModule.network`` (smp.Unet mobilenet_v2), running on libstarcop_hip.so."""
 
@@ -282,6 +475,10 @@ class HyperStarcopUNet(nn.Module):
         self._plans = {}
         self._pflat = self._gflat = None
         self._pack_version = None
+        self._wpk, self._pack_tables = {}, {}      # layer -> packed filter layouts (_pack_all); its device-side descriptor tables
+        self._pw_need = {}                         # pointwise layer -> the layouts some plan's routes name (sticky over all plans)
+        self._irb_layers = set()                   # pointwise layers inside a fused inference block of some plan
+        self._nbt = None                           # the BatchNorm step counters (_nbt_list)
         self.register_load_state_dict_post_hook(HyperStarcopUNet._after_load)
 
     MAX_IN_CHANNELS, MAX_CLASSES = 16, 8                 # forward kernels: the stem's channels, the head's classes
@@ -480,6 +677,12 @@ class HyperStarcopUNet(nn.Module):
                 off += op["conv"].out_channels * 9
         self._last_dw = min(self._dw_offs, default=-1)      # the depthwise op the backward walk reaches last
         self._tail_lo = sum(p.numel() for p in self.encoder.parameters())      # flat offset of the decoder's / head's parameters
+        self._layers = {}       # pointwise / 3x3 op -> its static facts, what the routes (_fwd_route ...) decide from
+        for i, op in enumerate(ops):
+            if op["type"] in ("pw", "conv3"):
+                cv, cup = op["conv"], op["ins"][0].C if op.get("up") else 0
+                self._layers[i] = _Layer(op["type"], cv.out_channels, cv.in_channels, cv.kernel_size[0], bool(op.get("up")), cup,
+                                         cv.in_channels - cup if cup else 0, len(op["ins"]))
         return ops, tensors
 
     # ------------------------------------------------------------------------------------------
@@ -563,81 +766,118 @@ class HyperStarcopUNet(nn.Module):
 
     # ------------------------------------------------------------------------------------------
     class _Plan:
-        pass
+        """buffers and kernel routes of one input shape (callers may hang scratch of their own on it: loss_acc, reg_work)"""
+
+        def __init__(self, N, H, W, route_key):
+            self.N, self.H, self.W, self.route_key = N, H, W, route_key
+            self.routes, self.irt, self.irt_of_dw, self.irb = {}, {}, {}, {}      # _route_table; irt_of_dw: depthwise op -> expand op
+            self.buf, self.grad, self.cst, self.cstb = {}, {}, {}, {}
+            self.stats_v, self.bsums_v, self.srows, self.brows, self.irt_rows = {}, {}, {}, {}, {}
+            self.bn_scratch = self.fin_amax = self.act_amax = self.classes = self.x_cst = self.head = None
+            self.fin_slot, self.act_slot = {}, {}
+            self.n_eval = self.generation = 0
+            self.training, self.eval_cst_key = False, None
+            # backward (need_grad)
+            self.has_grad = False
+            self.irt_esums, self.irt_work, self.pw_part, self.dwrows, self.dwsums = {}, {}, {}, {}, {}
+            self.ws = self.spw_ws = self.spw_skip = self.up_tmp = self.dw_acc = self.gmax = self.dlogits = None
+            self.pw_table, self.dw_cast_table = {}, {}      # device descriptor tables of the batched reduction / cast launches
+
+    def _route_key(self):
+        """everything a plan's routes are derived from besides its shape.  _get_plan rebuilds a plan whose key differs and _pack_all repacks
+        on the same change: a precision switch (check_split_range) never meets rows, workspaces or layouts sized for other kernels."""
+        return (self.split_bf16, self._terms, self.fuse_irt, _PW3, _IRT, _IRB, _SP)
+
+    def _route_table(self, N, H, W):
+        """The kernel choices at one input shape and the current precision, no device needed: (routes {pointwise / 3x3 op: _Routes},
+        irt {expand op: depthwise op} -- inverted-residual blocks whose expansion + depthwise pair runs fused in TRAINING --,
+        irb {expand op: (depthwise op, project op, add op or None)} -- blocks that run as one launch in INFERENCE)"""
+        split, terms = self.split_bf16, self._terms
+        routes, irt, irb = {}, {}, {}
+        for i, L in self._layers.items():
+            o = self._ops[i]["out"]
+            a = (L, N, H >> o.shift, W >> o.shift, split, terms)
+            routes[i] = _Routes(_fwd_route(*a), _dgrad_route(*a), _wgrad_route(*a))
+        for i_e, (i_dw, i_pr, stride) in self._ir_blocks.items():
+            cv_e, cv_p, tin = self._ops[i_e]["conv"], self._ops[i_pr]["conv"], self._ops[i_e]["ins"][0]
+            if tin.kind == "input":
+                continue
+            Hi, Wi = H >> tin.shift, W >> tin.shift
+            if self.fuse_irt and _use_irt(N, cv_e.in_channels, cv_e.out_channels, Hi, Wi, stride):
+                irt[i_e] = i_dw
+            if _use_irb(N, cv_e.in_channels, cv_e.out_channels, cv_p.out_channels, Hi, Wi, stride):
+                i_add = i_pr + 1 if (i_pr + 1 < len(self._ops) and self._ops[i_pr + 1]["type"] == "add"
+                                     and self._ops[i_pr + 1]["ins"][1] is self._ops[i_pr]["out"]) else None
+                irb[i_e] = (i_dw, i_pr, i_add)
+        return routes, irt, irb
+
+    def kernel_table(self, N, H, W, training=True):
+        """Which kernel runs each op's passes at this shape and the current precision, in walk order: a list of {"op": output tensor,
+        "type", "fwd"} plus, for training, "dgrad" and "wgrad" (None: the op has no such pass).  Pointwise and 3x3 layers carry the
+        names of their routes (_fwd_route, _dgrad_route, _wgrad_route), ops inside a fused block "irt" (training block; its forward
+        also serves inference) or "irb" (inference block), every other op its type.  Needs no device."""
+        routes, irt, irb = self._route_table(N, H, W)
+        fused = {}
+        if not training:
+            fused.update((k, "irb") for i_e, members in irb.items() if i_e not in irt for k in (i_e,) + members if k is not None)
+        for i_e, i_dw in irt.items():
+            fused[i_e] = fused[i_dw] = "irt"
+        table = []
+        for i, op in enumerate(self._ops):
+            r, ty = routes.get(i), op["type"]
+            row = {"op": op["out"].name, "type": ty, "fwd": fused.get(i) or (r.fwd.kernel if r else ty)}
+            if training:
+                row["dgrad"] = fused.get(i) or (r.dgrad.kernel if r else None if ty == "stem" else ty)
+                row["wgrad"] = fused.get(i) or (r.wgrad.kernel + ("+" + r.wgrad.skip.kernel if r.wgrad.skip else "") if r else None if ty == "add" else ty)
+            table.append(row)
+        return table
 
     def _get_plan(self, N, H, W, need_grad, want_logits=True, want_classes=None):
         """want_logits=False (predict_classes): a plan created by this call gets no logits buffer; the first call that wants one adds it.
         want_classes (default: not want_logits) likewise for the (N, H, W) class buffer, which predict_classes_into does without."""
         want_classes = (not want_logits) if want_classes is None else want_classes
         key = (N, H, W)
-        plan = self._plans.get(key)
+        plan, carry = self._plans.get(key), None
         dev = self._pflat.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        lib = _lib.load()
+        if plan is not None and plan.route_key != self._route_key():
+            # other kernels, other buffer sizes: a new plan; the old one's buffers go first, its sticky range records move over
+            plan, carry = None, (plan.fin_amax, plan.act_amax, plan.n_eval, plan.generation)
+            del self._plans[key]
         if plan is None:
-            plan = HyperStarcopUNet._Plan()
-            plan.N, plan.H, plan.W = N, H, W
-            plan.buf, plan.grad = {}, {}
-            f32 = dict(dtype=torch.float32, device=dev)
-            lib = _lib.load()
-            plan.cst, plan.cstb, plan.stats_v, plan.bsums_v, plan.srows, plan.brows = {}, {}, {}, {}, {}, {}
-            kind_of = {"stem": STAT_STEM, "dw": STAT_DW, "conv3": STAT_CONV3, "pw": STAT_CONV1}
-            # inverted-residual blocks whose expansion + depthwise pair runs fused in TRAINING at this resolution: expand op -> depthwise op
-            plan.irt, plan.irt_of_dw, plan.irt_rows = {}, {}, {}
-            if self.fuse_irt:
-                for i_e, (i_dw, i_pr, stride) in self._ir_blocks.items():
-                    cv, tin = self._ops[i_e]["conv"], self._ops[i_e]["ins"][0]
-                    if tin.kind != "input" and _use_irt(N, cv.in_channels, cv.out_channels, H >> tin.shift, W >> tin.shift, stride):
-                        plan.irt[i_e], plan.irt_of_dw[i_dw] = i_dw, i_e
-                        te, td = self._ops[i_e]["out"], self._ops[i_dw]["out"]
-                        plan.irt_rows[te.name] = lib.sc_irt_rows(0, N, H >> tin.shift, W >> tin.shift, stride)
-                        plan.irt_rows[td.name] = lib.sc_irt_rows(1, N, H >> tin.shift, W >> tin.shift, stride)
+            plan = HyperStarcopUNet._Plan(N, H, W, self._route_key())
+            plan.routes, plan.irt, plan.irb = self._route_table(N, H, W)
+            plan.irt_of_dw = {i_dw: i_e for i_e, i_dw in plan.irt.items()}
+            for i_e, i_dw in plan.irt.items():
+                tin, stride = self._ops[i_e]["ins"][0], self._ir_blocks[i_e][2]
+                for which, t in enumerate((self._ops[i_e]["out"], self._ops[i_dw]["out"])):
+                    plan.irt_rows[t.name] = lib.sc_irt_rows(which, N, H >> tin.shift, W >> tin.shift, stride)
             irt_e = {self._ops[i]["out"].name for i in plan.irt}
-            for op in self._ops:
+            for i, op in enumerate(self._ops):
                 t = op["out"]
                 if t.kind != "input" and t.name not in plan.buf and t.name not in irt_e and t.name != "logits":      # (a fused block's expanded tensor exists
                     plan.buf[t.name] = torch.empty((N, t.C, H >> t.shift, W >> t.shift), **f32)     #  only in inference: _forward_impl)
                 if t.bn is not None:
                     Ho, Wo = H >> t.shift, W >> t.shift
                     # per-work-group partial rows [rows][C][2] (plain stores; summed in fp64 by the finalize kernels)
-                    kind = kind_of[op["type"]]
-                    if op["type"] == "pw" and _use_pw3(0, N, Ho * Wo, op["conv"].in_channels, op["conv"].out_channels):
-                        kind = STAT_PW3
-                    elif op["type"] == "pw" and _use_ksplit(N, Ho * Wo, op["conv"].in_channels, op["conv"].out_channels):
-                        kind = STAT_CONV1K
-                    plan.srows[t.name] = max(lib.sc_stat_rows(kind, N, Ho, Wo), plan.irt_rows.get(t.name, 0))
+                    rows = plan.routes[i].fwd.rows if i in plan.routes else lib.sc_stat_rows({"stem": STAT_STEM, "dw": STAT_DW}[op["type"]], N, Ho, Wo)
+                    plan.srows[t.name] = max(rows, plan.irt_rows.get(t.name, 0))
                     plan.brows[t.name] = lib.sc_stat_rows(STAT_BNBWD, N, Ho, Wo)
                     plan.stats_v[t.name] = torch.empty(plan.srows[t.name] * t.C * 2, **f32)
                     plan.cst[t.name] = torch.zeros((t.C, SC_CST), **f32)
                     plan.cstb[t.name] = torch.zeros((t.C, SC_CST), **f32)
-            # inference: stride-1 inverted-residual blocks that run as one launch at this resolution: expand op -> (depthwise op,
-            # project op, add op or None); their two 1x1 filters are needed in the PW3 layout (packed for inference forwards only)
-            plan.irb = {}
-            for i_e, (i_dw, i_pr, stride) in self._ir_blocks.items():
-                cv_e, cv_p, tin = self._ops[i_e]["conv"], self._ops[i_pr]["conv"], self._ops[i_e]["ins"][0]
-                if tin.kind != "input" and _use_irb(N, cv_e.in_channels, cv_e.out_channels, cv_p.out_channels, H >> tin.shift, W >> tin.shift, stride):
-                    i_add = i_pr + 1 if (i_pr + 1 < len(self._ops) and self._ops[i_pr + 1]["type"] == "add"
-                                         and self._ops[i_pr + 1]["ins"][1] is self._ops[i_pr]["out"]) else None
-                    plan.irb[i_e] = (i_dw, i_pr, i_add)
-                    lay = getattr(self, "_irb_layers", None)
-                    if lay is None:
-                        lay = self._irb_layers = set()
-                    if not {i_e, i_pr} <= lay:
-                        lay.update((i_e, i_pr))
-                        self._pack_version = None
-                        self._pack_tables = {}
-            # which filter layouts the pointwise layers need at this resolution (sticky over all plans of the network)
-            need = getattr(self, "_pw_need", None)
-            if need is None:
-                need = self._pw_need = {}
-            for i, op in enumerate(self._ops):
-                if op["type"] == "pw":
-                    hw = (H >> op["out"].shift) * (W >> op["out"].shift)
-                    for tflip in (0, 1):
-                        cv = op["conv"]
-                        lay = "pw3" if _use_pw3(tflip, N, hw, cv.in_channels, cv.out_channels) else "mfma"
-                        if lay not in need.setdefault((i, tflip), set()):
-                            need[(i, tflip)].add(lay)
-                            self._pack_version = None
-                            self._pack_tables = {}
+            # the filter layouts the routes of this plan name (sticky over all plans of the network).  The two 1x1 filters of a fused
+            # inference block are read in the PW3 layout whatever their own routes are ("pfi", packed for inference forwards only)
+            for i, r in plan.routes.items():
+                named = {r.fwd.layout, r.dgrad.launches[0][1]}
+                if self._layers[i].type == "pw" and not named <= self._pw_need.setdefault(i, set()):
+                    self._pw_need[i] |= named
+                    self._pack_version, self._pack_tables = None, {}
+            for i_e, (i_dw, i_pr, i_add) in plan.irb.items():
+                if not {i_e, i_pr} <= self._irb_layers:
+                    self._irb_layers.update((i_e, i_pr))
+                    self._pack_version, self._pack_tables = None, {}
             fins = [t.name for t in self._tensors.values() if t.kind == "fin" and t.name != "logits"]
             plan.bn_scratch = torch.empty(64 * 2 * max(t.C for t in self._tensors.values()), dtype=torch.float64, device=dev)   # sc_bn_finalize: coalesced pre-reduction of many-row statistics
             plan.fin_slot = {n: i for i, n in enumerate(fins)}
@@ -645,187 +885,112 @@ class HyperStarcopUNet(nn.Module):
             raw_feed = self._split_feeders()[0]
             plan.act_slot = {n: i for i, n in enumerate(raw_feed)}
             plan.act_amax = torch.zeros(max(len(raw_feed), 1), **f32)   # sticky max |BN output| of the split kernels' BatchNorm-fed inputs
-            plan.n_eval = 0
-            plan.has_grad = False
+            if carry is not None:
+                plan.fin_amax, plan.act_amax, plan.n_eval, plan.generation = carry
             self._plans[key] = plan
         if want_logits and "logits" not in plan.buf:
             plan.buf["logits"] = torch.empty((N, self.classes, H, W), dtype=torch.float32, device=dev)
-        if want_classes and getattr(plan, "classes", None) is None:
+        if want_classes and plan.classes is None:
             plan.classes = torch.empty((N, H, W), dtype=torch.uint8, device=dev)
         if need_grad and not plan.has_grad:
-            lib = _lib.load()
-            f32 = dict(dtype=torch.float32, device=dev)
-            ws, up = 0, 0
-            n_dw = 0
-            irt_e = {self._ops[i]["out"].name for i in plan.irt}
-            plan.irt_esums, plan.irt_work = {}, {}
-            for i_e in plan.irt:
-                cv, tin, te = self._ops[i_e]["conv"], self._ops[i_e]["ins"][0], self._ops[i_e]["out"]
-                Hi, Wi = H >> tin.shift, W >> tin.shift
-                plan.irt_esums[te.name] = torch.empty(lib.sc_irt_bwd_rows(N, cv.out_channels, Hi, Wi) * cv.out_channels * 2, dtype=torch.float64, device=dev)
-                plan.irt_work[te.name] = torch.empty(lib.sc_irt_bwd_workspace_floats(N, cv.in_channels, cv.out_channels, Hi, Wi), **f32)
-            for op in self._ops:
-                o = op["out"]
-                Ho, Wo = H >> o.shift, W >> o.shift
-                if op["type"] != "head" and o.kind != "fin" and o.name not in irt_e:
-                    plan.grad[o.name] = torch.empty((N, o.C, Ho, Wo), **f32)
-                if op["type"] == "add":
-                    plan.grad[o.name] = torch.empty((N, o.C, Ho, Wo), **f32)
-                conv = op.get("conv")
-                if op["type"] in ("pw", "conv3"):
-                    ws = max(ws, lib.sc_wgrad_workspace_floats(N, Ho, Wo, conv.out_channels, conv.in_channels,
-                                                               conv.kernel_size[0]))
-                    if conv.kernel_size[0] == 3:
-                        ws = max(ws, lib.sc_wgrad_bx3_workspace_floats(N, Ho, Wo, conv.out_channels, conv.in_channels))
-                        if conv.out_channels <= 16 and conv.in_channels in (16, 32):
-                            ws = max(ws, lib.sc_wgrad_thin16_workspace_floats(N, Ho, Wo, conv.out_channels, conv.in_channels))
-                    if op.get("up"):
-                        up = max(up, N * op["ins"][0].C * Ho * Wo)
-                elif op["type"] == "stem":
-                    ws = max(ws, lib.sc_stem_wgrad_workspace_floats(N, conv.in_channels, H, W))
-                elif op["type"] == "head":
-                    ws = max(ws, lib.sc_head_wgrad_workspace_floats(N, conv.in_channels, Ho, Wo))
-                elif op["type"] == "dw":
-                    n_dw += conv.out_channels * 9
-            # decoder conv1 weight gradients as box-sum GEMMs (conv_spw.hip): box-sum planes, split source, K-slice partials; the skip
-            # channels' dense gradient before it is scattered into its columns
-            spw_b, spw_sk = 0, 0
-            for op in self._ops:
-                if op["type"] == "conv3" and op.get("up"):
-                    cv, o_ = op["conv"], op["out"]
-                    Hq, Wq = H >> o_.shift, W >> o_.shift
-                    cu_ = op["ins"][0].C
-                    if _use_spw(N, Hq, Wq, cv.out_channels, cu_):
-                        spw_b = max(spw_b, lib.sc_sp_wgrad_workspace_bytes(N, Hq, Wq, cv.out_channels, cu_))
-                        if cv.in_channels > cu_:
-                            spw_sk = max(spw_sk, cv.out_channels * (cv.in_channels - cu_) * 9)
-                            ws = max(ws, lib.sc_wgrad_bx3_workspace_floats(N, Hq, Wq, cv.out_channels, cv.in_channels - cu_),
-                                     lib.sc_wgrad_workspace_floats(N, Hq, Wq, cv.out_channels, cv.in_channels - cu_, 3))
-            plan.spw_ws = torch.empty(spw_b + 256, dtype=torch.uint8, device=dev) if spw_b else None
-            plan.spw_skip = torch.empty(spw_sk, **f32) if spw_sk else None
-            plan.ws = torch.empty(ws, **f32)
-            plan.ws_floats = ws
-            # pointwise weight gradients keep their K-slice partials in buffers of their own until ONE batched reduction at the
-            # end of the backward pass (sc_wgrad_reduce_batch) instead of 2-3 dependent few-microsecond launches per layer
-            plan.pw_part, plan.pw_table = {}, None
-            for i, op in enumerate(self._ops):
-                if op["type"] == "pw" and i not in plan.irt:
-                    conv, o = op["conv"], op["out"]
-                    Hq, Wq = H >> o.shift, W >> o.shift
-                    nfl = (lib.sc_wgrad_pw3_workspace_floats(N, Hq, Wq, conv.out_channels, conv.in_channels)
-                           if _use_pw3(2, N, Hq * Wq, conv.in_channels, conv.out_channels)
-                           else lib.sc_wgrad_workspace_floats(N, Hq, Wq, conv.out_channels, conv.in_channels, 1))
-                    plan.pw_part[i] = torch.empty(nfl, **f32)
-            plan.up_tmp = torch.empty(max(up, 1), **f32)
-            plan.dw_acc = torch.zeros(n_dw, dtype=torch.float64, device=dev)
-            # one float per BatchNorm'd tensor: max |gamma*invstd * g| of its gradient, the range hint of the fp16-split kernels
-            plan.gmax = torch.zeros(len(self._ops) + 1, dtype=torch.float32, device=dev)
-            for t in self._tensors.values():
-                if t.bn is not None:
-                    plan.bsums_v[t.name] = torch.empty(plan.brows[t.name] * t.C * 2, dtype=torch.float64, device=dev)
-            # inputs of the depthwise convolutions: their BatchNorm-backward sums come out of the fused depthwise backward
-            plan.dwrows, plan.dwsums = {}, {}
-            for op in self._ops:
-                if op["type"] == "dw" and op["ins"][0].bn is not None and op["ins"][0].name not in irt_e:
-                    ti = op["ins"][0]
-                    plan.dwrows[ti.name] = lib.sc_stat_rows(STAT_DW, N, H >> ti.shift, W >> ti.shift)
-                    plan.dwsums[ti.name] = torch.empty(plan.dwrows[ti.name] * ti.C * 2, dtype=torch.float64, device=dev)
-            plan.dlogits = torch.empty((N, 1, H, W), **f32)
-            plan.has_grad = True
+            self._size_backward(plan)
         return plan
 
+    def _size_backward(self, plan):
+        """gradient buffers and the workspaces of the backward kernels the plan's routes name"""
+        lib = _lib.load()
+        N, H, W = plan.N, plan.H, plan.W
+        dev = self._pflat.device
+        f32 = dict(dtype=torch.float32, device=dev)
+        irt_e = {self._ops[i]["out"].name for i in plan.irt}
+        for i_e in plan.irt:
+            cv, tin, te = self._ops[i_e]["conv"], self._ops[i_e]["ins"][0], self._ops[i_e]["out"]
+            Hi, Wi = H >> tin.shift, W >> tin.shift
+            plan.irt_esums[te.name] = torch.empty(lib.sc_irt_bwd_rows(N, cv.out_channels, Hi, Wi) * cv.out_channels * 2, dtype=torch.float64, device=dev)
+            plan.irt_work[te.name] = torch.empty(lib.sc_irt_bwd_workspace_floats(N, cv.in_channels, cv.out_channels, Hi, Wi), **f32)
+        # ws: K-slice partials of the weight gradients that reduce in their own launch.  Pointwise weight gradients keep theirs in
+        # buffers of their own (pw_part) until ONE batched reduction at the end of the backward pass (sc_wgrad_reduce_batch) instead of
+        # 2-3 dependent few-microsecond launches per layer.  Decoder conv1 weight gradients as box-sum GEMMs (conv_spw.hip): box-sum
+        # planes, split source, K-slice partials (spw_b); the skip channels' dense gradient before it is scattered into its columns (spw_sk)
+        ws = up = n_dw = spw_b = spw_sk = 0
+        for i, op in enumerate(self._ops):
+            o, conv, ty = op["out"], op.get("conv"), op["type"]
+            Ho, Wo = H >> o.shift, W >> o.shift
+            if ty != "head" and o.kind != "fin" and o.name not in irt_e:
+                plan.grad[o.name] = torch.empty((N, o.C, Ho, Wo), **f32)
+            if ty == "add":
+                plan.grad[o.name] = torch.empty((N, o.C, Ho, Wo), **f32)
+            if i in plan.routes:
+                L, r = self._layers[i], plan.routes[i]
+                # ws holds the fp32-MFMA and split kernels' partials of every layer whatever the precision routes it to (so that a
+                # precision switch finds the capacity it had), and the routed kernel's
+                ws = max(ws, _wgrad_floats("mfma", N, Ho, Wo, L.Cout, L.Cin, L.ks), _wgrad_floats("bx3", N, Ho, Wo, L.Cout, L.Cin, 3) if L.ks == 3 else 0)
+                if r.wgrad.kernel == "spw":
+                    spw_b = max(spw_b, lib.sc_sp_wgrad_workspace_bytes(N, Ho, Wo, L.Cout, L.Cup))
+                    if r.wgrad.skip:
+                        spw_sk = max(spw_sk, L.Cout * L.Csk * 9)
+                        ws = max(ws, _wgrad_floats(r.wgrad.skip.kernel, N, Ho, Wo, L.Cout, L.Csk, 3))
+                elif ty == "pw" and i not in plan.irt:
+                    plan.pw_part[i] = torch.empty(_wgrad_floats(r.wgrad.kernel, N, Ho, Wo, L.Cout, L.Cin, 1), **f32)
+                else:       # (a fused block's expansion, walked on its own by only_ops, reduces in its own launch on the fp32 MFMA)
+                    ws = max(ws, _wgrad_floats(r.wgrad.kernel if ty == "conv3" else "mfma", N, Ho, Wo, L.Cout, L.Cin, L.ks))
+                if r.dgrad.launches[0][3] == 2:
+                    up = max(up, N * L.Cup * Ho * Wo)
+            elif ty == "stem":
+                ws = max(ws, lib.sc_stem_wgrad_workspace_floats(N, conv.in_channels, H, W))
+            elif ty == "head":
+                ws = max(ws, lib.sc_head_wgrad_workspace_floats(N, conv.in_channels, Ho, Wo))
+            elif ty == "dw":
+                n_dw += conv.out_channels * 9
+                ti = op["ins"][0]
+                if ti.bn is not None and ti.name not in irt_e:      # its BatchNorm-backward sums come out of the fused depthwise backward
+                    plan.dwrows[ti.name] = lib.sc_stat_rows(STAT_DW, N, H >> ti.shift, W >> ti.shift)
+                    plan.dwsums[ti.name] = torch.empty(plan.dwrows[ti.name] * ti.C * 2, dtype=torch.float64, device=dev)
+        plan.spw_ws = torch.empty(spw_b + 256, dtype=torch.uint8, device=dev) if spw_b else None
+        plan.spw_skip = torch.empty(spw_sk, **f32) if spw_sk else None
+        plan.ws = torch.empty(ws, **f32)
+        plan.up_tmp = torch.empty(max(up, 1), **f32)
+        plan.dw_acc = torch.zeros(n_dw, dtype=torch.float64, device=dev)
+        # one float per BatchNorm'd tensor: max |gamma*invstd * g| of its gradient, the range hint of the fp16-split kernels
+        plan.gmax = torch.zeros(len(self._ops) + 1, dtype=torch.float32, device=dev)
+        for t in self._tensors.values():
+            if t.bn is not None:
+                plan.bsums_v[t.name] = torch.empty(plan.brows[t.name] * t.C * 2, dtype=torch.float64, device=dev)
+        plan.dlogits = torch.empty((N, 1, H, W), **f32)
+        plan.has_grad = True
+
     # ------------------------------------------------------------------------------------------
+    def _wanted_layouts(self, i):
+        """the filter layouts _pack_all keeps for layer i: all of a 3x3 layer's (_layouts); of a pointwise layer's what the plans' routes name,
+        plus "pfi" (filled by inference forwards only) for a fused inference block's filter that no plan runs on sc_conv1x1_pw3"""
+        if self._layers[i].type != "pw":
+            return set(_layouts(self._layers[i], self.split_bf16, self._terms))
+        need = self._pw_need.get(i, set())
+        return need | {"pfi"} if (i in self._irb_layers and "pf" not in need) else need
+
     def _pack_all(self, need_bwd):
         """(Re)pack conv filters into the MFMA kernels' layouts when the parameters changed."""
         lib = _lib.load()
-        ver = (tuple(p._version for p in self.parameters()), self._terms, self.split_bf16)    # a precision switch repacks too
+        split, terms = self.split_bf16, self._terms
+        ver = (tuple(p._version for p in self.parameters()), terms, split)    # a precision switch repacks too
         pv = self._pack_version
-        need_irb = (not need_bwd) and bool(getattr(self, "_irb_layers", None))      # the fused inference blocks' PW3 layouts
+        need_irb = (not need_bwd) and bool(self._irb_layers)      # the fused inference blocks' PW3 layouts
         if pv is not None and pv[0] == ver and (pv[1] or not need_bwd) and (pv[2] or not need_irb):
             return
         st = stream()
         dev = self._pflat.device
-        if not hasattr(self, "_wpk"):
-            self._wpk = {}
-        for i, op in enumerate(self._ops):
-            if op["type"] not in ("pw", "conv3"):
-                continue
-            conv = op["conv"]
-            co, ci, ks = conv.out_channels, conv.in_channels, conv.kernel_size[0]
+        for i, L in self._layers.items():
             ent = self._wpk.get(i)
-            tf_, tb_ = self._terms
-            if ent is None or ent["f"].device != dev or ent["split"] != (self.split_bf16, tf_, tb_):
-                cf, cb = _pick_cot(co, ks), _pick_cot(ci, ks)
-                if ks == 3 and co <= 16 and ci >= 32 and self.split_bf16:
-                    cf = 32       # decoder.blocks.4.conv1 (32 -> 16): the split kernel with half-empty cout blocks still beats
-                                  # the fp32-MFMA thin kernel (0.36 vs 0.50 ms); 16 -> 16 layers do not (tools/bench_thin_bx3.py)
-                # 3x3 layers with >= 32 output channels run on the 16-bit matrix cores with exactly-split operands
-                # (fp32-level accuracy, conv_bx3.hip; `precision` picks the split); thin ones stay on the fp32 MFMA kernels
-                xf = self.split_bf16 and ks == 3 and cf >= 32
-                xb = self.split_bf16 and ks == 3 and cb >= 32
-                nf = lib.sc_packed_weight_floats_bx3(co, ci, cf, 0, tf_) if xf else lib.sc_packed_weight_floats(co, ci, ks, cf, 0)
-                nb = lib.sc_packed_weight_floats_bx3(co, ci, cb, 1, tb_) if xb else lib.sc_packed_weight_floats(co, ci, ks, cb, 1)
-                ent = dict(cot_f=cf, cot_b=cb, bx3_f=xf, bx3_b=xb, split=(self.split_bf16, tf_, tb_), terms_f=tf_, terms_b=tb_,
-                           f=torch.empty(nf, dtype=torch.float32, device=dev),
-                           b=torch.empty(nb, dtype=torch.float32, device=dev), tf=None, tb=None, tsd=None)
-                # decoder.blocks.4 (<= 16 output channels at full resolution) under the two-fp16-term split: filters in registers
-                # (sc_conv3x3_thin16; 0.20-0.28 vs 0.31-0.51 ms per launch).  The backward-data kernel only takes the plain
-                # epilogue, so the regular pack is kept beside it.
-                if self.split_bf16 and ks == 3 and len(op["ins"]) == 1:
-                    if tf_ == TERMS_F16X2 and co <= 16 and ci in (16, 32):
-                        ent["tf"] = torch.empty(lib.sc_packed_weight_floats_thin16(co, ci, 0), dtype=torch.float32, device=dev)
-                    if tb_ == TERMS_F16X2 and ci <= 16 and co in (16, 32):
-                        ent["tb"] = torch.empty(lib.sc_packed_weight_floats_thin16(co, ci, 1), dtype=torch.float32, device=dev)
-                    if tb_ == TERMS_F16X2 and op.get("up") and co == 16 and ci == 32:
-                        # decoder.blocks.4.conv1: the half-resolution data gradient in its sub-pixel form (sc_conv3x3_thin16 with down0)
-                        ent["tsd"] = torch.empty(lib.sc_packed_weight_floats_thin16(co, ci, 1), dtype=torch.float32, device=dev)
-                # decoder conv1 data gradient (up-sampled channels + skip channels): the two outputs as TWO launches with their own
-                # cout tiles -- 64-wide for the up-sampled part (a multiple of 64), one 32-wide tile for the <= 32 skip channels --
-                # instead of one launch of 32-wide tiles (80 = 64 + 16: 3 x 32; 152 = 128 + 24: 5 x 32): every cout tile stages (loads,
-                # BatchNorm-backward prologue, split) the whole gradient patch again.  Measured at 16 x 512^2: decoder.blocks.2.conv1
-                # 212 -> 197 us (5 -> 3 passes), decoder.blocks.3.conv1 293 -> 288 us (a 64-wide pass costs two 32-wide ones there: the
-                # operand reads and MFMAs, not the staging, are what its work-groups wait for); 288 = 256 + 32, which already runs on
-                # 64-wide tiles, loses 5 us to the second launch and stays as it was.  Step +0.6 % (same-box pairs).
-                if xb and cb == 32 and op.get("up") and len(op["ins"]) == 2:
-                    cu, cs_ = op["ins"][0].C, op["ins"][1].C
-                    if cu % 64 == 0 and cs_ <= 32 and cu + cs_ == ci:
-                        ent["bA"] = torch.empty(lib.sc_packed_weight_floats_bx3(co, ci, 64, 1, tb_), dtype=torch.float32, device=dev)
-                        ent["bB"] = torch.empty(lib.sc_packed_weight_floats_bx3(co, ci, 32, 1, tb_), dtype=torch.float32, device=dev)
-                        ent["bB_off"] = ent["bB"].numel() // (-(-ci // 32)) * (cu // 32)      # floats before the skip channels' tile
-                # decoder conv1 forward as a sub-pixel convolution (the two-fp16-term arithmetic or, "bf16", one bf16 term): phase /
-                # parity filters
-                if op.get("up") and xf and tf_ in _SP_TERMS and _SP != "0":
-                    cu = op["ins"][0].C
-                    ent["sp"] = torch.empty(lib.sc_packed_weight_floats_sp(co, cu, ci - cu), dtype=torch.float32, device=dev)
-                    ent["sp_cu"] = cu
-                # ... and the data gradient of its up-sampled channels (the skip channels' gradient: a 3x3 launch on a 32-wide pack)
-                if op.get("up") and xb and tb_ in _SP_TERMS and _SP != "0" and op["ins"][0].C % 32 == 0:
-                    cu = op["ins"][0].C
-                    ent["spd_vskip"] = bool(ci > cu and lib.sc_spd_vskip_ok(cu, ci - cu))     # decoder.blocks.3: skip gradient in the same launch
-                    # ... or as additional channel tiles of that launch (skip tiles), where measured faster than a 3x3 launch of its own
-                    ent["spd_stiles"] = bool(ci > cu and not ent["spd_vskip"] and _use_spd_skip_tiles(cu, ci - cu))
-                    ent["spd"] = torch.empty(lib.sc_packed_weight_floats_spd(co, cu, ci - cu if ent["spd_stiles"] else 0), dtype=torch.float32, device=dev)
-                    ent["sp_cu"] = cu
-                    if ci > cu and ent.get("bB") is None and not ent["spd_vskip"] and not ent["spd_stiles"]:
-                        ent["bB"] = torch.empty(lib.sc_packed_weight_floats_bx3(co, ci, 32, 1, tb_), dtype=torch.float32, device=dev)
-                        ent["bB_off"] = ent["bB"].numel() // (-(-ci // 32)) * (cu // 32)
-                self._wpk[i] = ent
+            if ent is None or ent["key"] != (dev, split, terms, _SP):
+                ent = self._wpk[i] = {"key": (dev, split, terms, _SP), "spec": _layouts(L, split, terms)}
                 self._pack_tables = {}
-            if op["type"] == "pw":       # the split-bf16 layout of sc_conv1x1_pw3, where a plan runs this layer on it
-                need = getattr(self, "_pw_need", {})
-                for tflip, key in ((0, "pf"), (1, "pb")):
-                    if "pw3" in need.get((i, tflip), ()) and (ent.get(key) is None or ent[key].device != dev):
-                        ent[key] = torch.empty(lib.sc_packed_weight_floats_pw3(co, ci, tflip), dtype=torch.float32, device=dev)
-                        self._pack_tables = {}
-                # a fused inference block's filter whose layer does not run on sc_conv1x1_pw3 otherwise: a PW3 pack of its own, filled
-                # by inference forwards only (a training step never reads it)
-                if (i in getattr(self, "_irb_layers", ()) and "pw3" not in need.get((i, 0), ())
-                        and (ent.get("pfi") is None or ent["pfi"].device != dev)):
-                    ent["pfi"] = torch.empty(lib.sc_packed_weight_floats_pw3(co, ci, 0), dtype=torch.float32, device=dev)
+            for name in (self._wanted_layouts(i) if L.type == "pw" else ent["spec"]):
+                if name not in ent:
+                    ent[name] = torch.empty(ent["spec"][name][0], dtype=torch.float32, device=dev)
                     self._pack_tables = {}
         # one launch for all packs: device-side descriptor table, built once per (need_bwd, parameter storage)
-        key = (bool(need_bwd), self._pflat.data_ptr(), self._terms, need_irb)
-        tab = self._pack_tables.get(key) if hasattr(self, "_pack_tables") else None
+        key = (bool(need_bwd), self._pflat.data_ptr(), terms, need_irb)
+        tab = self._pack_tables.get(key)
         if tab is None:
             import numpy as np
             dt = np.dtype([("w", "<u8"), ("wpk", "<u8"), ("Cout", "<i4"), ("Cin", "<i4"), ("ks", "<i4"), ("co_t", "<i4"),
@@ -834,74 +999,36 @@ class HyperStarcopUNet(nn.Module):
             # decoder's 3x3 layouts and all backward layouts, most of the work -- which a training step packs on the weight-gradient
             # stream while the encoder runs (see the launches below)
             early, late = [], []
-
-            def add(is_early, w, buf, co, ci, ks, cot, tflip, code):
-                total = lib.sc_pack_work_items(co, ci, ks, cot, tflip, int(code))
-                (early if is_early else late).append((w.data_ptr(), buf.data_ptr(), co, ci, ks, cot, tflip, int(code), total))
-
-            for i, op in enumerate(self._ops):
-                if op["type"] not in ("pw", "conv3"):
-                    continue
-                conv, ent = op["conv"], self._wpk[i]
-                co, ci, ks = conv.out_channels, conv.in_channels, conv.kernel_size[0]
-                is_pw = op["type"] == "pw"
-                for tflip, buf, cot, bx in ((0, ent["f"], ent["cot_f"], ent["bx3_f"]), (1, ent["b"], ent["cot_b"], ent["bx3_b"])):
-                    if tflip and not need_bwd:
+            for i, L in self._layers.items():
+                w, ent = self._ops[i]["conv"].weight, self._wpk[i]
+                wanted = self._wanted_layouts(i) if L.type == "pw" else ent["spec"]
+                for name in _PACK_ORDER:
+                    if name not in wanted or (name in _BWD_LAYOUTS and not need_bwd) or (name == "pfi" and not need_irb):
                         continue
-                    if is_pw and "mfma" not in getattr(self, "_pw_need", {}).get((i, tflip), ("mfma",)):
-                        continue        # every plan runs this layer on sc_conv1x1_pw3: the fp32-MFMA layout is not needed
-                    add(is_pw and not tflip, conv.weight, buf, co, ci, ks, cot, tflip, (ent["terms_b"] if tflip else ent["terms_f"]) if bx else 0)
-                for cot, buf in ((64, ent.get("bA")), (32, ent.get("bB"))):
-                    if buf is not None and need_bwd:
-                        add(False, conv.weight, buf, co, ci, ks, cot, 1, ent["terms_b"])
-                if ent.get("spd") is not None and need_bwd:
-                    tfl = (3 if ent["spd_stiles"] else (2 if ent["spd_vskip"] else 1)) | (4 if ent["terms_b"] == 1 else 0)      # | 4: the one-bf16-term layout
-                    add(False, conv.weight, ent["spd"], co, ci, ks, ent["sp_cu"], tfl, PACK_SPD)
-                if ent.get("sp") is not None:
-                    add(False, conv.weight, ent["sp"], co, ci, ks, ent["sp_cu"], 4 if ent["terms_f"] == 1 else 0, PACK_SP)
-                for tflip, buf in ((0, ent["tf"]), (1, ent["tb"]), (1, ent.get("tsd"))):
-                    if buf is not None and (not tflip or need_bwd):
-                        add(False, conv.weight, buf, co, ci, ks, 16, tflip, PACK_THIN16)
-                for tflip, buf in ((0, ent.get("pf")), (1, ent.get("pb"))):
-                    if buf is not None and (not tflip or need_bwd):
-                        add(is_pw and not tflip, conv.weight, buf, co, ci, 1, 0, tflip, PACK_PW3)
-                if need_irb and ent.get("pfi") is not None and "pw3" not in getattr(self, "_pw_need", {}).get((i, 0), ()):
-                    add(True, conv.weight, ent["pfi"], co, ci, 1, 0, 0, PACK_PW3)
+                    _, cot, tflip, code = ent["spec"][name]
+                    total = lib.sc_pack_work_items(L.Cout, L.Cin, L.ks, cot, tflip, int(code))
+                    (early if L.type == "pw" and name in ("f", "pf", "pfi") else late).append(
+                        (w.data_ptr(), ent[name].data_ptr(), L.Cout, L.Cin, L.ks, cot, tflip, int(code), total))
 
-            def table(rows):
-                starts, nblk = [], 0
-                for r in rows:
-                    starts.append(nblk)
-                    nblk += -(-r[-1] // 256)
-                if not rows:
-                    return None
-                descs = torch.from_numpy(np.array(rows, dtype=dt).view(np.uint8).copy()).to(dev)
-                return (descs, torch.tensor(starts, dtype=torch.int32).to(dev), len(rows), nblk)
-            tab = (table(early), table(late))
-            if not hasattr(self, "_pack_tables"):
-                self._pack_tables = {}
-            self._pack_tables[key] = tab
+            tab = self._pack_tables[key] = tuple(
+                _block_table(np.array(rows, dtype=dt).tobytes(), [r[-1] for r in rows], dev) if rows else None for rows in (early, late))
         # launches: the encoder's layouts on the current stream; the rest, in a training step, on the weight-gradient stream behind a
         # device-scope wait (the parameters are final on the current stream) -- the forward walk waits for it before its first 3x3
         # convolution (_forward_impl), i.e. ~0.12 ms of packing leaves the critical path and runs beside the encoder.  Otherwise
         # (inference, no overlap stream, graph capture) on the current stream too.
         self._late_pack_stream = None
+
+        def pack(t, sx):
+            check(lib.sc_pack_weights_batch(ptr(t[0]), ptr(t[1]), t[2], t[3], sx))
         if tab[0] is not None:
-            check(lib.sc_pack_weights_batch(ptr(tab[0][0]), ptr(tab[0][1]), tab[0][2], tab[0][3], st))
-        if tab[1] is not None:
-            side = None
-            if need_bwd and self.overlap_wgrad and not torch.cuda.is_current_stream_capturing():
-                main = torch.cuda.current_stream()
-                if self._side_stream is None or self._side_stream.device != main.device:
-                    self._side_stream = torch.cuda.Stream(device=main.device)
-                side = self._side_stream
-            if side is not None:
-                sh = C.c_void_p(side.cuda_stream)
-                check(lib.sc_stream_wait_stream(sh, st))
-                check(lib.sc_pack_weights_batch(ptr(tab[1][0]), ptr(tab[1][1]), tab[1][2], tab[1][3], sh))
-                self._late_pack_stream = sh
-            else:
-                check(lib.sc_pack_weights_batch(ptr(tab[1][0]), ptr(tab[1][1]), tab[1][2], tab[1][3], st))
+            pack(tab[0], st)
+        if tab[1] is not None and need_bwd and self.overlap_wgrad and not torch.cuda.is_current_stream_capturing():
+            sh = C.c_void_p(self._wgrad_stream(torch.cuda.current_stream()).cuda_stream)
+            check(lib.sc_stream_wait_stream(sh, st))
+            pack(tab[1], sh)
+            self._late_pack_stream = sh
+        elif tab[1] is not None:
+            pack(tab[1], st)
         self._pack_version = (ver, bool(need_bwd), need_irb)
 
     # ------------------------------------------------------------------------------------------
@@ -950,20 +1077,17 @@ class HyperStarcopUNet(nn.Module):
         x = x.contiguous().float()
         plan = self._get_plan(N, H, W, need_grad, want_logits=head == "logits", want_classes=head == "classes")
         plan.buf["x"] = x
-        plan.x_cst = x_cst
-        plan.generation = getattr(plan, "generation", 0) + 1     # activations of an earlier forward of this shape are gone
+        plan.x_cst, plan.head = x_cst, (head, mosaic)
+        plan.generation += 1     # activations of an earlier forward of this shape are gone
         self._pack_all(need_grad)
         st = stream()
         # inference: the BatchNorm constants depend only on parameters and running statistics -- 62 five-microsecond launches of the
         # dependency chain (a tenth of a batch-16 forward) are skipped while neither has changed since this plan last computed them
-        eval_key = None
-        if not training:
-            eval_key = (tuple(p._version for p in self.parameters()), tuple(b._version for b in self.buffers()), self._stat_epoch)
+        eval_key = None if training else (tuple(p._version for p in self.parameters()), tuple(b._version for b in self.buffers()), self._stat_epoch)
         # (never while a hipGraph is being captured: the graph must contain the finalize launches, or its replays would keep the
         # constants of capture time whatever happens to the parameters afterwards.  Writers that bypass torch's version counters --
         # a broadcast into the flat buffer, raw-pointer updates -- must call mark_parameters_changed().)
-        eval_cst_ok = (eval_key is not None and getattr(plan, "eval_cst_key", None) == eval_key
-                       and not torch.cuda.is_current_stream_capturing())
+        eval_cst_ok = eval_key is not None and plan.eval_cst_key == eval_key and not torch.cuda.is_current_stream_capturing()
         if training:
             self._stat_epoch += 1            # running statistics are about to be updated through raw pointers
             plan.eval_cst_key = None
@@ -972,166 +1096,26 @@ class HyperStarcopUNet(nn.Module):
             # constants of tensors it never materialises
             for t in self._tensors.values():
                 if t.bn is not None:
-                    bn = t.bn
-                    check(lib.sc_bn_finalize(None, 0, 1.0, ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var),
-                                             float(bn.momentum), float(bn.eps), 0, ptr(plan.cst[t.name]), t.C, None, None, st))
+                    self._bn_finalize(plan, t, None, 0, 1.0, None, st)
         skip = set()
         for i, op in enumerate(self._ops):
             if i in skip:
                 continue
-            ty, o = op["type"], op["out"]
-            Ho, Wo = H >> o.shift, W >> o.shift
             if i in plan.irt:
-                if training:
-                    self._irt_forward(plan, i, st)
-                    skip.add(plan.irt[i])
-                    continue
-                # inference: the same fused forward with the running-statistics constants (computed up front above), no statistics
-                a_irt = self._irt_args(plan, i)
-                td = self._ops[plan.irt[i]]["out"]
-                self._cur_op = td.name + ":fwd"
-                tok = self._pb("k_irt_* (fused expand+dw)")
-                check(lib.sc_irt_fwd(C.byref(a_irt), ptr(plan.buf[td.name]), None, st))
-                self._pe(tok)
+                self._irt_forward(plan, i, training, st)
                 skip.add(plan.irt[i])
                 continue
             if not training and i in plan.irb:
-                # inference: the whole inverted-residual block in one launch (conv_irb.hip); covers the depthwise, projection and add ops
-                i_dw, i_pr, i_add = plan.irb[i]
-                op_d, op_p = self._ops[i_dw], self._ops[i_pr]
-                tin, te, td, tp = op["ins"][0], o, op_d["out"], op_p["out"]
-                ent_e, ent_p = self._wpk[i], self._wpk[i_pr]
-                pe = ent_e["pf"] if "pw3" in self._pw_need.get((i, 0), ()) else ent_e["pfi"]
-                pp_ = ent_p["pf"] if "pw3" in self._pw_need.get((i_pr, 0), ()) else ent_p["pfi"]
-                a = sc_irb_args()
-                a.x = self._src_of(plan, tin)
-                a.wpk_expand, a.cst_expand = pe.data_ptr(), plan.cst[te.name].data_ptr()
-                a.w_dw, a.cst_dw = op_d["conv"].weight.data_ptr(), plan.cst[td.name].data_ptr()
-                a.wpk_project = pp_.data_ptr()
-                a.N, a.Cin, a.hidden, a.Cout = N, op["conv"].in_channels, op["conv"].out_channels, op_p["conv"].out_channels
-                a.H, a.W, a.stride = H >> tin.shift, W >> tin.shift, self._ir_blocks[i][2]
-                if i_add is not None:
-                    tz = self._ops[i_add]["out"]
-                    a.residual, a.cst_project = 1, plan.cst[tp.name].data_ptr()
-                    a.out = plan.buf[tz.name].data_ptr()
-                    a.z_absmax = plan.fin_amax.data_ptr() + 4 * plan.fin_slot[tz.name]
-                    skip.add(i_add)
-                else:
-                    a.residual, a.cst_project, a.z_absmax = 0, None, None
-                    a.out = plan.buf[tp.name].data_ptr()
-                self._cur_op = tp.name + ":fwd"
-                tok = self._pb("k_irb (fused block, eval)")
-                check(lib.sc_irb_eval(C.byref(a), st))
-                self._pe(tok)
-                skip.update((i_dw, i_pr))
+                skip.update(self._fwd_irb(plan, i, st))
                 continue
+            ty, o = op["type"], op["out"]
             stats = ptr(plan.stats_v[o.name]) if (training and o.bn is not None) else None
-            srows = plan.srows.get(o.name, 0)
-            conv = op.get("conv")
-            ent = self._wpk[i] if ty in ("pw", "conv3") else None
-            # a decoder conv1 in its sub-pixel form (sc_conv3x3_sp)?
-            use_sp = bool(op.get("up") and ent.get("sp") is not None and ent["terms_f"] in _SP_TERMS and self.split_bf16
-                          and _use_sp(N, Ho, Wo, o.C))
-            tok = None
             self._cur_op = o.name + ":fwd"
-            if self.profile is not None:
-                if ty in ("pw", "conv3"):
-                    src_elems = sum(t.C * (H >> t.shift) * (W >> t.shift) for t in op["ins"])
-                    fl = 2.0 * N * Ho * Wo * conv.out_channels * conv.in_channels * conv.kernel_size[0] ** 2
-                    fle = None
-                    if use_sp and ent["tf"] is None:
-                        cu_ = op["ins"][0].C        # per low-resolution pixel: 16 slots per up-sampled channel, 16 per (skip channel, parity)
-                        fle = 2.0 * N * (Ho // 2) * (Wo // 2) * 16 * (-(-conv.out_channels // 32) * 32) * (cu_ + 4 * (conv.in_channels - cu_))
-                    tok = self._pb("k_conv3_thin_h (fwd+dgrad)" if ent["tf"] is not None else
-                                   self._bx3_family("fwd") if ent["bx3_f"] else f"k_conv_mfma<{conv.kernel_size[0]}> (fwd+dgrad)",
-                                   fl, 4.0 * (N * src_elems + N * o.C * Ho * Wo + conv.weight.numel()), fle)
-                else:
-                    tok = self._pb({"stem": "k_stem_*", "dw": "k_dw_*", "head": "k_head_*", "add": "elementwise/bn"}[ty])
-            if ty == "stem":
-                s = self._src_of(plan, op["ins"][0], x_cst=x_cst)
-                check(lib.sc_stem_conv_fwd(C.byref(s), ptr(conv.weight), ptr(plan.buf[o.name]), N, conv.in_channels,
-                                           H, W, stats, st))
-            elif ty == "dw":
-                tin = op["ins"][0]
-                s = self._src_of(plan, tin)
-                check(lib.sc_dwconv3x3_fwd(C.byref(s), ptr(conv.weight), ptr(plan.buf[o.name]), N, o.C,
-                                           H >> tin.shift, W >> tin.shift, op["stride"], stats, st))
-            elif ty in ("pw", "conv3"):
-                if ty == "conv3" and self._late_pack_stream is not None:      # the decoder's filter layouts were packed beside the encoder
-                    check(lib.sc_stream_wait_stream(st, self._late_pack_stream))
-                    self._late_pack_stream = None
-                a = sc_conv_args()
-                ins = op["ins"]
-                a.nsrc = len(ins)
-                a.src[0] = self._src_of(plan, ins[0], up=1 if op.get("up") else 0)
-                if len(ins) == 2:
-                    a.src[1] = self._src_of(plan, ins[1])
-                a.wpk = ent["f"].data_ptr()
-                a.N, a.H, a.W, a.Cout = N, Ho, Wo, o.C
-                a.ks, a.co_t = conv.kernel_size[0], ent["cot_f"]
-                a.out0 = plan.buf[o.name].data_ptr(); a.out1 = None
-                a.csplit, a.accum0, a.accum1 = o.C, 0, 0
-                a.add0 = None; a.add1 = None
-                a.stats = plan.stats_v[o.name].data_ptr() if stats is not None else None
-                a.terms = ent["terms_f"]
-                if ty == "conv3":
-                    for k_, t_ in enumerate(ins):
-                        a.xbound[k_] = self._xbound(plan, t_)
-                if ty == "pw" and _use_pw3(0, N, Ho * Wo, conv.in_channels, conv.out_channels):
-                    fconv = lib.sc_conv1x1_pw3
-                    a.wpk = ent["pf"].data_ptr()
-                elif use_sp:
-                    fconv = lib.sc_conv3x3_sp
-                    a.wpk = ent["sp"].data_ptr()
-                    srows = lib.sc_sp_stat_rows(N, Ho, Wo, o.C)       # one partial row per work-group tile (fewer than SC_STAT_CONV3's)
-                elif ent["tf"] is not None:
-                    fconv = lib.sc_conv3x3_thin16
-                    a.wpk = ent["tf"].data_ptr()
-                elif ent["bx3_f"]:
-                    fconv = lib.sc_conv3x3_bx3
-                elif _use_ksplit(N, Ho * Wo, conv.in_channels, conv.out_channels, a.ks):
-                    fconv = lib.sc_conv1x1_ksplit
-                else:
-                    fconv = lib.sc_conv2d_mfma
-                check(fconv(C.byref(a), st))
-            elif ty == "add":
-                sa = self._src_of(plan, op["ins"][0])
-                sb = self._src_of(plan, op["ins"][1])
-                # the residual sums are the only inputs of a split convolution that no BatchNorm bounds (the skips taken after
-                # features.3/6/13): their max |value| is recorded for split_range_report
-                check(lib.sc_add_srcs_absmax(C.byref(sa), C.byref(sb), ptr(plan.buf[o.name]), N, o.C, Ho * Wo,
-                                             plan.fin_amax.data_ptr() + 4 * plan.fin_slot[o.name], st))
-            elif ty == "head":
-                s = self._src_of(plan, op["ins"][0])
-                if head == "mosaic":
-                    mos = mosaic.classes
-                    check(lib.sc_head_conv_fwd_k_mosaic(C.byref(s), ptr(conv.weight), ptr(conv.bias), ptr(mos), mos.shape[0], mos.shape[1],
-                                                        mos.stride(0), mosaic.win, mosaic.win_host,
-                                                        N, conv.in_channels, self.classes, Ho, Wo, st))
-                elif head == "probmosaic":
-                    prob, mask, valid = mosaic.prob, mosaic.mask, mosaic.valid
-                    ref = prob if prob is not None else mask
-                    check(lib.sc_head_conv_fwd_mosaic_prob(
-                        C.byref(s), ptr(conv.weight), ptr(conv.bias), ptr(prob), prob.stride(0) if prob is not None else 0,
-                        ptr(mask), mask.stride(0) if mask is not None else 0, ref.shape[0], ref.shape[1],
-                        ptr(valid), valid.stride(0) if valid is not None else 0, valid.stride(1) if valid is not None else 0,
-                        mosaic.fill_bits, mosaic.nodata, mosaic.win, mosaic.win_host,
-                        N, conv.in_channels, Ho, Wo, st))
-                elif self.classes == 1 and head == "logits":
-                    check(lib.sc_head_conv_fwd(C.byref(s), ptr(conv.weight), ptr(conv.bias), ptr(plan.buf[o.name]),
-                                               N, conv.in_channels, Ho, Wo, st))
-                else:       # K classes and / or the fused argmax: exactly one of the two outputs
-                    check(lib.sc_head_conv_fwd_k(C.byref(s), ptr(conv.weight), ptr(conv.bias),
-                                                 ptr(plan.buf[o.name]) if head == "logits" else None,
-                                                 ptr(plan.classes) if head == "classes" else None,
-                                                 N, conv.in_channels, self.classes, Ho, Wo, st))
+            tok = self._fwd_profile(plan, i)
+            self._FWD[ty](self, plan, i, stats, st)
             self._pe(tok)
             if o.bn is not None and training:
-                bn = o.bn
-                check(lib.sc_bn_finalize(stats, srows, float(N * Ho * Wo), ptr(bn.weight), ptr(bn.bias),
-                                         ptr(bn.running_mean), ptr(bn.running_var), float(bn.momentum), float(bn.eps),
-                                         1 if training else 0, ptr(plan.cst[o.name]), o.C, ptr(plan.bn_scratch),
-                                         self._xbound(plan, o), st))
+                self._bn_finalize(plan, o, stats, plan.srows[o.name], float(N * (H >> o.shift) * (W >> o.shift)), self._xbound(plan, o), st)
         if self._late_pack_stream is not None:      # (no 3x3 layer ran: still order the main stream after the pack)
             check(lib.sc_stream_wait_stream(st, self._late_pack_stream))
             self._late_pack_stream = None
@@ -1140,37 +1124,173 @@ class HyperStarcopUNet(nn.Module):
         else:
             plan.eval_cst_key = eval_key
         plan.training = training
-        if (not training and self.precision == "fp32" and self.range_check_every and plan.act_slot
-                and not torch.cuda.is_current_stream_capturing()):
-            # inference: BatchNorm uses running statistics, so no bound of its output exists before the data has flowed.  The split
-            # convolutions scale their operands from the sticky records of the observed maxima (plan.act_amax); at the check cadence
-            # (first forward of a shape included) the handful of tensors is streamed once more and, if a value was beyond what the
-            # scale in force during THIS forward could carry (it was clamped), the forward is redone -- the records are updated by
-            # then, so the scales adapt; the precision mode does not change.  (Training needs none of this: sc_bn_finalize leaves
-            # the by-construction bound before any consumer runs.)
-            plan.n_eval += 1
-            if _recheck or plan.n_eval % self.range_check_every == 1 or self.range_check_every == 1:
-                before = plan.act_amax.clone()
-                self._record_activation_range(plan)
-                used = torch.where(before * 2 > self.FP16_MAX_ACT,
-                                   torch.exp2(torch.floor(torch.log2(self.FP16_MAX_ACT / before.clamp_min(1e-30)))), torch.full_like(before, 2.0))
-                if bool((plan.act_amax * used > 2 * self.FP16_MAX_ACT).any()):
-                    import warnings
-                    worst = float((plan.act_amax * used).max()) / 2.0
-                    if _recheck < 6:
-                        if _recheck == 0:
-                            self._inference_clamped += 1
-                            warnings.warn(f"HyperStarcopUNet (inference, precision='fp32'): an activation of {worst:.4g} (in units of the "
-                                          f"operand scale in force) exceeded the fp16 range of the split convolutions "
-                                          f"({self.FP16_MAX_ACT:g}) and was clamped; the forward is redone with the adapted scale.  "
-                                          f"Forwards between two checks (range_check_every={self.range_check_every}) are not re-examined: "
-                                          f"set range_check_every=1 for data of unknown range")
-                        return self._forward_impl(x, x_cst, training, need_grad, _recheck=_recheck + 1, head=head, mosaic=mosaic)
-                    self._inference_unrepaired += 1
-                    warnings.warn(f"HyperStarcopUNet (inference, precision='fp32'): activations still outside the fp16 range after 6 "
-                                  f"re-runs with adapted scales ({worst:.4g}); the returned logits carry operands clamped to "
-                                  f"+-65504/scale.  split_range_report()['ok'] is now False; use precision='fp32-x3' for this input")
+        if not training and self._inference_range_clamped(plan, _recheck):
+            return self._forward_impl(x, x_cst, training, need_grad, _recheck=_recheck + 1, head=head, mosaic=mosaic)
         return plan
+
+    def _fwd_profile(self, plan, i):
+        if self.profile is None:
+            return None
+        op = self._ops[i]
+        if i not in plan.routes:
+            return self._pb({"stem": "k_stem_*", "dw": "k_dw_*", "head": "k_head_*", "add": "elementwise/bn"}[op["type"]])
+        L, o, route = self._layers[i], op["out"], plan.routes[i].fwd
+        N, Ho, Wo = plan.N, plan.H >> o.shift, plan.W >> o.shift
+        src_elems = sum(t.C * (plan.H >> t.shift) * (plan.W >> t.shift) for t in op["ins"])
+        fl = 2.0 * N * Ho * Wo * L.Cout * L.Cin * L.ks ** 2
+        # sub-pixel form, per low-resolution pixel: 16 slots per up-sampled channel, 16 per (skip channel, parity)
+        fle = 2.0 * N * (Ho // 2) * (Wo // 2) * 16 * (-(-L.Cout // 32) * 32) * (L.Cup + 4 * L.Csk) if route.kernel == "sp" else None
+        return self._pb(route.family, fl, 4.0 * (N * src_elems + N * o.C * Ho * Wo + op["conv"].weight.numel()), fle)
+
+
+    def _fwd_irb(self, plan, i, st):
+        """inference: the whole inverted-residual block in one launch (conv_irb.hip); returns the depthwise, projection and add ops
+        it covers"""
+        i_dw, i_pr, i_add = plan.irb[i]
+        op, op_d, op_p = self._ops[i], self._ops[i_dw], self._ops[i_pr]
+        tin, te, td, tp = op["ins"][0], op["out"], op_d["out"], op_p["out"]
+        a = sc_irb_args()
+        a.x = self._src_of(plan, tin)
+        # (the PW3 layout of a filter: the layer's own where some plan runs it on sc_conv1x1_pw3, else the block's: _wanted_layouts)
+        a.wpk_expand = self._wpk[i]["pf" if "pf" in self._pw_need[i] else "pfi"].data_ptr()
+        a.wpk_project = self._wpk[i_pr]["pf" if "pf" in self._pw_need[i_pr] else "pfi"].data_ptr()
+        a.cst_expand = plan.cst[te.name].data_ptr()
+        a.w_dw, a.cst_dw = op_d["conv"].weight.data_ptr(), plan.cst[td.name].data_ptr()
+        a.N, a.Cin, a.hidden, a.Cout = plan.N, op["conv"].in_channels, op["conv"].out_channels, op_p["conv"].out_channels
+        a.H, a.W, a.stride = plan.H >> tin.shift, plan.W >> tin.shift, self._ir_blocks[i][2]
+        if i_add is not None:
+            tz = self._ops[i_add]["out"]
+            a.residual, a.cst_project = 1, plan.cst[tp.name].data_ptr()
+            a.out = plan.buf[tz.name].data_ptr()
+            a.z_absmax = plan.fin_amax.data_ptr() + 4 * plan.fin_slot[tz.name]
+        else:
+            a.residual, a.cst_project, a.z_absmax = 0, None, None
+            a.out = plan.buf[tp.name].data_ptr()
+        self._cur_op = tp.name + ":fwd"
+        tok = self._pb("k_irb (fused block, eval)")
+        check(_lib.load().sc_irb_eval(C.byref(a), st))
+        self._pe(tok)
+        return [k for k in plan.irb[i] if k is not None]
+
+    def _fwd_stem(self, plan, i, stats, st):
+        op = self._ops[i]
+        conv = op["conv"]
+        s = self._src_of(plan, op["ins"][0], x_cst=plan.x_cst)
+        check(_lib.load().sc_stem_conv_fwd(C.byref(s), ptr(conv.weight), ptr(plan.buf[op["out"].name]), plan.N, conv.in_channels,
+                                           plan.H, plan.W, stats, st))
+
+    def _fwd_dw(self, plan, i, stats, st):
+        op = self._ops[i]
+        tin, o = op["ins"][0], op["out"]
+        s = self._src_of(plan, tin)
+        check(_lib.load().sc_dwconv3x3_fwd(C.byref(s), ptr(op["conv"].weight), ptr(plan.buf[o.name]), plan.N, o.C,
+                                           plan.H >> tin.shift, plan.W >> tin.shift, op["stride"], stats, st))
+
+    def _fwd_conv(self, plan, i, stats, st):
+        """a pointwise or 3x3 layer on the kernel its forward route names"""
+        lib = _lib.load()
+        op, L, route = self._ops[i], self._layers[i], plan.routes[i].fwd
+        ins, o = op["ins"], op["out"]
+        if L.type == "conv3" and self._late_pack_stream is not None:      # the decoder's filter layouts were packed beside the encoder
+            check(lib.sc_stream_wait_stream(st, self._late_pack_stream))
+            self._late_pack_stream = None
+        a = sc_conv_args()
+        a.nsrc = len(ins)
+        a.src[0] = self._src_of(plan, ins[0], up=1 if L.up else 0)
+        if len(ins) == 2:
+            a.src[1] = self._src_of(plan, ins[1])
+        a.wpk = self._wpk[i][route.layout].data_ptr()
+        a.N, a.H, a.W, a.Cout = plan.N, plan.H >> o.shift, plan.W >> o.shift, o.C
+        a.ks, a.co_t = L.ks, route.cot
+        a.out0 = plan.buf[o.name].data_ptr(); a.out1 = None
+        a.csplit, a.accum0, a.accum1 = o.C, 0, 0
+        a.add0 = None; a.add1 = None
+        a.stats = plan.stats_v[o.name].data_ptr() if stats is not None else None
+        a.terms = self._terms[0]
+        if L.type == "conv3":
+            for k_, t_ in enumerate(ins):
+                a.xbound[k_] = self._xbound(plan, t_)
+        check(getattr(lib, route.entry)(C.byref(a), st))
+
+
+    def _fwd_add(self, plan, i, stats, st):
+        op = self._ops[i]
+        o = op["out"]
+        sa = self._src_of(plan, op["ins"][0])
+        sb = self._src_of(plan, op["ins"][1])
+        # the residual sums are the only inputs of a split convolution that no BatchNorm bounds (the skips taken after
+        # features.3/6/13): their max |value| is recorded for split_range_report
+        check(_lib.load().sc_add_srcs_absmax(C.byref(sa), C.byref(sb), ptr(plan.buf[o.name]), plan.N, o.C,
+                                             (plan.H >> o.shift) * (plan.W >> o.shift),
+                                             plan.fin_amax.data_ptr() + 4 * plan.fin_slot[o.name], st))
+
+    def _fwd_head(self, plan, i, stats, st):
+        lib, (head, mosaic) = _lib.load(), plan.head
+        conv, o, op = self._ops[i]["conv"], self._ops[i]["out"], self._ops[i]
+        N, Ho, Wo = plan.N, plan.H >> o.shift, plan.W >> o.shift
+        s = self._src_of(plan, op["ins"][0])
+        if head == "mosaic":
+            mos = mosaic.classes
+            check(lib.sc_head_conv_fwd_k_mosaic(C.byref(s), ptr(conv.weight), ptr(conv.bias), ptr(mos), mos.shape[0], mos.shape[1],
+                                                mos.stride(0), mosaic.win, mosaic.win_host,
+                                                N, conv.in_channels, self.classes, Ho, Wo, st))
+        elif head == "probmosaic":
+            prob, mask, valid = mosaic.prob, mosaic.mask, mosaic.valid
+            ref = prob if prob is not None else mask
+            check(lib.sc_head_conv_fwd_mosaic_prob(
+                C.byref(s), ptr(conv.weight), ptr(conv.bias), ptr(prob), prob.stride(0) if prob is not None else 0,
+                ptr(mask), mask.stride(0) if mask is not None else 0, ref.shape[0], ref.shape[1],
+                ptr(valid), valid.stride(0) if valid is not None else 0, valid.stride(1) if valid is not None else 0,
+                mosaic.fill_bits, mosaic.nodata, mosaic.win, mosaic.win_host,
+                N, conv.in_channels, Ho, Wo, st))
+        elif self.classes == 1 and head == "logits":
+            check(lib.sc_head_conv_fwd(C.byref(s), ptr(conv.weight), ptr(conv.bias), ptr(plan.buf[o.name]),
+                                       N, conv.in_channels, Ho, Wo, st))
+        else:       # K classes and / or the fused argmax: exactly one of the two outputs
+            check(lib.sc_head_conv_fwd_k(C.byref(s), ptr(conv.weight), ptr(conv.bias),
+                                         ptr(plan.buf[o.name]) if head == "logits" else None,
+                                         ptr(plan.classes) if head == "classes" else None,
+                                         N, conv.in_channels, self.classes, Ho, Wo, st))
+        plan.head = None      # (the caller's mosaics are not the plan's to keep)
+
+    _FWD = {"stem": _fwd_stem, "dw": _fwd_dw, "pw": _fwd_conv, "conv3": _fwd_conv, "add": _fwd_add, "head": _fwd_head}
+
+    def _inference_range_clamped(self, plan, _recheck):
+        """The range check of an inference forward: True if the forward has to be redone with adapted operand scales."""
+        if not (self.precision == "fp32" and self.range_check_every and plan.act_slot
+                and not torch.cuda.is_current_stream_capturing()):
+            return False
+        # inference: BatchNorm uses running statistics, so no bound of its output exists before the data has flowed.  The split
+        # convolutions scale their operands from the sticky records of the observed maxima (plan.act_amax); at the check cadence
+        # (first forward of a shape included) the handful of tensors is streamed once more and, if a value was beyond what the
+        # scale in force during THIS forward could carry (it was clamped), the forward is redone -- the records are updated by
+        # then, so the scales adapt; the precision mode does not change.  (Training needs none of this: sc_bn_finalize leaves
+        # the by-construction bound before any consumer runs.)
+        plan.n_eval += 1
+        if not (_recheck or plan.n_eval % self.range_check_every == 1 or self.range_check_every == 1):
+            return False
+        before = plan.act_amax.clone()
+        self._record_activation_range(plan)
+        used = torch.where(before * 2 > self.FP16_MAX_ACT,
+                           torch.exp2(torch.floor(torch.log2(self.FP16_MAX_ACT / before.clamp_min(1e-30)))), torch.full_like(before, 2.0))
+        if not bool((plan.act_amax * used > 2 * self.FP16_MAX_ACT).any()):
+            return False
+        import warnings
+        worst = float((plan.act_amax * used).max()) / 2.0
+        if _recheck < 6:
+            if _recheck == 0:
+                self._inference_clamped += 1
+                warnings.warn(f"HyperStarcopUNet (inference, precision='fp32'): an activation of {worst:.4g} (in units of the "
+                              f"operand scale in force) exceeded the fp16 range of the split convolutions "
+                              f"({self.FP16_MAX_ACT:g}) and was clamped; the forward is redone with the adapted scale.  "
+                              f"Forwards between two checks (range_check_every={self.range_check_every}) are not re-examined: "
+                              f"set range_check_every=1 for data of unknown range")
+            return True
+        self._inference_unrepaired += 1
+        warnings.warn(f"HyperStarcopUNet (inference, precision='fp32'): activations still outside the fp16 range after 6 "
+                      f"re-runs with adapted scales ({worst:.4g}); the returned logits carry operands clamped to "
+                      f"+-65504/scale.  split_range_report()['ok'] is now False; use precision='fp32-x3' for this input")
+        return False
 
     def _irt_args(self, plan, i_e):
         i_dw = plan.irt[i_e]
@@ -1183,38 +1303,39 @@ class HyperStarcopUNet(nn.Module):
         a.H, a.W, a.stride = plan.H >> tin.shift, plan.W >> tin.shift, self._ops[i_dw]["stride"]
         return a
 
-    def _irt_forward(self, plan, i_e, st):
-        """training forward of a fused block: statistics of the (never stored) expanded tensor -> its BatchNorm constants -> raw
-        depthwise output + statistics -> the depthwise BatchNorm's constants (conv_irt.hip)"""
+    def _bn_finalize(self, plan, t, stats, rows, count, xbound, st):
+        """BatchNorm constants of tensor t: from the partial statistics rows of its producer (training; updates the running
+        statistics), or with stats None from the running statistics (inference)"""
+        bn, train = t.bn, stats is not None
+        check(_lib.load().sc_bn_finalize(stats, rows, count, ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean), ptr(bn.running_var),
+                                         float(bn.momentum), float(bn.eps), int(train), ptr(plan.cst[t.name]), t.C,
+                                         ptr(plan.bn_scratch) if train else None, xbound, st))
+
+    def _irt_forward(self, plan, i_e, training, st):
+        """forward of a fused block.  Training: statistics of the (never stored) expanded tensor -> its BatchNorm constants -> raw
+        depthwise output + statistics -> the depthwise BatchNorm's constants (conv_irt.hip).  Inference: the same fused forward with
+        the running-statistics constants (computed up front, _forward_impl), no statistics"""
         lib = _lib.load()
-        i_dw = plan.irt[i_e]
-        te, td = self._ops[i_e]["out"], self._ops[i_dw]["out"]
+        te, td = self._ops[i_e]["out"], self._ops[plan.irt[i_e]]["out"]
         a = self._irt_args(plan, i_e)
-        cnt_e = float(plan.N * a.H * a.W)
-        Hd_, Wd_ = plan.H >> td.shift, plan.W >> td.shift
-        self._cur_op = te.name + ":fwd"
-        tok = self._pb("k_irt_* (fused expand+dw)")
-        check(lib.sc_irt_expand_stats(C.byref(a), ptr(plan.stats_v[te.name]), st))
-        self._pe(tok)
-        bn = te.bn
-        check(lib.sc_bn_finalize(ptr(plan.stats_v[te.name]), plan.irt_rows[te.name], cnt_e, ptr(bn.weight), ptr(bn.bias), ptr(bn.running_mean),
-                                 ptr(bn.running_var), float(bn.momentum), float(bn.eps), 1, ptr(plan.cst[te.name]), te.C,
-                                 ptr(plan.bn_scratch), None, st))
+        if training:
+            self._cur_op = te.name + ":fwd"
+            tok = self._pb("k_irt_* (fused expand+dw)")
+            check(lib.sc_irt_expand_stats(C.byref(a), ptr(plan.stats_v[te.name]), st))
+            self._pe(tok)
+            self._bn_finalize(plan, te, ptr(plan.stats_v[te.name]), plan.irt_rows[te.name], float(plan.N * a.H * a.W), None, st)
         self._cur_op = td.name + ":fwd"
         tok = self._pb("k_irt_* (fused expand+dw)")
-        check(lib.sc_irt_fwd(C.byref(a), ptr(plan.buf[td.name]), ptr(plan.stats_v[td.name]), st))
+        check(lib.sc_irt_fwd(C.byref(a), ptr(plan.buf[td.name]), ptr(plan.stats_v[td.name]) if training else None, st))
         self._pe(tok)
-        bn = td.bn
-        check(lib.sc_bn_finalize(ptr(plan.stats_v[td.name]), plan.irt_rows[td.name], float(plan.N * Hd_ * Wd_), ptr(bn.weight), ptr(bn.bias),
-                                 ptr(bn.running_mean), ptr(bn.running_var), float(bn.momentum), float(bn.eps), 1, ptr(plan.cst[td.name]), td.C,
-                                 ptr(plan.bn_scratch), None, st))
+        if training:
+            self._bn_finalize(plan, td, ptr(plan.stats_v[td.name]), plan.irt_rows[td.name],
+                              float(plan.N * (plan.H >> td.shift) * (plan.W >> td.shift)), None, st)
 
     def _nbt_list(self):
-        nbt = getattr(self, "_nbt", None)
-        if nbt is None or nbt[0].device != self._pflat.device:
-            nbt = [t.bn.num_batches_tracked for t in self._tensors.values() if t.bn is not None]
-            self._nbt = nbt
-        return nbt
+        if self._nbt is None or self._nbt[0].device != self._pflat.device:
+            self._nbt = [t.bn.num_batches_tracked for t in self._tensors.values() if t.bn is not None]
+        return self._nbt
 
     # weight gradients are off the critical path (nothing in the backward pass consumes them): they run on a second
     # HIP stream, forked after each layer's BatchNorm-backward constants and joined before the optimiser, so they fill
@@ -1233,12 +1354,6 @@ class HyperStarcopUNet(nn.Module):
     #   "bf16"       one bf16 term: plain bf16 matrix math, fp32 accumulation and fp32 tensors in HBM (BASELINE configs[3])
     precision = "fp32"
     _TERMS = {"fp32": (TERMS_F16X2, TERMS_F16X2), "fp32-x3": (3, 3), "fp32-bwd2": (3, 2), "fp32-2": (2, 2), "bf16": (1, 1)}
-
-    def _bx3_family(self, which):
-        """profiling family of the split-bf16 3x3 kernel: forward and dgrad launches are one family unless they run with a
-        different number of terms (then their MFMA ceilings differ)"""
-        tf_, tb_ = self._terms
-        return "k_conv3_bx3 (fwd+dgrad)" if tf_ == tb_ else f"k_conv3_bx3 ({which})"
 
     @property
     def _terms(self):
@@ -1265,445 +1380,327 @@ class HyperStarcopUNet(nn.Module):
         reducing that bucket while the encoder's backward still runs.  It is called with the weight-gradient stream
         current (ordered after the main stream), i.e. a collective issued inside it waits for both."""
         lib = _lib.load()
-        st = stream()
+        w = _BwdWalk(plan, stream(), dlogits.contiguous(), self._terms[1] == TERMS_F16X2)
         main = torch.cuda.current_stream()
-        side = sd = None
         if self.overlap_wgrad:
-            if self._side_stream is None or self._side_stream.device != main.device:
-                self._side_stream = torch.cuda.Stream(device=main.device)
-            side = self._side_stream
-            sd = C.c_void_p(side.cuda_stream)      # raw handle, looked up once per walk
-
-        def wgrad_launch(fn):
-            """run fn(stream_handle) on the weight-gradient stream, ordered after everything queued on the main stream.  (One fork per
-            launch: serving two to eight launches with one fork -- fewer markers in the main queue -- measured 0.5-2.5 % SLOWER, the
-            weight gradients then start too late to fill the gaps of the data-gradient chain.)"""
-            if side is None:
-                fn(st)
-            else:
-                check(lib.sc_stream_wait_stream(sd, st))      # same-device ordering without the system-scope fence of a default event
-                fn(sd)       # (every fn launches through the C ABI with the handle it is given: no stream context switch needed)
-
-        N, H, W = plan.N, plan.H, plan.W
-        if not getattr(plan, "training", False):
+            w.side = self._wgrad_stream(main)
+            w.sd = C.c_void_p(w.side.cuda_stream)      # raw handle, looked up once per walk
+        if not plan.training:
             raise RuntimeError("HyperStarcopUNet.backward: gradients need a train-mode forward (BatchNorm batch "
                                "statistics); call .train() first")
-        dlogits = dlogits.contiguous()
+        if plan.route_key != self._route_key():
+            raise RuntimeError("HyperStarcopUNet.backward: precision or a kernel switch changed since this plan's forward: run it again")
         plan.dw_acc.zero_()
-        half_bwd = self._terms[1] == TERMS_F16X2
-        gmax_slot = {}
-        if half_bwd:
+        if w.half_bwd:
             plan.gmax.zero_()
-        written = set()
-        res_of, n_cons, prod_idx, dw_offs, last_dw = self._res_of, self._n_cons, self._prod_idx, self._dw_offs, self._last_dw
-        gv = self._grad_view
-        reduced = set()      # tensors whose BatchNorm-backward sums were produced by the launch that wrote their gradient
-        pw_pending = []      # pointwise weight gradients whose K-slice partials await the batched reduction
-
-        def bn_backward(t, slot=None):
-            Ho, Wo = H >> t.shift, W >> t.shift
-            amax = None
-            if slot is not None:
-                amax = plan.gmax.data_ptr() + 4 * slot
-                gmax_slot[t.name] = amax
-            if t.name in reduced:          # the launch that wrote this gradient left the sums (and raised the range-hint slot)
-                check(lib.sc_bn_bwd_finalize(ptr(plan.dwsums[t.name]), plan.dwrows[t.name], float(N * Ho * Wo), ptr(plan.cst[t.name]),
-                                             ptr(gv(t.bn.weight)), ptr(gv(t.bn.bias)), ptr(plan.cstb[t.name]), t.C, st))
-                return
-            aslot = plan.act_slot.get(t.name)           # BatchNorm-fed input of a split convolution: sticky max |BN(y)| record
-            aact = plan.act_amax.data_ptr() + 4 * aslot if aslot is not None else None
-            if N * Ho * Wo <= self.bn_small_max and t.C >= 64:        # low-resolution layers: one launch, one block per channel
-                check(lib.sc_bn_bwd_small(ptr(plan.grad[t.name]), ptr(plan.buf[t.name]), ptr(plan.cst[t.name]), t.act, N, t.C,
-                                          Ho * Wo, ptr(gv(t.bn.weight)), ptr(gv(t.bn.bias)), ptr(plan.cstb[t.name]), amax, aact, st))
-                return
-            check(lib.sc_bn_bwd_reduce(ptr(plan.grad[t.name]), ptr(plan.buf[t.name]), ptr(plan.cst[t.name]), t.act,
-                                       ptr(plan.bsums_v[t.name]), N, t.C, Ho * Wo, amax, aact, st))
-            check(lib.sc_bn_bwd_finalize(ptr(plan.bsums_v[t.name]), plan.brows[t.name], float(N * Ho * Wo), ptr(plan.cst[t.name]),
-                                         ptr(gv(t.bn.weight)), ptr(gv(t.bn.bias)), ptr(plan.cstb[t.name]), t.C, st))
-
-        def reduce_pointwise_batch():
-            """ONE launch (weight-gradient stream) sums the K-slice partials of every pointwise weight gradient queued so far"""
-            if not pw_pending:
-                return
-            raw = b"".join(bytes(p_) for p_ in pw_pending)
-            if plan.pw_table is None:
-                plan.pw_table = {}
-            if raw not in plan.pw_table:
-                # descriptors are static for a plan, so the device table is built once -- and another one when a descriptor changes
-                # (parameters re-flattened / moved, a partial backward of the parity tests); earlier tables stay alive because a
-                # launch on the weight-gradient stream may still be reading them
-                import numpy as np
-                starts, nblk = [], 0
-                for p_ in pw_pending:
-                    starts.append(nblk)
-                    nblk += -(-int(p_.total) // 256)
-                plan.pw_table[raw] = (torch.from_numpy(np.frombuffer(raw, dtype=np.uint8).copy()).to(self._pflat.device),
-                                      torch.tensor(starts, dtype=torch.int32).to(self._pflat.device), len(pw_pending), nblk)
-            tab = plan.pw_table[raw]
-            tok = self._pb("k_wgrad_mfma<1> (+reduce)")
-            wgrad_launch(lambda sx: check(lib.sc_wgrad_reduce_batch(ptr(tab[0]), ptr(tab[1]), tab[2], tab[3], sx)))
-            self._pe(tok)
-            pw_pending.clear()
-
-        dw_casts = []        # (fp64 accumulator, flat fp32 gradient view, n) of the fused depthwise backward launches walked so far
-
-        def cast_dw_gradients():
-            """ONE launch (weight-gradient stream) rounds every depthwise filter gradient accumulated so far to fp32 -- per layer it was
-            a 5 us kernel behind its own fork of the weight-gradient stream, i.e. 17 more markers in the main queue per step"""
-            if not dw_casts:
-                return
-            key = tuple(dw_casts)
-            if getattr(plan, "dw_cast_table", None) is None:
-                plan.dw_cast_table = {}
-            if key not in plan.dw_cast_table:
-                import numpy as np
-                arr = np.array([(a, b, n) for a, b, n in dw_casts], dtype=np.uint64)
-                plan.dw_cast_table[key] = (torch.from_numpy(arr.view(np.uint8).copy()).to(self._pflat.device), len(dw_casts))
-            tab = plan.dw_cast_table[key]
-            wgrad_launch(lambda sx, tab=tab: check(lib.sc_cast_f64_f32_batch(ptr(tab[0]), tab[1], sx)))
-            dw_casts.clear()
-
-        last_pw = min((k for k, op_ in enumerate(self._ops) if op_["type"] == "pw" and k in plan.pw_part), default=-1)
         tail_lo = self._tail_lo
         tail_pending = on_tail_ready is not None
-        irt_done = set()
         for i in (range(len(self._ops) - 1, -1, -1) if only_ops is None else only_ops):
-            if i in irt_done:
+            if i in w.irt_done:
                 continue
             op = self._ops[i]
-            ty, o = op["type"], op["out"]
-            Ho, Wo = H >> o.shift, W >> o.shift
-            conv = op.get("conv")
+            ty, o, conv = op["type"], op["out"], op.get("conv")
             if tail_pending and (conv is None or (conv.weight.data_ptr() - self._pflat.data_ptr()) // 4 < tail_lo):
                 tail_pending = False            # first encoder op: the decoder/head bucket is complete
-                if side is not None:
-                    side.wait_stream(main)      # (a default event: the collective that starts here may leave the device)
-                    with torch.cuda.stream(side):
+                if w.side is not None:
+                    w.side.wait_stream(main)      # (a default event: the collective that starts here may leave the device)
+                    with torch.cuda.stream(w.side):
                         on_tail_ready(tail_lo, self._gflat.numel())
                 else:
                     on_tail_ready(tail_lo, self._gflat.numel())
             self._cur_op = o.name + ":bwd"
             if ty == "head":
-                tin = op["ins"][0]
-                s = self._src_of(plan, tin)
-                tok = self._pb("k_head_*")
-                # one sweep over (dlogits, x) for gin, dW and dbias (sc_head_conv_bwd) -- and, the head being the only consumer
-                # of the decoder's last tensor, that tensor's BatchNorm-backward sums and range hint (its raw values stream
-                # through the kernel anyway): saves sc_bn_bwd_reduce's pass over 2 x 268 MB at 16 x 512^2
-                bns = bna = None
-                if tin.bn is not None and tin.kind == "raw" and n_cons.get(tin.name, 0) == 1:
-                    if tin.name not in plan.dwsums:
-                        plan.dwrows[tin.name] = lib.sc_head_bwd_bn_rows(N, Ho, Wo)
-                        plan.dwsums[tin.name] = torch.empty(plan.dwrows[tin.name] * tin.C * 2, dtype=torch.float64, device=self._pflat.device)
-                    bns = ptr(plan.dwsums[tin.name])
-                    if half_bwd:
-                        bna = plan.gmax.data_ptr() + 4 * prod_idx[tin.name]
-                    reduced.add(tin.name)
-                check(lib.sc_head_conv_bwd(ptr(dlogits), C.byref(s), ptr(conv.weight), ptr(plan.grad[tin.name]), ptr(plan.ws),
-                                           plan.ws_floats, ptr(gv(conv.weight)), ptr(gv(conv.bias)), N, conv.in_channels, Ho, Wo,
-                                           bns, bna, st))
-                self._pe(tok)
-                written.add(tin.name)
+                self._bwd_head(w, i)
                 continue
             if ty == "add":
                 # z = a + BN(p): dL/d(BN(p)) = dL/dz (alias); a receives dL/dz through its expand-conv dgrad epilogue
                 p_t = op["ins"][1]
                 plan.grad[p_t.name] = plan.grad[o.name]
-                written.add(p_t.name)
+                w.written.add(p_t.name)
                 continue
             tok = self._pb("elementwise/bn")
-            bn_backward(o, i if (half_bwd and ty == "conv3") else None)
+            self._bn_backward(w, o, i if (w.half_bwd and ty == "conv3") else None)
             self._pe(tok)
             dy = self._dy_src(plan, o)
             if ty == "stem":
-                s = self._src_of(plan, op["ins"][0], x_cst=plan.x_cst)
-                tok = self._pb("k_stem_*")
-                wgrad_launch(lambda sx, dy=dy, s=s, conv=conv: check(lib.sc_stem_conv_wgrad(
-                    C.byref(dy), C.byref(s), ptr(plan.ws), plan.ws_floats, ptr(gv(conv.weight)), N, conv.in_channels, H, W, sx)))
-                self._pe(tok)
-                continue
-            if ty == "dw" and i in plan.irt_of_dw:
-                # fused block: ONE sweep over (dy_d, x) for the depthwise filter gradient, the BatchNorm-backward sums of the
-                # expanded tensor and the part of dx that does not depend on them; the constants; the Cin -> Cin fix-up of dx; the
-                # expansion filter's gradient from the partial rows on the weight-gradient stream.  Covers the expand op too.
-                i_e = plan.irt_of_dw[i]
-                irt_done.add(i_e)
-                op_e = self._ops[i_e]
-                te, tin, cv_e = op_e["out"], op_e["ins"][0], op_e["conv"]
-                a_irt = self._irt_args(plan, i_e)
-                acc = plan.dw_acc[dw_offs[i]:dw_offs[i] + o.C * 9]
-                work, esums = plan.irt_work[te.name], plan.irt_esums[te.name]
-                tok = self._pb("k_irt_* (fused expand+dw)")
-                wgrad_launch(lambda sx, a_irt=a_irt, work=work: check(lib.sc_irt_xmoments(C.byref(a_irt), ptr(work), sx)))
-                check(lib.sc_irt_bwd(C.byref(a_irt), C.byref(dy), ptr(esums), ptr(acc), ptr(work), st))
-                dw_casts.append((acc.data_ptr(), gv(conv.weight).data_ptr(), o.C * 9))
-                check(lib.sc_bn_bwd_finalize(ptr(esums), lib.sc_irt_bwd_rows(N, te.C, a_irt.H, a_irt.W), float(N * a_irt.H * a_irt.W),
-                                             ptr(plan.cst[te.name]), ptr(gv(te.bn.weight)), ptr(gv(te.bn.bias)), ptr(plan.cstb[te.name]), te.C, st))
-                z = res_of.get(tin.name)
-                check(lib.sc_irt_bwd_fix(C.byref(a_irt), ptr(plan.cstb[te.name]), ptr(work), ptr(plan.grad[tin.name]),
-                                         ptr(plan.grad[z]) if z is not None else None, 1 if tin.name in written else 0, st))
-                wgrad_launch(lambda sx, a_irt=a_irt, work=work, te=te, cv_e=cv_e: check(lib.sc_irt_wgrad_finalize(
-                    C.byref(a_irt), ptr(plan.cstb[te.name]), ptr(work), ptr(gv(cv_e.weight)), sx)))
-                self._pe(tok)
-                written.add(tin.name)
-                if i == last_dw:
-                    cast_dw_gradients()
-                continue
-            if ty == "dw":
-                tin = op["ins"][0]
-                Hi, Wi = H >> tin.shift, W >> tin.shift
-                s = self._src_of(plan, tin)
-                acc = plan.dw_acc[dw_offs[i]:dw_offs[i] + o.C * 9]
-                tok = self._pb("k_dw_*")
-                if (tin.name not in written and tin.bn is not None and tin.name in plan.dwsums
-                        and n_cons.get(tin.name, 0) == 1):      # the fused sums are complete only for a single-consumer input
-                    # one pass: dx, dW and the BatchNorm-backward sums of the (6x expanded) input tensor
-                    check(lib.sc_dwconv3x3_bwd_fused(C.byref(dy), C.byref(s), ptr(conv.weight), ptr(plan.grad[tin.name]), ptr(acc),
-                                                     ptr(plan.dwsums[tin.name]), N, o.C, Hi, Wi, op["stride"], st))
-                    dw_casts.append((acc.data_ptr(), gv(conv.weight).data_ptr(), o.C * 9))
-                    self._pe(tok)
-                    written.add(tin.name)
-                    reduced.add(tin.name)
-                    if i == last_dw:
-                        cast_dw_gradients()
-                    continue
-
-                def dw_wgrad(sx, dy=dy, s=s, acc=acc, conv=conv, o=o, Hi=Hi, Wi=Wi, stride=op["stride"]):
-                    check(lib.sc_dwconv3x3_wgrad(C.byref(dy), C.byref(s), ptr(acc), N, o.C, Hi, Wi, stride, sx))
-                    check(lib.sc_cast_f64_f32(ptr(acc), ptr(gv(conv.weight)), o.C * 9, sx))
-                wgrad_launch(dw_wgrad)
-                check(lib.sc_dwconv3x3_dgrad(C.byref(dy), ptr(conv.weight), ptr(plan.grad[tin.name]),
-                                             1 if tin.name in written else 0, N, o.C, Hi, Wi, op["stride"], st))
-                self._pe(tok)
-                written.add(tin.name)
-                if i == last_dw:
-                    cast_dw_gradients()
-                continue
-            # pw / conv3 : weight gradient
-            ins = op["ins"]
-            ks = conv.kernel_size[0]
-            wa = sc_wgrad_args()
-            wa.dy = dy
-            wa.nsrc = len(ins)
-            wa.src[0] = self._src_of(plan, ins[0], up=1 if op.get("up") else 0)
-            if len(ins) == 2:
-                wa.src[1] = self._src_of(plan, ins[1])
-            wa.N, wa.H, wa.W, wa.Cout, wa.Cin, wa.ks = N, Ho, Wo, o.C, conv.in_channels, ks
-            wa.part = plan.ws.data_ptr(); wa.part_floats = plan.ws_floats
-            wa.dw = gv(conv.weight).data_ptr()
-            wa.terms = self._terms[1]
-            wa.absmax = gmax_slot.get(o.name)
-            if ty == "conv3":
-                for k_, t_ in enumerate(ins):
-                    wa.xbound[k_] = self._xbound(plan, t_)
-            flop = 2.0 * N * Ho * Wo * conv.out_channels * conv.in_channels * ks * ks
-            if (op.get("up") and plan.spw_ws is not None and self.split_bf16 and self._terms[1] == TERMS_F16X2
-                    and _use_spw(N, Ho, Wo, conv.out_channels, ins[0].C)):
-                # decoder conv1 with many up-sampled channels: their filter gradient as nine plain GEMMs between the low-resolution source
-                # and tap-aligned 2x2 box sums of dy (conv_spw.hip); the skip channels' columns from the 3x3 kernel on the skip source alone
-                cu_ = ins[0].C
-                wu = sc_wgrad_args()
-                wu.dy, wu.nsrc = dy, 1
-                wu.src[0] = wa.src[0]
-                wu.N, wu.H, wu.W, wu.Cout, wu.Cin, wu.ks = N, Ho, Wo, o.C, conv.in_channels, 3
-                wu.part, wu.part_floats, wu.dw = None, 0, gv(conv.weight).data_ptr()
-                wu.terms, wu.absmax = self._terms[1], gmax_slot.get(o.name)
-                wu.xbound[0] = self._xbound(plan, ins[0])
-                wsb = C.c_void_p((plan.spw_ws.data_ptr() + 255) & ~255)
-                nb = plan.spw_ws.numel() - 256
-                tok = self._pb("k_wgrad3_bx3 (+reduce)", flop, 0.0, 2.0 * N * (Ho // 2) * (Wo // 2) * 9 * conv.out_channels * cu_
-                               + 2.0 * N * Ho * Wo * 9 * conv.out_channels * (conv.in_channels - cu_))
-                wgrad_launch(lambda sx, wu=wu, wsb=wsb, nb=nb: check(lib.sc_conv3x3_sp_wgrad(C.byref(wu), wsb, nb, sx)))
-                if len(ins) == 2:
-                    csk_ = ins[1].C
-                    wk = sc_wgrad_args()
-                    wk.dy, wk.nsrc = dy, 1
-                    wk.src[0] = wa.src[1]
-                    wk.N, wk.H, wk.W, wk.Cout, wk.Cin, wk.ks = N, Ho, Wo, o.C, csk_, 3
-                    wk.part, wk.part_floats, wk.dw = plan.ws.data_ptr(), plan.ws_floats, plan.spw_skip.data_ptr()
-                    wk.terms, wk.absmax = self._terms[1], gmax_slot.get(o.name)
-                    wk.xbound[0] = self._xbound(plan, ins[1])
-                    wsk = lib.sc_conv3x3_wgrad_bx3 if (o.C >= 32 and csk_ >= 32) else lib.sc_conv2d_wgrad_mfma
-
-                    def skip_cols(sx, wk=wk, wsk=wsk, csk_=csk_, cu_=cu_, conv=conv, o=o):
-                        check(wsk(C.byref(wk), sx))
-                        check(lib.sc_wgrad_scatter_cols(ptr(plan.spw_skip), ptr(gv(conv.weight)), o.C, csk_, conv.in_channels, cu_, sx))
-                    wgrad_launch(skip_cols)
-                self._pe(tok)
-                wfn = None
+                self._bwd_stem(w, i, dy)
+            elif ty == "dw":
+                (self._bwd_irt if i in plan.irt_of_dw else self._bwd_dw)(w, i, dy)
+                if i == self._last_dw:
+                    self._cast_dw_gradients(w)
             else:
-                wfn = (lib.sc_conv3x3_wgrad_bx3 if (self.split_bf16 and ks == 3 and conv.out_channels >= 32 and conv.in_channels >= 32)
-                       else lib.sc_conv2d_wgrad_mfma)     # 16-channel layers outside the cases below stay on the fp32 MFMA
-            if (wfn is not None and self.split_bf16 and ks == 3 and self._terms[1] == TERMS_F16X2 and len(ins) == 1
-                    and conv.out_channels <= 16 and conv.in_channels in (16, 32) and Wo % 2 == 0):
-                wfn = lib.sc_conv3x3_wgrad_thin16     # decoder.blocks.4: two fp16 terms on the 16x16x32 MFMA (was MFMA-bound in fp32)
-            tok = None if wfn is None else self._pb(
-                "k_wgrad3_bx3 (+reduce)" if wfn is lib.sc_conv3x3_wgrad_bx3 else
-                "k_wgrad_thin_h (+reduce)" if wfn is lib.sc_conv3x3_wgrad_thin16 else f"k_wgrad_mfma<{ks}> (+reduce)", flop)
-            if wfn is None:
-                pass                      # (the box-sum GEMM path above has queued this layer's weight gradient)
-            elif ty == "pw" and i in plan.pw_part:
-                wa.part = plan.pw_part[i].data_ptr(); wa.part_floats = plan.pw_part[i].numel()
-                pend = sc_wgrad_pending()
-                wdef = (lib.sc_conv1x1_wgrad_pw3 if _use_pw3(2, N, Ho * Wo, conv.in_channels, conv.out_channels)
-                        else lib.sc_conv2d_wgrad_mfma_deferred)
-                wgrad_launch(lambda sx, wa=wa, pend=pend, wdef=wdef: check(wdef(C.byref(wa), C.byref(pend), sx)))
-                pw_pending.append(pend)
-                if i == last_pw:
-                    # every pointwise layer has been walked: queue the batched reduction NOW, behind this layer's weight gradient, where it
-                    # runs beside the main stream's last data-gradient kernels (features.1's depthwise backward, 0.16 ms).  At the end of
-                    # the walk it was the side stream's last launch, 67 us exposed behind the stem's weight gradient before Adam.
-                    reduce_pointwise_batch()
-            else:
-                wgrad_launch(lambda sx, wfn=wfn, wa=wa: check(wfn(C.byref(wa), sx)))
-            self._pe(tok)
-            # data gradient
-            if ins[0].kind == "input":
-                continue
-            ent = self._wpk[i]
-            a = sc_conv_args()
-            a.nsrc = 1
-            a.src[0] = dy
-            a.wpk = ent["b"].data_ptr()
-            a.N, a.H, a.W, a.Cout = N, Ho, Wo, conv.in_channels
-            a.ks, a.co_t = ks, ent["cot_b"]
-            a.terms = ent["terms_b"]
-            a.absmax = gmax_slot.get(o.name)
-            if ent["bx3_b"]:
-                conv_dgrad = lib.sc_conv3x3_bx3
-            elif ty == "pw" and _use_pw3(1, N, Ho * Wo, conv.in_channels, conv.out_channels):
-                conv_dgrad = lib.sc_conv1x1_pw3
-                a.wpk = ent["pb"].data_ptr()
-            elif _use_ksplit(N, Ho * Wo, conv.out_channels, conv.in_channels, ks):
-                conv_dgrad = lib.sc_conv1x1_ksplit
-            else:
-                conv_dgrad = lib.sc_conv2d_mfma
-            a.add0 = None; a.add1 = None; a.stats = None
-            a.accum0 = a.accum1 = 0
-            # algorithmic bytes of the data gradient: g and y of the output once each, the input gradient once, the filter
-            gin_elems = N * conv.in_channels * Ho * Wo
-            if op.get("up") and ent["bx3_b"]:      # the upsampled source's gradient is stored 2x2-summed (quarter size)
-                gin_elems -= N * ins[0].C * Ho * Wo * 3 // 4
-            thin_b = (ent["tb"] is not None and not op.get("up") and ins[0].name not in written and res_of.get(ins[0].name) is None)
-            # decoder.blocks.4.conv1: 16 gradient channels -> 32 channels at half resolution, the sub-pixel form on the thin layer's MFMA
-            # (sc_conv3x3_thin16 with down0: 251 -> see DESIGN 16; otherwise sc_conv3x3_bx3 with its summing store)
-            thin_sd = (ent.get("tsd") is not None and op.get("up") and len(ins) == 1 and a.terms == TERMS_F16X2
-                       and Ho % 2 == 0 and Wo % 2 == 0)
-            # a decoder conv1's data gradient in its sub-pixel form (sc_conv3x3_sp_dgrad)?
-            use_spd = bool(op.get("up") and ent.get("spd") is not None and ent["terms_b"] in _SP_TERMS and self.split_bf16
-                           and _use_spd(N, Ho, Wo, ins[0].C, conv.in_channels - ins[0].C))
-            fle = None
-            if use_spd:
-                cu_ = ins[0].C          # up-sampled channels: 4 parity planes x 4 taps per low-resolution pixel; skip channels: the 3x3 form
-                fle = (2.0 * N * (Ho // 2) * (Wo // 2) * 16 * conv.out_channels * (-(-cu_ // 128) * 128 + (128 * -(-(conv.in_channels - cu_) // 32) if ent["spd_stiles"] else 0))
-                       + (0.0 if (ent["spd_vskip"] or ent["spd_stiles"]) else 2.0 * N * Ho * Wo * 9 * conv.out_channels * (conv.in_channels - cu_)))
-            tok = self._pb("k_conv3_thin_h (fwd+dgrad)" if (thin_b or thin_sd) else
-                           self._bx3_family("dgrad") if ent["bx3_b"] else f"k_conv_mfma<{ks}> (fwd+dgrad)", flop,
-                           4.0 * (2 * N * o.C * Ho * Wo + gin_elems + conv.weight.numel()), fle)
-            if use_spd:
-                if ent["spd_vskip"] or ent["spd_stiles"]:
-                    # <= 64 up-sampled + <= 16 skip channels (decoder.blocks.3): the skip channels' gradient as virtual channels of the
-                    # 128-channel tile's second half -- dy (g, y) is staged ONCE for both gradients (289 us in two 3x3 launches before);
-                    # skip tiles: as additional channel tiles of the launch (32 skip channels x 4 output parities each)
-                    t_up, t_sk = ins
-                    a.Cout, a.csplit = conv.in_channels, t_up.C
-                    a.wpk = ent["spd"].data_ptr()
-                    a.out0, a.out1 = plan.grad[t_up.name].data_ptr(), plan.grad[t_sk.name].data_ptr()
-                    a.accum0, a.accum1, a.down0 = (1 if t_up.name in written else 0), (1 if t_sk.name in written else 0), 0
-                    check(lib.sc_conv3x3_sp_dgrad(C.byref(a), st))
-                    written.add(t_up.name); written.add(t_sk.name)
-                    self._pe(tok)
-                    continue
-                # sub-pixel form: the up-sampled channels' gradient at half resolution from the four parity planes of dy (2.25x fewer
-                # MFMAs, 128 output channels per staged patch), the skip channels' by the 3x3 kernel on their own 32-wide tiles
-                t_up = ins[0]
-                a.Cout = a.csplit = t_up.C
-                a.wpk = ent["spd"].data_ptr()
-                a.out0, a.out1 = plan.grad[t_up.name].data_ptr(), None
-                a.accum0, a.down0 = (1 if t_up.name in written else 0), 0
-                check(lib.sc_conv3x3_sp_dgrad(C.byref(a), st))
-                written.add(t_up.name)
-                if len(ins) == 2:
-                    t_sk = ins[1]
-                    a.Cout = a.csplit = t_sk.C
-                    a.wpk, a.co_t = ent["bB"].data_ptr() + 4 * ent["bB_off"], 32
-                    a.out0 = plan.grad[t_sk.name].data_ptr()
-                    a.accum0 = 1 if t_sk.name in written else 0
-                    check(lib.sc_conv3x3_bx3(C.byref(a), st))
-                    written.add(t_sk.name)
-                self._pe(tok)
-                continue
-            if thin_sd:
-                t_up = ins[0]
-                a.Cout = a.csplit = t_up.C
-                a.wpk, a.co_t = ent["tsd"].data_ptr(), 16
-                a.out0, a.out1 = plan.grad[t_up.name].data_ptr(), None
-                a.accum0, a.down0 = (1 if t_up.name in written else 0), 1
-                check(lib.sc_conv3x3_thin16(C.byref(a), st))
-                self._pe(tok)
-                written.add(t_up.name)
-                continue
-            if op.get("up"):
-                t_up = ins[0]
-                fused_down = conv_dgrad is lib.sc_conv3x3_bx3      # the split-bf16 kernel stores the 2x2 sums itself
-                if fused_down and ent.get("bA") is not None:
-                    t_sk = ins[1]
-                    a.Cout = a.csplit = t_up.C
-                    a.wpk, a.co_t = ent["bA"].data_ptr(), 64
-                    a.out0, a.out1 = plan.grad[t_up.name].data_ptr(), None
-                    a.accum0, a.down0 = (1 if t_up.name in written else 0), 1
-                    check(conv_dgrad(C.byref(a), st))
-                    a.Cout = a.csplit = t_sk.C
-                    a.wpk, a.co_t = ent["bB"].data_ptr() + 4 * ent["bB_off"], 32
-                    a.out0 = plan.grad[t_sk.name].data_ptr()
-                    a.accum0, a.down0 = (1 if t_sk.name in written else 0), 0
-                    check(conv_dgrad(C.byref(a), st))
-                    self._pe(tok)
-                    written.add(t_sk.name); written.add(t_up.name)
-                    continue
-                a.csplit = t_up.C
-                if fused_down:
-                    a.out0 = plan.grad[t_up.name].data_ptr()
-                    a.accum0 = 1 if t_up.name in written else 0
-                    a.down0 = 1
-                else:
-                    a.out0 = plan.up_tmp.data_ptr()
-                if len(ins) == 2:
-                    t_sk = ins[1]
-                    a.out1 = plan.grad[t_sk.name].data_ptr()
-                    a.accum1 = 1 if t_sk.name in written else 0
-                    written.add(t_sk.name)
-                else:
-                    a.out1 = None
-                check(conv_dgrad(C.byref(a), st))
-                self._pe(tok)
-                if not fused_down:
-                    check(lib.sc_downsum2x2(ptr(plan.up_tmp), ptr(plan.grad[t_up.name]), 1 if t_up.name in written else 0,
-                                            N, t_up.C, Ho // 2, Wo // 2, st))
-                written.add(t_up.name)
-            else:
-                tin = ins[0]
-                a.out0 = plan.grad[tin.name].data_ptr(); a.out1 = None
-                a.csplit = conv.in_channels
-                a.accum0 = 1 if tin.name in written else 0
-                z = res_of.get(tin.name)
-                if z is not None:
-                    a.add0 = plan.grad[z].data_ptr()
-                if thin_b:
-                    conv_dgrad = lib.sc_conv3x3_thin16
-                    a.wpk = ent["tb"].data_ptr()
-                check(conv_dgrad(C.byref(a), st))
-                self._pe(tok)
-                written.add(tin.name)
-        reduce_pointwise_batch()
-        cast_dw_gradients()
-        if side is not None:
+                self._bwd_wgrad(w, i, dy)
+                if op["ins"][0].kind != "input":
+                    self._bwd_dgrad(w, i, dy)
+        self._reduce_pointwise_batch(w)
+        self._cast_dw_gradients(w)
+        if w.side is not None:
             # join: every weight gradient is in the flat buffer before Adam / all-reduce.  With a gradient exchange to follow
             # (on_tail_ready: the data-parallel path) a default event, otherwise the device-scope one
             if exchange_follows if exchange_follows is not None else on_tail_ready is not None:
-                main.wait_stream(side)
+                main.wait_stream(w.side)
             else:
-                check(lib.sc_stream_wait_stream(st, sd))
+                check(lib.sc_stream_wait_stream(w.st, w.sd))
+
+    def _wgrad_stream(self, main):
+        if self._side_stream is None or self._side_stream.device != main.device:
+            self._side_stream = torch.cuda.Stream(device=main.device)
+        return self._side_stream
+
+    def _wgrad_launch(self, w, fn):
+        """run fn(stream_handle) on the weight-gradient stream, ordered after everything queued on the main stream.  (One fork per
+        launch: serving two to eight launches with one fork -- fewer markers in the main queue -- measured 0.5-2.5 % SLOWER, the
+        weight gradients then start too late to fill the gaps of the data-gradient chain.)"""
+        if w.side is None:
+            fn(w.st)
+        else:
+            check(_lib.load().sc_stream_wait_stream(w.sd, w.st))      # same-device ordering without the system-scope fence of a default event
+            fn(w.sd)       # (every fn launches through the C ABI with the handle it is given: no stream context switch needed)
+
+    def _bn_backward(self, w, t, slot=None):
+        lib, plan, st, gv = _lib.load(), w.plan, w.st, self._grad_view
+        N, Ho, Wo = plan.N, plan.H >> t.shift, plan.W >> t.shift
+        amax = w.gmax_slot[t.name] = plan.gmax.data_ptr() + 4 * slot if slot is not None else None
+        if t.name in w.reduced:          # the launch that wrote this gradient left the sums (and raised the range-hint slot)
+            self._bn_bwd_finalize(w, t, plan.dwsums[t.name], plan.dwrows[t.name], N * Ho * Wo)
+            return
+        aslot = plan.act_slot.get(t.name)           # BatchNorm-fed input of a split convolution: sticky max |BN(y)| record
+        aact = plan.act_amax.data_ptr() + 4 * aslot if aslot is not None else None
+        if N * Ho * Wo <= self.bn_small_max and t.C >= 64:        # low-resolution layers: one launch, one block per channel
+            check(lib.sc_bn_bwd_small(ptr(plan.grad[t.name]), ptr(plan.buf[t.name]), ptr(plan.cst[t.name]), t.act, N, t.C,
+                                      Ho * Wo, ptr(gv(t.bn.weight)), ptr(gv(t.bn.bias)), ptr(plan.cstb[t.name]), amax, aact, st))
+            return
+        check(lib.sc_bn_bwd_reduce(ptr(plan.grad[t.name]), ptr(plan.buf[t.name]), ptr(plan.cst[t.name]), t.act,
+                                   ptr(plan.bsums_v[t.name]), N, t.C, Ho * Wo, amax, aact, st))
+        self._bn_bwd_finalize(w, t, plan.bsums_v[t.name], plan.brows[t.name], N * Ho * Wo)
+
+    def _bn_bwd_finalize(self, w, t, sums, rows, count):
+        gv, plan = self._grad_view, w.plan
+        check(_lib.load().sc_bn_bwd_finalize(ptr(sums), rows, float(count), ptr(plan.cst[t.name]), ptr(gv(t.bn.weight)), ptr(gv(t.bn.bias)),
+                                             ptr(plan.cstb[t.name]), t.C, w.st))
+
+    def _reduce_pointwise_batch(self, w):
+        """ONE launch (weight-gradient stream) sums the K-slice partials of every pointwise weight gradient queued so far"""
+        if not w.pw_pending:
+            return
+        lib, plan = _lib.load(), w.plan
+        raw = b"".join(bytes(p_) for p_ in w.pw_pending)
+        if raw not in plan.pw_table:
+            # descriptors are static for a plan, so the device table is built once -- and another one when a descriptor changes
+            # (parameters re-flattened / moved, a partial backward of the parity tests); earlier tables stay alive because a
+            # launch on the weight-gradient stream may still be reading them
+            plan.pw_table[raw] = _block_table(raw, [p_.total for p_ in w.pw_pending], self._pflat.device)
+        tab = plan.pw_table[raw]
+        tok = self._pb("k_wgrad_mfma<1> (+reduce)")
+        self._wgrad_launch(w, lambda sx: check(lib.sc_wgrad_reduce_batch(ptr(tab[0]), ptr(tab[1]), tab[2], tab[3], sx)))
+        self._pe(tok)
+        w.pw_pending.clear()
+
+    def _cast_dw_gradients(self, w):
+        """ONE launch (weight-gradient stream) rounds every depthwise filter gradient accumulated so far to fp32 -- per layer it was
+        a 5 us kernel behind its own fork of the weight-gradient stream, i.e. 17 more markers in the main queue per step"""
+        if not w.dw_casts:
+            return
+        lib, plan = _lib.load(), w.plan
+        key = tuple(w.dw_casts)
+        if key not in plan.dw_cast_table:
+            import numpy as np
+            arr = np.array([(a, b, n) for a, b, n in w.dw_casts], dtype=np.uint64)
+            plan.dw_cast_table[key] = (torch.from_numpy(arr.view(np.uint8).copy()).to(self._pflat.device), len(w.dw_casts))
+        tab = plan.dw_cast_table[key]
+        self._wgrad_launch(w, lambda sx: check(lib.sc_cast_f64_f32_batch(ptr(tab[0]), tab[1], sx)))
+        w.dw_casts.clear()
+
+    def _bwd_head(self, w, i):
+        lib, plan, gv = _lib.load(), w.plan, self._grad_view
+        op = self._ops[i]
+        conv, tin, o = op["conv"], op["ins"][0], op["out"]
+        N, Ho, Wo = plan.N, plan.H >> o.shift, plan.W >> o.shift
+        s = self._src_of(plan, tin)
+        tok = self._pb("k_head_*")
+        # one sweep over (dlogits, x) for gin, dW and dbias (sc_head_conv_bwd) -- and, the head being the only consumer
+        # of the decoder's last tensor, that tensor's BatchNorm-backward sums and range hint (its raw values stream
+        # through the kernel anyway): saves sc_bn_bwd_reduce's pass over 2 x 268 MB at 16 x 512^2
+        bns = bna = None
+        if tin.bn is not None and tin.kind == "raw" and self._n_cons.get(tin.name, 0) == 1:
+            if tin.name not in plan.dwsums:
+                plan.dwrows[tin.name] = lib.sc_head_bwd_bn_rows(N, Ho, Wo)
+                plan.dwsums[tin.name] = torch.empty(plan.dwrows[tin.name] * tin.C * 2, dtype=torch.float64, device=self._pflat.device)
+            bns = ptr(plan.dwsums[tin.name])
+            if w.half_bwd:
+                bna = plan.gmax.data_ptr() + 4 * self._prod_idx[tin.name]
+            w.reduced.add(tin.name)
+        check(lib.sc_head_conv_bwd(ptr(w.dlogits), C.byref(s), ptr(conv.weight), ptr(plan.grad[tin.name]), ptr(plan.ws),
+                                   plan.ws.numel(), ptr(gv(conv.weight)), ptr(gv(conv.bias)), N, conv.in_channels, Ho, Wo,
+                                   bns, bna, w.st))
+        self._pe(tok)
+        w.written.add(tin.name)
+
+    def _bwd_stem(self, w, i, dy):
+        lib, plan, gv = _lib.load(), w.plan, self._grad_view
+        conv = self._ops[i]["conv"]
+        s = self._src_of(plan, self._ops[i]["ins"][0], x_cst=plan.x_cst)
+        tok = self._pb("k_stem_*")
+        self._wgrad_launch(w, lambda sx: check(lib.sc_stem_conv_wgrad(
+            C.byref(dy), C.byref(s), ptr(plan.ws), plan.ws.numel(), ptr(gv(conv.weight)), plan.N, conv.in_channels, plan.H, plan.W, sx)))
+        self._pe(tok)
+
+    def _bwd_irt(self, w, i, dy):
+        """fused block: ONE sweep over (dy_d, x) for the depthwise filter gradient, the BatchNorm-backward sums of the
+        expanded tensor and the part of dx that does not depend on them; the constants; the Cin -> Cin fix-up of dx; the
+        expansion filter's gradient from the partial rows on the weight-gradient stream.  Covers the expand op too."""
+        lib, plan, st, gv = _lib.load(), w.plan, w.st, self._grad_view
+        op = self._ops[i]
+        conv, o = op["conv"], op["out"]
+        i_e = plan.irt_of_dw[i]
+        w.irt_done.add(i_e)
+        op_e = self._ops[i_e]
+        te, tin, cv_e = op_e["out"], op_e["ins"][0], op_e["conv"]
+        a_irt = self._irt_args(plan, i_e)
+        acc = plan.dw_acc[self._dw_offs[i]:self._dw_offs[i] + o.C * 9]
+        work, esums = plan.irt_work[te.name], plan.irt_esums[te.name]
+        tok = self._pb("k_irt_* (fused expand+dw)")
+        self._wgrad_launch(w, lambda sx: check(lib.sc_irt_xmoments(C.byref(a_irt), ptr(work), sx)))
+        check(lib.sc_irt_bwd(C.byref(a_irt), C.byref(dy), ptr(esums), ptr(acc), ptr(work), st))
+        w.dw_casts.append((acc.data_ptr(), gv(conv.weight).data_ptr(), o.C * 9))
+        self._bn_bwd_finalize(w, te, esums, lib.sc_irt_bwd_rows(plan.N, te.C, a_irt.H, a_irt.W), plan.N * a_irt.H * a_irt.W)
+        z = self._res_of.get(tin.name)
+        check(lib.sc_irt_bwd_fix(C.byref(a_irt), ptr(plan.cstb[te.name]), ptr(work), ptr(plan.grad[tin.name]),
+                                 ptr(plan.grad[z]) if z is not None else None, 1 if tin.name in w.written else 0, st))
+        self._wgrad_launch(w, lambda sx: check(lib.sc_irt_wgrad_finalize(
+            C.byref(a_irt), ptr(plan.cstb[te.name]), ptr(work), ptr(gv(cv_e.weight)), sx)))
+        self._pe(tok)
+        w.written.add(tin.name)
+
+    def _bwd_dw(self, w, i, dy):
+        lib, plan, st, gv = _lib.load(), w.plan, w.st, self._grad_view
+        op = self._ops[i]
+        conv, o, tin = op["conv"], op["out"], op["ins"][0]
+        N, Hi, Wi = plan.N, plan.H >> tin.shift, plan.W >> tin.shift
+        s = self._src_of(plan, tin)
+        acc = plan.dw_acc[self._dw_offs[i]:self._dw_offs[i] + o.C * 9]
+        tok = self._pb("k_dw_*")
+        if (tin.name not in w.written and tin.bn is not None and tin.name in plan.dwsums
+                and self._n_cons.get(tin.name, 0) == 1):      # the fused sums are complete only for a single-consumer input
+            # one pass: dx, dW and the BatchNorm-backward sums of the (6x expanded) input tensor
+            check(lib.sc_dwconv3x3_bwd_fused(C.byref(dy), C.byref(s), ptr(conv.weight), ptr(plan.grad[tin.name]), ptr(acc),
+                                             ptr(plan.dwsums[tin.name]), N, o.C, Hi, Wi, op["stride"], st))
+            w.dw_casts.append((acc.data_ptr(), gv(conv.weight).data_ptr(), o.C * 9))
+            w.reduced.add(tin.name)
+        else:
+            def dw_wgrad(sx):
+                check(lib.sc_dwconv3x3_wgrad(C.byref(dy), C.byref(s), ptr(acc), N, o.C, Hi, Wi, op["stride"], sx))
+                check(lib.sc_cast_f64_f32(ptr(acc), ptr(gv(conv.weight)), o.C * 9, sx))
+            self._wgrad_launch(w, dw_wgrad)
+            check(lib.sc_dwconv3x3_dgrad(C.byref(dy), ptr(conv.weight), ptr(plan.grad[tin.name]),
+                                         1 if tin.name in w.written else 0, N, o.C, Hi, Wi, op["stride"], st))
+        self._pe(tok)
+        w.written.add(tin.name)
+
+    def _bwd_wgrad(self, w, i, dy):
+        """weight gradient of a pointwise / 3x3 layer on the kernel its route names, on the weight-gradient stream"""
+        lib, plan, gv = _lib.load(), w.plan, self._grad_view
+        op, L, route = self._ops[i], self._layers[i], plan.routes[i].wgrad
+        conv, ins, o = op["conv"], op["ins"], op["out"]
+        N, Ho, Wo = plan.N, plan.H >> o.shift, plan.W >> o.shift
+
+        def args(src, xb_of, Cin, part, part_floats, dw):
+            wa = sc_wgrad_args()
+            wa.dy, wa.nsrc = dy, len(src)
+            for k_, s_ in enumerate(src):
+                wa.src[k_] = s_
+            wa.N, wa.H, wa.W, wa.Cout, wa.Cin, wa.ks = N, Ho, Wo, o.C, Cin, L.ks
+            wa.part, wa.part_floats, wa.dw = part, part_floats, dw
+            wa.terms, wa.absmax = self._terms[1], w.gmax_slot.get(o.name)
+            if L.type == "conv3":
+                for k_, t_ in enumerate(xb_of):
+                    wa.xbound[k_] = self._xbound(plan, t_)
+            return wa
+
+        srcs = [self._src_of(plan, ins[0], up=1 if L.up else 0)] + ([self._src_of(plan, ins[1])] if len(ins) == 2 else [])
+        flop = 2.0 * N * Ho * Wo * L.Cout * L.Cin * L.ks * L.ks
+        if L.type == "pw" and i not in plan.pw_part:
+            # (a fused block's expansion walked on its own -- only_ops -- has no partials buffer: its own launch on the fp32 MFMA)
+            route = route._replace(kernel="mfma", entry="sc_conv2d_wgrad_mfma")
+        wfn = getattr(lib, route.entry)
+        if route.kernel == "spw":
+            wu = args(srcs[:1], ins[:1], L.Cin, None, 0, gv(conv.weight).data_ptr())
+            wsb, nb = C.c_void_p((plan.spw_ws.data_ptr() + 255) & ~255), plan.spw_ws.numel() - 256
+            tok = self._pb(route.family, flop, 0.0, 2.0 * N * (Ho // 2) * (Wo // 2) * 9 * L.Cout * L.Cup + 2.0 * N * Ho * Wo * 9 * L.Cout * L.Csk)
+            self._wgrad_launch(w, lambda sx: check(wfn(C.byref(wu), wsb, nb, sx)))
+            if route.skip:
+                wk = args(srcs[1:], ins[1:], L.Csk, plan.ws.data_ptr(), plan.ws.numel(), plan.spw_skip.data_ptr())
+                wsk = getattr(lib, route.skip.entry)
+
+                def skip_cols(sx):
+                    check(wsk(C.byref(wk), sx))
+                    check(lib.sc_wgrad_scatter_cols(ptr(plan.spw_skip), ptr(gv(conv.weight)), o.C, L.Csk, L.Cin, L.Cup, sx))
+                self._wgrad_launch(w, skip_cols)
+            self._pe(tok)
+            return
+        tok = self._pb(route.family, flop)
+        part = plan.pw_part.get(i, plan.ws)
+        wa = args(srcs, ins, L.Cin, part.data_ptr(), part.numel(), gv(conv.weight).data_ptr())
+        if i in plan.pw_part:
+            pend = sc_wgrad_pending()
+            self._wgrad_launch(w, lambda sx: check(wfn(C.byref(wa), C.byref(pend), sx)))
+            w.pw_pending.append(pend)
+            if i == w.last_pw:
+                # every pointwise layer has been walked: queue the batched reduction NOW, behind this layer's weight gradient, where it
+                # runs beside the main stream's last data-gradient kernels (features.1's depthwise backward, 0.16 ms).  At the end of
+                # the walk it was the side stream's last launch, 67 us exposed behind the stem's weight gradient before Adam.
+                self._reduce_pointwise_batch(w)
+        else:
+            self._wgrad_launch(w, lambda sx: check(wfn(C.byref(wa), sx)))
+        self._pe(tok)
+
+    def _bwd_dgrad(self, w, i, dy):
+        """data gradient of a pointwise / 3x3 layer by the launches its route names, on the main stream"""
+        lib, plan, st, written = _lib.load(), w.plan, w.st, w.written
+        op, L, route, ent = self._ops[i], self._layers[i], plan.routes[i].dgrad, self._wpk[i]
+        conv, ins, o = op["conv"], op["ins"], op["out"]
+        N, Ho, Wo = plan.N, plan.H >> o.shift, plan.W >> o.shift
+        if route.fallback is not None and (ins[0].name in written or self._res_of.get(ins[0].name) is not None):
+            route = route.fallback
+        a = sc_conv_args()
+        a.nsrc = 1
+        a.src[0] = dy
+        a.N, a.H, a.W, a.ks = N, Ho, Wo, L.ks
+        a.terms = self._terms[1]
+        a.absmax = w.gmax_slot.get(o.name)
+        a.add1 = None; a.stats = None
+        flop = 2.0 * N * Ho * Wo * L.Cout * L.Cin * L.ks * L.ks
+        # algorithmic bytes of the data gradient: g and y of the output once each, the input gradient once, the filter
+        gin_elems = N * L.Cin * Ho * Wo
+        if L.up and _tiles(L, self.split_bf16)[3]:      # the upsampled source's gradient is stored 2x2-summed (quarter size)
+            gin_elems -= N * L.Cup * Ho * Wo * 3 // 4
+        fle = None
+        if route.launches[0][1] == "spd":
+            # up-sampled channels: 4 parity planes x 4 taps per low-resolution pixel; skip channels: the 3x3 form
+            fle = (2.0 * N * (Ho // 2) * (Wo // 2) * 16 * L.Cout * (-(-L.Cup // 128) * 128 + (128 * -(-L.Csk // 32) if route.kernel == "spd+stiles" else 0))
+                   + (2.0 * N * Ho * Wo * 9 * L.Cout * L.Csk if route.kernel == "spd+bx3" else 0.0))
+        tok = self._pb(route.family, flop, 4.0 * (2 * N * o.C * Ho * Wo + gin_elems + conv.weight.numel()), fle)
+        for entry, lay, cot, down, srcs in route.launches:
+            ts = [ins[k] for k in srcs]
+            acc = [1 if t.name in written else 0 for t in ts]
+            a.Cout, a.csplit, a.co_t = sum(t.C for t in ts), ts[0].C, cot
+            a.wpk = ent[lay].data_ptr()
+            if lay == "bB":       # the skip channels' tile of the 32-wide pack
+                a.wpk += 4 * (ent[lay].numel() // (-(-L.Cin // 32)) * (L.Cup // 32))
+            if down == 2:
+                a.out0, a.accum0, a.down0 = plan.up_tmp.data_ptr(), 0, 0
+            else:
+                a.out0, a.accum0, a.down0 = plan.grad[ts[0].name].data_ptr(), acc[0], down
+            a.out1, a.accum1 = (plan.grad[ts[1].name].data_ptr(), acc[1]) if len(ts) == 2 else (None, 0)
+            z = None if L.up else self._res_of.get(ts[0].name)
+            a.add0 = plan.grad[z].data_ptr() if z is not None else None
+            check(getattr(lib, entry)(C.byref(a), st))
+            if down == 2:
+                self._pe(tok)
+                tok = None
+                check(lib.sc_downsum2x2(ptr(plan.up_tmp), ptr(plan.grad[ts[0].name]), acc[0], N, L.Cup, Ho // 2, Wo // 2, st))
+            written.update(t.name for t in ts)
+        self._pe(tok)
 
     # ------------------------------------------------------------------------------------------
     def forward(self, x, normalizer_consts=None):

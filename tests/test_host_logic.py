@@ -267,3 +267,96 @@ def test_sub_pixel_rules():
     assert lib.sc_sp_stat_rows(16, 32, 32, 256) == 32 and lib.sc_sp_stat_rows(64, 32, 32, 256) == 64 and lib.sc_sp_stat_rows(16, 32, 32, 320) == 16
     assert lib.sc_packed_weight_floats_sp(128, 256, 32) == 4 * (16 + 4 * 2) * 2048 * 4
     assert lib.sc_packed_weight_floats_spd(128, 256, 0) == 2 * 4 * 8 * 2048 * 4 and lib.sc_packed_weight_floats_spd(128, 256, 33) == 4 * 4 * 8 * 2048 * 4
+
+
+_ROUTE_PRECISIONS = ("fp32", "fp32-x3", "bf16")
+_TABLE_SHAPES = ((4, 512, 512), (16, 512, 512), (64, 512, 512), (16, 128, 128))
+
+
+def test_kernel_table_matches_recorded(monkeypatch):
+    """HyperStarcopUNet.kernel_table (which kernel runs each op's passes, network._fwd_route / _dgrad_route / _wgrad_route) against
+    tests/golden/kernel_table.json: batches 4, 16 and 64 at 512 x 512 and 16 at 128 x 128, each at fp32, fp32-x3 and bf16, training
+    and inference.  The table was recorded from these functions only after the launch logs of a training step and an eval forward
+    (tools/step_digest.py --launches) had been shown equal to those of the scattered rules they replace, on the GPU
+    (profiles/network_routes_neutral.txt): a change of this table is a change of what runs."""
+    import json
+    from starcop_amd import network as nw
+    for switch in ("_PW3", "_IRT", "_IRB", "_SP"):       # the measured rules, whatever STARCOP_* this run of the suite forces
+        monkeypatch.setattr(nw, switch, "1")
+    with open(os.path.join(G, "kernel_table.json")) as f:
+        want = json.load(f)
+    net = nw.HyperStarcopUNet(4, 1)
+    net.fuse_irt = True
+    for N, H, W in _TABLE_SHAPES:
+        for prec in _ROUTE_PRECISIONS:
+            net.precision = prec
+            for mode, training in (("train", True), ("eval", False)):
+                got = [" ".join(str(r.get(k)) for k in ("op", "type", "fwd", "dgrad", "wgrad") if k in r) for r in net.kernel_table(N, H, W, training)]
+                assert got == want[f"{N}x{H}x{W}"][prec][mode], (N, H, W, prec, mode)
+
+
+@pytest.mark.parametrize("N,H,W", _TABLE_SHAPES + ((1, 32, 32), (3, 96, 160)))
+def test_plan_sizes_cover_the_routed_kernels(N, H, W):
+    """For every layer, what a plan allocates (on the meta device: sizes only) is at least what the host query of the kernel its route
+    names reports -- statistics rows (sc_stat_rows, sc_sp_stat_rows: the sub-pixel forward has its own count, sc_irt_rows) and
+    weight-gradient workspaces (the *_workspace_floats family, sc_sp_wgrad_workspace_bytes) -- and every layout a route names is one
+    that network._layouts returns and the pack keeps, the PW3 layouts a fused inference block reads included.  The sub-pixel forward's
+    rows are also held against SC_STAT_CONV3's: fewer, as the walk once only claimed in a comment."""
+    from starcop_amd import _lib, network as nw
+    lib = _lib.load()
+    stat_kind = {("pw", "pw3"): _lib.STAT_PW3, ("pw", "ksplit"): _lib.STAT_CONV1K, ("pw", "mfma"): _lib.STAT_CONV1}
+    for prec in _ROUTE_PRECISIONS:
+        net = nw.HyperStarcopUNet(4, 1).to("meta")
+        net.precision = prec
+        net._ensure_flat()
+        plan = net._get_plan(N, H, W, True)
+        assert set(plan.routes) == {i for i, op in enumerate(net._ops) if op["type"] in ("pw", "conv3")}
+        for i_e, (i_dw, i_pr, i_add) in plan.irb.items():      # a fused inference block reads "pf", or "pfi" where no plan packs "pf"
+            for i in (i_e, i_pr):
+                assert {"pf", "pfi"} & net._wanted_layouts(i) and {"pf", "pfi"} <= set(nw._layouts(net._layers[i], net.split_bf16, net._terms))
+        for i, op in enumerate(net._ops):
+            o, ty, cv = op["out"], op["type"], op.get("conv")
+            Ho, Wo = H >> o.shift, W >> o.shift
+            r = plan.routes.get(i)
+            if o.bn is not None:
+                if r is None:
+                    rows = lib.sc_stat_rows({"stem": _lib.STAT_STEM, "dw": _lib.STAT_DW}[ty], N, Ho, Wo)
+                elif r.fwd.kernel == "sp":
+                    rows = lib.sc_sp_stat_rows(N, Ho, Wo, o.C)
+                    assert rows <= lib.sc_stat_rows(_lib.STAT_CONV3, N, Ho, Wo), (prec, o.name)
+                else:
+                    rows = lib.sc_stat_rows(stat_kind.get((ty, r.fwd.kernel), _lib.STAT_CONV3), N, Ho, Wo)
+                if i in plan.irt or i in plan.irt_of_dw:
+                    i_e = plan.irt_of_dw.get(i, i)
+                    tin, cv_e, stride = net._ops[i_e]["ins"][0], net._ops[i_e]["conv"], net._ir_blocks[i_e][2]
+                    Hi, Wi = H >> tin.shift, W >> tin.shift
+                    rows = max(rows, lib.sc_irt_rows(int(i in plan.irt_of_dw), N, Hi, Wi, stride))
+                    if i in plan.irt:
+                        assert plan.irt_work[o.name].numel() >= lib.sc_irt_bwd_workspace_floats(N, cv_e.in_channels, cv_e.out_channels, Hi, Wi)
+                        assert plan.irt_esums[o.name].numel() >= lib.sc_irt_bwd_rows(N, cv_e.out_channels, Hi, Wi) * cv_e.out_channels * 2
+                assert plan.srows[o.name] >= rows and plan.stats_v[o.name].numel() >= rows * o.C * 2, (prec, o.name)
+            if ty == "stem":
+                assert plan.ws.numel() >= lib.sc_stem_wgrad_workspace_floats(N, cv.in_channels, H, W)
+            if ty == "head":
+                assert plan.ws.numel() >= lib.sc_head_wgrad_workspace_floats(N, cv.in_channels, Ho, Wo)
+            if r is None:
+                continue
+            L, lay = net._layers[i], set(nw._layouts(net._layers[i], net.split_bf16, net._terms))
+            named = {r.fwd.layout} | {launch[1] for d in (r.dgrad, r.dgrad.fallback) if d is not None for launch in d.launches}
+            assert named <= lay and named <= net._wanted_layouts(i), (prec, o.name, named)
+            co, ci, ks = cv.out_channels, cv.in_channels, cv.kernel_size[0]
+            need = {"mfma": lambda c: lib.sc_wgrad_workspace_floats(N, Ho, Wo, co, c, ks),
+                    "bx3": lambda c: lib.sc_wgrad_bx3_workspace_floats(N, Ho, Wo, co, c),
+                    "thin16": lambda c: lib.sc_wgrad_thin16_workspace_floats(N, Ho, Wo, co, c),
+                    "pw3": lambda c: lib.sc_wgrad_pw3_workspace_floats(N, Ho, Wo, co, c)}
+            if r.wgrad.kernel == "spw":
+                assert plan.spw_ws.numel() - 256 >= lib.sc_sp_wgrad_workspace_bytes(N, Ho, Wo, co, L.Cup), (prec, o.name)
+                if r.wgrad.skip:
+                    assert plan.ws.numel() >= need[r.wgrad.skip.kernel](L.Csk) and plan.spw_skip.numel() >= co * L.Csk * 9, (prec, o.name)
+            elif i in plan.pw_part:
+                assert plan.pw_part[i].numel() >= need[r.wgrad.kernel](ci), (prec, o.name)
+            else:
+                assert ty == "conv3" or i in plan.irt
+                assert plan.ws.numel() >= need[r.wgrad.kernel if ty == "conv3" else "mfma"](ci), (prec, o.name)
+            if r.dgrad.kernel.endswith("+downsum"):       # (the one route that goes through the full-resolution scratch)
+                assert plan.up_tmp.numel() >= N * L.Cup * Ho * Wo, (prec, o.name)
