@@ -335,8 +335,8 @@ typedef struct sc_irb_args {
 } sc_irb_args;
 int sc_irb_supported(int Cin, int hidden, int Cout, int H, int W, int stride);
 /* HOST: the kernel variant sc_irb_eval launches for a block shape: -1 = unsupported, else
- *   10000 * tiling (0 = A: 4 x 8 output pixels, 64-channel chunks; 1 = B: 8 x 8, 32-channel chunks; 2 = C: 8 x 8, 64-channel chunks,
- *   8 waves -- development knob only; 3 = the stride-2 form of A) + 1000 * projection pairs per wave (1..3)
+ *   10000 * tiling (0 = A: 4 x 8 output pixels, 64-channel chunks; 1 = B: 8 x 8, 32-channel chunks; 3 = the stride-2 form of A;
+ *   2 was a third tiling that lost to A and is gone) + 1000 * projection pairs per wave (1..3)
  *   + 10 * expansion K steps held in registers (2, 4, 6 or 10) + work-groups per CU (1 | 2).
  * The entry point dispatches on this value. */
 int sc_irb_variant(int Cin, int hidden, int Cout, int stride);
@@ -405,8 +405,8 @@ int sc_conv3x3_wgrad_bx3(const sc_wgrad_args* a, sc_stream stream);
  * The entry points dispatch on these values.  M = 1, 2, 3: that many bf16 terms per operand (terms 0 = 3), 4: two fp16 terms.
  *   sc_conv3_variant (sc_conv3x3_bx3):  1000 * WS + 100 * Q + 10 * BNB + M -- WS: the wave-specialised k_conv3_ws<Q, BNB> (M = 4 only),
  *     else k_conv3_bx3<Q, BNB, ..>; Q = co_t / 32; BNB: src[0] is SC_SRC_BNBWD
- *   sc_thin16_variant (sc_conv3x3_thin16):  100 * (C / 16) + 10 * BNB + UPS for k_conv3_thin_h<C, BNB, UPS> (100, 110, 200, 201, 210),
- *     1200 = k_conv3_thin_sp (an up-sampled 32-channel RAW / AFFINE source), 2110 = k_conv3_thin_spd (down0)
+ *   sc_thin16_variant (sc_conv3x3_thin16):  100 * (C / 16) + 10 * BNB for k_conv3_thin_h<C, BNB> (100, 110, 200, 210),
+ *     1200 = k_conv3_thin_sp (every up-sampled 32-channel RAW / AFFINE source; 200: not up-sampled), 2110 = k_conv3_thin_spd (down0)
  *   sc_wgrad3_variant (sc_conv3x3_wgrad_bx3):  10000 * PIPE + 1000 * M + 100 * WM + 10 * NCI + R for k_wgrad3_bx3<WM, .., NCI, .., PIPE>;
  *     R = 1: the kernel sums its K parts itself (sc_wgrad_finish sees one row per slice)
  *   sc_wgrad_thin16_variant (sc_conv3x3_wgrad_thin16):  100 * (Cin / 16) + 10 * (dy is SC_SRC_BNBWD) for k_wgrad_thin_h<Cin, BNB> */
@@ -452,7 +452,7 @@ int sc_dwconv3x3_bwd_fused(const sc_src* dy, const sc_src* in, const float* w, f
 /* HOST: the kernel variant a depthwise entry point launches for a shape.  op: 0 = sc_dwconv3x3_fwd / _fwd_bn, 1 = _dgrad, 2 = _wgrad,
  * 3 = _bwd_fused; aligned16: whether every tensor pointer the entry point tests for 16-byte alignment passes (in->x and out for 0;
  * dy->x, dy->aux, in->x and dx for 3; ignored for 1 and 2).  -1 = the entry point rejects the arguments (stride outside {1, 2}; odd
- * sizes at stride 2 for op 3), 9000 + PS = the wave-per-plane kernel for PS x PS planes (PS = 16; 32 only with STARCOP_DW_P32 set),
+ * sizes at stride 2 for op 3), 9016 = the wave-per-plane kernel (16 x 16 planes at stride 1, N C % 4 == 0),
  * else 1000 * stride + 10 * TW + V4: TW = tile width 64 | 32 | 16 (64 x 32, 32 x 32, 16 x 16 pixels per work-group, by the width of
  * the plane the work-groups tile: the output for ops 0 and 2, the input for 1 and 3), V4 = 1 for float4 staging, 0 for element-wise
  * staging (always 0 for ops 1 and 2).  The entry points dispatch on this value. */

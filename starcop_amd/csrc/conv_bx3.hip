@@ -43,7 +43,6 @@ struct ConvXP {
   int down0;
   const float* absmax;
   const float* xb0; const float* xb1;      // activation bounds of the sources (h_act_scale)
-  int xcdmap;          // 1: 1-D grid, the cout tiles of a pixel tile numbered 8 apart (same XCD, back to back: its L2 serves the patch re-reads)
   // sc_bnr_args: BatchNorm-backward sums of out0's tensor from the data-gradient epilogue (bnr_y = NULL: off)
   const float* bnr_y; const float* bnr_cst; float* bnr_rows; float* bnr_absmax; int bnr_act;
 };
@@ -51,6 +50,27 @@ struct ConvXP {
 static inline void set_bnr(ConvXP& p, const sc_bnr_args* b) {
   p.bnr_y = b ? b->y : nullptr; p.bnr_cst = b ? b->cst : nullptr; p.bnr_rows = b ? b->rows : nullptr;
   p.bnr_absmax = b ? b->absmax : nullptr; p.bnr_act = b ? b->act : SC_ACT_NONE;
+}
+
+// Work-group numbering of k_conv3_bx3 and k_conv3_ws: image n, cout tile cot and pixel tile of blockIdx.x (false: padding slot).
+// Work-groups go to the 8 XCDs round-robin by linear id and each XCD has its own L2, so the grid is 1-D and the ncot cout tiles
+// of one pixel tile run on ONE XCD back to back: the patch they all stage is fetched from memory once, not once per cout tile
+// (a plain 3-D grid moved 2.7x instead of 1.24x the algorithmic bytes).
+// Each XCD walks a CONTIGUOUS eighth of the pixel tiles in order: x- and y-neighbouring tiles (which share halo columns / rows
+// and the 128-byte lines their misaligned 34-pixel row segments straddle) run on one XCD within its ~64 resident work-groups,
+// so those lines are L2 hits instead of separate memory requests.
+// (A cout-major numbering -- an XCD keeps the filters of a few cout tiles in its L2 and walks all pixel tiles -- was measured on
+// decoder.blocks.0, 12.7 MB of packed filters: level on the forward (292 vs 291 us), +6 % slower on the backward-data launch
+// (392 vs 368 us).  The Infinity Cache absorbs the filter re-reads; the patches are what an XCD should share.)
+__device__ __forceinline__ bool bx3_tile_of(const ConvXP& p, int ncot, int per_img, int& n, int& cot, int& tile) {
+  const int slot = blockIdx.x >> 3, xcd = blockIdx.x & 7;
+  const int total = per_img * p.N, per_xcd = (total + 7) >> 3;
+  const int j = slot / ncot;
+  const int pt = xcd * per_xcd + j;
+  if (j >= per_xcd || pt >= total) return false;
+  cot = slot % ncot;
+  n = pt / per_img; tile = pt - n * per_img;
+  return true;
 }
 
 __device__ __forceinline__ void wave_absmax_to(float mx, float* slot) {      // one atomic per wave, only when it raises the slot
@@ -201,51 +221,7 @@ __global__ __launch_bounds__(256, Q == 2 ? 2 : 3) void k_conv3_bx3(const ConvXP 
   const int H = p.H, W = p.W;
   const int tiles_x = (W + 31) >> 5;
   int n, cot, tile;
-  if (p.xcdmap) {
-    // work-groups go to the 8 XCDs round-robin by linear id and each XCD has its own L2: number the cout tiles of one pixel tile 8
-    // apart so that they run on ONE XCD back to back and the patch they all stage is fetched from memory once, not once per cout tile
-    const int ncot = (p.Cout + CO_T - 1) / CO_T;
-    const int per_img = tiles_x * ((H + 7) >> 3);
-    const int slot = blockIdx.x >> 3, xcd = blockIdx.x & 7;
-    int pt;
-    if (p.xcdmap == 3) {
-      // cout-major: every XCD owns a few cout tiles (or, with fewer than 8 tiles, 8/ncot XCDs share one and split the pixel
-      // tiles) and walks all pixel tiles for them.  For layers whose packed filters exceed an XCD's 4 MB L2 (decoder.blocks.0:
-      // 12.7 MB) the pixel-major orders re-stream ALL filters from memory for every group of pixel tiles (0.8 GB per launch,
-      // the work-groups then run at the ~9 B/clk/CU of memory-side loads); this way an XCD's filters stay in its L2 and the
-      // (much smaller) patches are what is fetched 8 times
-      const int total = per_img * p.N;
-      if (ncot >= 8) {
-        const int mine = (ncot - xcd + 7) >> 3;             // cout tiles xcd, xcd + 8, ...
-        const int k = slot / total;
-        if (k >= mine) return;
-        cot = xcd + 8 * k; pt = slot - k * total;
-      } else {
-        const int g = 8 / ncot;                             // ncot in {1, 2, 4} (host-checked)
-        const int per = (total + g - 1) / g;
-        cot = xcd / g; pt = (xcd - cot * g) * per + slot;
-        if (slot >= per || pt >= total) return;
-      }
-      n = pt / per_img; tile = pt - n * per_img;
-    } else {
-    if (p.xcdmap == 2) {
-      // each XCD walks a CONTIGUOUS eighth of the pixel tiles in order: x- and y-neighbouring tiles (which share halo columns /
-      // rows and the 128-byte lines their misaligned 34-pixel row segments straddle) run on one XCD within its ~64 resident
-      // work-groups, so those lines are L2 hits instead of separate memory requests
-      const int total = per_img * p.N, per_xcd = (total + 7) >> 3;
-      const int j = slot / ncot;
-      pt = xcd * per_xcd + j;
-      if (j >= per_xcd || pt >= total) return;
-    } else {
-      pt = (slot / ncot) * 8 + xcd;
-      if (pt >= per_img * p.N) return;
-    }
-    cot = slot % ncot;
-    n = pt / per_img; tile = pt - n * per_img;
-    }
-  } else {
-    n = blockIdx.z; cot = blockIdx.y; tile = blockIdx.x;
-  }
+  if (!bx3_tile_of(p, (p.Cout + CO_T - 1) / CO_T, tiles_x * ((H + 7) >> 3), n, cot, tile)) return;
   // (integer division has no scalar form: its uniform results come back in VGPRs and drag every address derived from them into
   // 64-bit VALU arithmetic; readfirstlane says that they are uniform)
   n = __builtin_amdgcn_readfirstlane(n); cot = __builtin_amdgcn_readfirstlane(cot); tile = __builtin_amdgcn_readfirstlane(tile);
@@ -776,51 +752,7 @@ __global__ __launch_bounds__(512, 4) void k_conv3_ws(const ConvXP p) {
   const int H = p.H, W = p.W;
   const int tiles_x = (W + 31) >> 5;
   int n, cot, tile;
-  if (p.xcdmap) {
-    // work-groups go to the 8 XCDs round-robin by linear id and each XCD has its own L2: number the cout tiles of one pixel tile 8
-    // apart so that they run on ONE XCD back to back and the patch they all stage is fetched from memory once, not once per cout tile
-    const int ncot = (p.Cout + CO_T - 1) / CO_T;
-    const int per_img = tiles_x * ((H + 7) >> 3);
-    const int slot = blockIdx.x >> 3, xcd = blockIdx.x & 7;
-    int pt;
-    if (p.xcdmap == 3) {
-      // cout-major: every XCD owns a few cout tiles (or, with fewer than 8 tiles, 8/ncot XCDs share one and split the pixel
-      // tiles) and walks all pixel tiles for them.  For layers whose packed filters exceed an XCD's 4 MB L2 (decoder.blocks.0:
-      // 12.7 MB) the pixel-major orders re-stream ALL filters from memory for every group of pixel tiles (0.8 GB per launch,
-      // the work-groups then run at the ~9 B/clk/CU of memory-side loads); this way an XCD's filters stay in its L2 and the
-      // (much smaller) patches are what is fetched 8 times
-      const int total = per_img * p.N;
-      if (ncot >= 8) {
-        const int mine = (ncot - xcd + 7) >> 3;             // cout tiles xcd, xcd + 8, ...
-        const int k = slot / total;
-        if (k >= mine) return;
-        cot = xcd + 8 * k; pt = slot - k * total;
-      } else {
-        const int g = 8 / ncot;                             // ncot in {1, 2, 4} (host-checked)
-        const int per = (total + g - 1) / g;
-        cot = xcd / g; pt = (xcd - cot * g) * per + slot;
-        if (slot >= per || pt >= total) return;
-      }
-      n = pt / per_img; tile = pt - n * per_img;
-    } else {
-    if (p.xcdmap == 2) {
-      // each XCD walks a CONTIGUOUS eighth of the pixel tiles in order: x- and y-neighbouring tiles (which share halo columns /
-      // rows and the 128-byte lines their misaligned 34-pixel row segments straddle) run on one XCD within its ~64 resident
-      // work-groups, so those lines are L2 hits instead of separate memory requests
-      const int total = per_img * p.N, per_xcd = (total + 7) >> 3;
-      const int j = slot / ncot;
-      pt = xcd * per_xcd + j;
-      if (j >= per_xcd || pt >= total) return;
-    } else {
-      pt = (slot / ncot) * 8 + xcd;
-      if (pt >= per_img * p.N) return;
-    }
-    cot = slot % ncot;
-    n = pt / per_img; tile = pt - n * per_img;
-    }
-  } else {
-    n = blockIdx.z; cot = blockIdx.y; tile = blockIdx.x;
-  }
+  if (!bx3_tile_of(p, (p.Cout + CO_T - 1) / CO_T, tiles_x * ((H + 7) >> 3), n, cot, tile)) return;
   // (integer division has no scalar form: its uniform results come back in VGPRs and drag every address derived from them into
   // 64-bit VALU arithmetic; readfirstlane says that they are uniform)
   n = __builtin_amdgcn_readfirstlane(n); cot = __builtin_amdgcn_readfirstlane(cot); tile = __builtin_amdgcn_readfirstlane(tile);
@@ -1243,19 +1175,14 @@ __device__ __forceinline__ void split_filter(float v, bool half, unsigned short 
 //   D: lane -> pixel l&15, couts 4*(l>>4) .. +3
 // Work-group = 4 waves, tile 8 rows x 32 px; wave = 2 rows = four 16-pixel blocks.  Single source (may be upsampled), single
 // output, optional statistics rows (SC_STAT_CONV3 layout); anything else stays on the other kernels.
-// UPS: the source is the nearest-neighbour 2x up-sampling of a half-resolution tensor (decoder.blocks.4.conv1) and the patch is staged
-// AT THE SOURCE RESOLUTION -- 6 x (TW/2 + 2) entries per channel group instead of 10 x (TW + 2): every source value is requested,
-// run through the prologue, split and written to LDS once instead of 3.1 times (the staging was more VALU work than the kernel's MFMAs);
-// the operand reads address the source entry of their output pixel: row (r + 1) >> 1, column (c + 1) >> 1 of the patch (tile origins
-// are even, so output row / column -1 and H / W fall on source -1 and H/2 / W/2: the same zero padding).
-template <int CIN, bool BNB, bool UPS = false>
+template <int CIN, bool BNB>
 __global__ __launch_bounds__(256, 2) void k_conv3_thin_h(const ConvXP p) {
   // Tile 8 rows x TW px.  16 input channels: TW = 64 -- the runs a work-group reads and writes per (plane, row) are 264 / 256 B instead
   // of 136 / 128 B, worth 14-17 % at 16 x 512^2 (forward 177 -> 152 us, backward 269 -> 224 us; these layers run at 3 TB/s and neither the
   // MFMAs -- removed: same time -- nor exposed latency -- persistent work-groups with the next patch in flight: same time -- limit them:
   // what is left is how DRAM likes the access pattern).  32 channels: the 85 KB patch would leave one work-group per CU (205 -> 308 us).
   constexpr int TW = CIN == 16 ? 64 : 32, PBW = TW / 16, NPB = 2 * PBW;
-  constexpr int PR = UPS ? 6 : 10, PC = UPS ? TW / 2 + 2 : TW + 2, NPX = PR * PC;
+  constexpr int PR = 10, PC = TW + 2, NPX = PR * PC;
   constexpr int NH = CIN / 8;                 // 8-channel groups
   constexpr int NG = 9 * NH, NS = (NG + 3) / 4;
   // Pitch between the 8-channel groups: a multiple of 16 entries (256 B).  ds_read_b128 is serviced in four NON-contiguous 16-lane
@@ -1272,13 +1199,11 @@ __global__ __launch_bounds__(256, 2) void k_conv3_thin_h(const ConvXP p) {
   const int H = p.H, W = p.W;
   const int tiles_x = (W + TW - 1) / TW;
   int n, tile;
-  if (p.xcdmap) {      // each XCD walks a contiguous eighth of the pixel tiles (see k_conv3_bx3): halo lines shared in its L2
+  {      // each XCD walks a contiguous eighth of the pixel tiles (see bx3_tile_of): halo lines shared in its L2
     const int per_img = tiles_x * ((H + 7) >> 3), total = per_img * p.N, per_xcd = (total + 7) >> 3;
     const int j = blockIdx.x >> 3, pt = (blockIdx.x & 7) * per_xcd + j;
     if (j >= per_xcd || pt >= total) return;
     n = pt / per_img; tile = pt - n * per_img;
-  } else {
-    n = blockIdx.z; tile = blockIdx.x;
   }
   n = __builtin_amdgcn_readfirstlane(n); tile = __builtin_amdgcn_readfirstlane(tile);      // uniform (see k_conv3_bx3)
   const int ty = __builtin_amdgcn_readfirstlane(tile / tiles_x), tx = tile - ty * tiles_x;
@@ -1301,7 +1226,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3_thin_h(const ConvXP p) {
   const int grp = __builtin_amdgcn_readfirstlane(wave / WPG);
   const int g8 = grp * 8;
   const int e0 = tid - grp * TPG;
-  const int up = UPS ? 1 : src.up;
+  const int up = src.up;
   const int Ws = W >> up;
   const size_t plane = (size_t)(H >> up) * Ws;
   // (operand scale -- and for forward sources the clamp -- folded into the constants, see split2h)
@@ -1314,11 +1239,10 @@ __global__ __launch_bounds__(256, 2) void k_conv3_thin_h(const ConvXP p) {
   for (int r = 0; r < NR; ++r) {
     const int e = e0 + TPG * r;
     const int pr = e / PC, pc = e - pr * PC;
-    // (UPS: y, x are SOURCE coordinates and the patch covers source rows y0/2 - 1 .. y0/2 + 4)
-    const int y = UPS ? (y0 >> 1) - 1 + pr : y0 - 1 + pr, x = UPS ? (x0 >> 1) - 1 + pc : x0 - 1 + pc;
-    const bool ok = UPS ? ((e < NPX) && y >= 0 && y < (H >> 1) && x >= 0 && x < Ws) : ((e < NPX) && y >= 0 && y < H && x >= 0 && x < W);
+    const int y = y0 - 1 + pr, x = x0 - 1 + pc;
+    const bool ok = (e < NPX) && y >= 0 && y < H && x >= 0 && x < W;
     okv[r] = ok;
-    const unsigned off = ok ? (UPS ? (unsigned)(y * Ws + x) : (unsigned)((y >> up) * Ws + (x >> up))) : 0u;
+    const unsigned off = ok ? (unsigned)((y >> up) * Ws + (x >> up)) : 0u;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
       xv[r][j] = xg[(size_t)j * plane + off];
@@ -1390,8 +1314,7 @@ __global__ __launch_bounds__(256, 2) void k_conv3_thin_h(const ConvXP p) {
     const int kh = tap / 3, kw = tap - 3 * kh;
 #pragma unroll
     for (int pb = 0; pb < NPB; ++pb) {
-      const int e = UPS ? ((2 * wave + pb / PBW + kh + 1) >> 1) * PC + ((16 * (pb % PBW) + l15 + kw + 1) >> 1)
-                        : (2 * wave + pb / PBW + kh) * PC + 16 * (pb % PBW) + l15 + kw;
+      const int e = (2 * wave + pb / PBW + kh) * PC + 16 * (pb % PBW) + l15 + kw;
       const halfx8 b0 = __builtin_bit_cast(halfx8, s_p[0][half][e]);
       const halfx8 b1 = __builtin_bit_cast(halfx8, s_p[1][half][e]);
       const halfx8 a0 = __builtin_bit_cast(halfx8, A[s][0]);
@@ -1514,13 +1437,11 @@ __global__ __launch_bounds__(256, 2) void k_conv3_thin_sp(const ConvXP p) {
   const int H = p.H, W = p.W, Hs = H >> 1, Ws = W >> 1;
   const int tiles_x = (W + 63) >> 6;
   int n, tile;
-  if (p.xcdmap) {      // each XCD walks a contiguous eighth of the pixel tiles (see k_conv3_bx3)
+  {      // each XCD walks a contiguous eighth of the pixel tiles (see bx3_tile_of)
     const int per_img = tiles_x * ((H + 7) >> 3), total = per_img * p.N, per_xcd = (total + 7) >> 3;
     const int j = blockIdx.x >> 3, pt = (blockIdx.x & 7) * per_xcd + j;
     if (j >= per_xcd || pt >= total) return;
     n = pt / per_img; tile = pt - n * per_img;
-  } else {
-    n = blockIdx.z; tile = blockIdx.x;
   }
   n = __builtin_amdgcn_readfirstlane(n); tile = __builtin_amdgcn_readfirstlane(tile);
   const int ty = __builtin_amdgcn_readfirstlane(tile / tiles_x), tx = tile - ty * tiles_x;
@@ -1675,13 +1596,11 @@ __global__ __launch_bounds__(256, 2) void k_conv3_thin_spd(const ConvXP p) {
   const int H = p.H, W = p.W, Hs = H >> 1, Ws = W >> 1;
   const int tiles_x = (W + 63) >> 6;
   int n, tile;
-  if (p.xcdmap) {
+  {
     const int per_img = tiles_x * ((H + 7) >> 3), total = per_img * p.N, per_xcd = (total + 7) >> 3;
     const int j = blockIdx.x >> 3, pt = (blockIdx.x & 7) * per_xcd + j;
     if (j >= per_xcd || pt >= total) return;
     n = pt / per_img; tile = pt - n * per_img;
-  } else {
-    n = blockIdx.z; tile = blockIdx.x;
   }
   n = __builtin_amdgcn_readfirstlane(n); tile = __builtin_amdgcn_readfirstlane(tile);
   const int ty = __builtin_amdgcn_readfirstlane(tile / tiles_x), tx = tile - ty * tiles_x;
@@ -2782,11 +2701,10 @@ static int conv3_bx3_variant_of(const sc_conv_args* a) {
   const int C0 = a->src[0].C, C1 = a->nsrc == 2 ? a->src[1].C : 0;
   const int bnb = a->src[0].mode == SC_SRC_BNBWD ? 1 : 0;
   const int m = a->terms == SC_TERMS_F16X2 ? 4 : (a->terms == 1 || a->terms == 2 ? a->terms : 3);
-  constexpr int ws_env = 1;
   static const int ws_env_min = [] { const char* e = getenv("STARCOP_BX3_WS_MINCHUNKS"); return e ? atoi(e) : 16; }();
   // the wave-specialised kernel pays for its 8-wave work-groups (prologue / epilogue of only two per CU) on short K loops:
   // measured faster from 16 chunks of 16 input channels up (decoder.blocks.0), level at 8-10, slower below
-  const int ws = (m == 4 && ws_env && (C0 + C1 + 15) / 16 >= ws_env_min && (!bnb || a->src[0].C <= 256) && !a->bnr) ? 1 : 0;
+  const int ws = (m == 4 && (C0 + C1 + 15) / 16 >= ws_env_min && (!bnb || a->src[0].C <= 256) && !a->bnr) ? 1 : 0;
   return 1000 * ws + 100 * (a->co_t / 32) + 10 * bnb + m;
 }
 
@@ -2796,7 +2714,6 @@ extern "C" int sc_conv3_variant(const sc_conv_args* a) {
 
 extern "C" int sc_conv3x3_bx3(const sc_conv_args* a, sc_stream stream) {
   if (const int rc = conv3_bx3_check(a)) return rc;
-  const int C0 = a->src[0].C, C1 = a->nsrc == 2 ? a->src[1].C : 0;
   ConvXP p;
   p.s0 = to_srcd(a->src[0]);
   p.s1 = a->nsrc == 2 ? to_srcd(a->src[1]) : empty_srcd();
@@ -2805,28 +2722,10 @@ extern "C" int sc_conv3x3_bx3(const sc_conv_args* a, sc_stream stream) {
   p.add0 = a->add0; p.add1 = a->add1; p.stats = a->stats;
   p.down0 = a->down0 ? 1 : 0;
   const int co_tiles = (a->Cout + a->co_t - 1) / a->co_t;
-  dim3 grid(((a->W + 31) / 32) * ((a->H + 7) / 8), co_tiles, a->N);
-  constexpr int xcdmap_env = 2;   // XCD-aware 1-D numbering (0 = plain 3-D grid: 2.7x instead of 1.24x the algorithmic bytes)
-  p.xcdmap = xcdmap_env >= 2 ? 2 : ((xcdmap_env && co_tiles > 1) ? 1 : 0);
-  {
-    // cout-major numbering (3) for launches whose packed filters exceed this many bytes.  Off by default: measured on
-    // decoder.blocks.0 (12.7 MB of filters) it is level on the forward (292 vs 291 us) and slower on the backward-data launch
-    // (392 vs 368 us) -- the Infinity Cache absorbs the filter re-reads, the patches are what an XCD should share
-    constexpr long big_env = 0L;      // cout-major numbering above this filter size: measured +6 % slower backward-data -> off
-    const long nkc = (C0 + C1 + 15) / 16;
-    const long wbytes = (long)co_tiles * nkc * 3 * 6 * (a->terms == SC_TERMS_F16X2 || a->terms == 2 ? 2 : (a->terms == 1 ? 1 : 3)) * a->co_t * 16;
-    if (xcdmap_env >= 2 && big_env > 0 && wbytes > big_env && (co_tiles >= 8 || co_tiles == 1 || co_tiles == 2 || co_tiles == 4)) p.xcdmap = 3;
-  }
-  if (p.xcdmap == 3) {
-    const long total = (long)grid.x * a->N;
-    const long slots = co_tiles >= 8 ? (long)((co_tiles + 7) / 8) * total : (total + (8 / co_tiles) - 1) / (8 / co_tiles);
-    SC_REQUIRE(slots * 8 < (1L << 31), "sc_conv3x3_bx3: grid too large");
-    grid = dim3((unsigned)(slots * 8));
-  } else if (p.xcdmap) {
-    const long pt8 = ((long)grid.x * a->N + 7) / 8 * 8;
-    SC_REQUIRE(pt8 * co_tiles < (1L << 31), "sc_conv3x3_bx3: grid too large");
-    grid = dim3((unsigned)(pt8 * co_tiles));
-  }
+  // the XCD-aware 1-D grid of bx3_tile_of: the pixel tiles rounded up to a multiple of 8, times the cout tiles
+  const long pt8 = ((long)((a->W + 31) / 32) * ((a->H + 7) / 8) * a->N + 7) / 8 * 8;
+  SC_REQUIRE(pt8 * co_tiles < (1L << 31), "sc_conv3x3_bx3: grid too large");
+  const dim3 grid((unsigned)(pt8 * co_tiles));
   hipStream_t st = (hipStream_t)stream;
   p.absmax = a->absmax; p.xb0 = a->xbound[0]; p.xb1 = a->xbound[1];
   set_bnr(p, a->bnr);
@@ -2889,13 +2788,12 @@ static int wgrad3_bx3_check(const sc_wgrad_args* a) {
 // Which k_wgrad3_bx3 instantiation sc_conv3x3_wgrad_bx3 launches for checked arguments, and its plan: 10000 * PIPE + 1000 * M (1, 2, 3
 // bf16 terms or 4 = two fp16 terms) + 100 * WM + 10 * NCI + (the kernel sums its K parts itself, so that sc_wgrad_finish sees nsl rows).
 static int wgrad3_bx3_variant_of(const sc_wgrad_args* a, WgradXPlan* plan) {
-  static const bool no96 = [] { const char* e = getenv("STARCOP_WGRAD96"); return e && atoi(e) == 0; }();      // (same-box A/B)
-  constexpr int pipe_env = 1;      // one-barrier refill pipeline (0 = the two-barrier stages it replaced: 1.89 vs 1.63 ms per step)
-  // the pipelined variant: BatchNorm-backward gradients, 8-byte gradient loads (even W), 32-bit byte offsets within a tensor
-  bool pipe = pipe_env && a->terms == SC_TERMS_F16X2 && a->dy.mode == SC_SRC_BNBWD && a->W % 2 == 0 && (((uintptr_t)a->dy.x | (uintptr_t)a->dy.aux) & 7) == 0 &&
+  // the pipelined variant (one-barrier refill pipeline; the two-barrier stages it replaced: 1.89 vs 1.63 ms per step):
+  // BatchNorm-backward gradients, 8-byte gradient loads (even W), 32-bit byte offsets within a tensor
+  bool pipe = a->terms == SC_TERMS_F16X2 && a->dy.mode == SC_SRC_BNBWD && a->W % 2 == 0 && (((uintptr_t)a->dy.x | (uintptr_t)a->dy.aux) & 7) == 0 &&
               (size_t)a->Cout * a->H * a->W * 4 < (1ull << 32);
   for (int s = 0; s < a->nsrc; ++s) pipe = pipe && (size_t)a->N * a->src[s].C * (a->H >> a->src[s].up) * (a->W >> a->src[s].up) * 4 < (1ull << 32);
-  const WgradXPlan pl = plan_wgrad_bx3(a->N, a->H, a->W, a->Cout, a->Cin, pipe && !no96);      // (the 96-wide tile: pipelined kernel only)
+  const WgradXPlan pl = plan_wgrad_bx3(a->N, a->H, a->W, a->Cout, a->Cin, pipe);      // (the 96-wide tile: pipelined kernel only)
   if (plan) *plan = pl;
   const int m = a->terms == SC_TERMS_F16X2 ? 4 : (a->terms == 1 || a->terms == 2 ? a->terms : 3);
   return 10000 * (pipe ? 1 : 0) + 1000 * m + 100 * pl.wm + 10 * pl.nci + (pipe && wgrad3_pipe_reduces(pl) ? 1 : 0);
@@ -3059,17 +2957,15 @@ static int thin16_check(const sc_conv_args* a) {
   return SC_OK;
 }
 
-// Which kernel sc_conv3x3_thin16 launches for checked arguments: 1000 * K + 100 * (source channels / 16) + 10 * (BNBWD source) + UPS,
-// K = 0: k_conv3_thin_h<CIN, BNB, UPS>, 1: k_conv3_thin_sp (the sub-pixel form of an up-sampled 32-channel source), 2: k_conv3_thin_spd
+// Which kernel sc_conv3x3_thin16 launches for checked arguments: 1000 * K + 100 * (source channels / 16) + 10 * (BNBWD source),
+// K = 0: k_conv3_thin_h<CIN, BNB>, 1: k_conv3_thin_sp (the sub-pixel form of an up-sampled 32-channel source), 2: k_conv3_thin_spd
 // (down0: the half-resolution data gradient)
 static int thin16_variant_of(const sc_conv_args* a) {
   const sc_src& s = a->src[0];
   if (a->down0) return 2110;
-  static const bool sp_off = [] { const char* e = getenv("STARCOP_THIN_SP"); return e && atoi(e) == 0; }();       // (same-box A/B)
-  static const bool ups_off = [] { const char* e = getenv("STARCOP_THIN_UPS"); return e && atoi(e) == 0; }();      // (same-box A/B)
   const bool bnb = s.mode == SC_SRC_BNBWD;
-  if (s.C == 32 && s.up == 1 && !bnb && !sp_off) return 1200;      // the sub-pixel form (k_conv3_thin_sp)
-  return 100 * (s.C / 16) + 10 * (bnb ? 1 : 0) + (s.C == 32 && s.up == 1 && !bnb && !ups_off ? 1 : 0);
+  if (s.C == 32 && s.up == 1 && !bnb) return 1200;      // the sub-pixel form (k_conv3_thin_sp)
+  return 100 * (s.C / 16) + 10 * (bnb ? 1 : 0);
 }
 
 extern "C" int sc_thin16_variant(const sc_conv_args* a) {
@@ -3090,7 +2986,6 @@ extern "C" int sc_conv3x3_thin16(const sc_conv_args* a, sc_stream stream) {
     p.out0 = a->out0; p.csplit = a->Cout; p.accum0 = a->accum0; p.absmax = a->absmax;
     set_bnr(p, nullptr);
     const long total = (long)((a->W + 63) / 64) * ((a->H + 7) / 8) * a->N, per_xcd = (total + 7) / 8;
-    p.xcdmap = 2;
     hipLaunchKernelGGL(k_conv3_thin_spd, dim3((unsigned)(per_xcd * 8)), dim3(256), 0, (hipStream_t)stream, p);
     SC_LAUNCH_OK("sc_conv3x3_thin16(down0)");
     return SC_OK;
@@ -3101,19 +2996,13 @@ extern "C" int sc_conv3x3_thin16(const sc_conv_args* a, sc_stream stream) {
   p.out0 = a->out0; p.csplit = a->Cout; p.stats = a->stats; p.absmax = a->absmax; p.xb0 = a->xbound[0]; p.xb1 = a->xbound[1];
   set_bnr(p, a->bnr);
   const int tw = (Cin == 16 || variant == 1200) ? 64 : 32;        // (k_conv3_thin_h: TW)
-  dim3 grid(((a->W + tw - 1) / tw) * ((a->H + 7) / 8), 1, a->N);
-  constexpr int xcdmap_env = 2;
-  p.xcdmap = xcdmap_env ? 2 : 0;
-  if (p.xcdmap) {
-    const long total = (long)grid.x * a->N, per_xcd = (total + 7) / 8;
-    grid = dim3((unsigned)(per_xcd * 8));
-  }
+  const long total = (long)((a->W + tw - 1) / tw) * ((a->H + 7) / 8) * a->N, per_xcd = (total + 7) / 8;
+  const dim3 grid((unsigned)(per_xcd * 8));      // a contiguous eighth of the pixel tiles per XCD (see bx3_tile_of)
   hipStream_t st = (hipStream_t)stream;
   switch (variant) {
     case 1200: hipLaunchKernelGGL(k_conv3_thin_sp, grid, dim3(256), 0, st, p); break;
     case 100: hipLaunchKernelGGL((k_conv3_thin_h<16, false>), grid, dim3(256), 0, st, p); break;
     case 110: hipLaunchKernelGGL((k_conv3_thin_h<16, true>), grid, dim3(256), 0, st, p); break;
-    case 201: hipLaunchKernelGGL((k_conv3_thin_h<32, false, true>), grid, dim3(256), 0, st, p); break;
     case 200: hipLaunchKernelGGL((k_conv3_thin_h<32, false>), grid, dim3(256), 0, st, p); break;
     case 210: hipLaunchKernelGGL((k_conv3_thin_h<32, true>), grid, dim3(256), 0, st, p); break;
     default: SC_REQUIRE(false, "sc_conv3x3_thin16: no kernel for variant %d", variant);

@@ -381,35 +381,28 @@ static int irb_launch(const IrbP& p, int nke, hipStream_t st) {
 // Tilings (tools/bench_irb.py):
 //   A  4 x 8 output pixels, 64-channel chunks, 4 waves; two work-groups per CU while the patch fits 80 KB of LDS (Cin <= 96, Cout <= 128)
 //   B  8 x 8, 32-channel chunks, 4 waves  (hidden % 64 != 0)
-//   C  8 x 8, 64-channel chunks, 8 waves  (Cin <= 96): every work-group streams the block's whole filter set, so twice the pixels per
-//      work-group is half the L2 -> L1 filter traffic of A -- measured LEVEL with A on the 32 x 32 blocks (35.3 / 56.5 vs 33.7 / 55.1 us on
-//      features.8 / .12 at batch 16) and slower at 64 x 64 (65 vs 51 us): the filter traffic is not what a chunk waits for either; kept
-//      behind STARCOP_IRB_CFG=2 as the measured alternative
-enum { IRB_A = 0, IRB_B = 1, IRB_C = 2, IRB_A2 = 3 };      // (IRB_A2: the stride-2 form of A, below)
+// Why two and not three: a tiling C (8 x 8, 64-channel chunks, 8 waves, Cin <= 96: twice the pixels per work-group, so half the L2 -> L1
+// filter traffic of A) passed only where A passes too, and measured LEVEL with A on the 32 x 32 blocks (35.3 / 56.5 vs 33.7 / 55.1 us on
+// features.8 / .12 at batch 16) and slower at 64 x 64 (65 vs 51 us) and on scenes: the filter traffic is not what a chunk waits for.
+enum { IRB_A = 0, IRB_B = 1, IRB_A2 = 3 };      // the tiling digit of sc_irb_variant (IRB_A2: the stride-2 form of A, below; 2 was tiling C)
 static inline int irb_pairs_per_wave(int cfg, int Cout) {
   const int CB = (Cout + 31) / 32;
-  return cfg == IRB_A ? (CB + 3) / 4 : (cfg == IRB_B ? (2 * CB + 3) / 4 : (2 * CB + 7) / 8);
+  return cfg == IRB_A ? (CB + 3) / 4 : (2 * CB + 3) / 4;
 }
 static inline size_t irb_cfg_lds(int cfg, int nks_e) {
-  return cfg == IRB_A ? irb_smem_bytes<4, 8, 64>(nks_e) : (cfg == IRB_B ? irb_smem_bytes<8, 8, 32>(nks_e) : irb_smem_bytes<8, 8, 64>(nks_e));
+  return cfg == IRB_A ? irb_smem_bytes<4, 8, 64>(nks_e) : irb_smem_bytes<8, 8, 32>(nks_e);
 }
 static inline bool irb_cfg_ok(int cfg, int Cin, int hid, int Cout) {
   const int nks_e = (Cin + 15) / 16;
   if (cfg != IRB_B && hid % 64) return false;
   if (irb_cfg_lds(cfg, nks_e) > 160 * 1024) return false;
-  if (cfg == IRB_C && nks_e > 6) return false;               // (8 waves: 256 registers per lane)
-  const int pw = irb_pairs_per_wave(cfg, Cout);
-  if (cfg == IRB_C) return pw <= 1 || (pw == 2 && nks_e <= 4);      // (two pairs per wave with Cin > 64 would spill)
-  return pw <= 3;
+  return irb_pairs_per_wave(cfg, Cout) <= 3;
 }
 static inline bool irb_occ2(int Cin, int Cout) {      // tiling A with two resident work-groups (one projection pair per wave: no spills at 256 registers)
   return irb_smem_bytes<4, 8, 64>((Cin + 15) / 16) <= 80 * 1024 && Cin <= 96 && irb_pairs_per_wave(IRB_A, Cout) <= 1;
 }
 static int irb_pick_cfg(int Cin, int hid, int Cout) {
-  static const int forced = [] { const char* e = getenv("STARCOP_IRB_CFG"); return e ? atoi(e) : -1; }();      // development knob (A/B runs)
-  if (forced >= 0 && forced <= 2 && irb_cfg_ok(forced, Cin, hid, Cout)) return forced;
-  if (irb_cfg_ok(IRB_A, Cin, hid, Cout)) return IRB_A;      // (C measured level with A at 32 x 32, 25 % slower at 64 x 64 and on scenes)
-  if (irb_cfg_ok(IRB_C, Cin, hid, Cout)) return IRB_C;
+  if (irb_cfg_ok(IRB_A, Cin, hid, Cout)) return IRB_A;
   return irb_cfg_ok(IRB_B, Cin, hid, Cout) ? IRB_B : -1;
 }
 
@@ -427,7 +420,7 @@ extern "C" int sc_irb_supported(int Cin, int hidden, int Cout, int H, int W, int
 }
 
 // Which k_irb instantiation sc_irb_eval launches for a block shape, without touching the GPU: -1 = unsupported, else
-//   10000 * tiling (0 = A: 4 x 8 pixels, 64-channel chunks; 1 = B: 8 x 8, 32-channel chunks; 2 = C: 8 x 8, 64-channel chunks, 8 waves;
+//   10000 * tiling (0 = A: 4 x 8 pixels, 64-channel chunks; 1 = B: 8 x 8, 32-channel chunks;
 //                   3 = the stride-2 form of A) + 1000 * projection pairs per wave (1..3) + 10 * NKE (expansion K steps in registers:
 //   2, 4, 6, 10) + work-groups per CU (1 | 2).  sc_irb_eval dispatches on this value.
 extern "C" int sc_irb_variant(int Cin, int hidden, int Cout, int stride) {
@@ -470,7 +463,6 @@ extern "C" int sc_irb_eval(const sc_irb_args* a, sc_stream stream) {
     if (mpp == 2) return irb_launch<4, 8, 64, 2, 1, 10>(p, nke, st);
     return irb_launch<4, 8, 64, 3, 1, 10>(p, nke, st);
   }
-  if (cfg == IRB_C) return mpp <= 1 ? irb_launch<8, 8, 64, 1, 1, 6>(p, nke, st) : irb_launch<8, 8, 64, 2, 1, 6>(p, nke, st);
   if (mpp <= 1) return irb_launch<8, 8, 32, 1, 1, 10>(p, nke, st);
   if (mpp == 2) return irb_launch<8, 8, 32, 2, 1, 10>(p, nke, st);
   return irb_launch<8, 8, 32, 3, 1, 10>(p, nke, st);

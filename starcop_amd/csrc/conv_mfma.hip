@@ -17,7 +17,6 @@
 // prologue), one barrier per chunk.
 #include "sc_common.h"
 #include <vector>
-#include <cstdlib>
 
 namespace {
 
@@ -29,11 +28,10 @@ struct ConvP {
   int csplit, accum0, accum1;
   const float* add0; const float* add1;
   float* stats;
-  int xcdmap;     // 1: 1-D grid; each XCD walks a contiguous eighth of the pixel tiles, the cout tiles of a pixel tile back to back
 };
 
 // BNB: the (single) source is a BatchNorm-backward source (dgrad launches); mixing it with other modes in a concat is not used
-template <int KS, int RM, bool BNB, int PF_ = 1>
+template <int KS, int RM, bool BNB>
 __global__ __launch_bounds__(256, 2) void k_conv_mfma(const ConvP p) {
   constexpr int TAPS = KS * KS;
   constexpr int CO_T = 32 * RM;
@@ -60,21 +58,8 @@ __global__ __launch_bounds__(256, 2) void k_conv_mfma(const ConvP p) {
   const int l31 = lane & 31, lhi = lane >> 5;
   const int H = p.H, W = p.W;
   const int per_img = (KS == 3) ? ((W + 31) >> 5) * ((H + 3) >> 2) : (H * W + 127) >> 7;
-  int n, cot, tile;
-  if (p.xcdmap) {
-    // work-groups go to the 8 XCDs round-robin by linear id; each XCD has its own L2.  XCD k walks the k-th contiguous eighth of
-    // the pixel tiles, all cout tiles of a pixel tile back to back: the input tile they share (and, for 3x3, the halo lines of
-    // neighbouring tiles) is fetched from memory once and then hits in that L2 -- lower latency for these latency-bound kernels
-    const int ncot = (p.Cout + CO_T - 1) / CO_T;
-    const int total = per_img * p.N, per_xcd = (total + 7) >> 3;
-    const int slot = blockIdx.x >> 3, j = slot / ncot;
-    const int pt = (blockIdx.x & 7) * per_xcd + j;
-    if (j >= per_xcd || pt >= total) return;
-    cot = slot - j * ncot;
-    n = pt / per_img; tile = pt - n * per_img;
-  } else {
-    n = blockIdx.z; cot = blockIdx.y; tile = blockIdx.x;
-  }
+  // plain 3-D grid (an XCD-aware 1-D numbering as in conv_bx3.hip was measured: no gain for the 1x1 layers, 2.82 vs 2.89 ms per step)
+  int n = blockIdx.z, cot = blockIdx.y, tile = blockIdx.x;
   // integer division has no scalar form: its (uniform) results come back in VGPRs and drag every address derived from them into
   // 64-bit VALU arithmetic (11 instructions per channel plane and chunk in the 1x1 kernel).  Say that they are uniform.
   n = __builtin_amdgcn_readfirstlane(n); cot = __builtin_amdgcn_readfirstlane(cot); tile = __builtin_amdgcn_readfirstlane(tile);
@@ -127,10 +112,9 @@ __global__ __launch_bounds__(256, 2) void k_conv_mfma(const ConvP p) {
       inb |= ok ? (1u << i) : 0u;
     }
   }
-  // Staging registers of one K chunk.  1x1 layers keep TWO chunks in flight (PF = 2): their work per chunk (16 channels x 128 pixels,
-  // 8-16 MFMAs per wave) is far shorter than a memory round trip, so with one chunk of look-ahead every iteration waits for its loads
-  // (measured: 2.9k cycles per chunk against ~1k of MFMA); 3x3 chunks carry 9x the MFMA work and stay at one.
-  constexpr int PF = (KS == 1) ? PF_ : 1;
+  // Staging registers of one K chunk: ONE chunk of look-ahead.  (The work of a 1x1 chunk -- 16 channels x 128 pixels, 8-16 MFMAs per
+  // wave -- is far shorter than a memory round trip, 2.9k cycles per chunk against ~1k of MFMA, but a straight-line look-ahead of two
+  // chunks measured slower twice: 2.93 vs 2.78 ms per step.)
   struct Stg {
     float xv[NC][NE], av[BNB ? NC : 1][NE];
     bool chok[NC];
@@ -139,7 +123,7 @@ __global__ __launch_bounds__(256, 2) void k_conv_mfma(const ConvP p) {
     floatx4 wv[NW];
     float slo, shi;
   };
-  Stg stg[PF];
+  Stg stg;
 
   auto load_chunk = [&](int kc, Stg& g) {
     // the source (of a concat) is uniform per chunk: KC divides the first source's channel count when nsrc == 2
@@ -260,38 +244,15 @@ __global__ __launch_bounds__(256, 2) void k_conv_mfma(const ConvP p) {
     }
   };
 
-  if (PF == 1) {
-    load_chunk(0, stg[0]);
-    store_chunk(0, stg[0]);
+  load_chunk(0, stg);
+  store_chunk(0, stg);
+  __syncthreads();
+  for (int kc = 0; kc < nk; ++kc) {
+    const bool more = (kc + 1) < nk;
+    if (more) load_chunk(kc + 1, stg);
+    compute_chunk(kc & 1);
+    if (more) store_chunk((kc + 1) & 1, stg);
     __syncthreads();
-    for (int kc = 0; kc < nk; ++kc) {
-      const bool more = (kc + 1) < nk;
-      if (more) load_chunk(kc + 1, stg[0]);
-      compute_chunk(kc & 1);
-      if (more) store_chunk((kc + 1) & 1, stg[0]);
-      __syncthreads();
-    }
-  } else {
-    // Two chunks of look-ahead, STRAIGHT-LINE: chunk kc + 2 is requested into the register set that the store of chunk kc just
-    // freed, every load is unconditional (past the end: the last chunk again, stored but never multiplied) and only the
-    // LDS-read + MFMA block of an odd tail sits under a (uniform) branch.  The first version of this path had `if (kc + 2 < nk)`
-    // around its loads; hipcc merges the two request histories at such a join into s_waitcnt vmcnt(0), which turned the
-    // look-ahead into "wait for everything" (and measured slower than PF = 1).
-    auto ld = [&](int kc, Stg& g) { load_chunk(kc < nk ? kc : nk - 1, g); };
-    ld(0, stg[0]);
-    ld(1, stg[PF - 1]);
-    store_chunk(0, stg[0]);
-    __syncthreads();
-    for (int kc = 0; kc < nk; kc += 2) {
-      ld(kc + 2, stg[0]);
-      compute_chunk(0);
-      store_chunk(1, stg[PF - 1]);
-      __syncthreads();
-      ld(kc + 3, stg[PF - 1]);
-      if (kc + 1 < nk) compute_chunk(1);
-      store_chunk(0, stg[0]);
-      __syncthreads();
-    }
   }
 
   // ---- epilogue ----
@@ -1396,7 +1357,6 @@ const float* sc_identity_cst_table(int C) { return sc_identity_cst(C); }
 extern "C" int sc_pw_stream_variant(const sc_conv_args* a) {
   if (a == nullptr || a->ks != 1 || a->nsrc != 1 || a->N <= 0 || a->H <= 0 || a->W <= 0 || a->Cout <= 0) return -1;
   if (a->co_t != 32 && a->co_t != 64) return -1;
-  static const bool pws_off = [] { const char* e = getenv("STARCOP_PWS"); return e && atoi(e) == 0; }();      // (same-box A/B)
   const long HWl = (long)a->H * a->W;
   const int K = a->src[0].C, M = a->Cout;
   if (K <= 0 || K % 8 != 0) return -1;
@@ -1410,7 +1370,7 @@ extern "C" int sc_pw_stream_variant(const sc_conv_args* a) {
   // short contractions only: the long-K projections (96 / 144 -> 24 at 128^2) measured a tie without and 3-8 us slower with the
   // statistics epilogue (a lane keeps NKS filter registers per cout block: two waves per SIMD)
   const bool ks_ok = bnb ? (nks == 4 || nks == 6 || nks == 8) : (nks == 6 || nks == 8);
-  if (pws_off || !plain || !aligned || !ks_ok || M > 192 || HWl < 4096 || HWl % 256 != 0 || HWl >= (1L << 30)) return -1;
+  if (!plain || !aligned || !ks_ok || M > 192 || HWl < 4096 || HWl % 256 != 0 || HWl >= (1L << 30)) return -1;
   const int ncb = bnb ? (M <= 32 ? 2 : (M <= 96 ? 3 : (M <= 160 ? 5 : 6))) : (M <= 16 ? 1 : (M <= 32 ? 2 : (M <= 160 ? 5 : 6)));
   return (bnb ? 100 : 0) + 10 * ncb + nks;
 }
@@ -1486,14 +1446,6 @@ extern "C" int sc_conv2d_mfma(const sc_conv_args* a, sc_stream stream) {
   if (a->ks == 3) grid = dim3(((a->W + 31) / 32) * ((a->H + 3) / 4), co_tiles, a->N);
   else grid = dim3((a->H * a->W + 127) / 128, co_tiles, a->N);
   hipStream_t st = (hipStream_t)stream;
-  p.xcdmap = 0;
-  constexpr int xcdmap_env = 0;   // measured: no gain for the 1x1 layers (2.82 vs 2.89 ms per step): off
-  if (a->co_t != 16 && xcdmap_env) {
-    const long total = (long)grid.x * a->N, per_xcd = (total + 7) / 8;
-    SC_REQUIRE(per_xcd * 8 * co_tiles < (1L << 31), "sc_conv2d_mfma: grid too large");
-    grid = dim3((unsigned)(per_xcd * 8 * co_tiles));
-    p.xcdmap = 1;
-  }
   if (a->co_t == 16) {
     const bool bnb = a->src[0].mode == SC_SRC_BNBWD;
     if (a->H >= 8) {          // 8-row tiles (two rows per wave): measured 0.58 -> 0.49 ms on 32->16 channels at 512^2
@@ -1512,17 +1464,10 @@ extern "C" int sc_conv2d_mfma(const sc_conv_args* a, sc_stream stream) {
       if (bnb) hipLaunchKernelGGL((k_conv_mfma<KS_, RM_, true>), grid, dim3(256), 0, st, p);          \
       else hipLaunchKernelGGL((k_conv_mfma<KS_, RM_, false>), grid, dim3(256), 0, st, p);             \
     } while (0)
-    constexpr int pf_env = 1;          // K chunks of look-ahead (2 measured slower twice: 2.93 vs 2.78 ms)
-#define SC_CM2(RM_)                                                                                  \
-    do {                                                                                              \
-      if (bnb) hipLaunchKernelGGL((k_conv_mfma<1, RM_, true, 2>), grid, dim3(256), 0, st, p);         \
-      else hipLaunchKernelGGL((k_conv_mfma<1, RM_, false, 2>), grid, dim3(256), 0, st, p);            \
-    } while (0)
     if (a->ks == 3 && a->co_t == 64) SC_CM(3, 2);
     else if (a->ks == 3) SC_CM(3, 1);
-    else if (a->co_t == 64) { if (pf_env == 2) SC_CM2(2); else SC_CM(1, 2); }
-    else { if (pf_env == 2) SC_CM2(1); else SC_CM(1, 1); }
-#undef SC_CM2
+    else if (a->co_t == 64) SC_CM(1, 2);
+    else SC_CM(1, 1);
 #undef SC_CM
   }
   SC_LAUNCH_OK("sc_conv2d_mfma");
@@ -1541,7 +1486,6 @@ extern "C" int sc_conv1x1_ksplit(const sc_conv_args* a, sc_stream stream) {
   SC_REQUIRE(a->csplit > 0 && a->csplit <= a->Cout, "sc_conv1x1_ksplit: bad csplit");
   SC_REQUIRE(a->csplit == a->Cout || (a->add0 == nullptr && a->add1 == nullptr), "sc_conv1x1_ksplit: add tensors need a single output");
   ConvP p;
-  p.xcdmap = 0;
   p.s0 = to_srcd(a->src[0]); p.s1 = empty_srcd();
   if (p.s0.mode == SC_SRC_RAW) { p.s0.cst = sc_identity_cst(p.s0.C); SC_REQUIRE(p.s0.cst != nullptr, "sc_conv1x1_ksplit: identity constants unavailable (C = %d)", p.s0.C); }
   p.wpk = a->wpk; p.N = a->N; p.H = a->H; p.W = a->W; p.Cout = a->Cout;

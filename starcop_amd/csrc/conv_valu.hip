@@ -749,16 +749,15 @@ __global__ __launch_bounds__(256) void k_dw_bwd(const SrcD dy, const SrcD in, co
   if (in_sums && threadIdx.x < 2) in_sums[(((size_t)n * tiles + tile) * C + c) * 2 + threadIdx.x] = (double)all[9 + threadIdx.x];
 }
 
-// The same fused backward for whole 16x16 / 32x32 planes at stride 1 (features.8-13 and 15-17 at 512^2 input: up to 15360 planes
+// The same fused backward for whole 16x16 planes at stride 1 (features.15-17 at 512^2 input: up to 15360 planes
 // per layer).  One plane is one tile there, and a 256-thread work-group per plane spends its time on launch, barrier and an
 // 11-value block reduction (16x16: 65 us per layer = 1 TB/s, slower than the three separate kernels).  Here a WAVE owns a plane:
-// G float4 loads per lane and tensor (PS = 16: G = 1, four lanes per row; PS = 32: G = 4, two lanes per row), a wave-private LDS
-// patch with a zero border, 4 G outputs per lane, DPP wave sums, atomics from lane 0.
-template <int PS>
+// G float4 loads per lane and tensor (G = 1, four lanes per row), a wave-private LDS patch with a zero border, 4 G outputs per lane,
+// DPP wave sums, atomics from lane 0.
 __global__ __launch_bounds__(256) void k_dw_bwd_plane(const SrcD dy, const SrcD in, const float* __restrict__ w, float* __restrict__ dx,
                                                       double* __restrict__ dw_acc, double* __restrict__ in_sums, int C) {
-  constexpr int P = PS + 8, PR = PS + 2;         // patch pitch (interior at columns 4..PS+3, halo columns 3 and PS+4), patch rows
-  constexpr int LPR = (PS == 16) ? 4 : 2, G = PS / (4 * LPR), HW = PS * PS;
+  constexpr int PS = 16, P = PS + 8, PR = PS + 2;         // plane size, patch pitch (interior at columns 4..PS+3, halo columns 3 and PS+4), patch rows
+  constexpr int LPR = 4, G = PS / (4 * LPR), HW = PS * PS;
   __shared__ __attribute__((aligned(16))) float s_d[4][PR * P];
   __shared__ __attribute__((aligned(16))) float s_x[4][PR * P];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -858,12 +857,11 @@ __global__ __launch_bounds__(256) void k_dw_bwd_plane(const SrcD dy, const SrcD 
   }
 }
 
-// forward for whole 16x16 / 32x32 planes at stride 1, a wave per plane (see k_dw_bwd_plane)
-template <int PS>
+// forward for whole 16x16 planes at stride 1, a wave per plane (see k_dw_bwd_plane)
 __global__ __launch_bounds__(256) void k_dw_fwd_plane(const SrcD in, const float* __restrict__ w, float* __restrict__ out, int C,
                                                       float* __restrict__ stats, const BnTailD tail) {
-  constexpr int P = PS + 8, PR = PS + 2;
-  constexpr int LPR = (PS == 16) ? 4 : 2, G = PS / (4 * LPR), HW = PS * PS;
+  constexpr int PS = 16, P = PS + 8, PR = PS + 2;
+  constexpr int LPR = 4, G = PS / (4 * LPR), HW = PS * PS;
   __shared__ __attribute__((aligned(16))) float s_x[4][PR * P];
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int plane = __builtin_amdgcn_readfirstlane(blockIdx.x * 4 + wave);
@@ -2174,8 +2172,8 @@ int head_blocks(int N, int H, int W) {
   } while (0)
 
 // Which instantiation a depthwise launch gets, without touching the GPU.  op: 0 = forward (sc_dwconv3x3_fwd / _fwd_bn), 1 = dgrad,
-// 2 = wgrad, 3 = bwd_fused.  -1 for what the entry point rejects, 9000 + PS for the wave-per-plane kernels (PS = 16, or 32 behind
-// STARCOP_DW_P32), else 1000 * stride + 10 * TW + V4 (V4: float4 staging; always 0 for dgrad and wgrad).  The tile width follows
+// 2 = wgrad, 3 = bwd_fused.  -1 for what the entry point rejects, 9016 for the wave-per-plane kernels (16 x 16 planes),
+// else 1000 * stride + 10 * TW + V4 (V4: float4 staging; always 0 for dgrad and wgrad).  The tile width follows
 // the plane the work-groups tile: the output for forward and wgrad, the input for dgrad and bwd_fused.  al_v4: the tensors the
 // float4 staging reads are 16-byte aligned; al_plane: so are those the plane kernels also access as float4 (out, dx).
 static int dw_variant(int op, int N, int C, int Hin, int Win, int stride, bool al_v4, bool al_plane) {
@@ -2187,11 +2185,10 @@ static int dw_variant(int op, int N, int C, int Hin, int Win, int stride, bool a
   if (op == 1 || op == 2) return 1000 * stride + 10 * tw;
   // float4 staging where every patch row is 16-byte aligned
   const bool v4 = al_v4 && Win % 4 == 0 && (op == 0 || Wout % 4 == 0);
-  // (32 x 32 planes through the plane kernels measured SLOWER than the work-group-per-plane form -- backward 50 -> 63 us, forward
-  // 22 -> 27 us on features.12: 16 pixels per lane, 43 KB of LDS per work-group -- so it is opt-in: STARCOP_DW_P32=1)
-  static const bool p32_env = [] { const char* e = getenv("STARCOP_DW_P32"); return e && atoi(e) != 0; }();
+  // a wave per plane: 16 x 16 only (32 x 32 planes through the plane kernels measured SLOWER than the work-group-per-plane form --
+  // backward 50 -> 63 us, forward 22 -> 27 us on features.12: 16 pixels per lane, 43 KB of LDS per work-group)
   const bool plane_ok = (op == 0 ? al_v4 : v4) && al_plane && stride == 1 && Hin == Win && ((long)N * C) % 4 == 0;
-  if (plane_ok && (Hin == 16 || (p32_env && Hin == 32))) return 9000 + Hin;      // a wave per plane
+  if (plane_ok && Hin == 16) return 9016;
   return 1000 * stride + 10 * tw + (v4 ? 1 : 0);
 }
 extern "C" int sc_dw_variant(int op, int N, int C, int Hin, int Win, int stride, int aligned16) {
@@ -2234,9 +2231,8 @@ static int dwconv3x3_fwd(const sc_src* in, const float* w, float* out, int N, in
     tail.count = (double)N * Hout * Wout;
   }
   const int variant = dw_variant(0, N, C, Hin, Win, stride, (((uintptr_t)in->x) & 15) == 0, (((uintptr_t)out) & 15) == 0);
-  if (variant >= 9000) {      // a wave per plane
-    if (variant == 9016) hipLaunchKernelGGL(k_dw_fwd_plane<16>, dim3((unsigned)((long)N * C / 4)), dim3(256), 0, st, to_srcd(*in), w, out, C, stats, tail);
-    else hipLaunchKernelGGL(k_dw_fwd_plane<32>, dim3((unsigned)((long)N * C / 4)), dim3(256), 0, st, to_srcd(*in), w, out, C, stats, tail);
+  if (variant == 9016) {      // a wave per plane
+    hipLaunchKernelGGL(k_dw_fwd_plane, dim3((unsigned)((long)N * C / 4)), dim3(256), 0, st, to_srcd(*in), w, out, C, stats, tail);
     SC_LAUNCH_OK("sc_dwconv3x3_fwd");
     return SC_OK;
   }
@@ -2291,9 +2287,8 @@ extern "C" int sc_dwconv3x3_bwd_fused(const sc_src* dy, const sc_src* in, const 
   dim3 grid((unsigned)(planes8 * dw_tiles(Hin, Win)));
   const int variant = dw_variant(3, N, C, Hin, Win, stride, ((((uintptr_t)dy->x) | ((uintptr_t)dy->aux) | ((uintptr_t)in->x)) & 15) == 0,
                                  ((uintptr_t)dx & 15) == 0);
-  if (variant >= 9000) {      // a wave per plane
-    if (variant == 9016) hipLaunchKernelGGL(k_dw_bwd_plane<16>, dim3((unsigned)((long)N * C / 4)), dim3(256), 0, st, to_srcd(*dy), to_srcd(*in), w, dx, dw_acc, in_sums, C);
-    else hipLaunchKernelGGL(k_dw_bwd_plane<32>, dim3((unsigned)((long)N * C / 4)), dim3(256), 0, st, to_srcd(*dy), to_srcd(*in), w, dx, dw_acc, in_sums, C);
+  if (variant == 9016) {      // a wave per plane
+    hipLaunchKernelGGL(k_dw_bwd_plane, dim3((unsigned)((long)N * C / 4)), dim3(256), 0, st, to_srcd(*dy), to_srcd(*in), w, dx, dw_acc, in_sums, C);
     SC_LAUNCH_OK("sc_dwconv3x3_bwd_fused");
     return SC_OK;
   }
@@ -2370,8 +2365,7 @@ extern "C" int sc_stem_conv_fwd(const sc_src* in, const float* w, float* out, in
 extern "C" int sc_stem_fwd_kernel(int Cin, int Win, int out_aligned16) {
   if (Cin < 1 || Cin > STEM_MAXCI_FWD) return SC_ERR_ARG;
   const int Wout = (Win - 1) / 2 + 1;
-  static const bool mfma_off = [] { const char* e = getenv("STARCOP_STEM_MFMA"); return e && atoi(e) == 0; }();      // (same-box A/B)
-  if (Cin <= 4) return (!mfma_off && Wout % 4 == 0 && out_aligned16) ? SC_STEM_K_MFMA4 : SC_STEM_K_VALU4;
+  if (Cin <= 4) return (Wout % 4 == 0 && out_aligned16) ? SC_STEM_K_MFMA4 : SC_STEM_K_VALU4;
   return Cin <= STEM_MAXCI ? SC_STEM_K_VALU8 : SC_STEM_K_VALU16;
 }
 

@@ -95,7 +95,7 @@ MAX_SORT_WORK_INTS = 64 << 20        # histogram ints of the device counting sor
 MAX_GROUP_IDS = 1 << 16      # group ids up to this take the device counting sort (detector widths are ~600-1300); larger / negative ids
                              # fall back to the general sort
 COLUMN_FAST_PATH = True      # False: always take the general (device sort) layout path; tests compare the two bit for bit
-DIRECT_TILES = os.environ.get("STARCOP_MAG1C_DIRECT", "1") == "1"    # column groups of <= 512 pixels (a 512-row tile per detector column):
+DIRECT_TILES = True          # column groups of <= 512 pixels (a 512-row tile per detector column):
                              # the filter kernel gathers from the cube and scatters to image order itself (no pack / scatter passes)
 _TEMPLATE_CACHE = {}
 

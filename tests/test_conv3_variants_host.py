@@ -15,7 +15,7 @@ from test_gpu_conv3_variants import (CAPS, CASES, KNOBS, OP_CONV3, OP_THIN, OP_W
 OPS = (OP_CONV3, OP_THIN, OP_WGRAD3, OP_WTHIN)
 WANT = {
     OP_CONV3: {1000 * ws + 100 * q + 10 * b + m for ws in (0, 1) for q in (1, 2) for b in (0, 1) for m in (1, 2, 3, 4) if m == 4 or not ws},
-    OP_THIN: {100, 110, 200, 210, 1200, 2110},      # (201, k_conv3_thin_h<32, false, true>: only with STARCOP_THIN_SP=0)
+    OP_THIN: {100, 110, 200, 210, 1200, 2110},      # (200: 32 channels, not up-sampled; up-sampled RAW / AFFINE: 1200)
     OP_WGRAD3: {1000 * m + 100 * wm + 10 * nci for m in (1, 2, 3, 4) for wm in (1, 2) for nci in (1, 2)} | {14111, 14121, 14210, 14221, 14131},
     OP_WTHIN: {100, 110, 200, 210},
 }

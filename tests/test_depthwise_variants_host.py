@@ -6,21 +6,13 @@ or a dispatcher gaining a branch without a case, fails this test; so does a tabl
 next to it, and a table that loses one of the edges it is there for."""
 import pytest
 
-from test_gpu_depthwise_variants import (DW_BWD_CASES, DW_CASES, DW_DGRAD_CASES, DW_FWD_CASES, DW_P32_CASES, DW_WGRAD_CASES, OP_BWD,
+from test_gpu_depthwise_variants import (DW_BWD_CASES, DW_CASES, DW_DGRAD_CASES, DW_FWD_CASES, DW_WGRAD_CASES, OP_BWD,
                                          OP_DGRAD, OP_FWD, OP_WGRAD, chain_tile, chain_wgrad, dw_code, dw_tile, dw_tiled_plane, dw_tiles,
                                          wgrad_tiles_per_group)
 
 TILE_CODES = {1000 * s + 10 * tw for s in (1, 2) for tw in (64, 32, 16)}
 STAGED_CODES = {c + v4 for c in TILE_CODES for v4 in (0, 1)} | {9016}
 WANT = {OP_FWD: STAGED_CODES, OP_DGRAD: TILE_CODES, OP_WGRAD: TILE_CODES, OP_BWD: STAGED_CODES}
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _no_dispatch_knobs():
-    """the development knob changes what the query answers (that is its meaning): this test describes the default dispatch"""
-    import os
-    if "STARCOP_DW_P32" in os.environ:
-        pytest.fail("STARCOP_DW_P32 is set: the case tables cover the default dispatch")
 
 
 def _flags(case):
@@ -114,10 +106,8 @@ def test_required_edge_cases_are_present():
     assert any("nosums" in _flags(c) for c in DW_BWD_CASES)
     assert all("nosums" in _flags(c) for c in DW_BWD_CASES if c[6][1] == "raw")
     assert {c[0] for c in DW_BWD_CASES if "nosums" not in _flags(c)} == STAGED_CODES
-    # the 32 x 32 plane kernels: forward and fused backward, N C % 4 == 0, not what the default dispatch selects
-    assert {c[0] for c in DW_P32_CASES} == {OP_FWD, OP_BWD}
-    for op, code, N, C_, H, W, stride, _, _ in DW_P32_CASES:
-        assert code == 9032 and (H, W, stride) == (32, 32, 1) and (N * C_) % 4 == 0 and dw_code(op, N, C_, H, W, stride, True) == 1321
+    # 32 x 32 planes take the tile kernels (the plane kernels are for 16 x 16 only)
+    assert all(dw_code(op, 2, 4, 32, 32, 1, True) == 1321 for op in (OP_FWD, OP_BWD))
 
 
 def test_rejected_arguments():
@@ -135,4 +125,4 @@ def test_chain_counts():
     assert chain_wgrad(1640, 1, 8, 32, 64, 1) == 8 + 9 + 3 and chain_wgrad(1160, 8, 960, 8, 8, 1) == 2 * 1 + 9 + 3
     assert wgrad_tiles_per_group(2160, 8, 960, 16, 16, 2) == 2
     assert chain_tile(1641) == 8 + 9 + 3 and chain_tile(2161, 2) == 4 + 9 + 3 and chain_tile(2641, 2) == 8 + 9 + 3
-    assert chain_tile(9016) == 4 + 6 + 3 and chain_tile(9032) == 16 + 6 + 3
+    assert chain_tile(9016) == 4 + 6 + 3

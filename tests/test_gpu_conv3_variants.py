@@ -5,8 +5,8 @@ The host queries sc_conv3_variant, sc_thin16_variant, sc_wgrad3_variant and sc_w
 launchers switch on the same functions.  Here every code they can return under the default dispatch has a plain case, a ragged case
 and exact probes; every case asserts the code it was written for before it launches.  tests/test_conv3_variants_host.py holds the
 tables below to the swept set of codes on a box without a GPU, which is why the tables, the argument builders and the code helpers
-sit at module level and touch no device.  (k_conv3_thin_h<32, false, true>, code 201, is selected only with STARCOP_THIN_SP=0: the
-sub-pixel kernel 1200 takes every such launch by default, so it has no case here.)
+sit at module level and touch no device.  (An up-sampled 32-channel RAW / AFFINE source of the thin forward always takes the sub-pixel
+kernel 1200; code 200 is the 32-channel source that is not up-sampled.)
 
 Codes (M = 1, 2, 3 bf16 terms per operand, 4 = two fp16 terms):
   conv3   1000 WS + 100 Q + 10 BNB + M          Q = co_t / 32, BNB = BatchNorm-backward source (the data gradient), WS = k_conv3_ws
@@ -68,7 +68,7 @@ D_SPLIT = {1: 2.0 ** -8, 2: 2.0 ** -16, 3: 3 * U, 4: 2.0 ** -22}      # (a): the
 D_PROBE = {1: 2.0 ** -8, 2: 2.0 ** -16, 3: 0.0, 4: 2.0 ** -22}        # (c): the remainder of the one inexact operand
 PRODUCTS = {1: 1, 2: 3, 3: 6, 4: 3}
 FLOOR_ACT, FLOOR_W, FLOOR_GRAD1 = 2.0 ** -26, 2.0 ** -33, 2.0 ** -25
-KNOBS = ("STARCOP_BX3_WS_MINCHUNKS", "STARCOP_WGRAD96", "STARCOP_THIN_SP", "STARCOP_THIN_UPS")
+KNOBS = ("STARCOP_BX3_WS_MINCHUNKS",)
 CAPS = dict(N=3, H=40, W=72, C=96)
 WIDE_AREA = 16 * 32
 

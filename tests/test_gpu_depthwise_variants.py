@@ -21,8 +21,6 @@ close to their bound by construction.
 The masks of ReLU / ReLU6 are discontinuous, so the inputs they are taken from are moved off the thresholds (by 0.01 where a value
 lies within 1e-3 of 0 or 6): no element is excluded from any comparison.  Every case prints its error-to-bound ratios before it asserts."""
 import ctypes as C
-import os
-
 import pytest
 import torch
 import torch.nn.functional as F
@@ -39,7 +37,7 @@ from test_gpu_ops import rnd  # noqa: E402
 U = 2.0 ** -24
 OP_FWD, OP_DGRAD, OP_WGRAD, OP_BWD = 0, 1, 2, 3
 
-# ---- case tables: (code, N, C, H, W, stride, source modes, flags).  code = 1000 stride + 10 TW + V4, or 9000 + PS for the plane kernels.
+# ---- case tables: (code, N, C, H, W, stride, source modes, flags).  code = 1000 stride + 10 TW + V4, or 9016 for the plane kernels (16 x 16 planes).
 # H, W: the INPUT plane of the layer.  The work-groups tile the output plane in the forward and the filter gradient and the input
 # plane in the data gradient and the fused backward; TW = 64 above 32 columns of that plane (64 x 32 tiles), 32 above 16 (32 x 32), else
 # 16 (16 x 16).  Input modes: raw (no activation) | affine6 (BatchNorm constants + ReLU6) | affine_relu; dy modes: raw | affine |
@@ -161,14 +159,6 @@ DW_BWD_CASES = [
     (9016, 1, 4, 16, 16, 1, ("bnbwd6", "raw"), "nosums"),
 ]
 
-# the 32 x 32 plane kernels, behind STARCOP_DW_P32 (a per-process switch): (op, code, N, C, H, W, stride, source modes, flags)
-DW_P32_CASES = [
-    (OP_FWD, 9032, 2, 4, 32, 32, 1, "affine6", ""),
-    (OP_FWD, 9032, 1, 12, 32, 32, 1, "raw", "ragged"),
-    (OP_BWD, 9032, 2, 4, 32, 32, 1, ("bnbwd6", "affine6"), ""),
-    (OP_BWD, 9032, 1, 12, 32, 32, 1, ("affine", "affine_relu"), "ragged"),
-]
-
 DW_CASES = {OP_FWD: DW_FWD_CASES, OP_DGRAD: DW_DGRAD_CASES, OP_WGRAD: DW_WGRAD_CASES, OP_BWD: DW_BWD_CASES}
 
 
@@ -213,9 +203,9 @@ def chain_wgrad(code, N, C_, H, W, stride):
 def chain_tile(code, stride=1):
     """per-tile sums of k_dw_fwd (statistics) and k_dw_bwd (filter gradient, in_sums): a thread adds its R pixels (stride-2 backward: the
     4 pixels of each of its max(R / 4, 1) 2 x 2 blocks, so at most max(R, 4) terms), then the 6 + 3 steps of the block sum.  Plane
-    kernels: a lane adds its 4 G pixels (G float4 groups: 4 pixels at 16 x 16, 16 at 32 x 32), then the 6 steps of the wave sum."""
-    if code >= 9000:
-        return (4 if code == 9016 else 16) + 6 + 3
+    kernels: a lane adds its 4 pixels (one float4 of a 16 x 16 plane), then the 6 steps of the wave sum."""
+    if code == 9016:
+        return 4 + 6 + 3
     R = dw_tile(code)[2]
     return (R if stride == 1 else max(R, 4)) + 9 + 3
 
@@ -443,9 +433,6 @@ def run_bwd(lib, code, N, C_, H, W, stride, modes, flags):
     assert torch.equal(dx, dx2)
 
 
-RUN = {OP_FWD: run_fwd, OP_DGRAD: run_dgrad, OP_WGRAD: run_wgrad, OP_BWD: run_bwd}
-
-
 @pytest.mark.parametrize("case", DW_FWD_CASES, ids=_id)
 def test_dw_fwd_variant(hip, case):
     run_fwd(hip, *case)
@@ -464,30 +451,3 @@ def test_dw_wgrad_variant(hip, case):
 @pytest.mark.parametrize("case", DW_BWD_CASES, ids=_id)
 def test_dw_bwd_fused_variant(hip, case):
     run_bwd(hip, *case)
-
-
-def _p32_set():
-    e = os.environ.get("STARCOP_DW_P32")
-    try:
-        return e is not None and int(e) != 0
-    except ValueError:
-        return False
-
-
-@pytest.mark.parametrize("case", DW_P32_CASES, ids=_id)
-def test_dw_p32_plane_cases(hip, case):
-    """the wave-per-plane kernels at 32 x 32: chosen only in a process started with STARCOP_DW_P32 set (see the test below)"""
-    if not _p32_set():
-        pytest.skip("STARCOP_DW_P32 is not set: 32 x 32 planes take the tile kernels")
-    RUN[case[0]](hip, *case[1:])
-
-
-def test_dw_plane_kernels_at_32_in_a_child_process():
-    """STARCOP_DW_P32 is read once per process: run DW_P32_CASES in a fresh one that has it set"""
-    import subprocess
-    import sys
-    env = dict(os.environ, STARCOP_DW_P32="1")
-    r = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-s", "-k", "test_dw_p32_plane_cases"],
-                       env=env, capture_output=True, text=True, timeout=600)
-    print("\n".join(l for l in r.stdout.splitlines() if l.startswith("DWRATIO")))
-    assert r.returncode == 0 and f"{len(DW_P32_CASES)} passed" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]

@@ -360,3 +360,27 @@ def test_plan_sizes_cover_the_routed_kernels(N, H, W):
                 assert plan.ws.numel() >= need[r.wgrad.kernel if ty == "conv3" else "mfma"](ci), (prec, o.name)
             if r.dgrad.kernel.endswith("+downsum"):       # (the one route that goes through the full-resolution scratch)
                 assert plan.up_tmp.numel() >= N * L.Cup * Ho * Wo, (prec, o.name)
+
+
+def test_design_switch_table_is_the_list_of_environment_reads():
+    """DESIGN.md section 12 calls its table the one list of switches: the STARCOP_* variables it names are exactly those the library
+    (getenv in starcop_amd/csrc) and the package (os.environ in starcop_amd/*.py) read."""
+    import glob
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+    def found(pattern, regex):
+        names = set()
+        for path in glob.glob(os.path.join(root, "starcop_amd", pattern)):
+            with open(path, encoding="utf-8", errors="replace") as f:
+                names |= set(re.findall(regex, f.read()))
+        return names
+
+    read = found(os.path.join("csrc", "*"), r'getenv\(\s*"(STARCOP_[A-Z0-9_]+)"') | \
+        found("*.py", r'os\.environ(?:\.get\(|\[)\s*["\'](STARCOP_[A-Z0-9_]+)["\']')
+    with open(os.path.join(root, "DESIGN.md"), encoding="utf-8") as f:
+        section = f.read().split("\n## 12. ", 1)[1].split("\n## ", 1)[0]
+    rows = [l for l in section.splitlines() if l.startswith("| `STARCOP_")]
+    table = {n for l in rows for n in re.findall(r"`(STARCOP_[A-Z0-9_]+)`", l.split("|")[1])}
+    assert read and read == table, (sorted(read - table), sorted(table - read))
+    assert f"({len(table)} environment variables" in section.splitlines()[0]

@@ -48,14 +48,6 @@ WANT_HEAD_BWD = {
 }
 
 
-@pytest.fixture(scope="module", autouse=True)
-def _no_dispatch_knobs():
-    """the development knob changes what the query answers (that is its meaning): this test describes the default dispatch"""
-    import os
-    if "STARCOP_STEM_MFMA" in os.environ:
-        pytest.fail("STARCOP_STEM_MFMA is set: the case tables cover the default dispatch")
-
-
 def _fl(flags):
     return set(flags.split())
 

@@ -1,6 +1,6 @@
 """How often does tests/test_gpu_unet.py::test_train_forward_backward_and_adam's per-parameter gate (HIP error vs the fp64 oracle <=
 max(1e-3, 6 x the fp32 CPU path's own error)) trip for OTHER seeds than the test's -- i.e. is a failing parameter a property of a kernel
-or a draw?   usage: python tools/grad_gate_seeds.py [first_seed=3] [n=6]     (run under STARCOP_STEM_MFMA=0 / 1 to compare kernels)"""
+or a draw?   usage: python tools/grad_gate_seeds.py [first_seed=3] [n=6]"""
 import copy, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tests"))
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
