@@ -1484,6 +1484,46 @@ typedef struct sc_cstats_args {
 size_t sc_component_stats_workspace_bytes(int N, int H, int W, int M, int P);
 int sc_component_stats(const sc_cstats_args* a, void* work, size_t work_bytes, sc_stream stream);
 
+/* Radial profiles per component: the integrated enhancement inside circles around an origin, the plume's extent and its second
+ * moments (starcop_amd/plumes.py: component_radial; starcop_amd/quantify.py turns them into emission rates).  labels, counts, M and
+ * the rows are those of sc_component_stats; row_min .. col_max are the box columns that call returned (inclusive; they are cut
+ * to the image before they are walked, so a wrong box gives other numbers and never another address).  origin[(n*M + k-1)*2 + {0,
+ * 1}] is the (row, column) the distances of component k are taken from, anywhere within +-2^30; a negative row skips the plume.
+ * For every pixel (r, c) of value k inside its box, d2 = (r - r0)^2 + (c - c0)^2 in integers.  edge2[0 .. K-1], 0 <= edge2[0],
+ * strictly increasing, are the squared bin edges: bin j is the smallest j with d2 <= edge2[j], bin K holds what lies beyond.
+ * Per row:  bin_count (int64) and bin_sum (fp64), [K+1] each, over the pixels whose plane value is FINITE;
+ *   d2_max (int64, over all pixels of the component, finite or not; -1 for a row without pixels or a skipped one);
+ *   sum_rr sum_cc sum_rc (int64: the sums of r^2, c^2 and r c of the pixel indices over all pixels; with H, W <= 32767 and
+ *   H*W < 2^31 they stay below 2^62).
+ * Rows at or above counts[n], rows without pixels and skipped rows are zero with d2_max = -1.
+ * The plane of image n is the dense H x W float32 block at plane + n*plane_stride (elements).  N <= 65535, H, W <=
+ * SC_CRADIAL_MAX_SIDE, H*W < 2^31, 1 <= K <= SC_CRADIAL_MAX_BINS, M >= 0 (M = 0: nothing launched); SC_ERR_ARG, before any
+ * launch, for bad dims, K out of range, edges that do not increase, a null pointer, a plane stride below H*W in a batch or a
+ * workspace that is too small.
+ * No floating-point atomics.  One wave walks a row band of a box in raster order, 64 pixels a step; per step and per distinct bin
+ * one fixed butterfly sums the values of the lanes in that bin, the bins of a step in the order of their first lane, and the
+ * bands are folded in order: the order of every fp64 addition is fixed by the label image, the boxes, the origins and the edges,
+ * so repeated calls give identical bits and an image gives the same bits alone and inside any batch.  3 launches per call.
+ * work: sc_component_radial_workspace_bytes(N, H, W, M, K) bytes (4 bytes and 32 + 16 (K+1) bytes per row, the latter also per
+ * 512 pixels of an image).                                                                                                   */
+#define SC_CRADIAL_MAX_BINS 64
+#define SC_CRADIAL_MAX_SIDE 32767
+typedef struct sc_cradial_args {
+  const int32_t* labels;                          /* [N][H][W] device                                              */
+  const int32_t* counts;                          /* [N] device                                                    */
+  int32_t N, H, W, M, K, reserved;
+  const int32_t *row_min, *row_max, *col_min, *col_max;   /* [N][M] device: the boxes of sc_component_stats        */
+  const int32_t* origin;                          /* [N][M][2] device: (row, column); row < 0 skips the plume      */
+  const float* plane;                             /* element (0, 0) of image 0                                     */
+  int64_t plane_stride;                           /* elements between images                                       */
+  int32_t edge2[SC_CRADIAL_MAX_BINS];             /* host values: the squared bin edges, K of them                 */
+  int64_t* bin_count;                             /* [N][M][K+1] columns ...                                       */
+  double* bin_sum;
+  int64_t *d2_max, *sum_rr, *sum_cc, *sum_rc;     /* [N][M] columns                                                */
+} sc_cradial_args;
+size_t sc_component_radial_workspace_bytes(int N, int H, int W, int M, int K);
+int sc_component_radial(const sc_cradial_args* a, void* work, size_t work_bytes, sc_stream stream);
+
 /* Outlines of the components of a label image: polygon rings per plume (starcop_amd/plumes.py: component_outlines).  labels is
  * one int32 H x W image, 0 (and anything below) background, component k the pixels of value k.  The outline of k is made of
  * directed unit edges on the (H+1) x (W+1) lattice of pixel corners (corner (r, c) = the upper-left corner of pixel (r, c)),

@@ -284,7 +284,21 @@ class sc_cstats_args(C.Structure):
                 ("argmax", C.c_void_p)]
 
 
-OUTLINE_COUNT, OUTLINE_TRACE, OUTLINE_RINGS, OUTLINE_SCATTER, OUTLINE_COMPACT = range(5)       # enum sc_outline_stage
+CRADIAL_MAX_BINS, CRADIAL_MAX_SIDE = 64, 32767
+
+
+class sc_cradial_args(C.Structure):
+    """per-component radial profile operands (include/starcop_hip.h: sc_cradial_args)"""
+    _fields_ = [("labels", C.c_void_p), ("counts", C.c_void_p),
+                ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("M", C.c_int32), ("K", C.c_int32), ("reserved", C.c_int32),
+                ("row_min", C.c_void_p), ("row_max", C.c_void_p), ("col_min", C.c_void_p), ("col_max", C.c_void_p),
+                ("origin", C.c_void_p), ("plane", C.c_void_p), ("plane_stride", C.c_int64),
+                ("edge2", C.c_int32 * CRADIAL_MAX_BINS),
+                ("bin_count", C.c_void_p), ("bin_sum", C.c_void_p), ("d2_max", C.c_void_p), ("sum_rr", C.c_void_p),
+                ("sum_cc", C.c_void_p), ("sum_rc", C.c_void_p)]
+
+
+OUTLINE_COUNT, OUTLINE_TRACE,OUTLINE_RINGS, OUTLINE_SCATTER, OUTLINE_COMPACT = range(5)       # enum sc_outline_stage
 
 
 class sc_outline_args(C.Structure):
@@ -522,6 +536,8 @@ SIGNATURES = {
     "sc_render_panels": (_i, [_vp, C.POINTER(sc_panel), _i, _vp, _vp, _i, _i, _vp]),
     "sc_component_stats_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "sc_component_stats": (_i, [C.POINTER(sc_cstats_args), _vp, _sz, _vp]),
+    "sc_component_radial_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "sc_component_radial": (_i, [C.POINTER(sc_cradial_args), _vp, _sz, _vp]),
     "sc_component_outlines_workspace_bytes": (_sz, [_i, _i, C.c_int64]),
     "sc_component_outlines_rounds": (_i, [C.c_int64]),
     "sc_component_outlines": (_i, [C.POINTER(sc_outline_args), _i, _vp]),

@@ -41,6 +41,7 @@ __host__ __device__ inline size_t item_bytes(int P) { return sizeof(ItemRec) + (
 struct StatsP {
   const int* labels; const int* counts;
   int N, H, W, M, P, cap;              // cap: item slots per image = M + extra
+  int min_band;                        // smallest band height (BAND_ROWS here; sc_component_radial cuts finer)
   long long extra;
   const float* plane[MAXP]; long long plane_stride[MAXP];
   const unsigned char* other; long long other_stride;
@@ -96,8 +97,8 @@ __global__ __launch_bounds__(256) void k_cs_plan(const StatsP p) {
   atomicAdd(reinterpret_cast<unsigned long long*>(&tot), (unsigned long long)hs);      // integer: any order, one value
   __syncthreads();
   const long long need = (tot + p.extra - 1) / p.extra;
-  const long long top = p.H > BAND_ROWS ? p.H : BAND_ROWS;     // a band of H rows is the whole box already
-  const int bh = (int)(need < BAND_ROWS ? BAND_ROWS : (need > top ? top : need));
+  const long long low = p.min_band, top = p.H > low ? p.H : low;      // a band of H rows is the whole box already
+  const int bh = (int)(need < low ? low : (need > top ? top : need));
   const int per = (cnt + 255) / 256, k0 = min(cnt, tid * per), k1 = min(cnt, k0 + per);
   int s = 0;
   for (int k = k0; k < k1; ++k)
@@ -294,7 +295,7 @@ extern "C" int sc_component_stats(const sc_cstats_args* a, void* work, size_t wo
   StatsP p{};
   p.labels = a->labels; p.counts = a->counts;
   p.N = a->N; p.H = a->H; p.W = a->W; p.M = a->M; p.P = a->P;
-  p.extra = extra_items(a->H, a->W); p.cap = (int)(a->M + p.extra);
+  p.extra = extra_items(a->H, a->W); p.cap = (int)(a->M + p.extra); p.min_band = BAND_ROWS;
   for (int q = 0; q < a->P; ++q) { p.plane[q] = a->plane[q]; p.plane_stride[q] = a->plane_stride[q]; }
   p.other = a->other; p.other_stride = a->other_stride;
   p.area = (long long*)a->area; p.row_min = a->row_min; p.row_max = a->row_max; p.col_min = a->col_min; p.col_max = a->col_max;
@@ -316,5 +317,229 @@ extern "C" int sc_component_stats(const sc_cstats_args* a, void* work, size_t wo
   SC_LAUNCH_OK("k_cs_walk");
   hipLaunchKernelGGL(k_cs_combine, dim3((unsigned)((a->M + 255) / 256), a->N), dim3(256), 0, st, p);
   SC_LAUNCH_OK("k_cs_combine");
+  return SC_OK;
+}
+
+// Radial profiles per component (sc_component_radial): the fetch profiles behind starcop_amd/plumes.py: component_radial.
+// The boxes come from sc_component_stats, so three launches do: the plan above (k_cs_plan with a lower floor for the band height:
+// band height and first item of every component from the boxes), then
+//   walk    : one wave per (component, band) item, four to a work-group.  The wave steps through its band of the box in raster
+//             order, 64 pixels a step.  Every lane finds the bin of its pixel (the smallest j with d2 <= edge2[j], a binary search
+//             of the edges in LDS).  Then, while lanes remain: the bin of the first remaining lane is broadcast, ONE fixed xor
+//             butterfly sums `lane in that bin ? value : 0.0`, and lane 0 adds the result to the wave's own fp64 sum of that bin in
+//             LDS (the count is the popcount of the ballot).  Along a row a 64-pixel run crosses few bins, so the loop is short.
+//             The moments and the largest d2 are per-lane integers folded by a butterfly at the end.
+//   combine : one thread per (row, bin) folds the records of its component in band order.
+// Which lanes a bin's butterfly selects, the order in which the bins of a step are taken (by their first lane) and the order of
+// the steps depend on the label image, the box, the origin, the edges and which values are finite -- not on the values, the batch
+// or the call: every fp64 sum is a fixed expression tree, so the bits repeat.
+namespace {
+
+constexpr int MAXK = SC_CRADIAL_MAX_BINS;
+// Bands of 4 rows and one spare item per 512 pixels: a plume mask has a few hundred boxes, and a wave's step is a chain of a
+// load, a search and a few butterflies -- many short waves hide that latency, few long ones do not.  The bound of the plan holds
+// for any floor and any spare count: sum_k ceil(h_k / bh) <= counts[n] + extra with bh >= ceil(sum of heights / extra).
+constexpr int RAD_BAND_ROWS = 4;
+constexpr int RAD_EXTRA_PX = 512;
+inline long long rad_extra_items(int H, int W) { return ((long long)H * W + RAD_EXTRA_PX - 1) / RAD_EXTRA_PX; }
+
+struct RadRec { long long d2_max, sum_rr, sum_cc, sum_rc; };
+struct BinRec { long long n; double s; };
+__host__ __device__ inline size_t rad_item_bytes(int K) { return sizeof(RadRec) + (size_t)(K + 1) * sizeof(BinRec); }
+
+struct RadP {
+  const int* labels; const int* counts;
+  int N, H, W, M, K, cap;
+  const int* row_min; const int* row_max; const int* col_min; const int* col_max; const int* origin;
+  const float* plane; long long plane_stride;
+  int edge2[MAXK];
+  long long* bin_count; double* bin_sum; long long* d2_max; long long* sum_rr; long long* sum_cc; long long* sum_rc;
+  const int* off; const int* bandh; unsigned char* items;
+};
+
+__device__ __forceinline__ int n_components(const RadP& p, int n) { return min(max(p.counts[n], 0), p.M); }
+// items of image n: what the plan counted, inside the slots there are whatever boxes the caller passed
+__device__ __forceinline__ int n_items(const RadP& p, int n, int cnt) { return min(max(p.off[(size_t)n * (p.M + 1) + cnt], 0), p.cap); }
+
+__global__ __launch_bounds__(256) void k_cr_walk(const RadP p) {
+  __shared__ int s_edge[MAXK];
+  __shared__ double s_sum[4][MAXK + 1];
+  __shared__ long long s_cnt[4][MAXK + 1];
+  const int n = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+  const int w = blockIdx.x * 4 + wv;                              // item of this wave; no wave leaves before the last barrier
+  const int K = p.K, W = p.W;
+  if ((int)threadIdx.x < K) s_edge[threadIdx.x] = p.edge2[threadIdx.x];
+  for (int j = lane; j <= K; j += 64) { s_sum[wv][j] = 0.0; s_cnt[wv][j] = 0; }
+  __syncthreads();
+  const int cnt = n_components(p, n);
+  const int* off = p.off + (size_t)n * (p.M + 1);
+  const bool live = w < n_items(p, n, cnt);
+  int k = 0;
+  if (live) {
+    int lo = 0, hi = cnt - 1;                                     // the last k with off[k] <= w, as k_cs_walk finds it
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if (off[mid] <= w) lo = mid; else hi = mid - 1;
+    }
+    k = lo;
+  }
+  const size_t row = (size_t)n * p.M + k;
+  const int bh = p.bandh[n];
+  const long long o_r = p.origin[2 * row], o_c = p.origin[2 * row + 1];
+  // the box, cut to the image: a box that is not the component's own gives other numbers, never another address
+  const int c0 = max(p.col_min[row], 0), c1 = min(p.col_max[row], W - 1);
+  long long r0 = p.row_min[row] + (long long)(w - off[k]) * bh;
+  long long r1 = min(min((long long)p.row_max[row] + 1, r0 + bh), (long long)p.H);
+  r0 = max(r0, 0ll);
+  if (!live || o_r < 0) r1 = r0;                                  // a skipped plume leaves a record of zeros
+  const int bw = c1 - c0 + 1;
+  int sh = 6;
+  while (sh > 0 && (1 << (sh - 1)) >= bw) --sh;
+  const int pw = 1 << sh, rows_per_step = 64 >> sh;
+  const int* L = p.labels + (size_t)n * p.H * W;
+  const float* plane = p.plane + (long long)n * p.plane_stride;
+  const int lab = k + 1;
+
+  long long d2m = -1, srr = 0, scc = 0, src = 0;
+  for (long long rb = r0; rb < r1; rb += rows_per_step) {          // both loops run the same number of times in every lane
+    for (long long cb = c0; cb <= c1; cb += pw) {
+      const long long r = rb + (lane >> sh), c = cb + (lane & (pw - 1));
+      int bin = -1;
+      float v = 0.f;
+      if (r < r1 && c <= c1) {
+        const int i = (int)(r * W + c);
+        const int li = L[i];
+        v = plane[i];                                             // with the label, not after it: one load latency per step
+        if (li == lab) {
+          const long long dr = r - o_r, dc = c - o_c, d2 = dr * dr + dc * dc;
+          d2m = d2 > d2m ? d2 : d2m;
+          srr += r * r; scc += c * c; src += r * c;
+          if (finite_f(v)) {
+            int lo = 0, hi = K;                                   // the smallest j with d2 <= edge2[j]; K beyond the last edge
+            while (lo < hi) {
+              const int mid = (lo + hi) >> 1;
+              if (d2 > (long long)s_edge[mid]) lo = mid + 1; else hi = mid;
+            }
+            bin = lo;
+          }
+        }
+      }
+      unsigned long long rem = __ballot(bin >= 0);
+      while (rem) {                                               // one round per distinct bin of the step, by first lane
+        const int b = __shfl(bin, __ffsll((long long)rem) - 1, 64);
+        const bool sel = bin == b;
+        const unsigned long long m = __ballot(sel);
+        const double s = wave_sum_d(sel ? (double)v : 0.0);
+        if (lane == 0) { s_sum[wv][b] += s; s_cnt[wv][b] += __popcll(m); }
+        rem &= ~m;
+      }
+    }
+  }
+  srr = wave_sum_ll(srr); scc = wave_sum_ll(scc); src = wave_sum_ll(src);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const long long od = __shfl_xor(d2m, o, 64);
+    d2m = od > d2m ? od : d2m;
+  }
+  __syncthreads();                                                // lane 0's sums, before the other lanes read them
+  if (!live) return;
+  unsigned char* rec = p.items + ((size_t)n * p.cap + w) * rad_item_bytes(K);
+  if (lane == 0) {
+    RadRec* it = reinterpret_cast<RadRec*>(rec);
+    it->d2_max = d2m; it->sum_rr = srr; it->sum_cc = scc; it->sum_rc = src;
+  }
+  BinRec* br = reinterpret_cast<BinRec*>(rec + sizeof(RadRec));
+  for (int j = lane; j <= K; j += 64) { br[j].n = s_cnt[wv][j]; br[j].s = s_sum[wv][j]; }
+}
+
+__global__ __launch_bounds__(256) void k_cr_combine(const RadP p) {
+  const int n = blockIdx.y, K1 = p.K + 1;
+  const long long t = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (t >= (long long)p.M * K1) return;
+  const int m = (int)(t / K1), j = (int)(t - (long long)m * K1);
+  const size_t row = (size_t)n * p.M + m;
+  const int cnt = n_components(p, n);
+  int i0 = 0, i1 = 0;
+  if (m < cnt) {
+    const int* off = p.off + (size_t)n * (p.M + 1);
+    const int tot = n_items(p, n, cnt);
+    i0 = min(max(off[m], 0), tot); i1 = min(max(off[m + 1], i0), tot);
+  }
+  const size_t ib = rad_item_bytes(p.K);
+  const unsigned char* base = p.items + (size_t)n * p.cap * ib;
+  long long c = 0; double s = 0.0;
+  for (int i = i0; i < i1; ++i) {                                 // band order
+    const BinRec* br = reinterpret_cast<const BinRec*>(base + (size_t)i * ib + sizeof(RadRec)) + j;
+    c += br->n; s += br->s;
+  }
+  p.bin_count[row * K1 + j] = c; p.bin_sum[row * K1 + j] = s;
+  if (j != 0) return;
+  long long d2m = -1, srr = 0, scc = 0, src = 0;
+  for (int i = i0; i < i1; ++i) {
+    const RadRec* it = reinterpret_cast<const RadRec*>(base + (size_t)i * ib);
+    d2m = it->d2_max > d2m ? it->d2_max : d2m; srr += it->sum_rr; scc += it->sum_cc; src += it->sum_rc;
+  }
+  p.d2_max[row] = d2m; p.sum_rr[row] = srr; p.sum_cc[row] = scc; p.sum_rc[row] = src;
+}
+
+bool rad_dims_ok(int N, int H, int W, int M) {
+  return dims_ok(N, H, W, M, 0) && H <= SC_CRADIAL_MAX_SIDE && W <= SC_CRADIAL_MAX_SIDE && (long long)M * (MAXK + 1) < (1ll << 31) &&
+         M + rad_extra_items(H, W) < (1ll << 31);
+}
+size_t rad_work_bytes_of(int N, int H, int W, int M, int K) {
+  return off_bytes(N, M) + align256((size_t)N * 4) + align256((size_t)N * (size_t)(M + rad_extra_items(H, W)) * rad_item_bytes(K));
+}
+
+}  // namespace
+
+extern "C" size_t sc_component_radial_workspace_bytes(int N, int H, int W, int M, int K) {
+  if (!rad_dims_ok(N, H, W, M) || K < 1 || K > MAXK) return 0;
+  return rad_work_bytes_of(N, H, W, M, K);
+}
+
+extern "C" int sc_component_radial(const sc_cradial_args* a, void* work, size_t work_bytes, sc_stream stream) {
+  SC_REQUIRE(a, "sc_component_radial: null arguments");
+  SC_REQUIRE(rad_dims_ok(a->N, a->H, a->W, a->M),
+             "sc_component_radial: bad dims N=%d H=%d W=%d M=%d (N <= 65535, H, W <= %d, H*W < 2^31, N*(M+1) < 2^31, M*%d < 2^31)",
+             a->N, a->H, a->W, a->M, SC_CRADIAL_MAX_SIDE, MAXK + 1);
+  SC_REQUIRE(a->K >= 1 && a->K <= MAXK, "sc_component_radial: K=%d bin edges (1 .. %d)", a->K, MAXK);
+  SC_REQUIRE(a->edge2[0] >= 0, "sc_component_radial: edge2[0] = %d is negative", a->edge2[0]);
+  for (int j = 1; j < a->K; ++j)
+    SC_REQUIRE(a->edge2[j] > a->edge2[j - 1], "sc_component_radial: edge2 must increase strictly: edge2[%d] = %d, edge2[%d] = %d",
+               j - 1, a->edge2[j - 1], j, a->edge2[j]);
+  SC_REQUIRE(a->labels && a->counts, "sc_component_radial: null labels or counts");
+  SC_REQUIRE(a->plane, "sc_component_radial: null plane");
+  SC_REQUIRE(a->N == 1 || a->plane_stride >= (long long)a->H * a->W, "sc_component_radial: plane stride %lld overlaps %d x %d images",
+             (long long)a->plane_stride, a->H, a->W);
+  if (a->M == 0) return SC_OK;                                    // no rows to write
+  SC_REQUIRE(a->row_min && a->row_max && a->col_min && a->col_max && a->origin, "sc_component_radial: null box column or origin");
+  SC_REQUIRE(a->bin_count && a->bin_sum && a->d2_max && a->sum_rr && a->sum_cc && a->sum_rc, "sc_component_radial: null output column");
+  SC_REQUIRE(work && work_bytes >= rad_work_bytes_of(a->N, a->H, a->W, a->M, a->K), "sc_component_radial: workspace %zu < %zu bytes",
+             work_bytes, rad_work_bytes_of(a->N, a->H, a->W, a->M, a->K));
+  hipStream_t st = (hipStream_t)stream;
+  char* wp = static_cast<char*>(work);
+  StatsP sp{};                                                    // what k_cs_plan reads: the boxes, and where its plan goes
+  sp.counts = a->counts; sp.N = a->N; sp.H = a->H; sp.W = a->W; sp.M = a->M;
+  sp.extra = rad_extra_items(a->H, a->W); sp.cap = (int)(a->M + sp.extra); sp.min_band = RAD_BAND_ROWS;
+  sp.row_min = const_cast<int*>(a->row_min); sp.row_max = const_cast<int*>(a->row_max);
+  sp.off = reinterpret_cast<int*>(wp);
+  sp.bandh = reinterpret_cast<int*>(wp + off_bytes(a->N, a->M));
+  RadP p{};
+  p.labels = a->labels; p.counts = a->counts;
+  p.N = a->N; p.H = a->H; p.W = a->W; p.M = a->M; p.K = a->K; p.cap = sp.cap;
+  p.row_min = a->row_min; p.row_max = a->row_max; p.col_min = a->col_min; p.col_max = a->col_max; p.origin = a->origin;
+  p.plane = a->plane; p.plane_stride = a->plane_stride;
+  for (int j = 0; j < a->K; ++j) p.edge2[j] = a->edge2[j];
+  p.bin_count = (long long*)a->bin_count; p.bin_sum = a->bin_sum; p.d2_max = (long long*)a->d2_max;
+  p.sum_rr = (long long*)a->sum_rr; p.sum_cc = (long long*)a->sum_cc; p.sum_rc = (long long*)a->sum_rc;
+  p.off = sp.off; p.bandh = sp.bandh;
+  p.items = reinterpret_cast<unsigned char*>(wp + off_bytes(a->N, a->M) + align256((size_t)a->N * 4));
+  hipLaunchKernelGGL(k_cs_plan, dim3(a->N), dim3(256), 0, st, sp);
+  SC_LAUNCH_OK("k_cs_plan");
+  hipLaunchKernelGGL(k_cr_walk, dim3((unsigned)((p.cap + 3) / 4), a->N), dim3(256), 0, st, p);
+  SC_LAUNCH_OK("k_cr_walk");
+  const long long cells = (long long)a->M * (a->K + 1);
+  hipLaunchKernelGGL(k_cr_combine, dim3((unsigned)((cells + 255) / 256), a->N), dim3(256), 0, st, p);
+  SC_LAUNCH_OK("k_cr_combine");
   return SC_OK;
 }

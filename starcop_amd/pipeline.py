@@ -235,7 +235,7 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
                          out_folder=None, geotransform=None, overwrite=False, plumes=False, plume_outlines=False,
                          label_polygons=None, cog=False, crs=None, resolution=None, resampling="nearest", label_crs=None,
                          mask_resampling="nearest", clean=None, match_tolerance_px=0.0,
-                         plume_background=None):
+                         plume_background=None, plume_quantify=None):
     """The notebook path of the reference end to end FROM THE FILE (notebooks/inference_on_raw_EMIT_nc_file.ipynb cells 8-19:
     ``EMITImage(path)`` -> ``mag1c_emit`` -> RGB bands -> rescale -> ``model`` -> threshold): opens the EMIT L1B radiance granule
     (NetCDF-4) with :mod:`starcop_amd.hdf5_reader`, reads ONLY what the pipeline touches -- the contiguous band slice inside
@@ -286,11 +286,14 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
     ``min_area``, ``exclude``, ``exclude_buffer_px``, ``connectivity`` -- applied to ``pred_binary`` on the product grid (after the
     regrid) and before the annotations and the files, which then all describe the cleaned mask; ``out["clean"]`` has the pixel
     counts.  ``match_tolerance_px``: the ``tolerance_px`` of the match against ``label_polygons``.  ``plume_background``
-    (``{"ring_px": .., "gap_px": ..}``) adds the background-ring columns of ``plumes.plume_table`` to the plume table.  The defaults add
-    nothing."""
+    (``{"ring_px": .., "gap_px": ..}``) adds the background-ring columns of ``plumes.plume_table`` to the plume table.
+    ``plume_quantify`` (the ``quantify=`` dict of ``plumes.plume_table``: ``wind_speed_m_s``, ...) adds its shape, mass and
+    emission-rate columns to the plume table, ``plumes.csv`` and the GeoJSON properties; it needs mag1c and a metric grid
+    (``crs="utm"``: on the granule's longitude / latitude grid it is a ValueError).  The defaults add nothing."""
     from .hdf5_reader import H5File
     products.check_clean(clean, "emit_granule_predict")
     products.check_plume_background(plume_background, "emit_granule_predict")
+    products.check_plume_quantify(plume_quantify, "emit_granule_predict")
     if clean is not None and not georeferenced:
         raise ValueError("emit_granule_predict: clean works on the orthorectified products; pass georeferenced=True")
     if crs is not None and not georeferenced:
@@ -369,7 +372,7 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
     if clean is not None:
         products.clean(out, **clean)
     products.annotate(out, out["pred_binary"], mf, prob, gt if georeferenced else None, area, plumes, plume_outlines, label_polygons,
-                      match_tolerance_px, plume_background)
+                      match_tolerance_px, plume_background, plume_quantify)
     if out_folder is not None:
         from .ortho import emit_geo_tags
         if geo is None:
@@ -461,7 +464,7 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
                          normalize_by_acquisition_date=True, tile=None, halo=None, batch=None, plumes=False, overwrite=False,
                          device="cuda", plume_outlines=False, label_polygons=None, cog=False, north_up=False, resolution=None,
                          resampling="nearest", mask_resampling="nearest", clean=None, match_tolerance_px=0.0,
-                         plume_background=None):
+                         plume_background=None, plume_quantify=None):
     """An orthorectified AVIRIS-NG flight line through the plume model, file to file: ``{folder}/{name}_img`` (ENVI radiance,
     float32) -> the network's input products -> ``model.predict_scene`` -> (with ``out_folder``) ``pred.tif`` / ``predbinary.tif``.
 
@@ -508,8 +511,10 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
     files: ``predbinary.tif``, ``plumes.csv``, ``plumes.geojson`` and ``plume_match`` describe the cleaned mask, ``pred.tif`` is
     untouched, ``out["clean"]`` has the pixel counts.  ``match_tolerance_px``: the ``tolerance_px`` of the match against
     ``label_polygons``.  ``plume_background``
-    (``{"ring_px": .., "gap_px": ..}``) adds the background-ring columns of ``plumes.plume_table`` to the plume table.  The defaults add
-    nothing and change no byte."""
+    (``{"ring_px": .., "gap_px": ..}``) adds the background-ring columns of ``plumes.plume_table`` to the plume table.
+    ``plume_quantify`` (the ``quantify=`` dict of ``plumes.plume_table``: ``wind_speed_m_s``, ...) adds its shape, mass and
+    emission-rate columns to the plume table, ``plumes.csv`` and the GeoJSON properties; it needs mag1c and a metric grid
+    (a UTM ``map info``).  The defaults add nothing and change no byte."""
     import datetime
     import os
     import re
@@ -520,6 +525,7 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
         raise ValueError("aviris_scene_predict: plume_outlines=True needs plumes=True")
     products.check_clean(clean, "aviris_scene_predict")
     products.check_plume_background(plume_background, "aviris_scene_predict")
+    products.check_plume_quantify(plume_quantify, "aviris_scene_predict")
     if not north_up and (resolution is not None or resampling != "nearest" or mask_resampling != "nearest"):
         raise ValueError("aviris_scene_predict: resolution, resampling and mask_resampling regrid the products; pass north_up=True")
     inputs = aviris_scene_products(model.input_products, normalize_by_acquisition_date)
@@ -604,7 +610,7 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
     if clean is not None:
         products.clean(out, **clean)
     products.annotate(out, out["pred_binary"], mf, out["prediction"], gt, area, plumes, plume_outlines, label_polygons, match_tolerance_px,
-                      plume_background)
+                      plume_background, plume_quantify)
     if out_folder is not None:
         files += products.write_rasters(out, products.AVIRIS_RASTERS, str(out_folder), overwrite, geo, mag1c.NODATA, cog=cog)
         out["files"] = files + products.write_annotations(out, str(out_folder), overwrite, geo, cog)
@@ -614,7 +620,7 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
 @torch.no_grad()
 def mosaic_products(folders, out_folder, crs=None, resolution=None, rule="max", plumes=False, plume_outlines=False, label_polygons=None,
                     cog=False, overwrite=False, device="cuda", clean=None, match_tolerance_px=0.0,
-                    plume_background=None):
+                    plume_background=None, plume_quantify=None):
     """The product folders of N scenes -- what ``emit_granule_predict`` / ``aviris_scene_predict`` write -- composed into one:
     ``pred.tif``, ``predbinary.tif`` and, where every folder has one, ``mag1c.tif`` are read (``io_formats.read_tiff``; grid and
     CRS from the GeoTIFF tags, a file without them raises ValueError), put on the union grid of the scenes in ``crs`` (default:
@@ -625,7 +631,10 @@ def mosaic_products(folders, out_folder, crs=None, resolution=None, rule="max", 
     rasters is each file's GDAL_NODATA of the first folder (default -9999).  ``clean`` (a dict of :func:`starcop_amd.products.clean`
     keyword arguments) cleans the mosaicked mask before the annotations and the files; ``match_tolerance_px`` is the
     ``tolerance_px`` of the match against ``label_polygons``; ``plume_background`` (``{"ring_px": .., "gap_px": ..}``) adds the
-    background-ring columns of ``plumes.plume_table`` and needs the ``mf`` product among the folders'.  -> the dict of ``products.mosaic`` with ``files``."""
+    background-ring columns of ``plumes.plume_table`` and needs the ``mf`` product among the folders';
+    ``plume_quantify`` (the ``quantify=`` dict of ``plumes.plume_table``: ``wind_speed_m_s``, ...) adds its shape, mass and
+    emission-rate columns to the plume table, ``plumes.csv`` and the GeoJSON properties; it needs mag1c and a metric grid
+    (a UTM ``crs``).  -> the dict of ``products.mosaic`` with ``files``."""
     import os
     from . import io_formats as io
     from . import warp
@@ -634,6 +643,7 @@ def mosaic_products(folders, out_folder, crs=None, resolution=None, rule="max", 
         raise ValueError("mosaic_products: plume_outlines=True needs plumes=True")
     products.check_clean(clean, "mosaic_products")
     products.check_plume_background(plume_background, "mosaic_products")
+    products.check_plume_quantify(plume_quantify, "mosaic_products")
     folders = [str(f).rstrip("/") for f in folders]
     for path in folders + [out_folder]:
         if str(path).startswith("gs://"):
@@ -672,7 +682,7 @@ def mosaic_products(folders, out_folder, crs=None, resolution=None, rule="max", 
     if clean is not None:
         products.clean(out, **clean)
     products.annotate(out, out["pred_binary"], out.get("mf"), out["prediction"], gt, area, plumes, plume_outlines, label_polygons,
-                      match_tolerance_px, plume_background)
+                      match_tolerance_px, plume_background, plume_quantify)
     geo = warp.geo_tags(gt, epsg)
     out_folder = str(out_folder)
     files = []

@@ -4,7 +4,9 @@
 ``plume_table`` labels a mask (``mask_creation.connected_components``), reduces mag1c / probability / a second mask per
 component in one call and returns one pandas row per plume; ``match_plumes`` counts detected, spurious and missed plumes between
 a predicted and a labelled mask; ``component_outlines`` traces the polygon rings of every component (sc_component_outlines),
-``plume_outlines`` turns a mask into closed (x, y) rings per plume; ``write_plumes`` writes a table as CSV or GeoJSON (Points, or
+``plume_outlines`` turns a mask into closed (x, y) rings per plume; ``component_radial`` (sc_component_radial) gives the radial
+profile, extent and second moments of every component, from which ``plume_table(quantify=...)`` / ``fetch_profiles`` derive shape,
+mass and emission rates (starcop_amd/quantify.py); ``write_plumes`` writes a table as CSV or GeoJSON (Points, or
 Polygons with the outlines).  The other way: ``read_plumes`` reads such a GeoJSON back, ``rasterize_polygons`` burns polygons
 into a label image on the raster grid (sc_rasterize_polygons), ``match_plumes_polygons`` scores a mask against polygons.
 """
@@ -104,15 +106,134 @@ def _operands(planes, other):
     return ops, oth
 
 
+RADIAL_FIELDS = ("bin_count", "bin_sum", "d2_max", "sum_rr", "sum_cc", "sum_rc")
+MAX_RADII = _lib.CRADIAL_MAX_BINS
+
+
+def origins_from_argmax(stats, width, plane=0):
+    """The origin of every plume at the first maximum of one plane: the ``argmax`` column of a ``component_stats`` dict (the raster
+    index r * width + c) -> device int32 (N, M, 2) of (row, col), (-1, -1) where ``argmax`` is -1 (no finite value, or no such
+    component), which ``component_radial`` skips.  Device arithmetic only: nothing is read back."""
+    am = stats["argmax"]
+    if am.dim() != 3 or not 0 <= int(plane) < am.shape[-1]:
+        raise ValueError(f"origins_from_argmax: plane {plane!r} of an argmax column of shape {tuple(am.shape)}")
+    width = int(width)
+    if width <= 0:
+        raise ValueError(f"origins_from_argmax: width {width!r}")
+    am = am[..., int(plane)]
+    ok = am >= 0
+    row = torch.where(ok, torch.div(am, width, rounding_mode="floor"), -1)
+    col = torch.where(ok, am - torch.div(am, width, rounding_mode="floor") * width, -1)
+    return torch.stack([row, col], -1).to(torch.int32)
+
+
+def component_radial(labels, counts, stats, origins, radii_px, plane, M=None):
+    """Radial profile, extent and second moments of every component in one ``sc_component_radial`` call.
+
+    ``labels``, ``counts``, ``M`` as ``component_stats`` takes them; ``stats``: the dict that call returned for the same labels (its
+    ``row_min`` .. ``col_max`` columns are the boxes that are walked; they are not recomputed); ``origins``: device int32 (N, M, 2)
+    of (row, col), a negative row skips the plume (``origins_from_argmax``); ``plane``: one float32 tensor of the shape of
+    ``labels``, read in place where its H x W planes are dense.  ``radii_px``: 1 to 64 positive radii in pixels; the squared bin
+    edges are ``edge2[j] = floor(radii_px[j]^2)`` in float64 with no epsilon (as ``morphology.dilate`` and ``background_rings`` take
+    a radius), which must increase strictly and stay below 2^31 - 2: a ValueError otherwise, before the device is used.
+
+    With ``d2 = (r - r0)^2 + (c - c0)^2`` of a pixel from its component's origin, in integers, returns a dict of device tensors:
+    ``bin_count`` (int64) and ``bin_sum`` (float64), (N, M, K+1), over the component's pixels with a finite plane value -- bin j is the
+    smallest j with ``d2 <= edge2[j]``, bin K lies beyond the last edge; ``d2_max`` (int64, (N, M)), over all its pixels, -1 for a
+    component without pixels or a skipped one; ``sum_rr``, ``sum_cc``, ``sum_rc`` (int64, (N, M)), the sums of r^2, c^2 and r c over all
+    its pixels.  Rows at or above counts[n], rows without pixels and skipped rows are zero.  Repeated calls, and an image alone or
+    in a batch, give identical bits."""
+    from .quantify import squared_edges
+    who = "component_radial"
+    edges = squared_edges(radii_px, who, _lib.EDT_FAR - 1)
+    if not isinstance(labels, torch.Tensor) or not isinstance(plane, torch.Tensor) or not isinstance(origins, torch.Tensor):
+        raise ValueError(f"{who}: labels, origins and plane must be device tensors (plume_table takes numpy masks)")
+    lab = _as_batch(labels, f"{who}: labels")
+    N, H, W = lab.shape
+    pl = _as_batch(plane, f"{who}: plane")
+    if tuple(pl.shape) != (N, H, W):
+        raise ValueError(f"{who}: plane has shape {tuple(pl.shape)}, labels {(N, H, W)}")
+    if H > _lib.CRADIAL_MAX_SIDE or W > _lib.CRADIAL_MAX_SIDE:
+        raise ValueError(f"{who}: image of {H} x {W}; a side may have at most {_lib.CRADIAL_MAX_SIDE} pixels")
+    if isinstance(counts, int):
+        counts = torch.tensor([counts], dtype=torch.int32, device=lab.device)
+    counts = counts.reshape(-1)
+    if counts.numel() != N:
+        raise ValueError(f"{who}: {counts.numel()} counts for {N} images")
+    boxes = [stats[f] for f in ("row_min", "row_max", "col_min", "col_max")]
+    if M is None:
+        M = boxes[0].shape[-1]
+    M, K = int(M), len(edges)
+    for f, t in zip(("row_min", "row_max", "col_min", "col_max"), boxes):
+        if tuple(t.shape) != (N, M) or t.dtype != torch.int32:
+            raise ValueError(f"{who}: stats[{f!r}] is {t.dtype} {tuple(t.shape)}, expected int32 {(N, M)}")
+    if tuple(origins.shape) != (N, M, 2) or origins.dtype != torch.int32:
+        raise ValueError(f"{who}: origins is {origins.dtype} {tuple(origins.shape)}, expected int32 {(N, M, 2)}")
+    for t in [lab, pl, origins] + boxes:
+        if not t.is_cuda:
+            raise ValueError(f"{who}: labels, stats, origins and plane must be device tensors, got one on {t.device}")
+    _lib.require_device(lab)
+    lib = _lib.load()
+    if lab.dtype != torch.int32:
+        lab = lab.to(torch.int32)
+    lab = lab.contiguous()
+    counts = counts.to(device=lab.device, dtype=torch.int32).contiguous()
+    boxes = [t.contiguous() for t in boxes]
+    origins = origins.contiguous()
+    (op, stride), = _operands([pl], None)[0]          # holds the tensor the pointer belongs to until the call is enqueued
+    a = _lib.sc_cradial_args()
+    a.labels, a.counts, a.N, a.H, a.W, a.M, a.K = lab.data_ptr(), counts.data_ptr(), N, H, W, M, K
+    a.row_min, a.row_max, a.col_min, a.col_max = (t.data_ptr() if t.numel() else None for t in boxes)
+    a.origin = origins.data_ptr() if origins.numel() else None
+    a.plane, a.plane_stride = op.data_ptr(), stride
+    for j, e in enumerate(edges):
+        a.edge2[j] = e
+    out = {"bin_count": torch.empty((N, M, K + 1), dtype=torch.int64, device=lab.device),
+           "bin_sum": torch.empty((N, M, K + 1), dtype=torch.float64, device=lab.device)}
+    for f in RADIAL_FIELDS[2:]:
+        out[f] = torch.empty((N, M), dtype=torch.int64, device=lab.device)
+    for f, t in out.items():
+        setattr(a, f, t.data_ptr() if t.numel() else None)
+    wb = lib.sc_component_radial_workspace_bytes(N, H, W, M, K)         # 0 for bad dims: the call then raises with the message
+    work = torch.empty(max(wb, 1), dtype=torch.uint8, device=lab.device)
+    check(lib.sc_component_radial(a, ptr(work), wb, stream()))
+    return out
+
+
+def _read_back_radial(rad, origins):
+    """every column of a ``component_radial`` dict and the origins in ONE device-to-host copy -> numpy arrays (``origin`` added)"""
+    N, M = rad["d2_max"].shape
+    if M == 0:
+        K1 = rad["bin_count"].shape[-1]
+        out = {f: np.zeros((N, 0), dtype=np.int64) for f in RADIAL_FIELDS[2:]}
+        out.update(bin_count=np.zeros((N, 0, K1), np.int64), bin_sum=np.zeros((N, 0, K1), np.float64), origin=np.zeros((N, 0, 2), np.int64))
+        return out
+    tensors = [(f, rad[f]) for f in RADIAL_FIELDS] + [("origin", origins)]
+    flat = torch.cat([(t.view(torch.int64) if t.dtype == torch.float64 else t.to(torch.int64)).reshape(N, -1) for _, t in tensors], 1)
+    flat = flat.cpu().numpy()
+    out, at = {}, 0
+    for f, t in tensors:
+        n = int(np.prod(t.shape[1:]))
+        a = np.ascontiguousarray(flat[:, at:at + n])
+        at += n
+        out[f] = (a.view(np.float64) if t.dtype == torch.float64 else a).reshape(tuple(t.shape))
+    return out
+
+
 def table_from_stats(stats, counts, width, plane_names=(), with_other=False, min_area=1, geotransform=None, pixel_area_m2=None,
-                     ring_stats=None):
+                     ring_stats=None, quantify=None):
     """The DataFrame of ``plume_table`` from host copies of the ``component_stats`` columns (numpy, (N, M) and (N, M, P)),
     ``counts`` (N,) and the image width (for the row / column of ``argmax``).  ``plane_names``: which of ``"mag1c"``, ``"prob"``
     the P planes are, in order.  ``ring_stats``: the same columns reduced over the background-ring labels (``background_rings``)
-    with mag1c as plane 0, for the ring columns of ``plume_table``; it needs ``"mag1c"`` among the planes.  No device involved."""
+    with mag1c as plane 0, for the ring columns of ``plume_table``; it needs ``"mag1c"`` among the planes.  ``quantify``: for the
+    quantification columns of ``plume_table``, a dict with ``settings`` (the checked ``quantify=`` dict), ``radii_m``,
+    ``pixel_size_m`` and ``radial`` (host copies of the ``component_radial`` columns and ``origin``, (N, M, ..)); the per-plume
+    curves of ``fetch_profiles`` are left under its key ``curves``.  It needs mag1c as well.  No device involved."""
     import pandas as pd
     if ring_stats is not None and "mag1c" not in plane_names:
         raise ValueError("table_from_stats: ring_stats needs the mag1c plane")
+    if quantify is not None and "mag1c" not in plane_names:
+        raise ValueError("table_from_stats: quantify needs the mag1c plane")
     counts = np.asarray(counts).reshape(-1)
     area = np.asarray(stats["area"])
     N, M = area.shape
@@ -158,6 +279,21 @@ def table_from_stats(stats, counts, width, plane_names=(), with_other=False, min
             raise NotImplementedError(f"plume_table: rotated geotransform (terms {gt[2]}, {gt[4]}) is not supported")
         cols["x"] = gt[0] + (cols["centroid_col"] + 0.5) * gt[1]
         cols["y"] = gt[3] + (cols["centroid_row"] + 0.5) * gt[5]
+    if quantify is not None:
+        from .quantify import quantify_columns
+        q = list(plane_names).index("mag1c")
+        settings, rad = quantify["settings"], quantify["radial"]
+        wind = np.asarray(settings["wind_speed_m_s"], dtype=np.float64)
+        if wind.ndim:                                 # one per plume, in the order of the rows before the min_area filter
+            rank = np.concatenate([[0], np.cumsum(np.minimum(np.maximum(counts, 0), M))])[item] + k
+            wind = wind.reshape(-1)[rank]
+        qcols, curves = quantify_columns(
+            settings, quantify["radii_m"], quantify["pixel_size_m"], area[item, k], np.asarray(stats["sum_row"])[item, k],
+            np.asarray(stats["sum_col"])[item, k], cols["mag1c_sum"], np.asarray(stats["n_finite"])[item, k, q],
+            {f: np.asarray(v)[item, k] for f, v in rad.items()}, cols["mag1c_bg_mean"] if ring_stats is not None else None,
+            wind if wind.ndim else None)
+        cols.update(qcols)
+        quantify["curves"] = curves
     return pd.DataFrame(cols)
 
 
@@ -205,7 +341,7 @@ def background_rings(labels, ring_px, gap_px=0.0):
 
 
 def plume_table(mask, mag1c=None, prob=None, label_mask=None, connectivity=2, min_area=1, geotransform=None, pixel_area_m2=None,
-                background_ring_px=None, background_gap_px=0.0):
+                background_ring_px=None, background_gap_px=0.0, quantify=None):
     """One row per plume of ``mask != 0``: an (H, W) or (N, H, W) mask, numpy or device.  Labels the mask on the device
     (``connectivity`` 1 or 2 as ``connected_components``), reduces every component in one ``sc_component_stats`` call and reads
     the rows back once.  Components of fewer than ``min_area`` pixels are dropped.  Columns:
@@ -214,14 +350,101 @@ def plume_table(mask, mag1c=None, prob=None, label_mask=None, connectivity=2, mi
     ``col_max`` (inclusive), ``centroid_row``, ``centroid_col`` (float64 means of the pixel indices);
     with ``mag1c``: ``mag1c_sum``, ``mag1c_mean``, ``mag1c_max`` over the component's finite pixels, ``mag1c_max_row`` /
     ``mag1c_max_col`` of the first maximum in raster order, and with ``pixel_area_m2`` the integrated enhancement
-    ``ime_ppmm_m2 = mag1c_sum * pixel_area_m2`` (ppm m x m2; turning it into a mass needs a constant the caller supplies);
+    ``ime_ppmm_m2 = mag1c_sum * pixel_area_m2`` (ppm m x m2; ``quantify`` below turns it into a mass and emission rates);
     with ``prob``: ``prob_mean``, ``prob_max``;  with ``label_mask``: ``overlap_px``, the component's pixels inside it;
     with ``geotransform`` (GDAL 6-tuple, north up): ``x``, ``y`` of the centroid, pixel centres at +0.5;
     with ``background_ring_px`` (needs ``mag1c``): the local background of every plume, taken over its ring of
     ``background_rings(labels, background_ring_px, background_gap_px)`` in one more ``component_stats`` call: ``bg_px`` (ring pixels
     with finite mag1c), ``mag1c_bg_mean`` (NaN when ``bg_px`` is 0), ``mag1c_sum_bgsub = mag1c_sum - mag1c_bg_mean * n`` with n the
-    plume's finite pixels, and with ``pixel_area_m2`` ``ime_bgsub_ppmm_m2``.  None leaves the table as it is without."""
+    plume's finite pixels, and with ``pixel_area_m2`` ``ime_bgsub_ppmm_m2``.  None leaves the table as it is without.
+
+    ``quantify`` (needs ``mag1c`` and ``pixel_area_m2``, square pixels of ``pixel_size_m = sqrt(pixel_area_m2)``; a geotransform
+    with ``|gt1| != |gt5|`` is a ValueError) adds shape, mass and emission rates from one ``component_radial`` call, read back in
+    one more copy.  A dict with the keys (anything else is a ValueError):
+    ``wind_speed_m_s`` (required): the EFFECTIVE wind speed, used as given -- a number, or one per plume; no U10 model is applied;
+    ``radii_m`` (up to 64 increasing radii) or ``max_fetch_m`` (default 150 m, the AVIRIS-NG survey's choice): without ``radii_m`` the
+    circles are ``r_j = j * pixel_size_m`` for j = 1 .. min(64, floor(max_fetch_m / pixel_size_m)); no radius at all is a ValueError;
+    ``origin``: ``"max"`` (default), the plume's first mag1c maximum (``mag1c_max_row`` / ``mag1c_max_col``), or an (R, 2) array of
+    (row, col) -- floats are floored -- or, with ``origin_xy=True`` and a geotransform, of (x, y); a row that is negative or not
+    finite leaves that plume without the columns that need an origin (NaN);
+    ``min_fetch_m`` (default 0), ``temperature_k`` / ``pressure_pa`` (defaults 288.15 K, 101325 Pa) or ``kg_per_ppmm_m2`` in their
+    place (``quantify.kg_per_ppmm_m2``).
+    Arrays with one entry per plume (``origin``, ``wind_speed_m_s``) are aligned with the rows the table has BEFORE the ``min_area``
+    filter, i.e. with ``min_area=1``: image after image, ``plume_id`` ascending, R = the number of components of all images.
+    Columns: ``origin_row``, ``origin_col``; ``fetch_max_m``, the distance of the farthest pixel from the origin;
+    ``major_axis_m``, ``minor_axis_m``, ``orientation_rad`` (``quantify.shape_from_moments``); ``ime_kg = mag1c_sum * pixel_area_m2 *
+    kg_per_ppmm_m2``; ``q_sqrt_area_kg_h``, ``q_fetch_kg_h``, ``q_fetch_std_kg_h``, ``q_fetch_n`` (``quantify.emission_rates`` on the
+    cumulative profile inside the circles).  With ``background_ring_px`` the profile and ``ime_kg`` are taken above
+    ``mag1c_bg_mean``, and a plume whose ``bg_px`` is 0 gets NaN rates.  None leaves columns and bytes as they are without."""
+    return _plume_table(mask, mag1c, prob, label_mask, connectivity, min_area, geotransform, pixel_area_m2, background_ring_px,
+                        background_gap_px, quantify)[0]
+
+
+def fetch_profiles(mask, mag1c, quantify, prob=None, label_mask=None, connectivity=2, min_area=1, geotransform=None,
+                   pixel_area_m2=None, background_ring_px=None, background_gap_px=0.0):
+    """``plume_table(..., quantify=quantify)`` and the curves behind its rates, for plotting -> ``(table, curves)``: ``curves`` a
+    dict with ``radii_m`` (K,) and, one row per row of the table, ``n_px`` (pixels with finite mag1c inside circle j), ``ime_kg``
+    (IME_j, above the background with ``background_ring_px``), ``q_kg_h`` (``3600 U IME_j / r_j``) and ``used`` (bool: the radii
+    that enter ``q_fetch_kg_h``), all (rows, K).  The same device work as ``plume_table``."""
+    if quantify is None:
+        raise ValueError("fetch_profiles: quantify is required (a dict with wind_speed_m_s)")
+    return _plume_table(mask, mag1c, prob, label_mask, connectivity, min_area, geotransform, pixel_area_m2, background_ring_px,
+                        background_gap_px, quantify)
+
+
+def _quantify_plan(quantify, mag1c, geotransform, pixel_area_m2):
+    """what ``plume_table`` can settle about ``quantify`` before the device is used -> None or {settings, radii_m, radii_px,
+    pixel_size_m}"""
+    from . import quantify as qf
+    settings = qf.check_quantify(quantify, "plume_table")
+    if settings is None:
+        return None
+    if mag1c is None:
+        raise ValueError("plume_table: quantify needs mag1c")
+    if pixel_area_m2 is None:
+        raise ValueError("plume_table: quantify needs pixel_area_m2, the area of a pixel on a metric grid; a longitude / latitude "
+                         "grid has none (the scene calls put their products on one with crs=\"utm\")")
+    area = float(pixel_area_m2)
+    if not area > 0.0 or not np.isfinite(area):
+        raise ValueError(f"plume_table: pixel_area_m2 {pixel_area_m2!r} must be positive and finite")
+    if geotransform is not None:
+        gt = _gt6(geotransform, "plume_table")
+        if abs(gt[1]) != abs(gt[5]):
+            raise ValueError(f"plume_table: quantify needs square pixels, the geotransform has {abs(gt[1])} x {abs(gt[5])}")
+    elif settings.get("origin_xy"):
+        raise ValueError("plume_table: origin_xy=True needs a geotransform")
+    px = float(np.sqrt(area))
+    radii_m, radii_px = qf.radii_for(settings, px)
+    qf.squared_edges(radii_px, "plume_table: quantify", _lib.EDT_FAR - 1)
+    return {"settings": settings, "radii_m": radii_m, "radii_px": radii_px, "pixel_size_m": px}
+
+
+def _origins_from_rows(settings, counts, M, geotransform):
+    """the (R, 2) ``origin`` array of a quantify dict -> host int32 (N, M, 2) of (row, col), (-1, -1) for rows to skip"""
+    o = np.asarray(settings["origin"], dtype=np.float64)
+    per = np.minimum(np.maximum(np.asarray(counts).reshape(-1), 0), M)
+    if o.shape[0] != int(per.sum()):
+        raise ValueError(f"plume_table: quantify origin has {o.shape[0]} rows, the mask {int(per.sum())} plumes (before min_area)")
+    if settings.get("origin_xy"):
+        gt = _gt6(geotransform, "plume_table")
+        with np.errstate(invalid="ignore", divide="ignore"):
+            o = np.stack([(o[:, 1] - gt[3]) / gt[5], (o[:, 0] - gt[0]) / gt[1]], 1)
+    ok = np.isfinite(o).all(1)
+    o = np.clip(np.floor(np.where(ok[:, None], o, -1.0)), -1.0, 2.0 ** 30)
+    o[o[:, 0] < 0] = -1.0
+    out = np.full((per.size, M, 2), -1, dtype=np.int32)
+    at = 0
+    for n, c in enumerate(per):
+        out[n, :c] = o[at:at + c].astype(np.int32)
+        at += c
+    return out
+
+
+def _plume_table(mask, mag1c, prob, label_mask, connectivity, min_area, geotransform, pixel_area_m2, background_ring_px,
+                 background_gap_px, quantify):
+    """``plume_table`` -> (table, the curves of ``fetch_profiles`` or None)"""
     shape = tuple(mask.shape)
+    qplan = _quantify_plan(quantify, mag1c, geotransform, pixel_area_m2)
     if background_ring_px is not None:
         if mag1c is None:
             raise ValueError("plume_table: background_ring_px needs mag1c")
@@ -243,9 +466,22 @@ def plume_table(mask, mag1c=None, prob=None, label_mask=None, connectivity=2, mi
     if background_ring_px is not None:
         lab3 = _as_batch(labels, "plume_table").contiguous()
         ring_host = _read_back(component_stats(_rings(lab3, ring2, gap2), counts, planes[:1], M=M))
+    if qplan is not None:
+        settings = qplan["settings"]
+        if np.ndim(settings["wind_speed_m_s"]) and np.size(settings["wind_speed_m_s"]) != int(np.minimum(counts_h, M).sum()):
+            raise ValueError(f"plume_table: {np.size(settings['wind_speed_m_s'])} wind speeds for {int(np.minimum(counts_h, M).sum())} "
+                             "plumes (before min_area)")
+        if isinstance(settings.get("origin", "max"), str):
+            origins = origins_from_argmax(st, shape[-1], names.index("mag1c"))
+        else:
+            origins = torch.from_numpy(_origins_from_rows(settings, counts_h, M, geotransform)).to(m.device)
+        rad = component_radial(labels, counts, st, origins, qplan["radii_px"], planes[names.index("mag1c")], M=M)
+        qplan["radial"] = _read_back_radial(rad, origins)
     counts = counts_h
     host = _read_back(st)
-    return table_from_stats(host, counts, shape[-1], names, other is not None, min_area, geotransform, pixel_area_m2, ring_host)
+    table = table_from_stats(host, counts, shape[-1], names, other is not None, min_area, geotransform, pixel_area_m2, ring_host,
+                             qplan)
+    return table, (qplan["curves"] if qplan is not None else None)
 
 
 def _read_back(st):

@@ -275,17 +275,33 @@ def check_plume_background(plume_background, who):
     return {"background_ring_px": plume_background["ring_px"], "background_gap_px": plume_background.get("gap_px", 0.0)}
 
 
+def check_plume_quantify(plume_quantify, who):
+    """the ``plume_quantify=`` argument of ``annotate`` and the pipeline calls: None, or the ``quantify=`` dict of
+    ``plumes.plume_table`` -- ``wind_speed_m_s`` and keys from ``quantify.QUANTIFY_KEYS`` (``quantify.check_quantify``; no device
+    involved) -> the keyword arguments of ``plumes.plume_table``"""
+    from .quantify import check_quantify
+    if plume_quantify is None:
+        return {}
+    return {"quantify": check_quantify(plume_quantify, who)}
+
+
 def annotate(out, mask, mf, prob, geotransform=None, pixel_area_m2=None, plumes=False, plume_outlines=False, label_polygons=None,
-             match_tolerance_px=0.0, plume_background=None):
+             match_tolerance_px=0.0, plume_background=None, plume_quantify=None):
     """The plume annotations of a prediction dict, as asked for: ``plumes`` (``plumes.plume_table`` of ``mask`` with ``mf`` as mag1c
     and ``prob`` as probability), ``plume_outlines`` of the same mask in the same coordinates, and for ``label_polygons`` (a
     ``.geojson`` path or polygons) ``label_mask``, the polygons burnt into the grid of ``mask`` (device uint8), and ``plume_match``,
     the same burnt image scored against the mask, with ``match_tolerance_px`` as the ``tolerance_px`` of ``plumes.burn_and_match``.
     ``plume_background``: ``{"ring_px": .., "gap_px": ..}`` adds the background-ring columns of ``plumes.plume_table`` to the table
-    (and so to ``plumes.csv`` and the GeoJSON properties); it needs ``mf``."""
+    (and so to ``plumes.csv`` and the GeoJSON properties); it needs ``mf``.  ``plume_quantify``: the ``quantify=`` dict of
+    ``plumes.plume_table`` (``wind_speed_m_s``, ...) adds its shape, mass and emission-rate columns the same way; it needs ``mf`` and
+    ``pixel_area_m2``, i.e. a metric grid: on a longitude / latitude grid it is a ValueError (the scene calls take ``crs="utm"``)."""
     from . import plumes as pl
     ring = check_plume_background(plume_background, "annotate")
+    ring.update(check_plume_quantify(plume_quantify, "annotate"))
     if plumes:
+        if plume_quantify is not None and pixel_area_m2 is None:
+            raise ValueError("annotate: plume_quantify needs a metric grid (pixel_area_m2): this one has none -- a longitude / latitude "
+                             "grid is put on a UTM zone with crs=\"utm\"")
         out["plumes"] = pl.plume_table(mask, mag1c=mf, prob=prob, geotransform=geotransform, pixel_area_m2=pixel_area_m2, **ring)
         if plume_outlines:
             out["plume_outlines"] = pl.plume_outlines(mask, geotransform=geotransform)
