@@ -122,9 +122,7 @@ extern "C" int sc_glt_ortho(const sc_ortho_args* a, sc_stream stream) {
   for (int p = 0; p < ORTHO_PMAX; ++p) {
     const bool on = p < a->P;
     if (on) {
-      SC_REQUIRE(a->src[p], "sc_glt_ortho: null source plane %d", p);
-      SC_REQUIRE((uintptr_t)a->src[p] % eb == 0, "sc_glt_ortho: source plane %d is not aligned to its %d-byte elements", p, eb);
-      SC_REQUIRE(a->row_stride[p] >= 0 && a->col_stride[p] >= 0, "sc_glt_ortho: negative stride of plane %d", p);
+      SC_REQUIRE_PLANE("sc_glt_ortho", a->src[p], a->row_stride[p], a->col_stride[p], eb, p);
       SC_REQUIRE(a->plane_rows[p] >= 0 && a->plane_rows[p] <= a->rows && a->plane_cols[p] >= 0 && a->plane_cols[p] <= a->cols,
                  "sc_glt_ortho: plane %d extent %d x %d outside the %d x %d swath", p, a->plane_rows[p], a->plane_cols[p], a->rows, a->cols);
     }

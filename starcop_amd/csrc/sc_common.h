@@ -24,6 +24,14 @@ inline int sc_lds_limit(void (*kernel)(A...), size_t bytes, const char* who) {
     }                                         \
   } while (0)
 
+// plane `p` of an operator that reads its source planes in place, each through a pointer and two strides in `eb`-byte elements
+#define SC_REQUIRE_PLANE(who, ptr, row_stride, col_stride, eb, p)                                                            \
+  do {                                                                                                                       \
+    SC_REQUIRE(ptr, "%s: null source plane %d", who, p);                                                                     \
+    SC_REQUIRE((uintptr_t)(ptr) % (eb) == 0, "%s: source plane %d is not aligned to its %d-byte elements", who, p, eb);      \
+    SC_REQUIRE((row_stride) >= 0 && (col_stride) >= 0, "%s: negative stride of plane %d", who, p);                           \
+  } while (0)
+
 #define SC_LAUNCH_OK(name)                                                        \
   do {                                                                            \
     hipError_t e__ = hipGetLastError();                                           \

@@ -6,8 +6,12 @@
 // out samples that lie outside the raster, are NaN or carry the plane's no-data bit pattern, divides by the weight of those that
 // count and rounds once.  Both operators include this file, so a pixel of one source gets the same arithmetic from either.  The
 // footprint resampling (warp_area.hip) shares the projection and calls it on the host too, to estimate the size of a footprint.
+// The host side of a grid pair lives here as well: its checks and route (grid_pair_setup), the point transform of a destination
+// lattice point (grid_uv) and the plane descriptors (grid_planes) of sc_warp and sc_warp_area.
 #pragma once
 #include <math.h>
+
+#include <cmath>
 
 #include "sc_common.h"
 
@@ -154,6 +158,59 @@ inline void krueger_wgs84(Krueger& k) {
   k.bet[3] = 4397 * n4 / 161280 - 11 * n5 / 504 - 830251 * n6 / 7257600;
   k.bet[4] = 4583 * n5 / 161280 - 108847 * n6 / 3991680;
   k.bet[5] = 20648693 * n6 / 638668800;
+}
+
+// The grid pair of a kernel descriptor `d` (WarpD, AreaD: gt, inv, k, the four meridian fields, route) from the destination affine, the
+// inverse source affine and the two CRS codes.  `who`: the entry point, for the messages.
+template <class D>
+int grid_pair_setup(D& d, const char* who, const double* dst_gt, const double* src_inv, int dst_crs, int src_crs) {
+  for (int i = 0; i < 6; ++i) {
+    SC_REQUIRE(std::isfinite(dst_gt[i]) && std::isfinite(src_inv[i]), "%s: geotransform term %d is not finite", who, i);
+    d.gt[i] = dst_gt[i];
+    d.inv[i] = src_inv[i];
+  }
+  SC_REQUIRE(dst_gt[1] * dst_gt[5] - dst_gt[2] * dst_gt[4] != 0.0, "%s: the destination geotransform is singular", who);
+  SC_REQUIRE(src_inv[1] * src_inv[5] - src_inv[2] * src_inv[4] != 0.0, "%s: the inverse source geotransform is singular", who);
+  d.route = 0;
+  d.dst_lon0 = d.dst_fn = d.src_lon0 = d.src_fn = 0.0;
+  if (dst_crs != src_crs) {                       // equal codes (0 included): affine only
+    const int kd = crs_kind(dst_crs, d.dst_lon0, d.dst_fn), ks = crs_kind(src_crs, d.src_lon0, d.src_fn);
+    SC_REQUIRE(kd > 0 && ks > 0, "%s: CRS pair %d -> %d (0 with 0, else 4326 or 32601..32660 / 32701..32760 on both sides)", who, dst_crs,
+               src_crs);
+    d.route = (kd == 2 ? 1 : 0) | (ks == 2 ? 2 : 0);   // bit 0: destination is UTM (inverse first), bit 1: source is UTM (forward after)
+  } else {
+    SC_REQUIRE(dst_crs >= 0, "%s: negative CRS code %d", who, dst_crs);
+  }
+  krueger_wgs84(d.k);
+  return SC_OK;
+}
+
+// source pixel coordinates (u, v), unclipped, of the point (px, py) of the destination's pixel lattice: destination affine, the route
+// through longitude / latitude, inverse source affine.  false when the projection cannot place the point
+template <class D>
+__host__ __device__ __forceinline__ bool grid_uv(const D& a, double px, double py, double& u, double& v) {
+  double x = a.gt[0] + px * a.gt[1] + py * a.gt[2];
+  double y = a.gt[3] + px * a.gt[4] + py * a.gt[5];
+  bool ok = true;
+  if (a.route & 1) ok = tm_inverse(a.k, a.dst_lon0, a.dst_fn, x, y, x, y);
+  if (a.route & 2) ok = tm_forward(a.k, a.src_lon0, a.src_fn, x, y, x, y) && ok;
+  u = a.inv[0] + x * a.inv[1] + y * a.inv[2];
+  v = a.inv[3] + x * a.inv[4] + y * a.inv[5];
+  return ok;
+}
+
+// The P source planes of a call `a` (sc_warp_args, sc_warp_area_args) into the descriptor `d` (src, rs, cs, nod), nothing beyond P
+template <class D, class A>
+int grid_planes(D& d, const char* who, const A* a, int eb) {
+  for (int p = 0; p < SC_WARP_MAX_PLANES; ++p) {
+    const bool on = p < a->P;
+    if (on) SC_REQUIRE_PLANE(who, a->src[p], a->row_stride[p], a->col_stride[p], eb, p);
+    d.src[p] = on ? a->src[p] : nullptr;
+    d.rs[p] = on ? a->row_stride[p] : 0;
+    d.cs[p] = on ? a->col_stride[p] : 0;
+    d.nod[p] = on ? a->nodata_bits[p] : 0;
+  }
+  return SC_OK;
 }
 
 template <class T, int V>

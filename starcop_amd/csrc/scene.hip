@@ -205,9 +205,7 @@ extern "C" int sc_scene_gather_planes(const sc_scene_planes_args* a, sc_stream s
   for (int p = 0; p < SP_PMAX; ++p) {
     const bool on = p < a->P;
     if (on) {
-      SC_REQUIRE(a->src[p], "sc_scene_gather_planes: null source plane %d", p);
-      SC_REQUIRE((uintptr_t)a->src[p] % 4 == 0, "sc_scene_gather_planes: source plane %d is not aligned to its 4-byte elements", p);
-      SC_REQUIRE(a->row_stride[p] >= 0 && a->col_stride[p] >= 0, "sc_scene_gather_planes: negative stride of plane %d", p);
+      SC_REQUIRE_PLANE("sc_scene_gather_planes", a->src[p], a->row_stride[p], a->col_stride[p], 4, p);
       SC_REQUIRE((a->ops[p] & ~(uint32_t)(SC_WCUT_FILL | SC_WCUT_SCALE | SC_WCUT_CLIP)) == 0,
                  "sc_scene_gather_planes: unknown ops bits 0x%x of plane %d", a->ops[p], p);
       if (a->ops[p] & SC_WCUT_SCALE) SC_REQUIRE(a->scale[p] == a->scale[p], "sc_scene_gather_planes: scale of plane %d is NaN", p);

@@ -48,14 +48,7 @@ struct WarpD {
 
 // source pixel coordinates of the centre of destination pixel (r, c); NaN when the point is outside the source
 __device__ __forceinline__ bool source_uv(const WarpD& a, int r, long long c, double& u, double& v) {
-  const double px = (double)c + 0.5, py = (double)r + 0.5;
-  double x = a.gt[0] + px * a.gt[1] + py * a.gt[2];
-  double y = a.gt[3] + px * a.gt[4] + py * a.gt[5];
-  bool ok = true;
-  if (a.route & 1) ok = tm_inverse(a.k, a.dst_lon0, a.dst_fn, x, y, x, y);
-  if (a.route & 2) ok = tm_forward(a.k, a.src_lon0, a.src_fn, x, y, x, y) && ok;
-  u = a.inv[0] + x * a.inv[1] + y * a.inv[2];
-  v = a.inv[3] + x * a.inv[4] + y * a.inv[5];
+  bool ok = grid_uv(a, (double)c + 0.5, (double)r + 0.5, u, v);
   const bool inside = u >= 0.0 && u < (double)a.sw && v >= 0.0 && v < (double)a.sh;      // false for NaN and infinities
   ok = ok && (inside || (a.unbounded && fabs(u) < INFINITY && fabs(v) < INFINITY));
   if (!ok) u = v = __builtin_nan("");
@@ -135,39 +128,11 @@ extern "C" int sc_warp(const sc_warp_args* a, sc_stream stream) {
   SC_REQUIRE((uintptr_t)a->out % eb == 0 && (uintptr_t)a->coords % 8 == 0 && (uintptr_t)a->oob_count % 8 == 0,
              "sc_warp: misaligned output, coordinate or counter pointer");
   WarpD d;
-  for (int i = 0; i < 6; ++i) {
-    SC_REQUIRE(std::isfinite(a->dst_gt[i]) && std::isfinite(a->src_inv[i]), "sc_warp: geotransform term %d is not finite", i);
-    d.gt[i] = a->dst_gt[i];
-    d.inv[i] = a->src_inv[i];
-  }
-  SC_REQUIRE(a->dst_gt[1] * a->dst_gt[5] - a->dst_gt[2] * a->dst_gt[4] != 0.0, "sc_warp: the destination geotransform is singular");
-  SC_REQUIRE(a->src_inv[1] * a->src_inv[5] - a->src_inv[2] * a->src_inv[4] != 0.0, "sc_warp: the inverse source geotransform is singular");
-  d.route = 0;
-  d.dst_lon0 = d.dst_fn = d.src_lon0 = d.src_fn = 0.0;
-  if (a->dst_crs != a->src_crs) {                 // equal codes (0 included): affine only
-    const int kd = crs_kind(a->dst_crs, d.dst_lon0, d.dst_fn), ks = crs_kind(a->src_crs, d.src_lon0, d.src_fn);
-    SC_REQUIRE(kd > 0 && ks > 0, "sc_warp: CRS pair %d -> %d (0 with 0, else 4326 or 32601..32660 / 32701..32760 on both sides)",
-               a->dst_crs, a->src_crs);
-    d.route = (kd == 2 ? 1 : 0) | (ks == 2 ? 2 : 0);
-  } else {
-    SC_REQUIRE(a->dst_crs >= 0, "sc_warp: negative CRS code %d", a->dst_crs);
-  }
-  krueger_wgs84(d.k);
+  if (int rc = grid_pair_setup(d, "sc_warp", a->dst_gt, a->src_inv, a->dst_crs, a->src_crs)) return rc;
   d.H = a->out_h; d.W = a->out_w; d.sh = a->src_h; d.sw = a->src_w; d.P = a->P; d.tiles_x = 0;
   d.unbounded = a->flags & SC_WARP_UNBOUNDED;
   d.out = a->out; d.coords = a->coords; d.oob = (unsigned long long*)a->oob_count;
-  for (int p = 0; p < WARP_PMAX; ++p) {
-    const bool on = p < a->P;
-    if (on) {
-      SC_REQUIRE(a->src[p], "sc_warp: null source plane %d", p);
-      SC_REQUIRE((uintptr_t)a->src[p] % eb == 0, "sc_warp: source plane %d is not aligned to its %d-byte elements", p, eb);
-      SC_REQUIRE(a->row_stride[p] >= 0 && a->col_stride[p] >= 0, "sc_warp: negative stride of plane %d", p);
-    }
-    d.src[p] = on ? a->src[p] : nullptr;
-    d.rs[p] = on ? a->row_stride[p] : 0;
-    d.cs[p] = on ? a->col_stride[p] : 0;
-    d.nod[p] = on ? a->nodata_bits[p] : 0;
-  }
+  if (int rc = grid_planes(d, "sc_warp", a, eb)) return rc;
   const int V = eb == 8 ? 2 : 4;
   const uintptr_t store = (uintptr_t)(V * eb < 16 ? V * eb : 16);
   const bool vec = a->out_w % V == 0 && (uintptr_t)a->out % store == 0;

@@ -69,14 +69,7 @@ struct AreaD {
 
 // source pixel coordinates of the destination lattice point (px, py), unclipped; false when the projection has no finite result
 __host__ __device__ __forceinline__ bool corner_uv(const AreaD& a, double px, double py, double& u, double& v) {
-  double x = a.gt[0] + px * a.gt[1] + py * a.gt[2];
-  double y = a.gt[3] + px * a.gt[4] + py * a.gt[5];
-  bool ok = true;
-  if (a.route & 1) ok = tm_inverse(a.k, a.dst_lon0, a.dst_fn, x, y, x, y);
-  if (a.route & 2) ok = tm_forward(a.k, a.src_lon0, a.src_fn, x, y, x, y) && ok;
-  u = a.inv[0] + x * a.inv[1] + y * a.inv[2];
-  v = a.inv[3] + x * a.inv[4] + y * a.inv[5];
-  return ok && fabs(u) < INFINITY && fabs(v) < INFINITY;      // false for NaN too
+  return grid_uv(a, px, py, u, v) && fabs(u) < INFINITY && fabs(v) < INFINITY;      // false for NaN too
 }
 
 // the corners (y0 .. y0 + LH - 1) x (x0 .. x0 + LW - 1) of a tile into LDS; NaN for a corner without coordinates or beyond the grid
@@ -411,41 +404,12 @@ int prepare(const sc_warp_area_args* a, AreaD& d, int& eb, bool launch) {
   SC_REQUIRE((uintptr_t)a->out % eb == 0 && (uintptr_t)a->coverage % 4 == 0 && (uintptr_t)a->boxes % 8 == 0,
              "sc_warp_area: misaligned output, coverage or box pointer");
   SC_REQUIRE(a->P > 0 || !a->coverage, "sc_warp_area: a coverage output without planes");
-  for (int i = 0; i < 6; ++i) {
-    SC_REQUIRE(std::isfinite(a->dst_gt[i]) && std::isfinite(a->src_inv[i]), "sc_warp_area: geotransform term %d is not finite", i);
-    d.gt[i] = a->dst_gt[i];
-    d.inv[i] = a->src_inv[i];
-  }
-  SC_REQUIRE(a->dst_gt[1] * a->dst_gt[5] - a->dst_gt[2] * a->dst_gt[4] != 0.0, "sc_warp_area: the destination geotransform is singular");
-  SC_REQUIRE(a->src_inv[1] * a->src_inv[5] - a->src_inv[2] * a->src_inv[4] != 0.0, "sc_warp_area: the inverse source geotransform is singular");
-  d.route = 0;
-  d.dst_lon0 = d.dst_fn = d.src_lon0 = d.src_fn = 0.0;
-  if (a->dst_crs != a->src_crs) {                 // equal codes (0 included): affine only
-    const int kd = crs_kind(a->dst_crs, d.dst_lon0, d.dst_fn), ks = crs_kind(a->src_crs, d.src_lon0, d.src_fn);
-    SC_REQUIRE(kd > 0 && ks > 0, "sc_warp_area: CRS pair %d -> %d (0 with 0, else 4326 or 32601..32660 / 32701..32760 on both sides)",
-               a->dst_crs, a->src_crs);
-    d.route = (kd == 2 ? 1 : 0) | (ks == 2 ? 2 : 0);
-  } else {
-    SC_REQUIRE(a->dst_crs >= 0, "sc_warp_area: negative CRS code %d", a->dst_crs);
-  }
-  krueger_wgs84(d.k);
+  if (int rc = grid_pair_setup(d, "sc_warp_area", a->dst_gt, a->src_inv, a->dst_crs, a->src_crs)) return rc;
   d.H = a->out_h; d.W = a->out_w; d.sh = a->src_h; d.sw = a->src_w; d.P = a->P; d.tiles_x = 0;
   d.min_cov = a->min_coverage;
   d.flip = mode == SC_WARP_AREA_MIN ? 0xFFFFFFFFu : 0u;
   d.out = a->out; d.cov = a->coverage; d.boxes = a->boxes;
-  for (int p = 0; p < AREA_PMAX; ++p) {
-    const bool on = p < a->P;
-    if (on) {
-      SC_REQUIRE(a->src[p], "sc_warp_area: null source plane %d", p);
-      SC_REQUIRE((uintptr_t)a->src[p] % eb == 0, "sc_warp_area: source plane %d is not aligned to its %d-byte elements", p, eb);
-      SC_REQUIRE(a->row_stride[p] >= 0 && a->col_stride[p] >= 0, "sc_warp_area: negative stride of plane %d", p);
-    }
-    d.src[p] = on ? a->src[p] : nullptr;
-    d.rs[p] = on ? a->row_stride[p] : 0;
-    d.cs[p] = on ? a->col_stride[p] : 0;
-    d.nod[p] = on ? a->nodata_bits[p] : 0;
-  }
-  return SC_OK;
+  return grid_planes(d, "sc_warp_area", a, eb);
 }
 
 }  // namespace

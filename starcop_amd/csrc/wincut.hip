@@ -146,9 +146,7 @@ extern "C" int sc_window_cut(const sc_wcut_args* a, sc_stream stream) {
   for (int p = 0; p < WCUT_PMAX; ++p) {
     const bool on = p < a->P;
     if (on) {
-      SC_REQUIRE(a->src[p], "sc_window_cut: null source plane %d", p);
-      SC_REQUIRE((uintptr_t)a->src[p] % eb == 0, "sc_window_cut: source plane %d is not aligned to its %d-byte elements", p, eb);
-      SC_REQUIRE(a->row_stride[p] >= 0 && a->col_stride[p] >= 0, "sc_window_cut: negative stride of plane %d", p);
+      SC_REQUIRE_PLANE("sc_window_cut", a->src[p], a->row_stride[p], a->col_stride[p], eb, p);
       SC_REQUIRE(a->rows[p] >= 1 && a->cols[p] >= 1 && a->row0[p] >= 0 && a->col0[p] >= 0 &&
                      (long long)a->row0[p] + a->rows[p] <= a->scene_rows && (long long)a->col0[p] + a->cols[p] <= a->scene_cols,
                  "sc_window_cut: plane %d (%d x %d at row %d, col %d) is not inside the %d x %d scene", p, a->rows[p], a->cols[p],

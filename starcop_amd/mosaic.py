@@ -23,7 +23,7 @@ import torch
 
 from . import _lib, warp
 from ._lib import check as _check, sc_mosaic_args, sc_mosaic_source, stream
-from .ortho import _fill_bits, _numpy_dtype
+from .planes import as_planes, fill_bits, numpy_dtype, per_plane, set_planes
 
 MAX_SOURCES = _lib.MOSAIC_MAX_SOURCES
 MAX_PLANES = _lib.WARP_MAX_PLANES
@@ -42,7 +42,7 @@ def footprint_box(src_shape, src_gt, src_crs, dst_gt, dst_crs, dst_shape):
     Hd, Wd = (int(v) for v in dst_shape)
     if H < 1 or W < 1:
         raise ValueError(f"footprint_box: empty source {src_shape}")
-    gt = warp._gt6(src_gt, "footprint_box")
+    gt = warp.gt6(src_gt, "footprint_box")
     inv = warp.invert_geotransform(dst_gt)
     cols = np.concatenate([np.arange(W + 1.0), np.full(H + 1, float(W)), np.arange(W + 1.0), np.zeros(H + 1)])
     rows = np.concatenate([np.zeros(W + 1), np.arange(H + 1.0), np.full(W + 1, float(H)), np.arange(H + 1.0)])
@@ -82,27 +82,6 @@ def union_grid(grids, dst_crs, resolution=None):
 
 
 # ---------------------------------------------------------------------------------------------- the device side
-def _planes_of(data, who):
-    """-> (list of 2-D arrays or tensors, the input was 2-D, it was numpy)"""
-    if isinstance(data, np.ndarray):
-        if data.ndim == 2:
-            return [data], True, True
-        if data.ndim == 3 and data.shape[0] >= 1:
-            return list(data), False, True
-    elif isinstance(data, (list, tuple)):
-        planes = [torch.as_tensor(p) for p in data]
-        if planes and all(p.dim() == 2 for p in planes):
-            return planes, False, False
-        raise ValueError(f"{who}: a list must hold at least one 2-D tensor")
-    elif isinstance(data, torch.Tensor):
-        if data.dim() == 2:
-            return [data], True, False
-        if data.dim() == 3 and data.shape[0] >= 1:
-            return list(data.unbind(0)), False, False
-    raise ValueError(f"{who}: expected a tensor (H, W) or (P, H, W), a numpy array or a list of 2-D tensors, got "
-                     + (str(tuple(data.shape)) if hasattr(data, "shape") else type(data).__name__))
-
-
 def _code(crs):
     return 0 if crs is None else int(crs)
 
@@ -113,23 +92,13 @@ def _launch(lib, srcs, planes_of, idx, nd, bits, dgt, d_code, dst_shape, boxes, 
     table = (sc_mosaic_source * N)()
     for s, (shape, inv, code) in enumerate(srcs):
         q = table[s]
-        for i in range(6):
-            q.src_inv[i] = inv[i]
-        q.src_crs, (q.src_h, q.src_w) = code, shape
-        for i in range(4):
-            q.box[i] = boxes[s][i]
-        for k, p in enumerate(idx):
-            t = planes_of[s][p]
-            q.src[k] = t.data_ptr()
-            q.row_stride[k], q.col_stride[k] = t.stride()
+        q.src_inv[:], q.src_crs, (q.src_h, q.src_w), q.box[:] = inv, code, shape, boxes[s]
+        set_planes(q, [planes_of[s][p] for p in idx])
     a = sc_mosaic_args()
-    for i in range(6):
-        a.dst_gt[i] = dgt[i]
-    a.dst_crs, (a.out_h, a.out_w) = d_code, dst_shape
+    a.dst_gt[:], a.dst_crs, (a.out_h, a.out_w) = dgt, d_code, dst_shape
     a.N, a.P, a.elem_bytes, a.rule, a.key_plane, a.resampling = N, n, nd.itemsize, rule, key, mode
     a.flags = _lib.MOSAIC_KEY_FLOAT if key >= 0 and nd.kind == "f" and nd.itemsize in (4, 8) else 0
-    for k, p in enumerate(idx):
-        a.nodata_bits[k] = bits[p]
+    a.nodata_bits[:n] = [bits[p] for p in idx]
     a.sources = ctypes.cast(table, ctypes.POINTER(sc_mosaic_source))
     dev_table = torch.empty(ctypes.sizeof(table), dtype=torch.uint8, device=out.device)
     a.table, a.out = dev_table.data_ptr(), out.data_ptr()
@@ -162,19 +131,17 @@ def mosaic(sources, dst_gt, dst_crs, dst_shape, rule="first", key=0, resampling=
     N = len(sources)
     if N < 1 or N > MAX_SOURCES:
         raise ValueError(f"{who}: {N} sources; one call takes 1 to {MAX_SOURCES}")
-    dgt = warp._gt6(dst_gt, who)
-    Hd, Wd = warp._dst_shape(dst_shape, who)
-    parsed = [_planes_of(d, who) for d, _, _ in sources]
+    dgt = warp.gt6(dst_gt, who)
+    Hd, Wd = warp.dst_grid_shape(dst_shape, who)
+    parsed = [as_planes(d, who, same_shape=False) for d, _, _ in sources]
     host, single = parsed[0][2], all(p[1] for p in parsed)
     P = len(parsed[0][0])
-    dts = {str(p.dtype).replace("torch.", "") for pl, _, _ in parsed for p in pl}
+    dts = {str(pl[0].dtype).replace("torch.", "") for pl, _, _ in parsed}            # as_planes: one dtype and device per source
     if len(dts) != 1 or any(len(pl) != P for pl, _, _ in parsed):
         raise ValueError(f"{who}: all sources share one dtype and plane count; got dtypes {sorted(dts)}, plane counts "
                          f"{[len(pl) for pl, _, _ in parsed]}")
     first = parsed[0][0][0]
-    nd = np.dtype(first.dtype) if isinstance(first, np.ndarray) else _numpy_dtype(first.dtype)
-    if nd.kind not in "fiu" or nd.itemsize not in (1, 2, 4, 8):
-        raise ValueError(f"{who}: dtype {nd} is not supported (1-, 2-, 4- or 8-byte integers and floats)")
+    nd = numpy_dtype(first.dtype, who)
     if nd != np.float32 and (rule in ("max", "min", "mean") or resampling == "bilinear"):
         raise ValueError(f"{who}: the rules max, min and mean and bilinear resampling are defined for float32, not {nd}")
     key = int(key)
@@ -195,18 +162,12 @@ def mosaic(sources, dst_gt, dst_crs, dst_shape, rule="first", key=0, resampling=
     d_code = _code(dst_crs)
     srcs = []
     for (pl, _, _), (_, gt, crs) in zip(parsed, sources):
-        warp._crs_pair(crs, dst_crs, who)
+        warp.crs_pair(crs, dst_crs, who)
         shape = tuple(int(v) for v in pl[0].shape)
         if shape[0] < 1 or shape[1] < 1 or any(tuple(p.shape) != shape for p in pl):
             raise ValueError(f"{who}: the planes of a source share one non-empty shape")
         srcs.append((shape, warp.invert_geotransform(gt), _code(crs)))
-    if isinstance(nodata, (list, tuple, np.ndarray)) and np.ndim(nodata) == 1:
-        fills = list(nodata)
-        if len(fills) != P:
-            raise ValueError(f"{who}: {len(fills)} nodata values for {P} planes")
-    else:
-        fills = [0 if nodata is None else nodata] * P
-    bits = [_fill_bits(v, nd) for v in fills]
+    bits = [fill_bits(v, nd, who) for v in per_plane(nodata, P, who, "nodata values", default=0)]
     boxes = [footprint_box(shape, gt, crs, dgt, dst_crs, (Hd, Wd)) for (shape, _, _), (_, gt, crs) in zip(srcs, sources)]
     # ---- the device from here on
     _lib.require_device(None if host else first)
@@ -214,11 +175,9 @@ def mosaic(sources, dst_gt, dst_crs, dst_shape, rule="first", key=0, resampling=
     planes_of = []
     for pl, _, is_np in parsed:
         if is_np:
-            pl = [torch.from_numpy(p if all(s >= 0 for s in p.strides) else np.ascontiguousarray(p)).to(dev) for p in pl]
-        if any(p.device != dev for p in pl):
+            pl = [p.to(dev) for p in pl]
+        if pl[0].device != dev:
             raise ValueError(f"{who}: all planes live on one device")
-        if any(s < 0 for p in pl for s in p.stride()):
-            raise ValueError(f"{who}: negative strides are not supported")
         planes_of.append(pl)
     if select is not None:
         select = (torch.from_numpy(np.ascontiguousarray(select)) if isinstance(select, np.ndarray) else select).to(dev).contiguous()

@@ -15,6 +15,7 @@ import torch
 
 from . import _lib
 from ._lib import check as _check, sc_ortho_args, stream
+from .planes import as_planes, chunks, fill_bits, numpy_dtype, per_plane, set_planes
 
 NOUT_MAX = _lib.ORTHO_MAX_PLANES
 
@@ -31,29 +32,6 @@ def _glt_device(g, dev):
     return torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
 
 
-def _numpy_dtype(dt):
-    try:
-        nd = torch.empty(0, dtype=dt).numpy().dtype
-    except TypeError:
-        nd = None
-    if nd is None or nd.kind not in "fiu" or nd.itemsize not in (1, 2, 4, 8):
-        raise ValueError(f"georeference: dtype {dt} is not supported (1-, 2-, 4- or 8-byte integers and floats)")
-    return nd
-
-
-def _fill_bits(value, nd):
-    """bit pattern of ``value`` as numpy stores it in dtype ``nd`` (what ``np.full(shape, value, dtype)`` holds)"""
-    if nd.kind in "iu":
-        f = float(value)
-        info = np.iinfo(nd)
-        if f != f or f != int(f) or not info.min <= int(f) <= info.max:
-            raise ValueError(f"georeference: fill value {value!r} cannot be represented in {nd}")
-        a = np.array(int(f), dtype=nd)
-    else:
-        a = np.asarray(value).astype(nd) if isinstance(value, (np.generic, np.ndarray)) else np.array(value, dtype=nd)
-    return int(a.reshape(1).view(f"u{nd.itemsize}")[0])
-
-
 def georeference(data, glt_x, glt_y, fill_value_default=-9999.0, absolute=False, check=True, shape=None):
     """``EMITImage.georreference(data, fill_value_default)`` on the GPU for one or many planes.
 
@@ -68,31 +46,11 @@ def georeference(data, glt_x, glt_y, fill_value_default=-9999.0, absolute=False,
 
     GLT entries that point outside the swath are never dereferenced: the pixel gets the fill value and is counted on the device;
     ``check=True`` reads the counter back once and raises ``ValueError`` with the count, ``check=False`` skips the read-back."""
-    host = isinstance(data, np.ndarray)
-    if host:
-        _lib.require_device()
-        a = data if all(s >= 0 for s in data.strides) else np.ascontiguousarray(data)
-        data = torch.from_numpy(a).cuda()
-    single = False
-    if isinstance(data, (list, tuple)):
-        planes = [torch.as_tensor(p) for p in data]
-        if not planes:
-            raise ValueError("georeference: no planes")
-        if any(p.dim() != 2 for p in planes):
-            raise ValueError("georeference: a list must hold 2-D tensors")
-    else:
-        if not isinstance(data, torch.Tensor):
-            raise TypeError(f"georeference: expected a tensor, a numpy array or a list of tensors, got {type(data).__name__}")
-        if data.dim() == 2:
-            planes, single = [data], True
-        elif data.dim() == 3 and data.shape[0] >= 1:
-            planes = list(data.unbind(0))
-        else:
-            raise ValueError(f"georeference: expected (rows, cols) or (P, rows, cols), got {tuple(data.shape)}")
-    dt, dev = planes[0].dtype, planes[0].device
-    if any(p.dtype != dt or p.device != dev for p in planes):
-        raise ValueError("georeference: all planes of a call share one dtype and device")
-    nd = _numpy_dtype(dt)
+    who = "georeference"
+    planes, single, host = as_planes(data, who, "a tensor (rows, cols) or (P, rows, cols), a numpy array or a list of 2-D tensors",
+                                     TypeError, same_shape=False)
+    dt = planes[0].dtype
+    nd = numpy_dtype(dt, who)
     if shape is None:
         rows, cols = (int(v) for v in planes[0].shape)
         if any(tuple(p.shape) != (rows, cols) for p in planes):
@@ -101,17 +59,12 @@ def georeference(data, glt_x, glt_y, fill_value_default=-9999.0, absolute=False,
         rows, cols = (int(v) for v in shape)
     if rows < 1 or cols < 1 or any(p.shape[0] < 1 or p.shape[1] < 1 or p.shape[0] > rows or p.shape[1] > cols for p in planes):
         raise ValueError(f"georeference: every plane must be non-empty and inside the {rows} x {cols} swath")
-    if any(s < 0 for p in planes for s in p.stride()):
-        raise ValueError("georeference: negative strides are not supported")
     P = len(planes)
-    if isinstance(fill_value_default, (list, tuple, np.ndarray)) and np.ndim(fill_value_default) == 1:
-        fills = list(fill_value_default)
-        if len(fills) != P:
-            raise ValueError(f"georeference: {len(fills)} fill values for {P} planes")
-    else:
-        fills = [fill_value_default] * P
-    bits = [_fill_bits(v, nd) for v in fills]
-    _lib.require_device(planes[0])
+    bits = [fill_bits(v, nd, who) for v in per_plane(fill_value_default, P, who, "fill values")]
+    _lib.require_device(None if host else planes[0])
+    if host:
+        planes = [p.cuda() for p in planes]
+    dev = planes[0].device
     lib = _lib.load()
     gx, gy = _glt_device(glt_x, dev), _glt_device(glt_y, dev)
     if gx.shape != gy.shape:
@@ -121,18 +74,13 @@ def georeference(data, glt_x, glt_y, fill_value_default=-9999.0, absolute=False,
         raise ValueError("georeference: empty GLT")
     out = torch.empty((P, Ho, Wo), dtype=dt, device=dev)
     oob = torch.zeros(1, dtype=torch.int64, device=dev) if check else None
-    for p0 in range(0, P, NOUT_MAX):
-        n = min(NOUT_MAX, P - p0)
+    for p0, n in chunks(P, NOUT_MAX):
         a = sc_ortho_args()
         a.glt_x, a.glt_y = gx.data_ptr(), gy.data_ptr()
         a.out_h, a.out_w, a.rows, a.cols = Ho, Wo, rows, cols
         a.P, a.elem_bytes, a.absolute = n, nd.itemsize, int(bool(absolute))
-        for k in range(n):
-            t = planes[p0 + k]
-            a.src[k] = t.data_ptr()
-            a.row_stride[k], a.col_stride[k] = t.stride()
-            a.plane_rows[k], a.plane_cols[k] = t.shape
-            a.fill_bits[k] = bits[p0 + k]
+        set_planes(a, planes, p0, rows=a.plane_rows, cols=a.plane_cols)
+        a.fill_bits[:n] = bits[p0:p0 + n]
         a.out = out[p0].data_ptr()
         a.oob_count = oob.data_ptr() if oob is not None and p0 == 0 else None      # the GLT is the same for every chunk
         _check(lib.sc_glt_ortho(a, stream()))

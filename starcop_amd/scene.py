@@ -3,7 +3,7 @@
 The (virtual) reflect-padded scene is walked in equally shaped windows (:func:`scene_windows`); the plan travels as the int32 rows
 of ``sc_scene_win`` (:func:`scene_table`), on the device for the kernels and on the host for the argument checks of the entry
 points.  :func:`table_rows` is the one check of such a pair, :func:`window_batches` the batch loop of both models.  Depends on
-``_lib`` and ``padding`` only: ``network``, ``model_module``, ``pipeline`` and ``sentinel2`` import this module.
+``_lib``, ``padding`` and ``planes`` only: ``network``, ``model_module``, ``pipeline`` and ``sentinel2`` import this module.
 """
 import collections
 import ctypes as C
@@ -13,6 +13,7 @@ import torch
 
 from . import _lib
 from .padding import find_padding
+from .planes import set_plane_ops, set_planes
 
 # Receptive field of smp.Unet('mobilenet_v2'): encoder 3x3 convolutions at strides 1..32 reach 490 px, the decoder
 # adds 126 -> a logit depends on inputs at most 308 px away.  Halo >= 320 (a multiple of 32, the network's stride) therefore makes a
@@ -94,7 +95,8 @@ def window_batches(n, window, channels, device, batch=None):
 
 
 def float_bits(value):
-    """bit pattern of ``float32(value)``: how the plume-scene kernels compare a fill value"""
+    """bit pattern of ``float32(value)``: how the plume-scene kernels compare a fill value.  Beside ``planes.match_bits``, not over it:
+    the scenes' fill may be NaN, which matches the elements that hold this very pattern"""
     return int(np.array(value, dtype=np.float32).view(np.uint32))
 
 
@@ -146,21 +148,10 @@ def scene_gather_planes(planes, pads, table_dev, table_host, first, n, window, f
     a.P, a.H, a.W = P, H, W
     a.pad_top, a.pad_left = int(pads[0]), int(pads[1])
     a.n, a.win_h, a.win_w = int(n), int(wh), int(ww)
-    for i, p in enumerate(planes):
-        a.src[i] = p.data_ptr()
-        a.row_stride[i], a.col_stride[i] = p.stride()
+    set_planes(a, planes)
+    for i in range(P):
         fill, scale, clip = (seq[i] if seq is not None else None for seq in (fills, scales, clips))
-        ops = 0
-        if fill is not None:
-            ops |= _lib.WCUT_FILL
-            a.fill_bits[i] = float_bits(fill)
-        if scale is not None:
-            ops |= _lib.WCUT_SCALE
-            a.scale[i] = float(np.float32(scale))
-        if clip is not None:
-            ops |= _lib.WCUT_CLIP
-            a.clip_lo[i], a.clip_hi[i] = float(clip[0]), float(clip[1])
-        a.ops[i] = ops
+        set_plane_ops(a, i, float_bits(fill) if fill is not None else None, scale, clip)
     a.win, a.win_host = win, win_host
     a.out = out.data_ptr()
     _lib.check(_lib.load().sc_scene_gather_planes(C.byref(a), _lib.stream()))

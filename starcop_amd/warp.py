@@ -22,7 +22,7 @@ import torch
 
 from . import _lib
 from ._lib import check as _check, sc_warp_area_args, sc_warp_args, stream
-from .ortho import _fill_bits, _numpy_dtype
+from .planes import as_planes, chunks, fill_bits, numpy_dtype, per_plane, set_planes
 
 MAX_PLANES = _lib.WARP_MAX_PLANES
 RESAMPLING = {"nearest": _lib.WARP_NEAREST, "bilinear": _lib.WARP_BILINEAR, "average": _lib.WARP_AREA_AVERAGE,
@@ -72,7 +72,7 @@ def crs_kind(code) -> Tuple[int, float, float]:
     return -1, 0.0, 0.0
 
 
-def _crs_pair(src_crs, dst_crs, who):
+def crs_pair(src_crs, dst_crs, who):
     """-> (src code, dst code) for the kernel: (0, 0) when both are None or equal; NotImplementedError for a pair that needs a
     projection other than 4326 <-> UTM"""
     if src_crs is None and dst_crs is None:
@@ -145,7 +145,7 @@ def transform_points(x, y, src_crs, dst_crs):
     longitude from a zone's central meridian, latitudes beyond +-90 and non-finite results come back as NaN.  Equal codes (or None
     on both sides) return the input as float64."""
     x, y = np.broadcast_arrays(np.asarray(x, dtype=np.float64), np.asarray(y, dtype=np.float64))
-    s, d = _crs_pair(src_crs, dst_crs, "transform_points")
+    s, d = crs_pair(src_crs, dst_crs, "transform_points")
     if s == d:
         return x.copy(), y.copy()
     (ks, slon0, sfn), (kd, dlon0, dfn) = crs_kind(s), crs_kind(d)
@@ -168,7 +168,7 @@ def utm_crs_for(lon, lat) -> int:
 
 
 # ---------------------------------------------------------------------------------------------- grids
-def _gt6(gt, who):
+def gt6(gt, who):
     g = [float(v) for v in np.asarray(gt, dtype=np.float64).ravel()]
     if len(g) != 6 or not all(math.isfinite(v) for v in g):
         raise ValueError(f"{who}: a geotransform is 6 finite numbers in GDAL order, got {gt!r}")
@@ -180,7 +180,7 @@ def _gt6(gt, who):
 def invert_geotransform(gt):
     """the affine world -> pixel of a GDAL geotransform, in the same 6-term order: u = inv[0] + x inv[1] + y inv[2],
     v = inv[3] + x inv[4] + y inv[5] (float64)"""
-    x0, a, b, y0, c, d = _gt6(gt, "invert_geotransform")
+    x0, a, b, y0, c, d = gt6(gt, "invert_geotransform")
     det = a * d - b * c
     ia, ib, ic, id_ = d / det, -b / det, -c / det, a / det
     return (-(ia * x0 + ib * y0), ia, ib, -(ic * x0 + id_ * y0), ic, id_)
@@ -203,7 +203,7 @@ def suggest_grid(src_shape, src_gt, src_crs, dst_crs, resolution=None):
     H, W = (int(v) for v in src_shape)
     if H < 1 or W < 1:
         raise ValueError(f"suggest_grid: empty source {src_shape}")
-    gt = _gt6(src_gt, "suggest_grid")
+    gt = gt6(src_gt, "suggest_grid")
     cols = np.concatenate([np.arange(W + 1.0), np.full(H + 1, float(W)), np.arange(W + 1.0), np.zeros(H + 1)])
     rows = np.concatenate([np.zeros(W + 1), np.arange(H + 1.0), np.full(W + 1, float(H)), np.arange(H + 1.0)])
     x, y = transform_points(*apply_geotransform(gt, cols, rows), src_crs, dst_crs)
@@ -227,7 +227,7 @@ def geo_tags(gt, crs) -> Dict[int, tuple]:
     ModelTransformation (34264), and the GeoKeyDirectory (34735) in the layouts ``io_formats.envi_geo_tags`` and
     ``ortho.emit_geo_tags`` write: geographic for 4326, projected with ProjectedCSType = the EPSG code for WGS-84 UTM.  Any other
     ``crs`` (None included) gives no key directory."""
-    x0, a, b, y0, c, d = _gt6(gt, "geo_tags")
+    x0, a, b, y0, c, d = gt6(gt, "geo_tags")
     tags: Dict[int, tuple] = {}
     if b == 0.0 and c == 0.0 and a > 0.0 and d < 0.0:
         tags[33550] = (12, (a, -d, 0.0))
@@ -262,56 +262,50 @@ def transform_polygons(polygons, src_crs, dst_crs):
 
 
 # ---------------------------------------------------------------------------------------------- the device side
-def _launch(planes, nd, bits, src_shape, inv, s_code, d_code, dst_gt, dst_shape, mode, out, coords, oob=None, flags=0):
-    lib = _lib.load()
-    P = len(planes)
-    for p0 in range(0, max(P, 1), MAX_PLANES):
-        n = min(MAX_PLANES, P - p0)
-        a = sc_warp_args()
-        for i in range(6):
-            a.dst_gt[i], a.src_inv[i] = dst_gt[i], inv[i]
-        a.dst_crs, a.src_crs = d_code, s_code
-        a.out_h, a.out_w = dst_shape
-        a.src_h, a.src_w = src_shape
-        a.P, a.elem_bytes, a.resampling = n, nd.itemsize if nd is not None else 0, mode
-        a.flags = flags
-        for k in range(n):
-            t = planes[p0 + k]
-            a.src[k] = t.data_ptr()
-            a.row_stride[k], a.col_stride[k] = t.stride()
-            a.nodata_bits[k] = bits[p0 + k]
-        a.out = out[p0].data_ptr() if n else None
-        a.coords = coords.data_ptr() if coords is not None and p0 == 0 else None      # the coordinates are the same for every chunk
-        a.oob_count = oob.data_ptr() if oob is not None and p0 == 0 else None
-        _check(lib.sc_warp(a, stream()))
+def _grid_pair(who, src_gt, src_crs, dst_gt, dst_crs, dst_shape):
+    """the checked grid pair of a call -> (inverse source affine, source code, destination code, destination affine, (H_d, W_d))"""
+    s_code, d_code = crs_pair(src_crs, dst_crs, who)
+    return invert_geotransform(src_gt), s_code, d_code, gt6(dst_gt, who), dst_grid_shape(dst_shape, who)
 
 
-def _area_args(src_shape, inv, s_code, d_code, dst_gt, dst_shape, variant):
-    a = sc_warp_area_args()
-    for i in range(6):
-        a.dst_gt[i], a.src_inv[i] = dst_gt[i], inv[i]
-    a.dst_crs, a.src_crs = d_code, s_code
-    a.out_h, a.out_w = dst_shape
+def _grid_args(cls, grid, src_shape):
+    """a ``cls`` (sc_warp_args or sc_warp_area_args: the fields of the grid pair have one name in both) for a :func:`_grid_pair`"""
+    a = cls()
+    a.src_inv[:], a.src_crs, a.dst_crs, a.dst_gt[:], (a.out_h, a.out_w) = grid
     a.src_h, a.src_w = src_shape
-    if variant not in AREA_VARIANTS:
-        raise ValueError(f"variant {variant!r}; expected None (chosen by the library), 'thread' or 'lanes'")
-    a.variant = AREA_VARIANTS[variant]
     return a
 
 
-def _launch_area(planes, nd, bits, src_shape, inv, s_code, d_code, dst_gt, dst_shape, mode, min_coverage, out, cov, boxes, variant):
+def _chunk_args(cls, grid, src_shape, planes, nd, bits, out, p0, n):
+    """... and the planes [p0, p0 + n) of a call with their no-data patterns and their part of ``out``"""
+    a = _grid_args(cls, grid, src_shape)
+    a.P, a.elem_bytes = n, nd.itemsize if n else 0
+    set_planes(a, planes, p0)
+    a.nodata_bits[:n] = bits[p0:p0 + n]
+    a.out = out[p0].data_ptr() if n else None
+    return a
+
+
+def _launch(grid, src_shape, planes, nd, bits, mode, out, coords, flags=0):
     lib = _lib.load()
-    P = len(planes)
-    for p0 in range(0, max(P, 1), MAX_PLANES):
-        n = min(MAX_PLANES, P - p0)
-        a = _area_args(src_shape, inv, s_code, d_code, dst_gt, dst_shape, variant)
-        a.P, a.elem_bytes, a.mode, a.min_coverage = n, nd.itemsize if nd is not None else 0, mode, min_coverage
-        for k in range(n):
-            t = planes[p0 + k]
-            a.src[k] = t.data_ptr()
-            a.row_stride[k], a.col_stride[k] = t.stride()
-            a.nodata_bits[k] = bits[p0 + k]
-        a.out = out[p0].data_ptr() if n else None
+    for p0, n in chunks(len(planes), MAX_PLANES):
+        a = _chunk_args(sc_warp_args, grid, src_shape, planes, nd, bits, out, p0, n)
+        a.resampling, a.flags = mode, flags
+        a.coords = coords.data_ptr() if coords is not None and p0 == 0 else None      # the coordinates are the same for every chunk
+        _check(lib.sc_warp(a, stream()))
+
+
+def _variant_code(variant):
+    if variant not in AREA_VARIANTS:
+        raise ValueError(f"variant {variant!r}; expected None (chosen by the library), 'thread' or 'lanes'")
+    return AREA_VARIANTS[variant]
+
+
+def _launch_area(grid, src_shape, planes, nd, bits, mode, min_coverage, out, cov, boxes, variant):
+    lib = _lib.load()
+    for p0, n in chunks(len(planes), MAX_PLANES):
+        a = _chunk_args(sc_warp_area_args, grid, src_shape, planes, nd, bits, out, p0, n)
+        a.mode, a.min_coverage, a.variant = mode, min_coverage, _variant_code(variant)
         a.coverage = cov[p0].data_ptr() if cov is not None and n else None
         a.boxes = boxes.data_ptr() if boxes is not None and p0 == 0 else None        # the boxes are the same for every chunk
         _check(lib.sc_warp_area(a, stream()))
@@ -325,7 +319,7 @@ def _area_dtype_check(resampling, dt):
         raise ValueError(f"reproject: {resampling} resampling is defined for {' and '.join(ok)}, not {name}")
 
 
-def _dst_shape(shape, who):
+def dst_grid_shape(shape, who):
     H, W = (int(v) for v in shape)
     if H < 1 or W < 1 or H * W >= 2 ** 31:
         raise ValueError(f"{who}: destination shape {tuple(shape)} (at least 1 x 1, fewer than 2^31 pixels)")
@@ -365,57 +359,28 @@ def reproject(data, src_gt, src_crs, dst_gt, dst_crs, dst_shape, resampling="nea
     min_coverage = float(min_coverage)
     if not 0.0 <= min_coverage <= 1.0:
         raise ValueError(f"reproject: min_coverage {min_coverage!r} outside [0, 1]")
-    s_code, d_code = _crs_pair(src_crs, dst_crs, "reproject")
-    inv, dgt = invert_geotransform(src_gt), _gt6(dst_gt, "reproject")
-    Hd, Wd = _dst_shape(dst_shape, "reproject")
-    host = isinstance(data, np.ndarray)
-    if host:
-        if resampling == "bilinear" and data.dtype != np.float32:
-            raise ValueError(f"reproject: bilinear resampling is defined for float32, not {data.dtype}")
-        if area:
-            _area_dtype_check(resampling, data.dtype)
-        _lib.require_device()
-        data = torch.from_numpy(data if all(s >= 0 for s in data.strides) else np.ascontiguousarray(data)).cuda()
-    single = False
-    if isinstance(data, (list, tuple)):
-        planes = [torch.as_tensor(p) for p in data]
-        if not planes or any(p.dim() != 2 for p in planes):
-            raise ValueError("reproject: a list must hold at least one 2-D tensor")
-    elif isinstance(data, torch.Tensor) and data.dim() == 2:
-        planes, single = [data], True
-    elif isinstance(data, torch.Tensor) and data.dim() == 3 and data.shape[0] >= 1:
-        planes = list(data.unbind(0))
-    else:
-        raise ValueError("reproject: expected a tensor (H, W) or (P, H, W), a numpy array or a list of 2-D tensors, got "
-                         + (str(tuple(data.shape)) if isinstance(data, torch.Tensor) else type(data).__name__))
-    dt, dev, shape = planes[0].dtype, planes[0].device, tuple(planes[0].shape)
-    if any(p.dtype != dt or p.device != dev or tuple(p.shape) != shape for p in planes):
-        raise ValueError("reproject: all planes of a call share one dtype, device and shape")
-    if resampling == "bilinear" and dt != torch.float32:
-        raise ValueError(f"reproject: bilinear resampling is defined for float32, not {dt}")
+    grid = _grid_pair("reproject", src_gt, src_crs, dst_gt, dst_crs, dst_shape)
+    planes, single, host = as_planes(data, "reproject")
+    dt, shape = planes[0].dtype, tuple(planes[0].shape)
+    if resampling == "bilinear" and dt != torch.float32:       # a numpy input is named as numpy names it
+        raise ValueError(f"reproject: bilinear resampling is defined for float32, not {str(dt).replace('torch.', '') if host else dt}")
     if area:
         _area_dtype_check(resampling, dt)
-    nd = _numpy_dtype(dt)
+    nd = numpy_dtype(dt, "reproject")
     if shape[0] < 1 or shape[1] < 1:
         raise ValueError(f"reproject: empty source {shape}")
-    if any(s < 0 for p in planes for s in p.stride()):
-        raise ValueError("reproject: negative strides are not supported")
     P = len(planes)
-    if isinstance(nodata, (list, tuple, np.ndarray)) and np.ndim(nodata) == 1:
-        fills = list(nodata)
-        if len(fills) != P:
-            raise ValueError(f"reproject: {len(fills)} nodata values for {P} planes")
-    else:
-        fills = [0 if nodata is None else nodata] * P
-    bits = [_fill_bits(v, nd) for v in fills]
-    _lib.require_device(planes[0])
-    out = torch.empty((P, Hd, Wd), dtype=dt, device=dev)
-    cov = torch.empty((P, Hd, Wd), dtype=torch.float32, device=dev) if return_coverage else None
+    bits = [fill_bits(v, nd, "reproject") for v in per_plane(nodata, P, "reproject", "nodata values", default=0)]
+    _lib.require_device(None if host else planes[0])
+    if host:
+        planes = [p.cuda() for p in planes]
+    dev = planes[0].device
+    out = torch.empty((P, *grid[4]), dtype=dt, device=dev)
+    cov = torch.empty_like(out, dtype=torch.float32) if return_coverage else None
     if area:
-        _launch_area(planes, nd, bits, shape, inv, s_code, d_code, dgt, (Hd, Wd), RESAMPLING[resampling], min_coverage, out, cov, None,
-                     variant)
+        _launch_area(grid, shape, planes, nd, bits, RESAMPLING[resampling], min_coverage, out, cov, None, variant)
     else:
-        _launch(planes, nd, bits, shape, inv, s_code, d_code, dgt, (Hd, Wd), RESAMPLING[resampling], out, None)
+        _launch(grid, shape, planes, nd, bits, RESAMPLING[resampling], out, None)
     res = [t[0] if single else t for t in ((out, cov) if return_coverage else (out,))]
     res = [t.cpu().numpy() if host else t for t in res]
     return tuple(res) if return_coverage else res[0]
@@ -426,13 +391,11 @@ def source_coords(dst_shape, dst_gt, dst_crs, src_gt, src_crs, src_shape=None, d
     (2, H, W), u along columns and v along rows of the source (pixel (row, col) covers [col, col + 1) x [row, row + 1)).  With
     ``src_shape=(H_s, W_s)`` pixels outside the source are NaN, as they are no-data in :func:`reproject`; without it only points
     the projection cannot place are."""
-    s_code, d_code = _crs_pair(src_crs, dst_crs, "source_coords")
-    inv, dgt = invert_geotransform(src_gt), _gt6(dst_gt, "source_coords")
-    Hd, Wd = _dst_shape(dst_shape, "source_coords")
+    grid = _grid_pair("source_coords", src_gt, src_crs, dst_gt, dst_crs, dst_shape)
     _lib.require_device()
-    coords = torch.empty((2, Hd, Wd), dtype=torch.float64, device=device)
+    coords = torch.empty((2, *grid[4]), dtype=torch.float64, device=device)
     shape = (1, 1) if src_shape is None else tuple(int(v) for v in src_shape)
-    _launch([], None, [], shape, inv, s_code, d_code, dgt, (Hd, Wd), 0, None, coords, flags=_lib.WARP_UNBOUNDED if src_shape is None else 0)
+    _launch(grid, shape, [], None, [], 0, None, coords, flags=_lib.WARP_UNBOUNDED if src_shape is None else 0)
     return coords
 
 
@@ -440,20 +403,17 @@ def source_boxes(dst_shape, dst_gt, dst_crs, src_gt, src_crs, device="cuda", var
     """The footprint of every destination pixel in source pixel coordinates, as the kernel of the footprint modes computes it: device
     float64 (4, H, W) = u0, u1, v0, v1, the axis-aligned bounding box of the pixel's four projected corners, NOT clipped to the
     source; NaN where a corner has no coordinates.  The counterpart of :func:`source_coords`."""
-    s_code, d_code = _crs_pair(src_crs, dst_crs, "source_boxes")
-    inv, dgt = invert_geotransform(src_gt), _gt6(dst_gt, "source_boxes")
-    Hd, Wd = _dst_shape(dst_shape, "source_boxes")
+    grid = _grid_pair("source_boxes", src_gt, src_crs, dst_gt, dst_crs, dst_shape)
     _lib.require_device()
-    boxes = torch.empty((4, Hd, Wd), dtype=torch.float64, device=device)
-    _launch_area([], None, [], (1, 1), inv, s_code, d_code, dgt, (Hd, Wd), 0, 0.0, None, None, boxes, variant)
+    boxes = torch.empty((4, *grid[4]), dtype=torch.float64, device=device)
+    _launch_area(grid, (1, 1), [], None, [], 0, 0.0, None, None, boxes, variant)
     return boxes
 
 
 def area_variant(dst_shape, dst_gt, dst_crs, src_gt, src_crs) -> str:
     """the mapping the library chooses for the footprint modes on a grid pair: ``"thread"`` (one thread per destination pixel; boxes of
     a few source pixels) or ``"lanes"`` (16 lanes along the source columns of one pixel's box).  Host only."""
-    s_code, d_code = _crs_pair(src_crs, dst_crs, "area_variant")
-    a = _area_args((1, 1), invert_geotransform(src_gt), s_code, d_code, _gt6(dst_gt, "area_variant"), _dst_shape(dst_shape, "area_variant"), None)
+    a = _grid_args(sc_warp_area_args, _grid_pair("area_variant", src_gt, src_crs, dst_gt, dst_crs, dst_shape), (1, 1))
     rc = _lib.load().sc_warp_area_variant(a)
     if rc < 0:
         _check(rc)

@@ -30,6 +30,7 @@ import torch
 from . import _lib, aviris, mask_creation
 from . import io_formats as io
 from ._lib import check, sc_wcut_args, stream
+from .planes import chunks, match_bits, set_plane_ops, set_planes
 from .sampling import _nodata, _rchw
 
 NOUT_MAX = _lib.WCUT_MAX_PLANES
@@ -124,23 +125,6 @@ class Plane(NamedTuple):
     clip: Optional[Tuple[float, float]] = None
 
 
-def _fill_bits(value, nd) -> Optional[int]:
-    """bit pattern of a fill value in dtype ``nd``, or None when no element of that dtype can equal it"""
-    f = float(value)
-    if nd.kind in "iu":
-        info = np.iinfo(nd)
-        if f != f or f != int(f) or not info.min <= int(f) <= info.max:
-            return None
-        a = np.array(int(f), dtype=nd)
-    else:
-        if f != f:
-            return None
-        a = np.array(f, dtype=nd)
-        if float(a) != f:
-            return None
-    return int(a.reshape(1).view(f"u{nd.itemsize}")[0])
-
-
 def window_cut(planes: Sequence[Plane], offsets, out_size: Tuple[int, int], scene_shape: Optional[Tuple[int, int]] = None):
     """``sc_window_cut``: cut ``len(offsets)`` windows of ``out_size`` = (height, width) at ``offsets`` = [(row_off, col_off)]
     out of the planes -> dense device tensor (n_win, P, height, width) in the planes' dtype (one dtype of 1, 2 or 4 bytes per
@@ -169,32 +153,18 @@ def window_cut(planes: Sequence[Plane], offsets, out_size: Tuple[int, int], scen
     if scene_shape is None:
         scene_shape = (max(p.row0 + p.data.shape[0] for p in planes), max(p.col0 + p.data.shape[1] for p in planes))
     n = off.shape[0]
+    data = [p.data for p in planes]
     outs = []
-    for p0 in range(0, len(planes), NOUT_MAX):
-        part = planes[p0:p0 + NOUT_MAX]
-        out = torch.empty((n, len(part), oh, ow), dtype=dt, device=dev)
+    for p0, count in chunks(len(planes), NOUT_MAX):
+        out = torch.empty((n, count, oh, ow), dtype=dt, device=dev)
         a = sc_wcut_args()
         a.scene_rows, a.scene_cols, a.out_h, a.out_w = int(scene_shape[0]), int(scene_shape[1]), oh, ow
-        a.P, a.elem_bytes, a.n_win = len(part), nd.itemsize, n
+        a.P, a.elem_bytes, a.n_win = count, nd.itemsize, n
         a.win_off, a.win_off_host = off_d.data_ptr(), off.ctypes.data
-        for k, p in enumerate(part):
-            t = p.data
-            a.src[k] = t.data_ptr()
-            a.row_stride[k], a.col_stride[k] = t.stride()
+        set_planes(a, data, p0, rows=a.rows, cols=a.cols)
+        for k, p in enumerate(planes[p0:p0 + count]):
             a.row0[k], a.col0[k] = int(p.row0), int(p.col0)
-            a.rows[k], a.cols[k] = t.shape
-            ops = 0
-            bits = _fill_bits(p.fill, nd) if p.fill is not None else None
-            if bits is not None:
-                ops |= _lib.WCUT_FILL
-                a.fill_bits[k] = bits
-            if p.scale is not None:
-                ops |= _lib.WCUT_SCALE
-                a.scale[k] = float(np.float32(p.scale))
-            if p.clip is not None:
-                ops |= _lib.WCUT_CLIP
-                a.clip_lo[k], a.clip_hi[k] = float(np.float32(p.clip[0])), float(np.float32(p.clip[1]))
-            a.ops[k] = ops
+            set_plane_ops(a, k, match_bits(p.fill, nd) if p.fill is not None else None, p.scale, p.clip)
         a.out = out.data_ptr()
         check(lib.sc_window_cut(a, stream()))
         outs.append(out)

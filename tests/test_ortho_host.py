@@ -129,12 +129,12 @@ def test_wrapper_argument_checks_need_no_device():
 def test_oracle_is_the_restated_gather_and_fill_patterns_agree():
     """the oracle against a plain loop over the definition (1-based indices, 0 = no data, absolute for signed tables), and the
     bit patterns the wrapper hands the kernel for a fill value against what the oracle's np.full holds"""
-    from starcop_amd import ortho
+    from starcop_amd import planes
     for dt, fills in (("float32", [-9999.0, float("nan"), -0.0, np.float32(1e-40)]), ("float64", [-9999.0, float("nan"), -0.0]),
                       ("uint8", [0, 255, 7.0]), ("int16", [-9999, -9999.0, 32767]), ("int32", [-9999.0, -2 ** 31])):
         for f in fills:
             held = np.full((1,), f, dtype=dt)
-            assert ortho._fill_bits(f, np.dtype(dt)) == int(held.view(f"u{held.itemsize}")[0]), (dt, f)
+            assert planes.fill_bits(f, np.dtype(dt), "georeference") == int(held.view(f"u{held.itemsize}")[0]), (dt, f)
     rng = np.random.default_rng(3)
     src = rng.standard_normal((5, 7)).astype(np.float32)
     gx, gy = U.random_glt(rng, (6, 9), 5, 7, p_nodata=0.3)
