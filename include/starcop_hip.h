@@ -1524,6 +1524,52 @@ typedef struct sc_cradial_args {
 size_t sc_component_radial_workspace_bytes(int N, int H, int W, int M, int K);
 int sc_component_radial(const sc_cradial_args* a, void* work, size_t work_bytes, sc_stream stream);
 
+/* Exact order statistics per component: the ring median, the MAD and the percentiles of a plume's own pixels
+ * (starcop_amd/plumes.py: component_quantiles, component_median_mad).  labels, counts, M and the rows are those of
+ * sc_component_stats: component k of image n is the set of pixels of labels[n] with value k, 1 <= k <= min(counts[n], M), connected
+ * or not (a ring label image is an ordinary input); values outside that range are ignored and never index memory.
+ * The plane of image n is the dense H x W float32 block at plane + n*plane_stride (elements), read in place.  The value of a pixel
+ * is t = v without `center`, and t = |v - center[n*M + k-1]| with it (device float32 [N][M]; the subtraction rounded once to
+ * float32).  The MEMBERS of a component are its pixels with finite t: NaN and +-inf are dropped, and so is every pixel of a row
+ * whose centre is not finite.
+ * Per row n*M + k-1:  n_finite (int64) the number of members;  quantile[(n*M + k-1)*Q + j] (float32) order statistic j of them.
+ * No member, or a row at or above counts[n]: n_finite 0 and NaN quantiles.
+ * q[j], j < Q (1 <= Q <= SC_CQUANT_MAX_Q), is the fraction float32(percent) / float32(100) in [0, 1], a negative entry asks for
+ * the median.  With n members sorted ascending as s (the rule of sc_window_stats: what numpy >= 2.0 evaluates for float32 data):
+ *   percentile: vi = float32(n - 1) * q[j], lo = min(floor(vi), n-1), hi = min(lo+1, n-1), g = vi - floor(vi) (0 when n = 1),
+ *               d = s[hi] - s[lo], result s[lo] + d * g, or s[hi] - d * (1 - g) where g >= 0.5;
+ *   median:     (s[(n-1)/2] + s[n/2]) / 2;
+ * every operation rounded to float32, none fused.  The sign of a zero result is unspecified (-0.0 and +0.0 are equal values).
+ * Keys are the monotone map of the float bits (sign bit flipped for non-negatives, all bits inverted for negatives), so values of
+ * both signs are ordered.  Members are counted per row, every row takes a contiguous segment of a key buffer, the keys are
+ * scattered into the segments, and then a segment of at most 64 keys is sorted by one wave, one of at most SC_CQUANT_SMALL_MAX keys
+ * in LDS by one work-group, and the larger ones go through a four-pass 8-bit radix select over their contiguous keys, all 2 Q
+ * ranks of a segment together.
+ * Integer atomics only (counters, slots, histograms), no floating-point atomics, and the selection is exact: repeated calls give
+ * identical bytes and an image gives the same bytes alone and inside any batch.  13 launches and one clear per call (5 when no
+ * image can hold a segment above SC_CQUANT_SMALL_MAX).
+ * N <= 65535, H*W < 2^31, N*H*W < 2^32, N*M < 2^31, M >= 0 (M = 0: nothing launched); SC_ERR_ARG, before any launch, for bad dims,
+ * Q out of range, a q entry above 1 or NaN, a null pointer, a plane stride below H*W in a batch or a workspace that is too small.
+ * work: sc_component_quantiles_workspace_bytes(N, H, W, M, Q) bytes: with L = min(N*M, N*H*W / (SC_CQUANT_SMALL_MAX + 1)) the most
+ * large segments the images can hold, 4 bytes per pixel (keys) + 12 bytes per row (count, slot cursor, segment start) +
+ * L * (1 KiB + 16 KiB histograms + 272 bytes of state) + 8 bytes * (N*H*W / 4096 + L) work items, each part rounded up to 256
+ * bytes, + 256: about 8 bytes per pixel and 12 per row.                                                                        */
+#define SC_CQUANT_MAX_Q 8
+#define SC_CQUANT_SMALL_MAX 4096
+typedef struct sc_cquant_args {
+  const int32_t* labels;                          /* [N][H][W] device                                              */
+  const int32_t* counts;                          /* [N] device                                                    */
+  int32_t N, H, W, M, Q, reserved;
+  const float* plane;                             /* element (0, 0) of image 0                                     */
+  int64_t plane_stride;                           /* elements between images                                       */
+  const float* center;                            /* [N][M] device, or NULL                                        */
+  float q[SC_CQUANT_MAX_Q];                       /* host values: fractions in [0, 1]; negative = median           */
+  int64_t* n_finite;                              /* [N][M] device                                                 */
+  float* quantile;                                /* [N][M][Q] device                                              */
+} sc_cquant_args;
+size_t sc_component_quantiles_workspace_bytes(int N, int H, int W, int M, int Q);
+int sc_component_quantiles(const sc_cquant_args* a, void* work, size_t work_bytes, sc_stream stream);
+
 /* Outlines of the components of a label image: polygon rings per plume (starcop_amd/plumes.py: component_outlines).  labels is
  * one int32 H x W image, 0 (and anything below) background, component k the pixels of value k.  The outline of k is made of
  * directed unit edges on the (H+1) x (W+1) lattice of pixel corners (corner (r, c) = the upper-left corner of pixel (r, c)),

@@ -298,6 +298,17 @@ class sc_cradial_args(C.Structure):
                 ("sum_cc", C.c_void_p), ("sum_rc", C.c_void_p)]
 
 
+CQUANT_MAX_Q, CQUANT_SMALL_MAX = 8, 4096
+
+
+class sc_cquant_args(C.Structure):
+    """per-component order statistics operands (include/starcop_hip.h: sc_cquant_args)"""
+    _fields_ = [("labels", C.c_void_p), ("counts", C.c_void_p),
+                ("N", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("M", C.c_int32), ("Q", C.c_int32), ("reserved", C.c_int32),
+                ("plane", C.c_void_p), ("plane_stride", C.c_int64), ("center", C.c_void_p),
+                ("q", C.c_float * CQUANT_MAX_Q), ("n_finite", C.c_void_p), ("quantile", C.c_void_p)]
+
+
 OUTLINE_COUNT, OUTLINE_TRACE,OUTLINE_RINGS, OUTLINE_SCATTER, OUTLINE_COMPACT = range(5)       # enum sc_outline_stage
 
 
@@ -538,6 +549,8 @@ SIGNATURES = {
     "sc_component_stats": (_i, [C.POINTER(sc_cstats_args), _vp, _sz, _vp]),
     "sc_component_radial_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
     "sc_component_radial": (_i, [C.POINTER(sc_cradial_args), _vp, _sz, _vp]),
+    "sc_component_quantiles_workspace_bytes": (_sz, [_i, _i, _i, _i, _i]),
+    "sc_component_quantiles": (_i, [C.POINTER(sc_cquant_args), _vp, _sz, _vp]),
     "sc_component_outlines_workspace_bytes": (_sz, [_i, _i, C.c_int64]),
     "sc_component_outlines_rounds": (_i, [C.c_int64]),
     "sc_component_outlines": (_i, [C.POINTER(sc_outline_args), _i, _vp]),

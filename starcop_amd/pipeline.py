@@ -286,7 +286,8 @@ def emit_granule_predict(model, nc_path, column_step=2, num_iter=30, covariance_
     ``min_area``, ``exclude``, ``exclude_buffer_px``, ``connectivity`` -- applied to ``pred_binary`` on the product grid (after the
     regrid) and before the annotations and the files, which then all describe the cleaned mask; ``out["clean"]`` has the pixel
     counts.  ``match_tolerance_px``: the ``tolerance_px`` of the match against ``label_polygons``.  ``plume_background``
-    (``{"ring_px": .., "gap_px": ..}``) adds the background-ring columns of ``plumes.plume_table`` to the plume table.
+    (``{"ring_px": .., "gap_px": .., "stat": "mean" | "median"}``) adds the background-ring columns of ``plumes.plume_table`` to the plume table
+    (``stat="median"``: its ``background_stat``, the ring median and the noise columns).
     ``plume_quantify`` (the ``quantify=`` dict of ``plumes.plume_table``: ``wind_speed_m_s``, ...) adds its shape, mass and
     emission-rate columns to the plume table, ``plumes.csv`` and the GeoJSON properties; it needs mag1c and a metric grid
     (``crs="utm"``: on the granule's longitude / latitude grid it is a ValueError).  The defaults add nothing."""
@@ -511,7 +512,8 @@ def aviris_scene_predict(model, aviris_img_folder, out_folder=None, mag1c_path=N
     files: ``predbinary.tif``, ``plumes.csv``, ``plumes.geojson`` and ``plume_match`` describe the cleaned mask, ``pred.tif`` is
     untouched, ``out["clean"]`` has the pixel counts.  ``match_tolerance_px``: the ``tolerance_px`` of the match against
     ``label_polygons``.  ``plume_background``
-    (``{"ring_px": .., "gap_px": ..}``) adds the background-ring columns of ``plumes.plume_table`` to the plume table.
+    (``{"ring_px": .., "gap_px": .., "stat": "mean" | "median"}``) adds the background-ring columns of ``plumes.plume_table`` to the plume table
+    (``stat="median"``: its ``background_stat``, the ring median and the noise columns).
     ``plume_quantify`` (the ``quantify=`` dict of ``plumes.plume_table``: ``wind_speed_m_s``, ...) adds its shape, mass and
     emission-rate columns to the plume table, ``plumes.csv`` and the GeoJSON properties; it needs mag1c and a metric grid
     (a UTM ``map info``).  The defaults add nothing and change no byte."""
@@ -630,8 +632,9 @@ def mosaic_products(folders, out_folder, crs=None, resolution=None, rule="max", 
     of ``products.write_annotations``, made on the mosaic: a plume in the overlap of two scenes is one row.  No-data of the float
     rasters is each file's GDAL_NODATA of the first folder (default -9999).  ``clean`` (a dict of :func:`starcop_amd.products.clean`
     keyword arguments) cleans the mosaicked mask before the annotations and the files; ``match_tolerance_px`` is the
-    ``tolerance_px`` of the match against ``label_polygons``; ``plume_background`` (``{"ring_px": .., "gap_px": ..}``) adds the
-    background-ring columns of ``plumes.plume_table`` and needs the ``mf`` product among the folders';
+    ``tolerance_px`` of the match against ``label_polygons``; ``plume_background`` (``{"ring_px": .., "gap_px": .., "stat": "mean" | "median"}``) adds the
+    background-ring columns of ``plumes.plume_table`` (``stat="median"``: its ``background_stat``, the ring median and the noise
+    columns) and needs the ``mf`` product among the folders';
     ``plume_quantify`` (the ``quantify=`` dict of ``plumes.plume_table``: ``wind_speed_m_s``, ...) adds its shape, mass and
     emission-rate columns to the plume table, ``plumes.csv`` and the GeoJSON properties; it needs mag1c and a metric grid
     (a UTM ``crs``).  -> the dict of ``products.mosaic`` with ``files``."""

@@ -106,6 +106,117 @@ def _operands(planes, other):
     return ops, oth
 
 
+MAX_QUANTILES = _lib.CQUANT_MAX_Q
+BACKGROUND_STATS = ("mean", "median")
+MAD_TO_SIGMA = 1.4826          # sigma of a normal distribution = 1.4826 * its median absolute deviation
+
+
+def quantile_fractions(q, who):
+    """the ``q`` of ``component_quantiles`` -> the float32 fractions the kernel takes: ``float32(q_j) / float32(100)``, the quantile
+    numpy >= 2.0 forms for float32 data, and -1 for ``"median"``.  ValueError for an empty ``q``, more than 8 entries, a number
+    outside [0, 100] or NaN, or any other string.  No device involved."""
+    if isinstance(q, (str, bytes)) or not hasattr(q, "__len__"):
+        raise ValueError(f"{who}: q {q!r} must be a sequence of percentages in [0, 100] and / or \"median\"")
+    if not 1 <= len(q) <= MAX_QUANTILES:
+        raise ValueError(f"{who}: {len(q)} quantiles, 1 to {MAX_QUANTILES} per call")
+    out = []
+    for v in q:
+        if isinstance(v, str):
+            if v != "median":
+                raise ValueError(f"{who}: q entry {v!r} (a percentage in [0, 100] or \"median\")")
+            out.append(np.float32(-1.0))
+            continue
+        try:
+            f = float(v)
+        except (TypeError, ValueError):
+            raise ValueError(f"{who}: q entry {v!r} (a percentage in [0, 100] or \"median\")") from None
+        if not 0.0 <= f <= 100.0:                      # NaN fails both comparisons
+            raise ValueError(f"{who}: q entry {v!r} is outside [0, 100]")
+        out.append(np.float32(f) / np.float32(100))
+    return out
+
+
+def quantile_names(q, prefix="mag1c"):
+    """column names of the ``percentiles=`` of ``plume_table``: ``f"{prefix}_p{q:g}"``, ``f"{prefix}_median"`` for ``"median"``"""
+    return [f"{prefix}_median" if isinstance(v, str) else f"{prefix}_p{float(v):g}" for v in q]
+
+
+def component_quantiles(labels, counts, plane, q=("median",), center=None, M=None):
+    """Exact order statistics of one plane per labelled component in one ``sc_component_quantiles`` call.
+
+    ``labels``, ``counts``, ``M`` as ``component_stats`` takes them (they need not come from that call: the ring labels of
+    ``background_rings`` are an ordinary input).  ``plane``: one float32 tensor of the shape of ``labels``, read in place where its
+    H x W planes are dense.  ``q``: 1 to 8 entries, each a percentage in [0, 100] or the string ``"median"``.  ``center``: an optional
+    device float32 (N, M); with it the value of a pixel of component k is ``|v - center[n, k-1]|`` (rounded once to float32), which
+    makes the median of the result the median absolute deviation about ``center``.  A bad ``q``, a shape mismatch or a non-tensor
+    ``labels`` is a ValueError before the device is required.
+
+    Over the pixels of each component whose value is finite (NaN and +-inf are dropped, and every pixel of a row whose centre is
+    not finite) returns ``{"n_finite": (N, M) int64, "quantile": (N, M, Q) float32}`` on the device: what ``np.percentile(values,
+    q_j)`` and ``np.median(values)`` of numpy >= 2.0 give for the float32 values, bit for bit (the sign of a zero aside); NaN and
+    0 for a component without such a pixel and for rows at or above ``counts[n]``.  Exact selection with integer atomics only:
+    repeated calls, and an image alone or in a batch, give identical bytes."""
+    who = "component_quantiles"
+    fr = quantile_fractions(q, who)
+    if not isinstance(labels, torch.Tensor) or not isinstance(plane, torch.Tensor):
+        raise ValueError(f"{who}: labels and plane must be device tensors (plume_table takes numpy masks)")
+    lab = _as_batch(labels, f"{who}: labels")
+    N, H, W = lab.shape
+    pl = _as_batch(plane, f"{who}: plane")
+    if tuple(pl.shape) != (N, H, W):
+        raise ValueError(f"{who}: plane has shape {tuple(pl.shape)}, labels {(N, H, W)}")
+    if isinstance(counts, int):
+        counts = torch.tensor([counts], dtype=torch.int32)
+    counts = counts.reshape(-1)
+    if counts.numel() != N:
+        raise ValueError(f"{who}: {counts.numel()} counts for {N} images")
+    if center is not None:
+        if not isinstance(center, torch.Tensor) or center.dim() != 2 or center.shape[0] != N or center.dtype != torch.float32:
+            raise ValueError(f"{who}: center must be a float32 tensor of shape ({N}, M)")
+        if M is not None and center.shape[1] != int(M):
+            raise ValueError(f"{who}: center has shape {tuple(center.shape)}, expected {(N, int(M))}")
+        M = center.shape[1]
+    _lib.require_device(lab)
+    lib = _lib.load()
+    if lab.dtype != torch.int32:
+        lab = lab.to(torch.int32)
+    lab = lab.contiguous()
+    counts = counts.to(device=lab.device, dtype=torch.int32).contiguous()
+    if M is None:
+        M = max(int(counts.max().item()), 0)
+    M, Q = int(M), len(fr)
+    (op, stride), = _operands([pl], None)[0]          # holds the tensor the pointer belongs to until the call is enqueued
+    _lib.require_device(op)
+    a = _lib.sc_cquant_args()
+    a.labels, a.counts, a.N, a.H, a.W, a.M, a.Q = lab.data_ptr(), counts.data_ptr(), N, H, W, M, Q
+    a.plane, a.plane_stride = op.data_ptr(), stride
+    if center is not None:
+        center = center.to(lab.device).contiguous()
+        _lib.require_device(center)
+        a.center = center.data_ptr() if center.numel() else None
+    for j, f in enumerate(fr):
+        a.q[j] = float(f)
+    out = {"n_finite": torch.empty((N, M), dtype=torch.int64, device=lab.device),
+           "quantile": torch.empty((N, M, Q), dtype=torch.float32, device=lab.device)}
+    a.n_finite, a.quantile = (t.data_ptr() if t.numel() else None for t in out.values())
+    wb = lib.sc_component_quantiles_workspace_bytes(N, H, W, M, Q)      # 0 for bad dims: the call then raises with the message
+    work = torch.empty(max(wb, 1), dtype=torch.uint8, device=lab.device)
+    check(lib.sc_component_quantiles(a, ptr(work), wb, stream()))
+    return out
+
+
+def component_median_mad(labels, counts, plane, M=None):
+    """Median and median absolute deviation of one plane per labelled component: ``component_quantiles`` twice, the second call
+    with the medians of the first as ``center``; nothing is read back in between (with ``M`` given, nothing at all).  Returns
+    ``{"n_finite": (N, M) int64, "median": (N, M) float32, "mad": (N, M) float32}`` on the device: ``np.median(v)`` and
+    ``np.median(np.abs(v - np.median(v)))`` over the finite values v of each component, NaN where there is none.  (A component
+    whose values overflow float32 in ``v - median`` loses those pixels from the MAD, as numpy's ``isfinite`` filter would.)"""
+    first = component_quantiles(labels, counts, plane, ("median",), M=M)
+    med = first["quantile"][..., 0].contiguous()
+    second = component_quantiles(labels, counts, plane, ("median",), center=med, M=med.shape[1])
+    return {"n_finite": first["n_finite"], "median": med, "mad": second["quantile"][..., 0].contiguous()}
+
+
 RADIAL_FIELDS = ("bin_count", "bin_sum", "d2_max", "sum_rr", "sum_cc", "sum_rc")
 MAX_RADII = _lib.CRADIAL_MAX_BINS
 
@@ -221,17 +332,25 @@ def _read_back_radial(rad, origins):
 
 
 def table_from_stats(stats, counts, width, plane_names=(), with_other=False, min_area=1, geotransform=None, pixel_area_m2=None,
-                     ring_stats=None, quantify=None):
+                     ring_stats=None, quantify=None, ring_quantiles=None, plume_quantiles=None):
     """The DataFrame of ``plume_table`` from host copies of the ``component_stats`` columns (numpy, (N, M) and (N, M, P)),
     ``counts`` (N,) and the image width (for the row / column of ``argmax``).  ``plane_names``: which of ``"mag1c"``, ``"prob"``
     the P planes are, in order.  ``ring_stats``: the same columns reduced over the background-ring labels (``background_rings``)
     with mag1c as plane 0, for the ring columns of ``plume_table``; it needs ``"mag1c"`` among the planes.  ``quantify``: for the
     quantification columns of ``plume_table``, a dict with ``settings`` (the checked ``quantify=`` dict), ``radii_m``,
     ``pixel_size_m`` and ``radial`` (host copies of the ``component_radial`` columns and ``origin``, (N, M, ..)); the per-plume
-    curves of ``fetch_profiles`` are left under its key ``curves``.  It needs mag1c as well.  No device involved."""
+    curves of ``fetch_profiles`` are left under its key ``curves``.  It needs mag1c as well.  ``ring_quantiles``: for
+    ``background_stat="median"``, host copies of the ``component_median_mad`` columns of mag1c over the ring labels (``median``,
+    ``mad``, (N, M)); it needs ``ring_stats``, and the median then is the background that is subtracted.  ``plume_quantiles``: for
+    ``percentiles=``, a dict with ``q`` (the sequence) and ``quantile`` (the host copy of that ``component_quantiles`` column of
+    mag1c over the plume labels, (N, M, Q)); it needs mag1c.  No device involved."""
     import pandas as pd
     if ring_stats is not None and "mag1c" not in plane_names:
         raise ValueError("table_from_stats: ring_stats needs the mag1c plane")
+    if ring_quantiles is not None and ring_stats is None:
+        raise ValueError("table_from_stats: ring_quantiles needs ring_stats")
+    if plume_quantiles is not None and "mag1c" not in plane_names:
+        raise ValueError("table_from_stats: plume_quantiles needs the mag1c plane")
     if quantify is not None and "mag1c" not in plane_names:
         raise ValueError("table_from_stats: quantify needs the mag1c plane")
     counts = np.asarray(counts).reshape(-1)
@@ -262,9 +381,24 @@ def table_from_stats(stats, counts, width, plane_names=(), with_other=False, min
                 bg_s = np.asarray(ring_stats["sum"])[item, k, 0].astype(np.float64)
                 with np.errstate(invalid="ignore", divide="ignore"):
                     bg_mean = np.where(bg_n > 0, bg_s / np.maximum(bg_n, 1), np.nan)
-                cols.update(bg_px=bg_n, mag1c_bg_mean=bg_mean, mag1c_sum_bgsub=s - bg_mean * nf.astype(np.float64))
+                bg = bg_mean
+                if ring_quantiles is not None:             # float32 results, kept as float64 columns
+                    bg = np.asarray(ring_quantiles["median"])[item, k].astype(np.float64)
+                cols.update(bg_px=bg_n, mag1c_bg_mean=bg_mean, mag1c_sum_bgsub=s - bg * nf.astype(np.float64))
                 if pixel_area_m2 is not None:
                     cols["ime_bgsub_ppmm_m2"] = cols["mag1c_sum_bgsub"] * float(pixel_area_m2)
+                if ring_quantiles is not None:
+                    mad = np.asarray(ring_quantiles["mad"])[item, k].astype(np.float64)
+                    noise = MAD_TO_SIGMA * mad * np.sqrt(nf.astype(np.float64))      # of the sum over n pixels of independent noise
+                    cols.update(mag1c_bg_median=bg, mag1c_bg_mad=mad, mag1c_bg_sigma=MAD_TO_SIGMA * mad)
+                    if pixel_area_m2 is not None:
+                        cols["ime_sigma_ppmm_m2"] = noise * float(pixel_area_m2)
+                    with np.errstate(invalid="ignore", divide="ignore"):
+                        cols["snr"] = np.where(noise > 0, cols["mag1c_sum_bgsub"] / np.where(noise > 0, noise, 1.0), np.nan)
+            if plume_quantiles is not None:
+                pq = np.asarray(plume_quantiles["quantile"])
+                for j, cname in enumerate(quantile_names(plume_quantiles["q"])):
+                    cols[cname] = pq[item, k, j].astype(np.float64)
         elif name == "prob":
             cols.update(prob_mean=mean, prob_max=mx)
         else:
@@ -290,7 +424,8 @@ def table_from_stats(stats, counts, width, plane_names=(), with_other=False, min
         qcols, curves = quantify_columns(
             settings, quantify["radii_m"], quantify["pixel_size_m"], area[item, k], np.asarray(stats["sum_row"])[item, k],
             np.asarray(stats["sum_col"])[item, k], cols["mag1c_sum"], np.asarray(stats["n_finite"])[item, k, q],
-            {f: np.asarray(v)[item, k] for f, v in rad.items()}, cols["mag1c_bg_mean"] if ring_stats is not None else None,
+            {f: np.asarray(v)[item, k] for f, v in rad.items()},
+            None if ring_stats is None else cols["mag1c_bg_mean" if ring_quantiles is None else "mag1c_bg_median"],
             wind if wind.ndim else None)
         cols.update(qcols)
         quantify["curves"] = curves
@@ -341,7 +476,7 @@ def background_rings(labels, ring_px, gap_px=0.0):
 
 
 def plume_table(mask, mag1c=None, prob=None, label_mask=None, connectivity=2, min_area=1, geotransform=None, pixel_area_m2=None,
-                background_ring_px=None, background_gap_px=0.0, quantify=None):
+                background_ring_px=None, background_gap_px=0.0, quantify=None, background_stat="mean", percentiles=None):
     """One row per plume of ``mask != 0``: an (H, W) or (N, H, W) mask, numpy or device.  Labels the mask on the device
     (``connectivity`` 1 or 2 as ``connected_components``), reduces every component in one ``sc_component_stats`` call and reads
     the rows back once.  Components of fewer than ``min_area`` pixels are dropped.  Columns:
@@ -375,21 +510,36 @@ def plume_table(mask, mag1c=None, prob=None, label_mask=None, connectivity=2, mi
     ``major_axis_m``, ``minor_axis_m``, ``orientation_rad`` (``quantify.shape_from_moments``); ``ime_kg = mag1c_sum * pixel_area_m2 *
     kg_per_ppmm_m2``; ``q_sqrt_area_kg_h``, ``q_fetch_kg_h``, ``q_fetch_std_kg_h``, ``q_fetch_n`` (``quantify.emission_rates`` on the
     cumulative profile inside the circles).  With ``background_ring_px`` the profile and ``ime_kg`` are taken above
-    ``mag1c_bg_mean``, and a plume whose ``bg_px`` is 0 gets NaN rates.  None leaves columns and bytes as they are without."""
+    ``mag1c_bg_mean``, and a plume whose ``bg_px`` is 0 gets NaN rates.  None leaves columns and bytes as they are without.
+
+    ``background_stat``: ``"mean"`` (default: every column and byte as above) or ``"median"``, which needs ``background_ring_px`` (a
+    ValueError otherwise, as is any other string).  The ring is reduced once more, by ``component_median_mad`` (exact order statistics
+    of the ring pixels with finite mag1c), and the background that ``mag1c_sum_bgsub``, ``ime_bgsub_ppmm_m2`` and ``quantify``
+    (``ime_kg``, the fetch profile, the NaN rule for a plume without ring pixels) subtract is the ring MEDIAN; ``bg_px`` and
+    ``mag1c_bg_mean`` stay as they are.  Added columns: ``mag1c_bg_median``, ``mag1c_bg_mad`` (the median of ``|v - median|`` over the
+    ring; both float32 results kept as float64), ``mag1c_bg_sigma = 1.4826 * mag1c_bg_mad`` (the standard deviation of a normal
+    distribution with that MAD), with ``pixel_area_m2`` ``ime_sigma_ppmm_m2 = mag1c_bg_sigma * sqrt(n) * pixel_area_m2``, and ``snr =
+    mag1c_sum_bgsub / (mag1c_bg_sigma * sqrt(n))``, n the plume's finite pixels.  Both ASSUME that the noise of the n pixels is
+    uncorrelated and as large as in the ring; mag1c noise is spatially correlated, so they flatter the plume.  ``snr`` is NaN where
+    sigma is 0 or there is no ring.
+    ``percentiles``: a sequence as the ``q`` of ``component_quantiles``, e.g. ``(5, "median", 95)``; it needs ``mag1c`` and adds, over
+    the plume's own finite pixels and from one more ``component_quantiles`` call, ``mag1c_p5``, ``mag1c_median``, ``mag1c_p95`` (names
+    ``f"mag1c_p{q:g}"``).  None adds nothing."""
     return _plume_table(mask, mag1c, prob, label_mask, connectivity, min_area, geotransform, pixel_area_m2, background_ring_px,
-                        background_gap_px, quantify)[0]
+                        background_gap_px, quantify, background_stat, percentiles)[0]
 
 
 def fetch_profiles(mask, mag1c, quantify, prob=None, label_mask=None, connectivity=2, min_area=1, geotransform=None,
-                   pixel_area_m2=None, background_ring_px=None, background_gap_px=0.0):
+                   pixel_area_m2=None, background_ring_px=None, background_gap_px=0.0, background_stat="mean", percentiles=None):
     """``plume_table(..., quantify=quantify)`` and the curves behind its rates, for plotting -> ``(table, curves)``: ``curves`` a
     dict with ``radii_m`` (K,) and, one row per row of the table, ``n_px`` (pixels with finite mag1c inside circle j), ``ime_kg``
     (IME_j, above the background with ``background_ring_px``), ``q_kg_h`` (``3600 U IME_j / r_j``) and ``used`` (bool: the radii
-    that enter ``q_fetch_kg_h``), all (rows, K).  The same device work as ``plume_table``."""
+    that enter ``q_fetch_kg_h``), all (rows, K).  ``background_stat`` and ``percentiles`` are passed through: with ``"median"`` the
+    curves are taken above the ring median.  The same device work as ``plume_table``."""
     if quantify is None:
         raise ValueError("fetch_profiles: quantify is required (a dict with wind_speed_m_s)")
     return _plume_table(mask, mag1c, prob, label_mask, connectivity, min_area, geotransform, pixel_area_m2, background_ring_px,
-                        background_gap_px, quantify)
+                        background_gap_px, quantify, background_stat, percentiles)
 
 
 def _quantify_plan(quantify, mag1c, geotransform, pixel_area_m2):
@@ -441,9 +591,17 @@ def _origins_from_rows(settings, counts, M, geotransform):
 
 
 def _plume_table(mask, mag1c, prob, label_mask, connectivity, min_area, geotransform, pixel_area_m2, background_ring_px,
-                 background_gap_px, quantify):
+                 background_gap_px, quantify, background_stat="mean", percentiles=None):
     """``plume_table`` -> (table, the curves of ``fetch_profiles`` or None)"""
     shape = tuple(mask.shape)
+    if background_stat not in BACKGROUND_STATS:
+        raise ValueError(f"plume_table: background_stat {background_stat!r} (one of {BACKGROUND_STATS})")
+    if background_stat == "median" and background_ring_px is None:
+        raise ValueError("plume_table: background_stat=\"median\" needs background_ring_px")
+    if percentiles is not None:
+        if mag1c is None:
+            raise ValueError("plume_table: percentiles needs mag1c")
+        quantile_fractions(percentiles, "plume_table: percentiles")
     qplan = _quantify_plan(quantify, mag1c, geotransform, pixel_area_m2)
     if background_ring_px is not None:
         if mag1c is None:
@@ -462,10 +620,16 @@ def _plume_table(mask, mag1c, prob, label_mask, connectivity, min_area, geotrans
     counts_h = np.array([counts]) if isinstance(counts, int) else counts.cpu().numpy()      # the one read-back of the counts
     M = max(int(counts_h.max()), 0)
     st = component_stats(labels, counts, planes, other, M=M)
-    ring_host = None
+    ring_host = ring_q = plume_q = None
     if background_ring_px is not None:
         lab3 = _as_batch(labels, "plume_table").contiguous()
-        ring_host = _read_back(component_stats(_rings(lab3, ring2, gap2), counts, planes[:1], M=M))
+        rings = _rings(lab3, ring2, gap2)
+        ring_host = _read_back(component_stats(rings, counts, planes[:1], M=M))
+        if background_stat == "median":
+            ring_q = _read_back_f32(component_median_mad(rings, counts, planes[0], M=M), ("median", "mad"))
+    if percentiles is not None:
+        plume_q = {"q": tuple(percentiles), **_read_back_f32(component_quantiles(labels, counts, planes[0], percentiles, M=M),
+                                                             ("quantile",))}
     if qplan is not None:
         settings = qplan["settings"]
         if np.ndim(settings["wind_speed_m_s"]) and np.size(settings["wind_speed_m_s"]) != int(np.minimum(counts_h, M).sum()):
@@ -480,8 +644,20 @@ def _plume_table(mask, mag1c, prob, label_mask, connectivity, min_area, geotrans
     counts = counts_h
     host = _read_back(st)
     table = table_from_stats(host, counts, shape[-1], names, other is not None, min_area, geotransform, pixel_area_m2, ring_host,
-                             qplan)
+                             qplan, ring_q, plume_q)
     return table, (qplan["curves"] if qplan is not None else None)
+
+
+def _read_back_f32(res, fields):
+    """the float32 columns ``fields`` of a ``component_quantiles`` / ``component_median_mad`` dict in ONE device-to-host copy"""
+    N = res[fields[0]].shape[0]
+    flat = torch.cat([res[f].reshape(N, int(np.prod(res[f].shape[1:]))) for f in fields], 1).cpu().numpy()
+    out, at = {}, 0
+    for f in fields:
+        n = int(np.prod(res[f].shape[1:]))
+        out[f] = np.ascontiguousarray(flat[:, at:at + n]).reshape(tuple(res[f].shape))
+        at += n
+    return out
 
 
 def _read_back(st):

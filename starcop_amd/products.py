@@ -262,17 +262,24 @@ def clean(out, open_radius=0.0, min_area=1, exclude=None, exclude_buffer_px=0.0,
     return out
 
 
-BACKGROUND_KEYS = ("ring_px", "gap_px")
+BACKGROUND_KEYS = ("ring_px", "gap_px", "stat")
 
 
 def check_plume_background(plume_background, who):
     """the ``plume_background=`` argument of ``annotate`` and the pipeline calls: None, or a dict with ``ring_px`` and optionally
-    ``gap_px`` (no device involved) -> the keyword arguments of ``plumes.plume_table``"""
+    ``gap_px`` and ``stat`` (``"mean"`` or ``"median"``, the ``background_stat`` of ``plumes.plume_table``; no device involved) -> the
+    keyword arguments of ``plumes.plume_table``; ``background_stat`` is among them when ``stat`` is given"""
     if plume_background is None:
         return {}
     if not isinstance(plume_background, dict) or set(plume_background) - set(BACKGROUND_KEYS) or "ring_px" not in plume_background:
         raise ValueError(f"{who}: plume_background must be a dict with ring_px and keys from {BACKGROUND_KEYS}, got {plume_background!r}")
-    return {"background_ring_px": plume_background["ring_px"], "background_gap_px": plume_background.get("gap_px", 0.0)}
+    kw = {"background_ring_px": plume_background["ring_px"], "background_gap_px": plume_background.get("gap_px", 0.0)}
+    if "stat" in plume_background:
+        from .plumes import BACKGROUND_STATS
+        if plume_background["stat"] not in BACKGROUND_STATS:
+            raise ValueError(f"{who}: plume_background stat {plume_background['stat']!r} (one of {BACKGROUND_STATS})")
+        kw["background_stat"] = plume_background["stat"]
+    return kw
 
 
 def check_plume_quantify(plume_quantify, who):
@@ -291,8 +298,9 @@ def annotate(out, mask, mf, prob, geotransform=None, pixel_area_m2=None, plumes=
     and ``prob`` as probability), ``plume_outlines`` of the same mask in the same coordinates, and for ``label_polygons`` (a
     ``.geojson`` path or polygons) ``label_mask``, the polygons burnt into the grid of ``mask`` (device uint8), and ``plume_match``,
     the same burnt image scored against the mask, with ``match_tolerance_px`` as the ``tolerance_px`` of ``plumes.burn_and_match``.
-    ``plume_background``: ``{"ring_px": .., "gap_px": ..}`` adds the background-ring columns of ``plumes.plume_table`` to the table
-    (and so to ``plumes.csv`` and the GeoJSON properties); it needs ``mf``.  ``plume_quantify``: the ``quantify=`` dict of
+    ``plume_background``: ``{"ring_px": .., "gap_px": .., "stat": "mean" | "median"}`` adds the background-ring columns of ``plumes.plume_table`` to the table
+    (and so to ``plumes.csv`` and the GeoJSON properties), with ``stat="median"`` those of its ``background_stat="median"``; it needs
+    ``mf``.  ``plume_quantify``: the ``quantify=`` dict of
     ``plumes.plume_table`` (``wind_speed_m_s``, ...) adds its shape, mass and emission-rate columns the same way; it needs ``mf`` and
     ``pixel_area_m2``, i.e. a metric grid: on a longitude / latitude grid it is a ValueError (the scene calls take ``crs="utm"``)."""
     from . import plumes as pl
