@@ -9,7 +9,7 @@ import os
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, stacks
 from ._lib import check, ptr, stream
 
 THRESHOLD = 200.0          # mask_creation.py:11: mag1c_values[0] >= 200
@@ -18,16 +18,6 @@ THRESHOLD = 200.0          # mask_creation.py:11: mag1c_values[0] >= 200
 def _workspace(N, H, W, dev):
     wb = _lib.load().sc_label_workspace_bytes(N, H, W)          # 0 for bad dims: the call itself then raises with the dims message
     return torch.empty(max(wb, 1), dtype=torch.uint8, device=dev), wb
-
-
-def _planes(t):
-    """a (B, H, W) view whose H x W planes are dense at one non-overlapping stride (e.g. channel 3 of a (B, 4, H, W) tensor) is
-    used in place; anything else is copied -> (tensor, elements between planes)"""
-    B, H, W = t.shape
-    dense = (W == 1 or t.stride(2) == 1) and (H == 1 or t.stride(1) == W) and (B == 1 or t.stride(0) >= H * W)
-    if not dense:
-        t = t.contiguous()
-    return t, (t.stride(0) if B > 1 else H * W)
 
 
 def _proposed_mask_device(label_rgba, mag1c, threshold, se_bits):
@@ -40,14 +30,8 @@ def _proposed_mask_device(label_rgba, mag1c, threshold, se_bits):
     _lib.require_device(label_rgba)
     _lib.require_device(mag1c)
     B, H, W = mag1c.shape[0], mag1c.shape[-2], mag1c.shape[-1]
-    alpha = label_rgba[:, -1]                      # existing label: the last band, != 0
-    if alpha.dtype != torch.uint8:
-        alpha = (alpha != 0).to(torch.uint8)
-    mag = mag1c[:, 0]
-    if mag.dtype != torch.float32:
-        mag = mag.float()
-    mag, mstride = _planes(mag)
-    alpha, astride = _planes(alpha)
+    alpha, astride = stacks.plane_operand(label_rgba[:, -1], torch.uint8)      # existing label: the last band, != 0
+    mag, mstride = stacks.plane_operand(mag1c[:, 0], torch.float32)
     out = torch.empty((B, H, W), dtype=torch.uint8, device=mag.device)
     work, wb = _workspace(B, H, W, mag.device)
     check(lib.sc_proposed_mask(ptr(mag), mstride, ptr(alpha), astride, float(threshold), int(se_bits), ptr(out), ptr(work), wb,
@@ -82,29 +66,18 @@ def connected_components(mask, connectivity=2):
     components numbered from 1 in the raster order of their first pixel.  numpy in -> numpy labels and an int (H, W) or an
     (N,) int64 array of counts; device tensor in -> device labels and device int32 counts (an int for (H, W))."""
     lib = _lib.load()
-    host = isinstance(mask, np.ndarray)
-    m = torch.from_numpy(np.ascontiguousarray(mask)) if host else mask
-    if m.dim() not in (2, 3):
-        raise ValueError(f"connected_components: expected an (H, W) or (N, H, W) mask, got {tuple(m.shape)}")
-    if host:
-        _lib.require_device()
-        m = m.cuda()
-    _lib.require_device(m)
-    single = m.dim() == 2
-    m3 = m[None] if single else m
-    if m3.dtype != torch.uint8:
-        m3 = (m3 != 0).to(torch.uint8)
-    m3 = m3.contiguous()
+    stacks.check_stack(mask, "connected_components", "mask")
+    m3, single, host = stacks.device_mask(mask)
+    m3 = m3.contiguous()                           # the kernel takes no strides
     N, H, W = m3.shape
     labels = torch.empty((N, H, W), dtype=torch.int32, device=m3.device)
     counts = torch.empty((N,), dtype=torch.int32, device=m3.device)
     work, wb = _workspace(N, H, W, m3.device)
     check(lib.sc_connected_components(ptr(m3), int(connectivity), ptr(labels), ptr(counts), ptr(work), wb, N, H, W, stream()))
+    labels = stacks.finish(labels, single, host)
     if single:
-        labels, counts = labels[0], int(counts[0].item())
-    if host:
-        return labels.cpu().numpy(), (counts if single else counts.cpu().numpy().astype(np.int64))
-    return labels, counts
+        return labels, int(counts[0].item())
+    return labels, (counts.cpu().numpy().astype(np.int64) if host else counts)
 
 
 def write_label_masks(dataframe, batch_size=16, overwrite=False, threshold=THRESHOLD, device=None):

@@ -23,9 +23,9 @@ import math
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, stacks
 from ._lib import check, ptr, stream
-from .mask_creation import _planes, connected_components
+from .mask_creation import connected_components
 
 FAR = _lib.EDT_FAR
 WINDOW_MAX_R = _lib.EDT_WINDOW_MAX_R
@@ -34,10 +34,7 @@ _D2_MAX = FAR - 1
 
 
 def _check_mask(mask, who):
-    if not isinstance(mask, (np.ndarray, torch.Tensor)):
-        raise ValueError(f"{who}: expected a numpy array or a tensor, got {type(mask).__name__}")
-    if mask.ndim not in (2, 3):
-        raise ValueError(f"{who}: expected an (H, W) or (N, H, W) mask, got {tuple(mask.shape)}")
+    stacks.check_stack(mask, who, "mask")
     H, W = mask.shape[-2:]
     if not (0 < H <= 32767 and 0 < W <= 32767) or mask.shape[0] == 0:
         raise ValueError(f"{who}: bad shape {tuple(mask.shape)} (H, W in 1..32767, no empty batch)")
@@ -50,24 +47,6 @@ def _cap(v, who, what):
         raise ValueError(f"{who}: {what} {v!r} must be >= 0")
     sq = v * v
     return _D2_MAX if sq >= _D2_MAX else int(math.floor(sq))
-
-
-def _device_u8(mask):
-    """-> ((N, H, W) device uint8 view -- in place for uint8 / bool device tensors --, was (H, W), was numpy)"""
-    host = isinstance(mask, np.ndarray)
-    if host:
-        m = np.ascontiguousarray(mask if mask.dtype == np.uint8 else (mask != 0).astype(np.uint8))
-        _lib.require_device()
-        m = torch.from_numpy(m).cuda()
-    else:
-        _lib.require_device(mask)
-        m = mask
-        if m.dtype == torch.bool:
-            m = m.view(torch.uint8)
-        elif m.dtype != torch.uint8:
-            m = (m != 0).to(torch.uint8)
-    single = m.dim() == 2
-    return (m[None] if single else m), single, host
 
 
 def _edt(m3, invert, want, max_dist2=0, thresh2=0, negate=False, pixel_size=1.0, variant=0):
@@ -83,14 +62,8 @@ def _edt(m3, invert, want, max_dist2=0, thresh2=0, negate=False, pixel_size=1.0,
     a.pixel_size = float(pixel_size)
     setattr(a, want, out.data_ptr())
     wb = lib.sc_edt_call_workspace_bytes(a)                  # what this call's row pass needs; 0 where the call itself will refuse
-    work = torch.empty(max(wb, 1), dtype=torch.uint8, device=m3.device)
-    check(lib.sc_edt(a, ptr(work), wb, stream()))
+    stacks.call_with_workspace(lib.sc_edt, a, wb, m3.device)
     return out
-
-
-def _finish(out, single, host):
-    out = out[0] if single else out
-    return out.cpu().numpy() if host else out
 
 
 def edt_variant(H, W, max_dist2=0, forced=None):
@@ -123,14 +96,14 @@ def distance_transform(mask, to="set", max_distance=None, squared=False, pixel_s
         cap = None                                           # no distance in an image reaches it
     if variant == "window" and (cap is None or math.isqrt(cap) > WINDOW_MAX_R):
         raise ValueError(f"{who}: variant='window' needs a max_distance of at most {WINDOW_MAX_R} pixels")
-    m3, single, host = _device_u8(mask)
+    m3, single, host = stacks.device_mask(mask)
     invert = to == "unset"
     if cap == 0:                                             # only the targets themselves lie within the cap
         on = _edt(m3, invert, "within", thresh2=0, variant=VARIANTS[variant])
         out = torch.where(on != 0, 0, FAR).to(torch.int32) if squared else torch.where(on != 0, 0.0, math.inf).to(torch.float32)
-        return _finish(out, single, host)
+        return stacks.finish(out, single, host)
     out = _edt(m3, invert, "dist2" if squared else "dist", max_dist2=cap or 0, pixel_size=pixel_size, variant=VARIANTS[variant])
-    return _finish(out, single, host)
+    return stacks.finish(out, single, host)
 
 
 def _nearest(m3, invert, max_dist2=0, variant=0, index=False, dist2=False, planes=()):
@@ -145,13 +118,12 @@ def _nearest(m3, invert, max_dist2=0, variant=0, index=False, dist2=False, plane
     idx = torch.empty((N, H, W), dtype=torch.int32, device=m3.device) if index else None
     d2 = torch.empty((N, H, W), dtype=torch.int32, device=m3.device) if dist2 else None
     a.index, a.dist2 = (idx.data_ptr() if index else None), (d2.data_ptr() if dist2 else None)
-    srcs, outs = [_planes(p) for p in planes], []            # holds the tensors the pointers belong to until the call is enqueued
+    srcs, outs = [stacks.plane_operand(p) for p in planes], []      # holds the tensors the pointers belong to until the call is enqueued
     for i, (t, stride) in enumerate(srcs):
         outs.append(torch.empty((N, H, W), dtype=t.dtype, device=m3.device))
         a.src[i], a.src_stride[i], a.dst[i] = t.data_ptr(), stride, outs[i].data_ptr()
     wb = lib.sc_edt_nearest_call_workspace_bytes(a)          # 0 where the call itself will refuse
-    work = torch.empty(max(wb, 1), dtype=torch.uint8, device=m3.device)
-    check(lib.sc_edt_nearest(a, ptr(work), wb, stream()))
+    stacks.call_with_workspace(lib.sc_edt_nearest, a, wb, m3.device)
     return idx, d2, outs
 
 
@@ -177,7 +149,7 @@ def nearest_index(mask, to="set", max_distance=None, return_distance=False, vari
     cap = _distance_cap(max_distance, who)
     if variant == "window" and (cap is None or math.isqrt(cap) > WINDOW_MAX_R):
         raise ValueError(f"{who}: variant='window' needs a max_distance of at most {WINDOW_MAX_R} pixels")
-    m3, single, host = _device_u8(mask)
+    m3, single, host = stacks.device_mask(mask)
     invert = to == "unset"
     if cap == 0:                                             # only the targets themselves lie within the cap
         N, H, W = m3.shape
@@ -187,8 +159,8 @@ def nearest_index(mask, to="set", max_distance=None, return_distance=False, vari
     else:
         idx, d2, _ = _nearest(m3, invert, cap or 0, VARIANTS[variant], index=True, dist2=bool(return_distance))
     if return_distance:
-        return _finish(idx, single, host), _finish(d2, single, host)
-    return _finish(idx, single, host)
+        return stacks.finish(idx, single, host), stacks.finish(d2, single, host)
+    return stacks.finish(idx, single, host)
 
 
 def expand_labels(labels, distance=1.0):
@@ -198,23 +170,13 @@ def expand_labels(labels, distance=1.0):
     scipy's; the results agree away from ties).  ``distance=0`` returns the labels as int32.  One ``sc_edt_nearest`` call."""
     who = "expand_labels"
     _check_mask(labels, who)
-    host = isinstance(labels, np.ndarray)
-    if (labels.dtype.kind not in "iub") if host else (labels.dtype.is_floating_point or labels.dtype.is_complex):
-        raise ValueError(f"{who}: labels must be integers, got {labels.dtype}")
     t = _cap(distance, who, "distance")
-    if host:
-        _lib.require_device()
-        lab = torch.from_numpy(np.ascontiguousarray(labels).astype(np.int32)).cuda()
-    else:
-        _lib.require_device(labels)
-        lab = labels.to(torch.int32)
-    single = lab.dim() == 2
-    lab = (lab[None] if single else lab).contiguous()
+    lab, single, host = stacks.device_labels(labels, who, "mask", integers=True)
     if t == 0:
-        return _finish(lab if host or labels.dtype != torch.int32 else lab.clone(), single, host)
+        return stacks.finish(lab if host or labels.dtype != torch.int32 else lab.clone(), single, host)
     m3 = (lab != 0).to(torch.uint8)
     out = _nearest(m3, False, 0 if t == _D2_MAX else t, planes=[lab])[2][0]
-    return _finish(out, single, host)
+    return stacks.finish(out, single, host)
 
 
 MAX_FILL_PLANES = _lib.EDT_NEAREST_MAX_PLANES
@@ -242,9 +204,9 @@ def fill_nearest(data, invalid, max_distance=None):
         if p.dtype not in (np.float32, torch.float32):
             raise ValueError(f"{who}: plane {i} must be float32, got {p.dtype}")
     cap = _distance_cap(max_distance, who)
-    m3, single, _ = _device_u8(invalid)
+    m3, single, _ = stacks.device_mask(invalid)
     if host:
-        planes = [torch.from_numpy(np.ascontiguousarray(p)).to(m3.device) for p in planes]
+        planes = [stacks.upload(p, m3.device) for p in planes]
     else:
         for p in planes:
             _lib.require_device(p)
@@ -253,12 +215,12 @@ def fill_nearest(data, invalid, max_distance=None):
         outs = [p.clone() for p in planes]
     else:
         outs = _nearest(m3, True, cap or 0, planes=planes)[2]
-    outs = [_finish(o, single, host) for o in outs]
+    outs = [stacks.finish(o, single, host) for o in outs]
     return outs if many else outs[0]
 
 
 def _binary(mask, single, host):
-    return _finish((mask != 0).to(torch.uint8), single, host)
+    return stacks.finish((mask != 0).to(torch.uint8), single, host)
 
 
 def _disc_op(m3, t, erosion):
@@ -272,10 +234,10 @@ def _disc_ops(mask, radius, who, steps):
     """the arguments checked once, then ``steps`` (True: erosion, False: dilation) in order"""
     _check_mask(mask, who)
     t = _cap(radius, who, "radius")
-    m3, single, host = _device_u8(mask)
+    m3, single, host = stacks.device_mask(mask)
     for erosion in steps:
         m3 = _disc_op(m3, t, erosion)
-    return _finish(m3, single, host)
+    return stacks.finish(m3, single, host)
 
 
 def dilate(mask, radius):
@@ -305,7 +267,7 @@ def remove_small_objects(mask, min_area, connectivity=2):
     if connectivity not in (1, 2):
         raise ValueError(f"remove_small_objects: connectivity {connectivity!r} (1 or 2)")
     min_area = int(min_area)
-    m3, single, host = _device_u8(mask)
+    m3, single, host = stacks.device_mask(mask)
     if min_area <= 1:
         return _binary(m3, single, host)
     labels, counts = connected_components(m3, connectivity=connectivity)
@@ -316,4 +278,4 @@ def remove_small_objects(mask, min_area, connectivity=2):
     keep[:, 0] = 0
     out = torch.empty((N, H, W), dtype=torch.uint8, device=labels.device)
     check(_lib.load().sc_label_keep(ptr(labels), ptr(keep.contiguous()), ptr(out), N, M, H, W, stream()))
-    return _finish(out, single, host)
+    return stacks.finish(out, single, host)

@@ -15,21 +15,16 @@ import json
 import numpy as np
 import torch
 
-from . import _lib, metrics
-from ._lib import check, ptr, stream
-from .mask_creation import _planes, connected_components
+from . import _lib, metrics, stacks
+from ._lib import check, stream
+from .mask_creation import connected_components
 
 MAX_PLANES = _lib.CSTATS_MAX_PLANES
 COMPONENT_FIELDS = ("area", "row_min", "row_max", "col_min", "col_max", "sum_row", "sum_col", "first_pixel", "n_other")
 PLANE_FIELDS = ("n_finite", "sum", "max", "min", "argmax")
 _DTYPES = {"row_min": torch.int32, "row_max": torch.int32, "col_min": torch.int32, "col_max": torch.int32,
            "sum": torch.float64, "max": torch.float32, "min": torch.float32}
-
-
-def _as_batch(t, what):
-    if t.dim() not in (2, 3):
-        raise ValueError(f"{what}: expected an (H, W) or (N, H, W) array, got {tuple(t.shape)}")
-    return t[None] if t.dim() == 2 else t
+_COLUMNS = [(f, _DTYPES.get(f, torch.int64), f in PLANE_FIELDS) for f in COMPONENT_FIELDS + PLANE_FIELDS]      # (field, dtype, per plane)
 
 
 def component_stats(labels, counts, planes=(), other=None, M=None):
@@ -47,63 +42,37 @@ def component_stats(labels, counts, planes=(), other=None, M=None):
     (int64), ``sum`` (float64), ``max``, ``min`` (float32), ``argmax`` (int64, the first raster index of the maximum; -1 and NaN
     where a component has no finite value), all (N, M, P).  Rows at or above counts[n] are zero.  Repeated calls, and an image
     alone or in a batch, give identical bits."""
+    who = "component_stats"
     planes = list(planes)
     if len(planes) > MAX_PLANES:
-        raise ValueError(f"component_stats: {len(planes)} planes, at most {MAX_PLANES} per call")
+        raise ValueError(f"{who}: {len(planes)} planes, at most {MAX_PLANES} per call")
     if not isinstance(labels, torch.Tensor):
         raise ValueError("component_stats: labels must be a device tensor (plume_table takes numpy masks)")
-    lab = _as_batch(labels, "component_stats: labels")
-    N, H, W = lab.shape
-    planes = [_as_batch(p, f"component_stats: plane {i}") for i, p in enumerate(planes)]
-    for i, p in enumerate(planes):
-        if tuple(p.shape) != (N, H, W):
-            raise ValueError(f"component_stats: plane {i} has shape {tuple(p.shape)}, labels {(N, H, W)}")
+    lab = stacks.stack3(labels, "component_stats: labels")[0]
+    shape = N, H, W = lab.shape
+    planes = [stacks.stack_like(p, shape, f"component_stats: plane {i}") for i, p in enumerate(planes)]
     if other is not None:
-        other = _as_batch(other, "component_stats: other")
-        if tuple(other.shape) != (N, H, W):
-            raise ValueError(f"component_stats: other has shape {tuple(other.shape)}, labels {(N, H, W)}")
-    if isinstance(counts, int):
-        counts = torch.tensor([counts], dtype=torch.int32, device=lab.device)
-    counts = counts.reshape(-1)
-    if counts.numel() != N:
-        raise ValueError(f"component_stats: {counts.numel()} counts for {N} images")
-    _lib.require_device(lab)
+        other = stacks.stack_like(other, shape, "component_stats: other")
+    counts = stacks.counts_i32(counts, N, lab.device, who)
+    lab = stacks.labels_i32(lab)
     lib = _lib.load()
-    if lab.dtype != torch.int32:
-        lab = lab.to(torch.int32)
-    lab = lab.contiguous()
-    counts = counts.to(device=lab.device, dtype=torch.int32).contiguous()
     if M is None:
         M = max(int(counts.max().item()), 0)
     M, P = int(M), len(planes)
     a = _lib.sc_cstats_args()
     a.labels, a.counts, a.N, a.H, a.W, a.M, a.P = lab.data_ptr(), counts.data_ptr(), N, H, W, M, P
-    ops, oth = _operands(planes, other)          # holds the tensors the pointers belong to until the call is enqueued
+    ops = [stacks.plane_operand(p, torch.float32) for p in planes]      # holds the tensors the pointers belong to until the call is enqueued
     for i, (p, stride) in enumerate(ops):
         _lib.require_device(p)
         a.plane[i], a.plane_stride[i] = p.data_ptr(), stride
-    if oth is not None:
-        _lib.require_device(oth[0])
-        a.other, a.other_stride = oth[0].data_ptr(), oth[1]
-    out = {}
-    for f in COMPONENT_FIELDS:
-        out[f] = torch.empty((N, M), dtype=_DTYPES.get(f, torch.int64), device=lab.device)
-    for f in PLANE_FIELDS:
-        out[f] = torch.empty((N, M, P), dtype=_DTYPES.get(f, torch.int64), device=lab.device)
-    for f, t in out.items():
-        setattr(a, f, t.data_ptr() if t.numel() else None)
+    if other is not None:
+        other, a.other_stride = stacks.plane_operand(other, torch.uint8)
+        _lib.require_device(other)
+        a.other = other.data_ptr()
+    out = stacks.output_columns(a, [(f, dt, (N, M, P) if per_plane else (N, M)) for f, dt, per_plane in _COLUMNS], lab.device)
     wb = lib.sc_component_stats_workspace_bytes(N, H, W, M, P)          # 0 for bad dims: the call then raises with the message
-    work = torch.empty(max(wb, 1), dtype=torch.uint8, device=lab.device)
-    check(lib.sc_component_stats(a, ptr(work), wb, stream()))
+    stacks.call_with_workspace(lib.sc_component_stats, a, wb, lab.device)
     return out
-
-
-def _operands(planes, other):
-    """(N, H, W) planes and mask -> [(tensor, elements between images)], (tensor, bytes between images) or None: float32 / uint8
-    views with dense H x W planes are used in place, anything else is converted or copied"""
-    ops = [_planes(p if p.dtype == torch.float32 else p.float()) for p in planes]
-    oth = None if other is None else _planes(other if other.dtype == torch.uint8 else (other != 0).to(torch.uint8))
-    return ops, oth
 
 
 MAX_QUANTILES = _lib.CQUANT_MAX_Q
@@ -160,32 +129,22 @@ def component_quantiles(labels, counts, plane, q=("median",), center=None, M=Non
     fr = quantile_fractions(q, who)
     if not isinstance(labels, torch.Tensor) or not isinstance(plane, torch.Tensor):
         raise ValueError(f"{who}: labels and plane must be device tensors (plume_table takes numpy masks)")
-    lab = _as_batch(labels, f"{who}: labels")
-    N, H, W = lab.shape
-    pl = _as_batch(plane, f"{who}: plane")
-    if tuple(pl.shape) != (N, H, W):
-        raise ValueError(f"{who}: plane has shape {tuple(pl.shape)}, labels {(N, H, W)}")
-    if isinstance(counts, int):
-        counts = torch.tensor([counts], dtype=torch.int32)
-    counts = counts.reshape(-1)
-    if counts.numel() != N:
-        raise ValueError(f"{who}: {counts.numel()} counts for {N} images")
+    lab = stacks.stack3(labels, "component_quantiles: labels")[0]
+    shape = N, H, W = lab.shape
+    pl = stacks.stack_like(plane, shape, "component_quantiles: plane")
+    counts = stacks.counts_i32(counts, N, lab.device, who)
     if center is not None:
         if not isinstance(center, torch.Tensor) or center.dim() != 2 or center.shape[0] != N or center.dtype != torch.float32:
             raise ValueError(f"{who}: center must be a float32 tensor of shape ({N}, M)")
         if M is not None and center.shape[1] != int(M):
             raise ValueError(f"{who}: center has shape {tuple(center.shape)}, expected {(N, int(M))}")
         M = center.shape[1]
-    _lib.require_device(lab)
+    lab = stacks.labels_i32(lab)
     lib = _lib.load()
-    if lab.dtype != torch.int32:
-        lab = lab.to(torch.int32)
-    lab = lab.contiguous()
-    counts = counts.to(device=lab.device, dtype=torch.int32).contiguous()
     if M is None:
         M = max(int(counts.max().item()), 0)
     M, Q = int(M), len(fr)
-    (op, stride), = _operands([pl], None)[0]          # holds the tensor the pointer belongs to until the call is enqueued
+    op, stride = stacks.plane_operand(pl, torch.float32)      # holds the tensor the pointer belongs to until the call is enqueued
     _lib.require_device(op)
     a = _lib.sc_cquant_args()
     a.labels, a.counts, a.N, a.H, a.W, a.M, a.Q = lab.data_ptr(), counts.data_ptr(), N, H, W, M, Q
@@ -196,12 +155,9 @@ def component_quantiles(labels, counts, plane, q=("median",), center=None, M=Non
         a.center = center.data_ptr() if center.numel() else None
     for j, f in enumerate(fr):
         a.q[j] = float(f)
-    out = {"n_finite": torch.empty((N, M), dtype=torch.int64, device=lab.device),
-           "quantile": torch.empty((N, M, Q), dtype=torch.float32, device=lab.device)}
-    a.n_finite, a.quantile = (t.data_ptr() if t.numel() else None for t in out.values())
+    out = stacks.output_columns(a, [("n_finite", torch.int64, (N, M)), ("quantile", torch.float32, (N, M, Q))], lab.device)
     wb = lib.sc_component_quantiles_workspace_bytes(N, H, W, M, Q)      # 0 for bad dims: the call then raises with the message
-    work = torch.empty(max(wb, 1), dtype=torch.uint8, device=lab.device)
-    check(lib.sc_component_quantiles(a, ptr(work), wb, stream()))
+    stacks.call_with_workspace(lib.sc_component_quantiles, a, wb, lab.device)
     return out
 
 
@@ -259,19 +215,13 @@ def component_radial(labels, counts, stats, origins, radii_px, plane, M=None):
     edges = squared_edges(radii_px, who, _lib.EDT_FAR - 1)
     if not isinstance(labels, torch.Tensor) or not isinstance(plane, torch.Tensor) or not isinstance(origins, torch.Tensor):
         raise ValueError(f"{who}: labels, origins and plane must be device tensors (plume_table takes numpy masks)")
-    lab = _as_batch(labels, f"{who}: labels")
-    N, H, W = lab.shape
-    pl = _as_batch(plane, f"{who}: plane")
-    if tuple(pl.shape) != (N, H, W):
-        raise ValueError(f"{who}: plane has shape {tuple(pl.shape)}, labels {(N, H, W)}")
-    if H > _lib.CRADIAL_MAX_SIDE or W > _lib.CRADIAL_MAX_SIDE:
+    lab = stacks.stack3(labels, "component_radial: labels")[0]
+    shape = N, H, W = lab.shape
+    pl = stacks.stack_like(plane, shape, "component_radial: plane")
+    if H >_lib.CRADIAL_MAX_SIDE or W > _lib.CRADIAL_MAX_SIDE:
         raise ValueError(f"{who}: image of {H} x {W}; a side may have at most {_lib.CRADIAL_MAX_SIDE} pixels")
-    if isinstance(counts, int):
-        counts = torch.tensor([counts], dtype=torch.int32, device=lab.device)
-    counts = counts.reshape(-1)
-    if counts.numel() != N:
-        raise ValueError(f"{who}: {counts.numel()} counts for {N} images")
-    boxes = [stats[f] for f in ("row_min", "row_max", "col_min", "col_max")]
+    counts = stacks.counts_i32(counts, N, lab.device, who)
+    boxes =[stats[f] for f in ("row_min", "row_max", "col_min", "col_max")]
     if M is None:
         M = boxes[0].shape[-1]
     M, K = int(M), len(edges)
@@ -283,15 +233,11 @@ def component_radial(labels, counts, stats, origins, radii_px, plane, M=None):
     for t in [lab, pl, origins] + boxes:
         if not t.is_cuda:
             raise ValueError(f"{who}: labels, stats, origins and plane must be device tensors, got one on {t.device}")
-    _lib.require_device(lab)
+    lab = stacks.labels_i32(lab)
     lib = _lib.load()
-    if lab.dtype != torch.int32:
-        lab = lab.to(torch.int32)
-    lab = lab.contiguous()
-    counts = counts.to(device=lab.device, dtype=torch.int32).contiguous()
     boxes = [t.contiguous() for t in boxes]
     origins = origins.contiguous()
-    (op, stride), = _operands([pl], None)[0]          # holds the tensor the pointer belongs to until the call is enqueued
+    op, stride = stacks.plane_operand(pl, torch.float32)      # holds the tensor the pointer belongs to until the call is enqueued
     a = _lib.sc_cradial_args()
     a.labels, a.counts, a.N, a.H, a.W, a.M, a.K = lab.data_ptr(), counts.data_ptr(), N, H, W, M, K
     a.row_min, a.row_max, a.col_min, a.col_max = (t.data_ptr() if t.numel() else None for t in boxes)
@@ -299,35 +245,10 @@ def component_radial(labels, counts, stats, origins, radii_px, plane, M=None):
     a.plane, a.plane_stride = op.data_ptr(), stride
     for j, e in enumerate(edges):
         a.edge2[j] = e
-    out = {"bin_count": torch.empty((N, M, K + 1), dtype=torch.int64, device=lab.device),
-           "bin_sum": torch.empty((N, M, K + 1), dtype=torch.float64, device=lab.device)}
-    for f in RADIAL_FIELDS[2:]:
-        out[f] = torch.empty((N, M), dtype=torch.int64, device=lab.device)
-    for f, t in out.items():
-        setattr(a, f, t.data_ptr() if t.numel() else None)
+    out = stacks.output_columns(a, [("bin_count", torch.int64, (N, M, K + 1)), ("bin_sum", torch.float64, (N, M, K + 1))]
+                                + [(f, torch.int64, (N, M)) for f in RADIAL_FIELDS[2:]], lab.device)
     wb = lib.sc_component_radial_workspace_bytes(N, H, W, M, K)         # 0 for bad dims: the call then raises with the message
-    work = torch.empty(max(wb, 1), dtype=torch.uint8, device=lab.device)
-    check(lib.sc_component_radial(a, ptr(work), wb, stream()))
-    return out
-
-
-def _read_back_radial(rad, origins):
-    """every column of a ``component_radial`` dict and the origins in ONE device-to-host copy -> numpy arrays (``origin`` added)"""
-    N, M = rad["d2_max"].shape
-    if M == 0:
-        K1 = rad["bin_count"].shape[-1]
-        out = {f: np.zeros((N, 0), dtype=np.int64) for f in RADIAL_FIELDS[2:]}
-        out.update(bin_count=np.zeros((N, 0, K1), np.int64), bin_sum=np.zeros((N, 0, K1), np.float64), origin=np.zeros((N, 0, 2), np.int64))
-        return out
-    tensors = [(f, rad[f]) for f in RADIAL_FIELDS] + [("origin", origins)]
-    flat = torch.cat([(t.view(torch.int64) if t.dtype == torch.float64 else t.to(torch.int64)).reshape(N, -1) for _, t in tensors], 1)
-    flat = flat.cpu().numpy()
-    out, at = {}, 0
-    for f, t in tensors:
-        n = int(np.prod(t.shape[1:]))
-        a = np.ascontiguousarray(flat[:, at:at + n])
-        at += n
-        out[f] = (a.view(np.float64) if t.dtype == torch.float64 else a).reshape(tuple(t.shape))
+    stacks.call_with_workspace(lib.sc_component_radial, a, wb, lab.device)
     return out
 
 
@@ -406,11 +327,7 @@ def table_from_stats(stats, counts, width, plane_names=(), with_other=False, min
     if with_other:
         cols["overlap_px"] = np.asarray(stats["n_other"])[item, k].astype(np.int64)
     if geotransform is not None:
-        gt = [float(v) for v in np.asarray(geotransform, dtype=np.float64).ravel()]
-        if len(gt) != 6:
-            raise ValueError(f"plume_table: geotransform must have 6 numbers, got {len(gt)}")
-        if gt[2] != 0.0 or gt[4] != 0.0:
-            raise NotImplementedError(f"plume_table: rotated geotransform (terms {gt[2]}, {gt[4]}) is not supported")
+        gt = _gt6(geotransform, "plume_table")
         cols["x"] = gt[0] + (cols["centroid_col"] + 0.5) * gt[1]
         cols["y"] = gt[3] + (cols["centroid_row"] + 0.5) * gt[5]
     if quantify is not None:
@@ -430,13 +347,6 @@ def table_from_stats(stats, counts, width, plane_names=(), with_other=False, min
         cols.update(qcols)
         quantify["curves"] = curves
     return pd.DataFrame(cols)
-
-
-def _to_device(a, dev=None):
-    if isinstance(a, np.ndarray):
-        _lib.require_device()
-        return torch.from_numpy(np.ascontiguousarray(a)).to(dev if dev is not None else "cuda")
-    return a
 
 
 def _ring_caps(ring_px, gap_px, who):
@@ -461,25 +371,17 @@ def background_rings(labels, ring_px, gap_px=0.0):
     every other pixel 0.  With several plumes each ring pixel belongs to the nearest one, so rings never overlap.  One
     ``sc_edt_nearest`` call (squared distance and the gathered label plane) and one select."""
     who = "background_rings"
-    if not isinstance(labels, (np.ndarray, torch.Tensor)) or labels.ndim not in (2, 3):
-        raise ValueError(f"{who}: expected an (H, W) or (N, H, W) label image")
-    host = isinstance(labels, np.ndarray)
-    if (labels.dtype.kind not in "iub") if host else (labels.dtype.is_floating_point or labels.dtype.is_complex):
-        raise ValueError(f"{who}: labels must be integers, got {labels.dtype}")
     ring2, gap2 = _ring_caps(ring_px, gap_px, who)
-    lab = _to_device(labels.astype(np.int32) if host else labels)
-    _lib.require_device(lab)
-    lab = _as_batch(lab.to(torch.int32), who).contiguous()
-    out = _rings(lab, ring2, gap2)
-    out = out[0] if labels.ndim == 2 else out
-    return out.cpu().numpy() if host else out
+    lab, single, host = stacks.device_labels(labels, who, integers=True)
+    return stacks.finish(_rings(lab, ring2, gap2), single, host)
 
 
 def plume_table(mask, mag1c=None, prob=None, label_mask=None, connectivity=2, min_area=1, geotransform=None, pixel_area_m2=None,
                 background_ring_px=None, background_gap_px=0.0, quantify=None, background_stat="mean", percentiles=None):
     """One row per plume of ``mask != 0``: an (H, W) or (N, H, W) mask, numpy or device.  Labels the mask on the device
     (``connectivity`` 1 or 2 as ``connected_components``), reduces every component in one ``sc_component_stats`` call and reads
-    the rows back once.  Components of fewer than ``min_area`` pixels are dropped.  Columns:
+    back twice whatever the options: the component counts, which size the rows, and then every column of every option below in one
+    copy (``stacks.read_back``).  Components of fewer than ``min_area`` pixels are dropped.  Columns:
 
     ``item`` (index of the image), ``plume_id`` (the component's label), ``area_px``, ``row_min``, ``row_max``, ``col_min``,
     ``col_max`` (inclusive), ``centroid_row``, ``centroid_col`` (float64 means of the pixel indices);
@@ -494,8 +396,8 @@ def plume_table(mask, mag1c=None, prob=None, label_mask=None, connectivity=2, mi
     plume's finite pixels, and with ``pixel_area_m2`` ``ime_bgsub_ppmm_m2``.  None leaves the table as it is without.
 
     ``quantify`` (needs ``mag1c`` and ``pixel_area_m2``, square pixels of ``pixel_size_m = sqrt(pixel_area_m2)``; a geotransform
-    with ``|gt1| != |gt5|`` is a ValueError) adds shape, mass and emission rates from one ``component_radial`` call, read back in
-    one more copy.  A dict with the keys (anything else is a ValueError):
+    with ``|gt1| != |gt5|`` is a ValueError) adds shape, mass and emission rates from one ``component_radial`` call, read back with
+    the other columns.  A dict with the keys (anything else is a ValueError):
     ``wind_speed_m_s`` (required): the EFFECTIVE wind speed, used as given -- a number, or one per plume; no U10 model is applied;
     ``radii_m`` (up to 64 increasing radii) or ``max_fetch_m`` (default 150 m, the AVIRIS-NG survey's choice): without ``radii_m`` the
     circles are ``r_j = j * pixel_size_m`` for j = 1 .. min(64, floor(max_fetch_m / pixel_size_m)); no radius at all is a ValueError;
@@ -610,83 +512,52 @@ def _plume_table(mask, mag1c, prob, label_mask, connectivity, min_area, geotrans
     for name, p in (("mag1c", mag1c), ("prob", prob), ("label_mask", label_mask)):
         if p is not None and tuple(p.shape) != shape:
             raise ValueError(f"plume_table: {name} has shape {tuple(p.shape)}, the mask {shape}")
-    if len(shape) not in (2, 3):
-        raise ValueError(f"plume_table: expected an (H, W) or (N, H, W) mask, got {shape}")
-    m = _to_device(mask)
+    stacks.check_stack(mask, "plume_table", "mask")
+    m = stacks.upload(mask)
     labels, counts = connected_components(m, connectivity=connectivity)
     names = [n for n, p in (("mag1c", mag1c), ("prob", prob)) if p is not None]
-    planes = [_to_device(p, m.device) for p in (mag1c, prob) if p is not None]
-    other = _to_device(label_mask, m.device) if label_mask is not None else None
-    counts_h = np.array([counts]) if isinstance(counts, int) else counts.cpu().numpy()      # the one read-back of the counts
+    planes = [stacks.upload(p, m.device) for p in (mag1c, prob) if p is not None]
+    other = stacks.upload(label_mask, m.device) if label_mask is not None else None
+    counts_h = np.array([counts]) if isinstance(counts, int) else counts.cpu().numpy()      # the first read-back: the counts size M
     M = max(int(counts_h.max()), 0)
-    st = component_stats(labels, counts, planes, other, M=M)
-    ring_host = ring_q = plume_q = None
+    dev = {"stats": component_stats(labels, counts, planes, other, M=M)}      # {group: {column: device tensor}}, read back together
     if background_ring_px is not None:
-        lab3 = _as_batch(labels, "plume_table").contiguous()
-        rings = _rings(lab3, ring2, gap2)
-        ring_host = _read_back(component_stats(rings, counts, planes[:1], M=M))
+        rings = _rings(stacks.device_labels(labels, "plume_table")[0], ring2, gap2)
+        dev["ring"] = component_stats(rings, counts, planes[:1], M=M)
         if background_stat == "median":
-            ring_q = _read_back_f32(component_median_mad(rings, counts, planes[0], M=M), ("median", "mad"))
+            ring_q = component_median_mad(rings, counts, planes[0], M=M)
+            dev["ring_q"] = {f: ring_q[f] for f in ("median", "mad")}
     if percentiles is not None:
-        plume_q = {"q": tuple(percentiles), **_read_back_f32(component_quantiles(labels, counts, planes[0], percentiles, M=M),
-                                                             ("quantile",))}
+        dev["plume_q"] = {"quantile": component_quantiles(labels, counts, planes[0], percentiles, M=M)["quantile"]}
     if qplan is not None:
         settings = qplan["settings"]
         if np.ndim(settings["wind_speed_m_s"]) and np.size(settings["wind_speed_m_s"]) != int(np.minimum(counts_h, M).sum()):
             raise ValueError(f"plume_table: {np.size(settings['wind_speed_m_s'])} wind speeds for {int(np.minimum(counts_h, M).sum())} "
                              "plumes (before min_area)")
         if isinstance(settings.get("origin", "max"), str):
-            origins = origins_from_argmax(st, shape[-1], names.index("mag1c"))
+            origins = origins_from_argmax(dev["stats"], shape[-1], names.index("mag1c"))
         else:
             origins = torch.from_numpy(_origins_from_rows(settings, counts_h, M, geotransform)).to(m.device)
-        rad = component_radial(labels, counts, st, origins, qplan["radii_px"], planes[names.index("mag1c")], M=M)
-        qplan["radial"] = _read_back_radial(rad, origins)
-    counts = counts_h
-    host = _read_back(st)
-    table = table_from_stats(host, counts, shape[-1], names, other is not None, min_area, geotransform, pixel_area_m2, ring_host,
-                             qplan, ring_q, plume_q)
+        rad = component_radial(labels, counts, dev["stats"], origins, qplan["radii_px"], planes[names.index("mag1c")], M=M)
+        dev["radial"] = {**rad, "origin": origins}
+    flat = stacks.read_back({(g, f): t for g, cols in dev.items() for f, t in cols.items()})      # the second read-back: everything else
+    host = {g: {f: flat[g, f] for f in cols} for g, cols in dev.items()}
+    if qplan is not None:
+        qplan["radial"] = host["radial"]
+    plume_q = {"q": tuple(percentiles), **host["plume_q"]} if percentiles is not None else None
+    table = table_from_stats(host["stats"], counts_h, shape[-1], names, other is not None, min_area, geotransform, pixel_area_m2,
+                             host.get("ring"), qplan, host.get("ring_q"), plume_q)
     return table, (qplan["curves"] if qplan is not None else None)
 
 
-def _read_back_f32(res, fields):
-    """the float32 columns ``fields`` of a ``component_quantiles`` / ``component_median_mad`` dict in ONE device-to-host copy"""
-    N = res[fields[0]].shape[0]
-    flat = torch.cat([res[f].reshape(N, int(np.prod(res[f].shape[1:]))) for f in fields], 1).cpu().numpy()
-    out, at = {}, 0
-    for f in fields:
-        n = int(np.prod(res[f].shape[1:]))
-        out[f] = np.ascontiguousarray(flat[:, at:at + n]).reshape(tuple(res[f].shape))
-        at += n
-    return out
-
-
-def _read_back(st):
-    """every column of a ``component_stats`` dict in ONE device-to-host copy -> numpy arrays"""
-    N, M = st["area"].shape
-    P = st["sum"].shape[-1]
-    parts, layout = [], []
-    for f in COMPONENT_FIELDS + PLANE_FIELDS:
-        t = st[f]
-        if t.dtype == torch.float64:
-            t = t.view(torch.int64)
-        elif t.dtype == torch.float32:
-            t = t.view(torch.int32)
-        parts.append(t.reshape(N, -1).to(torch.int64))
-        layout.append((f, st[f].dtype, st[f].shape))
-    flat = torch.cat(parts, 1).cpu().numpy() if M else np.zeros((N, 0), dtype=np.int64)
-    out, at = {}, 0
-    for f, dt, shp in layout:
-        n = int(np.prod(shp[1:]))
-        a = np.ascontiguousarray(flat[:, at:at + n]) if M else np.zeros((N, n), dtype=np.int64)
-        at += n
-        if dt == torch.float64:
-            a = a.view(np.float64)
-        elif dt == torch.float32:
-            a = a.astype(np.int32).view(np.float32)
-        elif dt == torch.int32:
-            a = a.astype(np.int32)
-        out[f] = a.reshape(tuple(shp))
-    return out
+def _score(pred, lab, min_overlap_px):
+    """the dict ``match_plumes`` returns, from the two tables with their ``overlap_px`` columns"""
+    tp = int((pred["overlap_px"] >= min_overlap_px).sum())
+    fp = len(pred) - tp
+    fn = int((lab["overlap_px"] < min_overlap_px).sum())
+    cm = torch.tensor([[0, fp], [fn, tp]], dtype=torch.float64)
+    return {"pred": pred, "label": lab, "tp": tp, "fp": fp, "fn": fn,
+            "precision": float(metrics.precision(cm)), "recall": float(metrics.recall(cm))}
 
 
 def match_plumes(pred_mask, label_mask, connectivity=2, min_overlap_px=1, min_area=1, tolerance_px=0.0):
@@ -702,12 +573,7 @@ def match_plumes(pred_mask, label_mask, connectivity=2, min_overlap_px=1, min_ar
     near_label, near_pred = _dilated_others(pred_mask, label_mask, tolerance_px, "match_plumes")
     pred = plume_table(pred_mask, label_mask=near_label, connectivity=connectivity, min_area=min_area)
     lab = plume_table(label_mask, label_mask=near_pred, connectivity=connectivity, min_area=min_area)
-    tp = int((pred["overlap_px"] >= min_overlap_px).sum())
-    fp = len(pred) - tp
-    fn = int((lab["overlap_px"] < min_overlap_px).sum())
-    cm = torch.tensor([[0, fp], [fn, tp]], dtype=torch.float64)
-    return {"pred": pred, "label": lab, "tp": tp, "fp": fp, "fn": fn,
-            "precision": float(metrics.precision(cm)), "recall": float(metrics.recall(cm))}
+    return _score(pred, lab, min_overlap_px)
 
 
 def _dilated_others(pred_mask, label_mask, tolerance_px, who):
@@ -800,15 +666,12 @@ def component_outlines(labels, counts=None, connectivity=2, collinear=False):
         raise ValueError("component_outlines: labels must be a device tensor (plume_outlines takes numpy masks)")
     if connectivity not in (1, 2):
         raise ValueError(f"component_outlines: connectivity {connectivity!r} (1 or 2)")
-    lab = _as_batch(labels, "component_outlines: labels")
-    if counts is not None and not isinstance(counts, int) and counts.numel() != lab.shape[0]:
-        raise ValueError(f"component_outlines: {counts.numel()} counts for {lab.shape[0]} images")
-    _lib.require_device(lab)
-    if lab.dtype != torch.int32:
-        lab = lab.to(torch.int32)
-    lab = lab.contiguous()
+    lab, single = stacks.stack3(labels, "component_outlines: labels")
+    if counts is not None:
+        stacks.counts_i32(counts, lab.shape[0], None, "component_outlines")
+    lab = stacks.labels_i32(lab)
     res = [_outlines_one(lab[n], connectivity, bool(collinear)) for n in range(lab.shape[0])]
-    return res[0] if labels.dim() == 2 else res
+    return res[0] if single else res
 
 
 def _gt6(geotransform, who):
@@ -852,24 +715,17 @@ def plume_outlines(mask, connectivity=2, min_area=1, geotransform=None):
     """Polygons of the plumes of ``mask != 0``, an (H, W) or (N, H, W) mask, numpy or device: labels the mask as ``plume_table``
     does (same ``plume_id``), traces every component on the device (``component_outlines``, corners only) and reads the rings
     back in one copy.  Returns ``{(item, plume_id): [ring, ...]}`` as ``polygons_from_rings`` gives them."""
-    shape = tuple(mask.shape)
-    if len(shape) not in (2, 3):
-        raise ValueError(f"plume_outlines: expected an (H, W) or (N, H, W) mask, got {shape}")
+    stacks.check_stack(mask, "plume_outlines", "mask")
     if geotransform is not None:
         _gt6(geotransform, "plume_outlines")
-    m = _to_device(mask)
+    m = stacks.upload(mask)
     labels, counts = connected_components(m, connectivity=connectivity)
     res = component_outlines(labels, counts, connectivity=connectivity, collinear=False)
     res = [res] if isinstance(res, dict) else res
-    flat = torch.cat([r[f].reshape(-1).to(torch.int64) for r in res for f in OUTLINE_FIELDS]).cpu().numpy()      # the one read-back
-    out, at = {}, 0
-    for n, r in enumerate(res):
-        arrs = []
-        for f in OUTLINE_FIELDS:
-            k = r[f].numel()
-            arrs.append(flat[at:at + k])
-            at += k
-        out.update(polygons_from_rings(*arrs, geotransform=geotransform, min_area=min_area, item=n))
+    host = stacks.read_back({(n, f): r[f] for n, r in enumerate(res) for f in OUTLINE_FIELDS})      # the one read-back
+    out = {}
+    for n in range(len(res)):           # polygons_from_rings takes the int32 columns as they are: it widens them itself
+        out.update(polygons_from_rings(*(host[n, f] for f in OUTLINE_FIELDS), geotransform=geotransform, min_area=min_area, item=n))
     return out
 
 
@@ -1127,17 +983,12 @@ def burn_and_match(pred_mask, polygons, geotransform=None, connectivity=2, min_o
     polys, _ = _polygon_list(polygons)
     P = len(polys)
     burnt = rasterize_polygons(polys, tuple(pred_mask.shape), geotransform=geotransform)
-    other = _to_device(pred_mask, burnt.device)
+    other = stacks.upload(pred_mask, burnt.device)
     near_label, other = _dilated_others(other, (burnt != 0).to(torch.uint8), tolerance_px, "burn_and_match")
     pred = plume_table(pred_mask, label_mask=near_label, connectivity=connectivity, min_area=min_area)
     st = component_stats(burnt, P, other=other, M=P)
-    lab = table_from_stats(_read_back(st), [P], burnt.shape[-1], with_other=True, min_area=min_area)
-    tp = int((pred["overlap_px"] >= min_overlap_px).sum())
-    fp = len(pred) - tp
-    fn = int((lab["overlap_px"] < min_overlap_px).sum())
-    cm = torch.tensor([[0, fp], [fn, tp]], dtype=torch.float64)
-    return burnt, {"pred": pred, "label": lab, "tp": tp, "fp": fp, "fn": fn,
-                   "precision": float(metrics.precision(cm)), "recall": float(metrics.recall(cm))}
+    lab = table_from_stats(stacks.read_back(st), [P], burnt.shape[-1], with_other=True, min_area=min_area)
+    return burnt, _score(pred, lab, min_overlap_px)
 
 
 def match_plumes_polygons(pred_mask, polygons, geotransform=None, connectivity=2, min_overlap_px=1, min_area=1, tolerance_px=0.0):

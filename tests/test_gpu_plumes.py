@@ -14,7 +14,7 @@ import torch
 pytestmark = pytest.mark.gpu
 
 import plumes_util as pu  # noqa: E402
-from starcop_amd import _lib, mask_creation as mc, plumes  # noqa: E402
+from starcop_amd import _lib, mask_creation as mc, plumes, stacks  # noqa: E402
 
 DEV = "cuda"
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -227,7 +227,8 @@ def test_strided_planes_are_read_in_place(hip):
     d_lab, d_cnt = mc.connected_components(torch.from_numpy(masks).to(DEV))
     x = torch.from_numpy((rng.standard_normal((N, 3, H, W)) * 800).astype(np.float32)).to(DEV)
     rgba = torch.from_numpy((rng.random((N, 4, H, W)) < 0.3).astype(np.uint8) * 255).to(DEV)
-    ops, oth = plumes._operands([x[:, 0], x[:, 2]], rgba[:, 3])
+    ops = [stacks.plane_operand(p, torch.float32) for p in (x[:, 0], x[:, 2])]
+    oth = stacks.plane_operand(rgba[:, 3], torch.uint8)
     assert [t.data_ptr() for t, _ in ops] == [x[:, 0].data_ptr(), x[:, 2].data_ptr()] and [s for _, s in ops] == [3 * H * W] * 2
     assert oth[0].data_ptr() == rgba[:, 3].data_ptr() and oth[1] == 4 * H * W
     got = _host(plumes.component_stats(d_lab, d_cnt, [x[:, 0], x[:, 2]], rgba[:, 3]))
@@ -238,6 +239,22 @@ def test_strided_planes_are_read_in_place(hip):
     for n in range(N):
         assert counts[n] > 50
         _check_rows(got, n, pu.oracle_stats(labs[n], counts[n], [xs[n, 0], xs[n, 2]], oth_h[n, 3]), counts[n], ("strided", n))
+
+
+def test_read_back_of_the_stats_columns(hip):
+    """``stacks.read_back`` of a ``component_stats`` dict (int32, int64, float32 and float64 columns) is every column's own copy,
+    byte for byte, with rows and with M = 0"""
+    rng = np.random.default_rng(52)
+    N, H, W = 2, 33, 65
+    d_lab, d_cnt = mc.connected_components(torch.from_numpy(rng.random((N, H, W)) < 0.35).to(DEV))
+    x = torch.from_numpy((rng.standard_normal((N, H, W)) * 800).astype(np.float32)).to(DEV)
+    for M in (None, 0):
+        st = plumes.component_stats(d_lab, d_cnt, [x], M=M)
+        got, want = stacks.read_back(st), _host(st)
+        assert list(got) == list(want) and got["area"].shape[1] == (0 if M == 0 else int(d_cnt.max()))
+        for f in want:
+            assert got[f].dtype == want[f].dtype and got[f].shape == want[f].shape, f
+            assert got[f].tobytes() == want[f].tobytes() and got[f].flags.c_contiguous and got[f].flags.aligned, f
 
 
 @pytest.mark.parametrize("with_other", (False, True))
